@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — CSR SpMV throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload s32-band] [--kind auto]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload s32-band] [--kind auto] [--full] [--dump-outputs DIR]
     python bench.py --mtx FILE.mtx [--dtype f32|f64] [--offset 32|64]        # a Matrix Market file (main.cu:32-39)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -20,7 +20,7 @@ sub-blocks so that a slice travels while the next is computed)
 torch.distributed (gloo) only carries the control plane: the 128-byte RCCL id, the
 barriers and the max-over-ranks of the timings.  For N > 1 the line separates the step
 into its parts: `compute_only` (the blocks' kernels, no exchange), `exchange_only` (the
-allgatherv alone) and the step itself (both, overlapped).
+allgatherv alone) and the step itself (both, overlapped); those two legs are timed with --full.
 
 Default workload = the north-star target named in BASELINE.json / SURVEY.md §8(d):
 S32-band, 2^22 rows, exactly 32 nnz/row inside a +-4096 band, fp32 values, 32-bit
@@ -30,18 +30,26 @@ be timed with --workload.
 
 One JSON line on stdout (rank 0) — also when the run fails: a rank that dies, an RCCL
 or gloo call that does not return and a wall-clock limit all end in ONE line with an
-"error" field and a non-zero exit code, never in a hang.  Extra objects:
+"error" field and a non-zero exit code, never in a hang.  A plain run sets up, warms up
+(with --kind auto the warm-up also picks the kind), times the K steps and reports them.
+Extra objects:
   roofline      achieved = ALGORITHMIC bytes of one SpMV / mean device time of one
                 execute = (HIP events recorded on the launch stream around the K timed
-                executes) / K — for N > 1: this GPU's bytes / its compute-only time;
-                min / median from a second pass with events around every execute;
-                peak = 8000 GB/s (HBM3E spec, MI355X_MICROARCH.md);
+                executes) / K — for N > 1 (--full): this GPU's bytes / its compute-only
+                time; peak = 8000 GB/s (HBM3E spec, MI355X_MICROARCH.md);
                 traffic = HBM bytes per launch from rocprofv3 PMC passes (read from
-                profiles/, null if that file is absent)
+                profiles/, null if that file is absent);
+                --full: min / median from a second pass with events around every execute
+  --full also reports:
   cpu_baseline  the reference's serial CPU SpMV (cpu_navie.hpp:5-17) timed on this
                 box's host cores, rank 0 / N = 1 only: kind "reference" = the
                 reference's own header compiled by oracle/Makefile (oracle/_ref),
                 else "port" = oracle/spmv_oracle.cpp.  Reported, not the target.
+  one_shot_ms / one_shot_first_ms / library_auto_kind (N = 1), the compute-only and
+                exchange-only legs (N > 1).
+--dump-outputs DIR writes y of the last timed step (rank 0: the whole y) as DIR/y.npy in the
+matrix's value type; past 64 MB a fixed, seeded sample of its rows, sorted, as DIR/y_sample.npy.
+The inputs are seeded: the same arguments give the same matrix and x on every run.
 """
 import argparse
 import datetime
@@ -105,6 +113,12 @@ def parse():
                     help="row blocks per GPU in the multi-GPU path (0 = 4 when N > 1, else 1)")
     ap.add_argument("--exchange", default="auto", choices=("auto", "bcast", "sendrecv", "allgather"),
                     help="how the y slices travel when N > 1 (auto = the library's timed pick at create)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the instrumented per-execute pass, "
+                         "the N > 1 compute-only / exchange-only legs, the one-shot times, the library's own kind pick "
+                         "and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write y of the last timed step as DIR/y.npy (over 64 MB: a seeded sample, DIR/y_sample.npy)")
     return ap.parse_args()
 
 
@@ -502,6 +516,22 @@ def read_traffic(kernel, algorithmic_bytes):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, y):
+    """y as the caller receives it, in its own value type (float32 / float64); a larger y: a fixed sample of rows
+    (seed 0, sorted) that fits DUMP_LIMIT_BYTES with the file header."""
+    os.makedirs(out_dir, exist_ok=True)
+    yh = y.cpu().numpy()
+    cap = (DUMP_LIMIT_BYTES - 4096) // yh.itemsize
+    if yh.size <= cap:
+        np.save(os.path.join(out_dir, "y.npy"), yh)
+        return
+    rows = np.sort(np.random.default_rng(0).choice(yh.size, size=cap, replace=False))
+    np.save(os.path.join(out_dir, "y_sample.npy"), yh[rows])
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -583,10 +613,11 @@ def main():
 
     dog.phase = "timed region"
     wall, dev_list = time_steps(run, x, y, use_dist, args.steps)            # THE timed region
+    y_last = y.clone() if args.dump_outputs and rank == 0 else None          # (what the last timed step left)
     step_dev_ms = float(np.mean(dev_list))
     multi = use_dist and world > 1
     legs = {}
-    if multi or (use_dist and os.environ.get("MI355_BENCH_LEGS")):          # (the knob: N = 1 rehearsal of the two legs)
+    if args.full and (multi or (use_dist and os.environ.get("MI355_BENCH_LEGS"))):   # (the knob: N = 1 rehearsal of the two legs)
         dog.phase = "compute-only / exchange-only legs"
         for leg in ("compute", "exchange"):
             time_steps(run, x, y, use_dist, 5, leg=leg)
@@ -599,8 +630,10 @@ def main():
                          "ms_min_over_gpus": float(tmin[0].item()), "wall_ms_per_step": float(tmax[1].item())}
         run.execute(x, y)                                                    # (leave a whole y behind)
     dev_ms = legs["compute"]["ms"] if "compute" in legs else step_dev_ms     # this GPU's kernels
-    dog.phase = "instrumented pass"
-    _, step_list = time_steps(run, x, y, use_dist, args.steps, per_step=True, leg="compute" if legs else "step")   # spread of single executes
+    step_list = None
+    if args.full:
+        dog.phase = "instrumented pass"
+        _, step_list = time_steps(run, x, y, use_dist, args.steps, per_step=True, leg="compute" if legs else "step")   # spread of single executes
     tmax = torch.tensor([wall], dtype=torch.float64)
     nnz_all = torch.tensor([float(run.nnz_local)], dtype=torch.float64)
     v, o = m.Ax.element_size(), m.Ap.element_size()
@@ -662,18 +695,20 @@ def main():
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
                          "kernel": info["main_kernel"], "kernel_ms": dev_ms,
-                         "kernel_ms_min": float(np.min(step_list)), "kernel_ms_median": float(np.median(step_list)),
-                         "kernel_ms_mean_instrumented": float(np.mean(step_list)),
                          "algorithmic_bytes": bytes_alg,
                          "timed": ("kernel_ms = one pair of HIP events around the K executes of the timed region / K, on the "
-                                   "launch stream; min / median / mean_instrumented = a second pass of K executes with a "
-                                   "pair around each" if _FLUSH["buf"] is None else
+                                   "launch stream" + ("; min / median / mean_instrumented = a second pass of K executes "
+                                                      "with a pair around each" if step_list is not None else "")
+                                   if _FLUSH["buf"] is None else
                                    "HIP events around every execute of the timed region (cold mode)") +
                                   (" (N > 1: the compute-only leg of this GPU, its own bytes; the step with the exchange is "
                                    "ms_per_step)" if legs else "")},
             "warmup_probe_ms": probe,
         }
-        if not use_dist:
+        if step_list is not None:
+            out["roofline"].update({"kernel_ms_min": float(np.min(step_list)), "kernel_ms_median": float(np.median(step_list)),
+                                    "kernel_ms_mean_instrumented": float(np.mean(step_list))})
+        if not use_dist and args.full:
             # what the library itself would run for a caller with no opinion (MI355_KIND_AUTO: a rule on the structure,
             # no timing) — reported next to the measured pick
             try:
@@ -707,14 +742,17 @@ def main():
             out["exchange_check"] = checks[kind]
         if others:
             out["all_kinds"] = others
-        if world == 1:
+        if world == 1 and args.full:
             out["one_shot_ms"] = one_shot_ms(sp, kind, m, x, y)                     # repeated calls (plan found again)
             out["one_shot_first_ms"] = one_shot_ms(sp, kind, m, x, y, first=True)   # a first call: plan created
             sp.capi.cache_release()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             dog.phase = "cpu baseline"
             dog.deadline += args.cpu_seconds + 120
             out["cpu_baseline"] = cpu_baseline(m, x, args.cpu_seconds)
+        if y_last is not None:
+            dog.phase = "--dump-outputs"
+            dump_outputs(args.dump_outputs, y_last)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     dog.phase = "teardown"

@@ -8,7 +8,7 @@ ROUNDS=${ROUNDS:-3}
 T=$(mktemp)
 for round in $(seq $ROUNDS); do
 for L in "$@"; do
-  MI355_SPMV_LIB=$R/spmv-samples_amd/$L/libmi355spmv.so python $R/bench.py --no-cpu-baseline --steps ${STEPS:-200} --warmup 50 $ARGS 2>/dev/null | python -c "
+  MI355_SPMV_LIB=$R/spmv-samples_amd/$L/libmi355spmv.so python $R/bench.py --full --no-cpu-baseline --steps ${STEPS:-200} --warmup 50 $ARGS 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); c=d['config']; r=d['roofline']; print('%-14s' % '$L', c['kind'], 'T', c['lanes_per_row'], 'grid', c['grid_blocks'], 'win', c['x_window_elems'], 'seg', c['x_window_segments'], '%.2f us' % (r['kernel_ms']*1e3), 'min %.2f' % (r['kernel_ms_min']*1e3), 'frac %.3f' % r['frac'])" | tee -a $T
 done
 done

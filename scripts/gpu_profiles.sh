@@ -11,11 +11,11 @@ rm -rf $O; mkdir -p $O
 cd /tmp
 trace() {
   local tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$tag -- python3 $R/bench.py --steps 100 --warmup 50 --no-cpu-baseline "$@" > $O/trace_$tag.json 2> $O/trace_$tag.err || { echo "trace $tag failed"; tail -3 $O/trace_$tag.err; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$tag -- python3 $R/bench.py --steps 100 --warmup 50 --full --no-cpu-baseline "$@" > $O/trace_$tag.json 2> $O/trace_$tag.err || { echo "trace $tag failed"; tail -3 $O/trace_$tag.err; }
 }
 pmc() {
   local tag=$1 ctr="$2"; shift; shift
-  rocprofv3 --pmc $ctr --output-format csv -d $O/pmc_$tag -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" > $O/pmc_$tag.json 2> $O/pmc_$tag.err || { echo "pmc $tag failed"; tail -3 $O/pmc_$tag.err; }
+  rocprofv3 --pmc $ctr --output-format csv -d $O/pmc_$tag -- python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline "$@" > $O/pmc_$tag.json 2> $O/pmc_$tag.err || { echo "pmc $tag failed"; tail -3 $O/pmc_$tag.err; }
 }
 trace s32_vector --kind vector
 trace s32_light --kind light
@@ -56,10 +56,10 @@ MI355_MERGE_ROWS=0 pmc s32_mergewalk_lds "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE
 echo "pmc done"
 cd $R
 python3 scripts/summarize_pmc.py $O > $O/summary.json 2> $O/summary.err
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-python3 bench.py --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err
-python3 bench.py --cold --no-cpu-baseline --workload c2-cant --kind vector --steps 200 > $O/bench_c2_cold.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --workload c2-cant --kind vector --steps 2000 --warmup 200 > $O/bench_c2_warm.json 2>/dev/null
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err
+python3 bench.py --full --cold --no-cpu-baseline --workload c2-cant --kind vector --steps 200 > $O/bench_c2_cold.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --workload c2-cant --kind vector --steps 2000 --warmup 200 > $O/bench_c2_warm.json 2>/dev/null
 python3 scripts/probes/vendor_cmp.py s32-band c2-cant c3-webgoogle c4-nlpkkt c5-rmat24 s32-rand --no-torch-sparse > $O/vendor_rocsparse_same_box.txt 2> $O/vendor.err || tail -3 $O/vendor.err
 # keep the small per-run stats tables, drop the bulky traces
 for d in $O/trace_*/; do f=$(find $d -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/$(basename $d)_kernel_stats.csv; done

@@ -3,7 +3,7 @@ cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/small_long; rm -rf $O; mkdir -p $O
 for spec in "--nnz-per-row 64 --rows-log2 16" "--nnz-per-row 64 --rows-log2 17" "--nnz-per-row 128 --rows-log2 15" "--nnz-per-row 128 --rows-log2 16" "--nnz-per-row 16 --rows-log2 18" "--nnz-per-row 8 --rows-log2 19"; do for env in "MI355_SPMV_SMALL=0" "MI355_SPMV_PLAIN=1 MI355_SPMV_LANES=16" "MI355_SPMV_PLAIN=1 MI355_SPMV_LANES=8" "MI355_SPMV_PLAIN=1 MI355_SPMV_LANES=32"; do
   tag=$(echo "${spec}_$env" | tr ' =-' '___')
-  env $env rocprofv3 --kernel-trace --stats --output-format csv -d $O/$tag -- python3 $R/bench.py $spec --kind vector --steps 300 --warmup 100 --no-cpu-baseline > $O/$tag.json 2> $O/$tag.err
+  env $env rocprofv3 --kernel-trace --stats --output-format csv -d $O/$tag -- python3 $R/bench.py $spec --kind vector --steps 300 --warmup 100 --full --no-cpu-baseline > $O/$tag.json 2> $O/$tag.err
   f=$(find $O/$tag -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$spec | $env" <<'PY'
 import csv,sys
