@@ -376,6 +376,12 @@ static int plan_create_impl(mi355_spmv_plan** out, int kind, int off_type, int v
         if (p.n_chunks < 1) p.n_chunks = 1;
         p.n_kernels = 1;
         if (kind == MI355_KIND_VECTOR) block_grid_vector(p); else block_grid_light(p);
+        if (p.small_plain) {      // (what execute launches for it: the whole plan's plain kernel over this block's rows)
+            p.window_elems = 0;
+            p.n_seg = 0;
+            p.grid_blocks = (int64_t(p.n_rows) + kBlock / p.lanes_per_row - 1) / (kBlock / p.lanes_per_row);
+            snprintf(p.main_kernel, sizeof(p.main_kernel), "csr_vector_kernel");
+        }
         const int st2 = find_giant_rows(p);
         if (st2 != MI355_SPMV_OK) { delete h; return st2; }
         if (p.n_giant > 0) p.n_kernels = 3;

@@ -950,7 +950,11 @@ int launch_merge(Plan& p, const off_t* Ap, const mat_t* Ax, const val_t* x, val_
         MI355_HIP_TRY(hipGetLastError());
     }
     if (!reuse) p.coords_valid = true;
-    const int32_t cap = (aligned && p.nnz >= 4) ? (int32_t)p.window_elems : 0;
+    // a window sized for the row-parallel run kernel (512 / 1 024 threads, a swept band, a segment per band: up to
+    // ~155 KB) is not one for the tile kernel, which needs its own ~24 KB next to it: those plans' other executes
+    // (another semiring, an fp32 matrix under fp64 vectors) walk their tiles on plain gathers
+    const bool rows_window = p.merge_rows && (p.mr_block != kBlock || p.mr_sweep_lanes > 0 || p.n_seg >= 2);
+    const int32_t cap = (aligned && p.nnz >= 4 && !rows_window) ? (int32_t)p.window_elems : 0;
     const size_t dyn = size_t(cap) * sizeof(val_t);
     const BandHint hint{p.band_lo, p.band_hi, p.window_from_band};
     const dim3 grid((unsigned)p.n_super);

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from conftest import parity_bound
+from small_path import check_kernel, kind_paths, path  # noqa: F401  (path: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -43,16 +44,30 @@ def c2(sp):
     return m, sp.synth.dense_vector(m.n_cols, torch.float32, 2, DEV)
 
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_c2_cant_every_row(sp, oracle, c2, kind):
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
+def test_c2_cant_every_row(sp, oracle, c2, kind, path):
     """Config 2 (CSR-vector wave-reduce fp32 on cant): every row against the oracle bound, one-shot
-    and through a plan; x = 1 must also agree (the reference's harness input, main.cu:41)."""
+    and through a plan; x = 1 must also agree (the reference's harness input, main.cu:41).  The default arm is what a
+    user gets: the plain one-pass kernel at 16 lanes per row (4.0 M nonzeros, under kSmallPlainNnz)."""
     m, x = c2
     assert m.n_rows == 62451 and abs(m.nnz / m.n_rows - 64) < 1
     y = torch.full((m.n_rows,), float("nan"), device=DEV)
     sp.spmv(kind, m.n_rows, m.n_cols, m.nnz, m.Ap, m.Aj, m.Ax, x, y)
-    check_rows(oracle, m, x, y, "c2 %s one-shot" % kind)
+    check_rows(oracle, m, x, y, "c2 %s %s one-shot" % (kind, path))
     p = sp.Plan(kind, m.n_rows, m.n_cols, m.nnz, m.Ap, m.Aj, torch.float32)
+    check_kernel(p, path, lanes=16)
+    if path == "default":
+        print("c2 %s default: %d rows checked through %s, %d lanes per row" % (
+            kind, m.n_rows, p.info()["main_kernel"], p.info()["lanes_per_row"]))
+        # the plan and the one-shot call: the same bits; vector and light: the same kernel, the same bits
+        y_p = torch.full((m.n_rows,), float("nan"), device=DEV)
+        p.execute(m.Ax, x, y_p)
+        q = sp.Plan("vector" if kind == "light" else "light", m.n_rows, m.n_cols, m.nnz, m.Ap, m.Aj, torch.float32)
+        y_q = torch.full((m.n_rows,), float("nan"), device=DEV)
+        q.execute(m.Ax, x, y_q)
+        torch.cuda.synchronize()
+        q.destroy()
+        assert torch.equal(y_p, y) and torch.equal(y_q, y)
     ones = torch.ones(m.n_cols, device=DEV)
     y2 = torch.full((m.n_rows,), float("nan"), device=DEV)
     p.execute(m.Ax, ones, y2)

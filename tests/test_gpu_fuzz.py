@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import parity_bound
+from small_path import SMALL_PLAIN_NNZ, forced, path, small_choice  # noqa: F401  (path: the fixture)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -73,16 +74,51 @@ def draw_matrix(seed):
     return Ap.astype(off), cols.astype(np.int32), Ax, x, n_cols, desc
 
 
-@pytest.mark.parametrize("seed", range(36))
-def test_fuzz_all_kinds_against_the_oracle(sp, oracle, seed):
+# seeds whose matrix holds more than kSmallPlainNnz nonzeros: no kind can take the plain kernel, both arms are one plan
+# (their chunked arm asserts the count)
+ABOVE_SMALL = (28, 30, 32, 33, 34, 35)
+
+
+def seed_paths():
+    """The chunked arm of every seed (the ids the suite always had), and the default arm of every other seed: where the
+    product's default picks the plain kernel, the VECTOR and LIGHT kinds run again under it."""
+    return [pytest.param(seed, p, id=str(seed) if p == "chunked" else "%d-default" % seed)
+            for seed in range(36) for p in ("chunked", "default") if p == "chunked" or seed not in ABOVE_SMALL]
+
+
+@pytest.mark.parametrize("seed,path", seed_paths(), indirect=["path"])
+def test_fuzz_all_kinds_against_the_oracle(sp, oracle, seed, path):
     Ap, Aj, Ax, x, n_cols, desc = draw_matrix(seed)
     n_rows = len(Ap) - 1
     nnz = int(Ap[-1])
-    y64, bound = parity_bound(oracle, Ap, Aj, Ax, x, 8)
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     dAp, dAj, dAx, dx = d(Ap), d(Aj), d(Ax), d(x)
+    kinds = KINDS
+    assert (nnz > SMALL_PLAIN_NNZ) == (seed in ABOVE_SMALL), desc
+    if path == "default":
+        # the arms differ only where the default plan is the plain kernel; elsewhere it is the chunked arm's plan
+        kinds = []
+        for kind in ("vector", "light"):
+            p = sp.Plan(kind, n_rows, n_cols, nnz, dAp, dAj, dAx.dtype)
+            sh, info = p.shape(), p.info()
+            p.destroy()
+            if sh.small_plain:
+                assert nnz <= SMALL_PLAIN_NNZ and info["main_kernel"] == "csr_vector_kernel", "%s | %s: %s" % (desc, kind, info)
+                kinds.append(kind)
+                continue
+            with small_choice(sp, "chunked"):
+                q = sp.Plan(kind, n_rows, n_cols, nnz, dAp, dAj, dAx.dtype)
+                info_c = q.info()
+                q.destroy()
+            info.pop("knobs"), info_c.pop("knobs")          # (the chunked arm's MI355_SPMV_SMALL=0 is listed there)
+            if not forced():
+                assert info == info_c, "%s | %s: default %s, chunked %s" % (desc, kind, info, info_c)
+        print("%s | default arm: %s on the plain kernel" % (desc, kinds or "no kind"))
+        if not kinds:
+            return
+    y64, bound = parity_bound(oracle, Ap, Aj, Ax, x, 8)
     rng = np.random.default_rng(seed)
-    for kind in KINDS:
+    for kind in kinds:
         p = sp.Plan(kind, n_rows, n_cols, nnz, dAp, dAj, dAx.dtype)
         info = p.info()
         y = torch.full((n_rows,), float("nan"), dtype=dAx.dtype, device=DEV)

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import GOLD, parity_bound, random_csr, seeded_x, unhex
+from small_path import WEIGHT_CUT, check_kernel, kind_paths, path, small_choice  # noqa: F401  (path: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +42,15 @@ def gpu_spmv(sp, kind, n_cols, Ap, Aj, Ax, x, plan=False, flags=0):
     return y.cpu().numpy()
 
 
+def expect_kernel(sp, kind, path, n_cols, Ap, Aj, Ax, elsewhere=None, lanes=None):
+    """The kernel a plan of these arrays takes in this arm (small_path.check_kernel); the one-shot calls take the same."""
+    n_rows = len(Ap) - 1
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    p = sp.Plan(kind, n_rows, n_cols, int(Ap[-1]), d(Ap), d(Aj), d(Ax).dtype)
+    check_kernel(p, path, elsewhere, lanes)
+    p.destroy()
+
+
 def assert_parity(oracle, Ap, Aj, Ax, x, y, exact=False):
     assert not np.any(np.isnan(y)), "a row was skipped (NaN poison survived)"
     if exact:
@@ -54,12 +64,13 @@ def assert_parity(oracle, Ap, Aj, Ax, x, y, exact=False):
 
 # ---- the reference's own inputs/outputs (golden vectors made from its build) -----------------
 
-@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
 @pytest.mark.parametrize("off,val", COMBOS)
-def test_golden_fixtures(sp, oracle, golden, kind, off, val):
+def test_golden_fixtures(sp, oracle, golden, kind, off, val, path):
     for name in FIXTURES:
         nr, nc, Ap, Aj, Ax = oracle.load_mtx(os.path.join(GOLD, name), off, val)
         g = golden[name]
+        expect_kernel(sp, kind, path, nc, Ap, Aj, Ax)                # (every fixture is small and regular)
         for xname, x in (("y_ones", np.ones(nc, dtype=NP[val])), ("y_seeded", seeded_x(nc, NP[val]))):
             y = gpu_spmv(sp, kind, nc, Ap, Aj, Ax, x)
             want = unhex(g[val][xname], NP[val])
@@ -75,33 +86,47 @@ def test_golden_fixtures(sp, oracle, golden, kind, off, val):
 
 # ---- ragged random matrices: empty rows, duplicates, unsorted columns, one long row ----------
 
-@pytest.mark.parametrize("kind", KINDS)
+# where the small-matrix rule sends a ragged shape other than the plain kernel, and why
+HUB = "a hub row of %s: " + WEIGHT_CUT
+RAGGED_ELSEWHERE = {
+    (4099, 700, 40, 30000): HUB % "30 000 nonzeros in ~110 K",
+    (20011, 5000, 6, 9000): HUB % "9 000 nonzeros in ~60 K",
+}
+
+
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
 @pytest.mark.parametrize("off,val", COMBOS)
 @pytest.mark.parametrize("shape", [(1, 1, 1, None), (5, 3, 2, None), (257, 100, 9, None), (4099, 700, 40, 30000),
                                    (20011, 5000, 6, 9000), (3000, 1, 2, None), (1500, 2000, 300, None)])
-def test_random_ragged(sp, oracle, kind, off, val, shape):
+def test_random_ragged(sp, oracle, kind, off, val, shape, path):
     n_rows, n_cols, max_len, long_row = shape
     rng = np.random.RandomState(n_rows * 7 + max_len)
     Ap, Aj, Ax = random_csr(rng, n_rows, n_cols, max_len, NP[off], NP[val], long_row=long_row)
     x = (rng.rand(n_cols) * 2 - 1).astype(NP[val])
+    expect_kernel(sp, kind, path, n_cols, Ap, Aj, Ax, RAGGED_ELSEWHERE.get(shape))
     assert_parity(oracle, Ap, Aj, Ax, x, gpu_spmv(sp, kind, n_cols, Ap, Aj, Ax, x))
 
 
-@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
 @pytest.mark.parametrize("off,val", COMBOS)
-def test_integer_valued_is_bit_exact(sp, oracle, kind, off, val):
+def test_integer_valued_is_bit_exact(sp, oracle, kind, off, val, path):
     """Small integers sum exactly in any order -> the GPU result must equal the serial
     CPU result bit for bit (pattern matrices with x = 1)."""
     rng = np.random.RandomState(99)
     Ap, Aj, Ax = random_csr(rng, 6007, 900, 50, NP[off], NP[val], long_row=20000, integer_values=True)
     x = rng.randint(-2, 3, size=900).astype(NP[val])
+    expect_kernel(sp, kind, path, 900, Ap, Aj, Ax, HUB % "20 000 nonzeros in ~170 K")
+    assert_parity(oracle, Ap, Aj, Ax, x, gpu_spmv(sp, kind, 900, Ap, Aj, Ax, x), exact=True)
+    # the same without the hub row: the plain kernel in the default arm
+    Ap, Aj, Ax = random_csr(rng, 6007, 900, 50, NP[off], NP[val], integer_values=True)
+    expect_kernel(sp, kind, path, 900, Ap, Aj, Ax)
     assert_parity(oracle, Ap, Aj, Ax, x, gpu_spmv(sp, kind, 900, Ap, Aj, Ax, x), exact=True)
 
 
 # ---- edge cases ---------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_empty_and_degenerate(sp, oracle, kind):
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
+def test_empty_and_degenerate(sp, oracle, kind, path):
     f32 = np.float32
     # no rows at all: a no-op that must not fail
     y = gpu_spmv(sp, kind, 5, np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, f32), np.ones(5, f32))
@@ -109,24 +134,28 @@ def test_empty_and_degenerate(sp, oracle, kind):
     # rows but no nonzeros: y = 0 everywhere (cpu_navie.hpp:10-15)
     y = gpu_spmv(sp, kind, 5, np.zeros(1001, np.int32), np.zeros(0, np.int32), np.zeros(0, f32), np.ones(5, f32))
     assert np.array_equal(y, np.zeros(1000, f32))
+    expect_kernel(sp, kind, path, 5, np.zeros(1001, np.int32), np.zeros(0, np.int32), np.zeros(0, f32))
     # every nonzero in the last row
     Ap = np.zeros(301, np.int32); Ap[-1] = 7777
     rng = np.random.RandomState(4)
     Aj = rng.randint(0, 50, 7777).astype(np.int32)
     Ax = rng.randint(-3, 4, 7777).astype(f32)
     x = rng.randint(-2, 3, 50).astype(f32)
+    expect_kernel(sp, kind, path, 50, Ap, Aj, Ax, "every nonzero in one row of 300: " + WEIGHT_CUT)
     assert_parity(oracle, Ap, Aj, Ax, x, gpu_spmv(sp, kind, 50, Ap, Aj, Ax, x), exact=True)
     # every nonzero in the first row, then empty rows only
     Ap = np.full(301, 7777, np.int32); Ap[0] = 0
+    expect_kernel(sp, kind, path, 50, Ap, Aj, Ax, "every nonzero in one row of 300: " + WEIGHT_CUT)
     assert_parity(oracle, Ap, Aj, Ax, x, gpu_spmv(sp, kind, 50, Ap, Aj, Ax, x), exact=True)
     # one row, one column
     y = gpu_spmv(sp, kind, 1, np.array([0, 3], np.int32), np.zeros(3, np.int32), np.array([1, 2, 4], f32),
                  np.array([3], f32))
     assert y.tolist() == [21.0]
+    expect_kernel(sp, kind, path, 1, np.array([0, 3], np.int32), np.zeros(3, np.int32), np.array([1, 2, 4], f32))
 
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_nan_and_inf_propagate_only_to_their_rows(sp, kind):
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
+def test_nan_and_inf_propagate_only_to_their_rows(sp, kind, path):
     """A NaN/Inf in x must reach exactly the rows that reference it (masked lanes of the
     16-byte loads must not leak a neighbour's value)."""
     rng = np.random.RandomState(8)
@@ -134,20 +163,27 @@ def test_nan_and_inf_propagate_only_to_their_rows(sp, kind):
     Ax[:] = 1.0
     x = np.ones(64, np.float32)
     x[13] = np.nan
+    x[40] = np.inf
+    expect_kernel(sp, kind, path, 64, Ap, Aj, Ax)
     y = gpu_spmv(sp, kind, 64, Ap, Aj, Ax, x)
     touched = np.zeros(2000, bool)
+    inf_only = np.zeros(2000, bool)
     for r in range(2000):
         touched[r] = np.any(Aj[Ap[r]:Ap[r + 1]] == 13)
+        inf_only[r] = not touched[r] and np.any(Aj[Ap[r]:Ap[r + 1]] == 40)
     assert np.array_equal(np.isnan(y), touched)
+    assert inf_only.any() and np.array_equal(np.isposinf(y), inf_only)          # (Ax = 1: +inf, never -inf)
+    assert np.all(y[~touched & ~inf_only] == np.diff(Ap)[~touched & ~inf_only])
 
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_unaligned_views_take_the_4_byte_path(sp, oracle, kind):
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
+def test_unaligned_views_take_the_4_byte_path(sp, oracle, kind, path):
     """Aj/Ax that are not 16-byte aligned (offset views of a larger buffer) must still work."""
     rng = np.random.RandomState(21)
     Ap, Aj, Ax = random_csr(rng, 3000, 500, 30)
     x = (rng.rand(500) * 2 - 1).astype(np.float32)
     nnz = int(Ap[-1])
+    expect_kernel(sp, kind, path, 500, Ap, Aj, Ax)
     big_j = torch.zeros(nnz + 3, dtype=torch.int32, device=DEV)
     big_x = torch.zeros(nnz + 3, dtype=torch.float32, device=DEV)
     big_j[1:nnz + 1] = torch.from_numpy(Aj).to(DEV)
@@ -224,24 +260,46 @@ def test_array_tail_is_race_free(sp, oracle, tail):
         p.destroy()
 
 
+def vector_and_light_agree_bitwise(sp, path):
+    rng = np.random.RandomState(34)
+    for long_row, elsewhere in ((5000, HUB % "5 000 nonzeros in ~870 K"), (None, None)):   # (the second: no hub row)
+        Ap, Aj, Ax = random_csr(rng, 25000, 3000, 70, long_row=long_row)
+        x = (rng.rand(3000) * 2 - 1).astype(np.float32)
+        for kind in ("vector", "light"):
+            expect_kernel(sp, kind, path, 3000, Ap, Aj, Ax, elsewhere)
+        assert np.array_equal(gpu_spmv(sp, "vector", 3000, Ap, Aj, Ax, x), gpu_spmv(sp, "light", 3000, Ap, Aj, Ax, x))
+        # the one-shot call and a plan: the same bits
+        assert np.array_equal(gpu_spmv(sp, "vector", 3000, Ap, Aj, Ax, x), gpu_spmv(sp, "vector", 3000, Ap, Aj, Ax, x, plan=True))
+
+
 @pytest.mark.skipif(bool(os.environ.get("MI355_SPMV_PLAIN")), reason="the forced 4-byte kernel sums in another order")
 def test_vector_and_light_agree_bitwise(sp):
     """Both use the same per-row arithmetic; only the row -> wave assignment differs
     (results are assignment-independent)."""
-    rng = np.random.RandomState(34)
-    Ap, Aj, Ax = random_csr(rng, 25000, 3000, 70, long_row=5000)
-    x = (rng.rand(3000) * 2 - 1).astype(np.float32)
-    assert np.array_equal(gpu_spmv(sp, "vector", 3000, Ap, Aj, Ax, x), gpu_spmv(sp, "light", 3000, Ap, Aj, Ax, x))
+    with small_choice(sp, "chunked"):
+        vector_and_light_agree_bitwise(sp, "chunked")
 
 
-@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.skipif(bool(os.environ.get("MI355_SPMV_PLAIN")), reason="the forced 4-byte kernel sums in another order")
+def test_vector_and_light_agree_bitwise_on_the_default_path(sp):
+    """The same matrix through the product's default: both kinds take the plain kernel with the same lanes per row."""
+    with small_choice(sp, "default"):
+        vector_and_light_agree_bitwise(sp, "default")
+
+
+REUSE_ELSEWHERE = HUB % "12 000 nonzeros in ~160 K"
+GRAPH_ELSEWHERE = HUB % "9 000 nonzeros in ~80 K"
+
+
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
 @pytest.mark.parametrize("flags", [0, 1])
-def test_plan_reuse_across_executes(sp, oracle, kind, flags):
+def test_plan_reuse_across_executes(sp, oracle, kind, flags, path):
     rng = np.random.RandomState(35)
     Ap, Aj, Ax = random_csr(rng, 9000, 800, 33, long_row=12000)
     d = lambda a: torch.from_numpy(a).to(DEV)
     dAp, dAj, dAx = d(Ap), d(Aj), d(Ax)
     p = sp.Plan(kind, 9000, 800, int(Ap[-1]), dAp, dAj, torch.float32, flags)
+    check_kernel(p, path, REUSE_ELSEWHERE)
     for i in range(4):
         x = (rng.rand(800) * 2 - 1).astype(np.float32)
         y = torch.full((9000,), float("nan"), device=DEV)
@@ -251,8 +309,8 @@ def test_plan_reuse_across_executes(sp, oracle, kind, flags):
     p.destroy()
 
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_execute_on_a_side_stream(sp, oracle, kind):
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
+def test_execute_on_a_side_stream(sp, oracle, kind, path):
     rng = np.random.RandomState(36)
     Ap, Aj, Ax = random_csr(rng, 5000, 600, 20)
     x = (rng.rand(600) * 2 - 1).astype(np.float32)
@@ -262,6 +320,7 @@ def test_execute_on_a_side_stream(sp, oracle, kind):
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     p = sp.Plan(kind, 5000, 600, int(Ap[-1]), dAp, dAj, torch.float32)
+    check_kernel(p, path)
     with torch.cuda.stream(s):
         p.execute(dAx, dx, y)
     s.synchronize()
@@ -269,8 +328,8 @@ def test_execute_on_a_side_stream(sp, oracle, kind):
     p.destroy()
 
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_execute_is_capturable_in_a_hip_graph(sp, oracle, kind):
+@pytest.mark.parametrize("kind,path", kind_paths(KINDS), indirect=["path"])
+def test_execute_is_capturable_in_a_hip_graph(sp, oracle, kind, path):
     """plan_execute only enqueues (kernels + one memset for `light`): it can be captured once and
     replayed, the way the 2000-iteration loop of main.cu:102-113 would be run launch-free.  The
     replay reads the operands where they were at capture time, so new x values are copied in place."""
@@ -281,6 +340,7 @@ def test_execute_is_capturable_in_a_hip_graph(sp, oracle, kind):
     dx = torch.zeros(800, device=DEV)
     y = torch.full((6000,), float("nan"), device=DEV)
     p = sp.Plan(kind, 6000, 800, int(Ap[-1]), dAp, dAj, torch.float32)
+    check_kernel(p, path, GRAPH_ELSEWHERE)
     p.execute(dAx, dx, y)                      # warm-up outside the capture
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()

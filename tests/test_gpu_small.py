@@ -2,28 +2,17 @@
 common.hpp, kSmallPlainNnz).  tests/conftest.py switches that choice off for the rest of the suite (whose small matrices
 are there to exercise the chunked kernels); here it is switched back on, the knobs re-read, and the same kinds of
 matrices — ragged, empty rows, one long row, one column, every type combination, row blocks — go through it."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import random_csr
+from small_path import BLOCK, PLAIN, forced, small_on  # noqa: F401  (small_on: the fixture)
 from test_gpu_parity import assert_parity
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NP = {"i32": np.int32, "i64": np.int64, "f32": np.float32, "f64": np.float64}
-
-
-@pytest.fixture()
-def small_on(sp):
-    saved = os.environ.pop("MI355_SPMV_SMALL", None)
-    sp.capi.lib().mi355_spmv_knobs_reload()
-    yield
-    if saved is not None:
-        os.environ["MI355_SPMV_SMALL"] = saved
-    sp.capi.lib().mi355_spmv_knobs_reload()
 
 
 def d(a):
@@ -82,7 +71,8 @@ def test_a_skewed_or_big_matrix_keeps_the_chunked_kernels(sp, small_on):
 
 def test_row_blocks_of_a_small_matrix_equal_the_one_gpu_result(sp, small_on):
     """A block inherits the whole plan's choice (mi355_spmv_plan_shape.small_plain) and its lanes per row: the same
-    sums bit for bit — what the multi-GPU path promises for the VECTOR kind."""
+    sums bit for bit — what the multi-GPU path promises for the VECTOR kind.  Each block reports the kernel execute
+    launches for it: the plain kernel over its own rows, no window."""
     m = sp.synth.banded_fixed(30000, 24, 500, 3, DEV)
     x = sp.synth.dense_vector(m.n_cols, m.Ax.dtype, 1, DEV)
     whole = sp.Plan("vector", m.n_rows, m.n_cols, m.nnz, m.Ap, m.Aj, m.Ax.dtype)
@@ -91,6 +81,16 @@ def test_row_blocks_of_a_small_matrix_equal_the_one_gpu_result(sp, small_on):
     whole.execute(m.Ax, x, y1)
     for kind in ("vector", "light"):
         dp = sp.DistPlan.local(kind, m.n_rows, m.n_cols, m.nnz, m.Ap, m.Aj, m.Ax.dtype, sub_blocks=3)
+        cuts = dp.cuts()
+        assert len(cuts) == 4 and cuts[0] == 0 and cuts[-1] == m.n_rows, cuts
+        for part in range(3):
+            info = dp.info(part)
+            rows = cuts[part + 1] - cuts[part]
+            assert rows > 0, cuts
+            if not forced():
+                assert info["main_kernel"] == PLAIN and info["lanes_per_row"] == whole.info()["lanes_per_row"], (part, info)
+                assert info["grid_blocks"] == -(-rows // (BLOCK // info["lanes_per_row"])), (part, rows, info)
+                assert info["window_elems"] == 0 and info["window_segments"] == 0, (part, info)
         y2 = torch.full((m.n_rows,), float("nan"), device=DEV)
         dp.execute(m.Ax, x, y2)
         torch.cuda.synchronize()
