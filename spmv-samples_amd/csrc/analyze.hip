@@ -18,6 +18,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "row_dot.hpp"
 #include "xwindow.hpp"
 
 namespace mi355 {
@@ -299,7 +300,7 @@ int allow_dynamic_lds(const void* kernel, size_t bytes) {
 // Workgroups of the plan's size a CU holds by REGISTERS (the launch bounds of the VECTOR / LIGHT kernels): two of
 // 512 threads; four of 256 when the body keeps 2 rows per vector in flight (fp64; fp32 with 16+ lanes per row),
 // three with 4 rows (fp32, up to 8 lanes per row, and the per-chunk-width kernels of weight-cut plans).
-int workgroups_per_cu_by_registers(const Plan& p) {
+static int workgroups_per_cu_by_registers(const Plan& p) {
     if (p.block_threads == kHugeBlock) return 1;
     if (p.block_threads == kWideBlock) return 2;
     if (p.balanced) return p.val_type == MI355_VAL_F64 ? 4 : 3;
@@ -313,7 +314,7 @@ int long_steps_for(const Plan& p) {
     return p.balanced ? 4 : kLongSteps;
 }
 
-int decide_balance(Plan& p) {
+static int decide_balance(Plan& p) {
     p.balanced = false;
     p.chunk_row = nullptr;
     p.rows_cap = int(p.rows_per_chunk);
@@ -644,14 +645,13 @@ static int window_budget(const Plan& p, int block_threads, int64_t rows) {
     return int(avail < 0 ? 0 : avail);
 }
 
-// VECTOR / LIGHT: workgroup size, rows per chunk and the window of x.  R = rows a vector keeps in flight,
-// div = the kind's chunk divisor (LIGHT's tuning knob).
+// VECTOR / LIGHT: workgroup size, rows per chunk and the window of x.  div = the kind's chunk divisor (LIGHT's tuning knob).
 // Workgroup size: 512 threads own a chunk twice as long (64 K nonzeros) — the window of x is staged half as
 // often per row and 2 x 8 waves sit on a CU instead of 3 x 4 (LDS-bound either way): 190 -> 178 us on the
 // S32-band target (LIGHT: 199 -> 195 us once its kernel is held to 128 VGPRs; at 151 only one such workgroup
 // fits a CU and it lost, 237 us).
-void shape_chunks(Plan& p, int R, int64_t div, bool allow_wide, bool allow_huge) {
-    if (p.val_type == MI355_VAL_F32 && p.lanes_per_row >= 16 && R > 2) R = 2;   // (the kernels' rule: launch_*_window, wide_r)
+static void shape_chunks(Plan& p, int64_t div) {
+    const int R = rows_in_flight(p.val_type == MI355_VAL_F64 ? 8 : 4, p.lanes_per_row);
     int64_t rows_before_rounding = 0;        // of the last shape(): the chunk before it was shrunk to whole rounds
     auto shape = [&](int block_threads, int64_t nnz_per_chunk, int64_t rows_wanted = 0) {
         p.block_threads = block_threads;
@@ -702,7 +702,7 @@ void shape_chunks(Plan& p, int R, int64_t div, bool allow_wide, bool allow_huge)
         }
     };
     const bool force = p.knob.block > 0;
-    if (allow_wide && (!force || p.knob.block == kWideBlock)) {   // (the knob cannot force a workgroup size the kind has no kernel for)
+    if (!force || p.knob.block == kWideBlock) {   // (the knob cannot force a workgroup size the kind has no kernel for)
         shape(kWideBlock, 65536);   // (3 072- and 3 584-row chunks with 79 KB of LDS measured worse: 189-194 vs 180 us)
         const int64_t mean = p.n_rows > 0 ? (p.nnz + p.n_rows - 1) / p.n_rows : 1;
         // keep it when (a) the ">= 4 chunks per CU" rule left the chunk long and (b) one window placed from the
@@ -742,7 +742,7 @@ void shape_chunks(Plan& p, int R, int64_t div, bool allow_wide, bool allow_huge)
     // A band too wide for either budget (fp64 halves what 36 KB holds: the S32-band shape in fp64 ran on plain
     // gathers, 704 us): gfx950 lets a workgroup take more than the default 64 KB of LDS, and two workgroups of
     // 512 threads with ~78 KB each still fit a CU.  The chunk is then as long as the band leaves room for.
-    if (allow_wide && !force && p.probe_ok && !(p.window_elems > 0 && p.n_seg < 2 && p.window_from_band) &&
+    if (!force && p.probe_ok && !(p.window_elems > 0 && p.n_seg < 2 && p.window_from_band) &&
         p.knob.window < 0 && p.knob.rows_per_chunk <= 0) {
         const int64_t off_bytes = 4, val_bytes = p.val_type == MI355_VAL_F64 ? 8 : 4;   // (bounds are chunk-relative int32 in LDS)
         const int64_t band = p.band_hi - p.band_lo + 1;
@@ -771,7 +771,7 @@ void shape_chunks(Plan& p, int R, int64_t div, bool allow_wide, bool allow_huge)
     // plain-gather rate, 1.6-2.5 TB/s, once the band passed ~17 K columns in fp32 / ~9 K in fp64).  ONE workgroup
     // of 1 024 threads per CU can take ~155 of the CU's 160 KB: twice the band.  Its prologue is not hidden by a
     // neighbour, so this is only worth it where the alternative is the plain gather.
-    if (allow_huge && !force && p.probe_ok && p.window_elems == 0 && p.knob.window < 0 && p.knob.rows_per_chunk <= 0) {
+    if (!force && p.probe_ok && p.window_elems == 0 && p.knob.window < 0 && p.knob.rows_per_chunk <= 0) {
         const int64_t val_bytes = p.val_type == MI355_VAL_F64 ? 8 : 4;
         const int64_t band = p.band_hi - p.band_lo + 1;
         const int64_t pass = int64_t(kHugeBlock / p.lanes_per_row) * R;
@@ -796,11 +796,11 @@ void shape_chunks(Plan& p, int R, int64_t div, bool allow_wide, bool allow_huge)
 // workgroup, every row one step of its vector (T from the longest row the probe saw), and the chunk's band is
 // staged in `passes` windows.  Worth it while the staged bytes stay well below the line fills the same
 // nonzeros cost as plain gathers (128 bytes each, some of them L1 hits).  MI355_SPMV_SWEEP=0|1 forces the choice.
-bool shape_sweep(Plan& p) {
+static void shape_sweep(Plan& p) {
     p.sweep = false;
     if (p.balanced || p.knob.block > 0 || !p.probe_ok || p.window_elems != 0 || p.knob.window >= 0 ||
         p.knob.rows_per_chunk > 0 || p.knob.sweep == 0 || p.probe_len_max <= 0 || p.probe_len_max > 4 * kWave)
-        return false;
+        return;
     const int64_t val_bytes = p.val_type == MI355_VAL_F64 ? 8 : 4;
     const int64_t band = p.band_hi - p.band_lo + 1;
     int t = p.lanes_per_row;
@@ -813,21 +813,99 @@ bool shape_sweep(Plan& p) {
     const int64_t mean = p.n_rows > 0 ? (p.nnz - p.nnz_begin) / p.n_rows : 0;
     const int64_t n_chunks = (p.n_rows + rows - 1) / rows;
     const bool pays = span * val_bytes <= 64 * mean * rows;     // staged bytes vs half the gathers' line fills
-    if (!(band > 0 && passes >= 1 && passes <= 16 && n_chunks >= int64_t(kCus) * 2 && (pays || p.knob.sweep == 1))) return false;
+    if (!(band > 0 && passes >= 1 && passes <= 16 && n_chunks >= int64_t(kCus) * 2 && (pays || p.knob.sweep == 1))) return;
     p.sweep = true;
     p.lanes_per_row = t;
     p.block_threads = kHugeBlock;
     p.rows_per_chunk = rows;
     p.rows_cap = int(rows);
     p.n_chunks = n_chunks;
-    p.grid_blocks = n_chunks;
-    p.n_tiles = n_chunks;
     p.window_bytes = int(cap * val_bytes);
     p.window_elems = int(cap);
     p.window_from_band = true;
     p.n_seg = 0;
-    snprintf(p.main_kernel, sizeof(p.main_kernel), p.kind == MI355_KIND_LIGHT ? "light_rows_sweep_kernel" : "csr_vector_sweep_kernel");
-    return true;
+}
+
+// LIGHT: workgroups that stay resident on the chip.  A swept plan's: one per CU.  Otherwise bounded by LDS (160 KB: the
+// chunk's layout + ~1 KB static) and by registers (3 workgroups of 256 threads, 2 of 512).  Asking for more than fits
+// leaves the surplus workgroups to start when the others have finished everything (4 asked / 3 resident: 207 vs 200 us).
+static int64_t light_resident(const Plan& p) {
+    if (p.sweep) return kCus;
+    if (p.knob.light_blocks_per_cu > 0) return int64_t(kCus) * p.knob.light_blocks_per_cu;
+    const size_t val_bytes = p.val_type == MI355_VAL_F64 ? 8 : 4;
+    const size_t lds = chunk_lds_bytes(p.window_elems, p.balanced ? p.rows_cap : int(p.rows_per_chunk), val_bytes) + 1024;
+    int64_t per_cu = int64_t(160 * 1024 / lds);
+    const int64_t reg_bound = workgroups_per_cu_by_registers(p);
+    if (per_cu > reg_bound) per_cu = reg_bound;
+    if (per_cu < 1) per_cu = 1;
+    return int64_t(kCus) * per_cu;
+}
+
+// VECTOR / LIGHT: the launch that follows from the plan's shape — the kernel, its grid and the number of kernels — for
+// whole plans (end of shape_rows) and for row-block plans (after they inherit the whole plan's shape and find their
+// giant rows).
+void set_rows_launch(Plan& p) {
+    p.n_tiles = p.n_chunks;
+    p.n_kernels = p.n_giant > 0 ? 3 : 1;   // (+ the giant rows' slices and their sums)
+    p.light_dequeue_once = false;
+    const char* kernel;
+    if (p.small_plain) {   // either kind: the plain CSR-vector kernel over the plan's rows, no window
+        p.window_elems = 0;
+        p.n_seg = 0;
+        const int64_t rows_per_block = kBlock / p.lanes_per_row;
+        p.grid_blocks = (int64_t(p.n_rows) + rows_per_block - 1) / rows_per_block;
+        kernel = "csr_vector_kernel";
+    } else if (p.kind == MI355_KIND_LIGHT) {
+        // Equal-row chunks: one workgroup per chunk, which takes the chunk of its index while there are at most two
+        // chunks per workgroup slot and makes one dequeue beyond.  Weight-cut chunks: the same up to two per slot (the
+        // dequeue — two dependent atomics and a poll per workgroup — then costs more than it can balance away), else
+        // the persistent grid of what stays resident.
+        const int64_t resident = light_resident(p);
+        p.grid_blocks = (!p.balanced || p.n_chunks <= 2 * resident) ? p.n_chunks : resident;
+        p.light_dequeue_once = !p.balanced && p.n_chunks > 2 * resident;
+        kernel = p.sweep ? "light_rows_sweep_kernel" : "light_rows_window_kernel";
+    } else {
+        p.grid_blocks = p.n_chunks;
+        kernel = p.sweep ? "csr_vector_sweep_kernel" : "csr_vector_window_kernel";
+    }
+    snprintf(p.main_kernel, sizeof(p.main_kernel), "%s", kernel);
+}
+
+// VECTOR / LIGHT, whole plans: lanes per row, chunks and window (shape_chunks), equal-row or weight-cut chunks
+// (decide_balance), a window that sweeps a band too wide for one (shape_sweep), giant rows, the small-matrix rule, and
+// the launch that follows (set_rows_launch).  Synchronises (decide_balance, find_giant_rows).
+int shape_rows(Plan& p) {
+    p.lanes_per_row = pick_lanes_per_row(p.nnz - p.nnz_begin, p.n_rows, p.elems_per_lane);
+    const int t = p.knob.lanes;                                // tuning knob
+    if (t == 2 || t == 4 || t == 8 || t == 16 || t == 32 || t == 64) p.lanes_per_row = t;
+    // LIGHT's chunks: VECTOR's size unless its knob divides them (halving them cost 6 % on the S32-band target: the
+    // window of x is staged per chunk), never below one pass of the workgroup
+    const int div = p.kind == MI355_KIND_LIGHT ? p.knob.light_chunk_div : 0;
+    shape_chunks(p, div > 0 ? div : 1);
+    if (const int st = decide_balance(p)) return st;   // heaviest uniform chunk vs the mean
+    if (p.balanced) {   // weight-cut chunks are sized for 256 threads, the window for the rows a chunk may hold
+        p.block_threads = kBlock;
+        p.window_bytes = kWindowBytes;
+        p.window_elems = pick_window_elems(p, p.rows_cap);
+        if (p.n_seg >= 2) { p.window_elems = 0; p.n_seg = 0; }   // (the multi-band plan is sized for uniform chunks)
+    }
+    shape_sweep(p);
+    if (const int st = find_giant_rows(p)) return st;   // balanced plans: rows too long for one workgroup
+    // a small, regular matrix: the plain one-pass kernel (common.hpp, kSmallPlainNnz)
+    if (p.knob.small != 0 && p.knob.plain == 0 && !p.balanced && !p.sweep && p.n_giant == 0 && p.n_rows > 0 &&
+        (p.nnz - p.nnz_begin) <= kSmallPlainNnz) {
+        const int64_t mean = (p.nnz - p.nnz_begin) / p.n_rows;
+        // lanes per row: two 4-byte elements per lane and row up to 32 per row, four beyond (measured: 32 per row 16 lanes
+        // over 8 and 32; 64 per row 16 lanes over 32 and 64)
+        const int64_t per_lane = mean <= 32 ? 2 : 4;
+        int lanes = 2;
+        while (lanes < kWave && per_lane * lanes < mean) lanes *= 2;
+        p.small_plain = true;
+        p.lanes_per_row = lanes;
+        p.block_threads = kBlock;
+    }
+    set_rows_launch(p);
+    return MI355_SPMV_OK;
 }
 
 // Rows per workgroup for which the plan's bands fit the window exactly:

@@ -113,16 +113,12 @@ static int execute_typed(Plan& p, const void* Ax, const void* x, void* y, hipStr
     const val_t* xx = static_cast<const val_t*>(x);
     val_t* yy = static_cast<val_t*>(y);
     switch (p.kind) {
-        case MI355_KIND_VECTOR: return launch_vector<off_t, val_t>(p, Ap, ax, xx, yy, s);
+        case MI355_KIND_VECTOR: return launch_rows<VectorRows, off_t, val_t>(p, Ap, ax, xx, yy, s);
         case MI355_KIND_MERGE:
             if constexpr (sizeof(val_t) == 8)
                 if (p.mat_type == MI355_VAL_F32) return launch_merge<off_t, val_t, float>(p, Ap, static_cast<const float*>(Ax), xx, yy, s);
             return launch_merge<off_t, val_t, val_t>(p, Ap, ax, xx, yy, s);
-        case MI355_KIND_LIGHT:
-            // (a small regular matrix: handing rows out costs more than summing them — the plain one-pass kernel of the
-            // VECTOR kind, plan_create_impl; light's own dequeueing fallback took 29-133 us where this takes 3-6)
-            if (p.small_plain) return launch_vector<off_t, val_t>(p, Ap, ax, xx, yy, s);
-            return launch_light<off_t, val_t>(p, Ap, ax, xx, yy, s);
+        case MI355_KIND_LIGHT: return launch_rows<LightRows, off_t, val_t>(p, Ap, ax, xx, yy, s);
     }
     set_error("unknown kind %d", p.kind);
     return MI355_SPMV_EINVAL;
@@ -374,54 +370,16 @@ static int plan_create_impl(mi355_spmv_plan** out, int kind, int off_type, int v
         p.n_chunks = p.balanced ? blk->n_chunks
                                 : (p.rows_per_chunk > 0 ? (int64_t(n_rows) + p.rows_per_chunk - 1) / p.rows_per_chunk : 0);
         if (p.n_chunks < 1) p.n_chunks = 1;
-        p.n_kernels = 1;
-        if (kind == MI355_KIND_VECTOR) block_grid_vector(p); else block_grid_light(p);
-        if (p.small_plain) {      // (what execute launches for it: the whole plan's plain kernel over this block's rows)
-            p.window_elems = 0;
-            p.n_seg = 0;
-            p.grid_blocks = (int64_t(p.n_rows) + kBlock / p.lanes_per_row - 1) / (kBlock / p.lanes_per_row);
-            snprintf(p.main_kernel, sizeof(p.main_kernel), "csr_vector_kernel");
-        }
         const int st2 = find_giant_rows(p);
         if (st2 != MI355_SPMV_OK) { delete h; return st2; }
-        if (p.n_giant > 0) p.n_kernels = 3;
+        set_rows_launch(p);
     } else {
-        {
-            const int st = probe_structure(p);   // one tiny kernel + one 16-byte copy (synchronises)
-            if (st != MI355_SPMV_OK) { delete h; return st; }
+        int st = probe_structure(p);             // one tiny kernel + one 16-byte copy (synchronises)
+        if (st == MI355_SPMV_OK) {
+            if (kind == MI355_KIND_MERGE) shape_merge(p);
+            else st = shape_rows(p);             // (synchronises)
         }
-        switch (kind) {
-            case MI355_KIND_VECTOR: shape_vector(p); break;
-            case MI355_KIND_MERGE:  shape_merge(p); break;
-            case MI355_KIND_LIGHT:  shape_light(p); break;
-        }
-        if (kind == MI355_KIND_VECTOR || kind == MI355_KIND_LIGHT) {
-            const int st = decide_balance(p);    // heaviest uniform chunk vs the mean (synchronises)
-            if (st != MI355_SPMV_OK) { delete h; return st; }
-            if (kind == MI355_KIND_VECTOR) { reshape_vector_balanced(p); shape_sweep(p); }
-            else { reshape_light_balanced(p); if (shape_sweep(p)) reshape_light_sweep(p); }
-            const int st2 = find_giant_rows(p);  // balanced plans: rows too long for one workgroup (synchronises)
-            if (st2 != MI355_SPMV_OK) { delete h; return st2; }
-            if (p.n_giant > 0) p.n_kernels = 3;
-        }
-        // a small, regular matrix: the plain one-pass kernel (common.hpp, kSmallPlainNnz); two 4-byte elements per lane and row
-        if ((kind == MI355_KIND_VECTOR || kind == MI355_KIND_LIGHT) && !blk && p.knob.small != 0 && p.knob.plain == 0 && !p.balanced && !p.sweep &&
-            p.n_giant == 0 && p.n_rows > 0 && (p.nnz - p.nnz_begin) <= kSmallPlainNnz) {
-            const int64_t mean = (p.nnz - p.nnz_begin) / p.n_rows;
-            // lanes per row: two 4-byte elements per lane and row up to 32 per row, four beyond (measured: 32 per row 16 lanes
-            // over 8 and 32; 64 per row 16 lanes over 32 and 64)
-            const int64_t per_lane = mean <= 32 ? 2 : 4;
-            int t = 2;
-            while (t < kWave && per_lane * t < mean) t *= 2;
-            p.small_plain = true;
-            p.lanes_per_row = t;
-            p.block_threads = kBlock;
-            p.window_elems = 0;
-            p.n_seg = 0;
-            p.grid_blocks = (int64_t(p.n_rows) + kBlock / t - 1) / (kBlock / t);
-            p.n_kernels = 1;
-            snprintf(p.main_kernel, sizeof(p.main_kernel), "csr_vector_kernel");
-        }
+        if (st != MI355_SPMV_OK) { delete h; return st; }
     }
     int st = plan_alloc_scratch(p);
     if (st == MI355_SPMV_OK) st = build_chunk_table(p);

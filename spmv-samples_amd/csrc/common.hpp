@@ -25,6 +25,11 @@ inline int64_t giant_slice_for(int64_t giant_len) {
 }
 constexpr int kWideBlock = 512;      // VECTOR / LIGHT on big uniform matrices: 8 waves, chunks twice as long
 constexpr int kHugeBlock = 1024;     // VECTOR, band too wide for two workgroups per CU: ONE 16-wave workgroup with ~150 KB of LDS
+// Rows a vector of the chunked VECTOR / LIGHT kernels keeps in flight: 4, or 2 for fp64 and for fp32 with 16 or more lanes
+// per row (rows of 33+ nonzeros) — a long row keeps its lanes' loads busy by itself, and the body then needs ~95 VGPRs
+// instead of ~135 (four 256-thread workgroups per CU instead of three: what a small matrix's single round of chunks is
+// sized for).  The plan's chunks (analyze.hip, shape_chunks) and the kernel launched (row_launch.hpp) both follow it.
+constexpr int rows_in_flight(size_t val_bytes, int lanes_per_row) { return (val_bytes == 4 && lanes_per_row < 16) ? 4 : 2; }
 constexpr int kSweepRows = 4;        // rows a vector of the sweep kernel holds at least (its whole chunk stays in registers)
 // ... and 8 for fp32 where a chunk of 8 rows per vector stays within the 2 048 rows a chunk may have (T >= 4): the
 // same window passes then serve twice the nonzeros — staging the band, not the Aj / Ax stream, is what a swept chunk
@@ -189,7 +194,7 @@ struct Plan {
     unsigned long long* counters;  // LIGHT: kXcds shards, one 128-B line each
     bool light_dequeue_once;       // LIGHT, equal-row chunks: one workgroup and one dequeue per chunk (else by index)
     int n_kernels;
-    bool small_plain = false;   // VECTOR / LIGHT: a matrix small enough for the plain one-pass kernel to win (capi.hip, plan_create_impl)
+    bool small_plain = false;   // VECTOR / LIGHT: a matrix small enough for the plain one-pass kernel to win (analyze.hip, shape_rows)
     char main_kernel[64];
 };
 
@@ -197,33 +202,27 @@ struct Plan {
 // (gfx950: up to 160 KB per workgroup).  Remembered per kernel, so the call happens once.
 int allow_dynamic_lds(const void* kernel, size_t bytes);
 
-// kernel launchers (one translation unit per kind)
-template <typename off_t, typename val_t>
-int launch_vector(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s);
+// kernel launchers.  VECTOR / LIGHT: one launch path (row_launch.hpp) over each kind's kernels, instantiated in the
+// kind's translation units for its traits type (csr_vector.hip, light_rows.hip)
+struct VectorRows;
+struct LightRows;
+template <typename Kind, typename off_t, typename val_t>
+int launch_rows(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s);
+template <typename off_t, typename val_t>   // the plain CSR-vector kernel (small matrices of either kind)
+int launch_vector_plain(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s);
 template <typename off_t, typename val_t, typename mat_t>
 int launch_merge(Plan& p, const off_t* Ap, const mat_t* Ax, const val_t* x, val_t* y, hipStream_t s);
-template <typename off_t, typename val_t>
-int launch_light(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s);
 
 int merge_compute_coords(Plan& p);   // MERGE: run the search kernel now (null stream, synchronises)
 int probe_structure(Plan& p);
 int pick_window_elems(Plan& p, int64_t rows_per_workgroup);
 int64_t segment_rows_fit(const Plan& p);
-void shape_chunks(Plan& p, int rows_in_flight, int64_t chunk_div, bool allow_wide, bool allow_huge = false);
-bool shape_sweep(Plan& p);   // VECTOR / LIGHT: band wider than any window, after decide_balance (analyze.hip)   // VECTOR / LIGHT: block size, chunk, window
-int workgroups_per_cu_by_registers(const Plan& p);   // VECTOR / LIGHT: what the kernels' launch bounds allow
 int long_steps_for(const Plan& p);   // steps of its vector after which a row is left to the long-row pass
-int decide_balance(Plan& p);       // VECTOR / LIGHT, after shape_*: uniform or nnz-balanced chunks
 int build_chunk_table(Plan& p);    // after the scratch is allocated
 int find_giant_rows(Plan& p);      // balanced plans: rows beyond kGiantRow nonzeros (synchronises)
-void shape_vector(Plan& p);
 void shape_merge(Plan& p);
-void shape_light(Plan& p);
-void reshape_vector_balanced(Plan& p);
-void reshape_light_balanced(Plan& p);
-void block_grid_vector(Plan& p);   // row-block plans: grid / names from the inherited shape and the block's n_chunks
-void block_grid_light(Plan& p);
-void reshape_light_sweep(Plan& p);   // LIGHT: after shape_sweep said yes
+int shape_rows(Plan& p);           // VECTOR / LIGHT, whole plans: the shape, then set_rows_launch (synchronises)
+void set_rows_launch(Plan& p);     // VECTOR / LIGHT: kernel, grid and kernel count from the plan's shape
 // nnz-balanced cuts on the plan's chunk boundaries (analyze.hip; reads Ap on the device, synchronises)
 int partition_plan(const Plan& p, int parts, int64_t* row_cuts, int64_t* chunk_cuts, int64_t* nnz_cuts);
 

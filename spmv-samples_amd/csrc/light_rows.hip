@@ -39,7 +39,7 @@
 
 #include "common.hpp"
 #include "row_dot.hpp"
-#include "giant_rows.hpp"
+#include "row_launch.hpp"
 #include "xwindow.hpp"
 
 namespace mi355 {
@@ -333,240 +333,37 @@ __global__ __launch_bounds__(kHugeBlock, 4) void light_rows_sweep_kernel(
     if (!static_mode) light_leave(counters);
 }
 
-template <typename val_t> constexpr int light_rows_in_flight() { return sizeof(val_t) == 4 ? 4 : 2; }
-
-#ifndef MI355_TU_F64   // the host-side shape functions live in the fp32 translation unit only
-static int64_t light_resident(const Plan& p, int64_t rows) {
-    // persistent grid = what stays resident on a CU: bounded by LDS (160 KB: the chunk's layout + ~1 KB static)
-    // and by registers (3 workgroups of 256 threads, 2 of 512).  Asking for more than fits leaves the surplus
-    // workgroups to start when the others have finished everything (4 asked / 3 resident: 207 vs 200 us).
-    if (p.knob.light_blocks_per_cu > 0) return int64_t(kCus) * p.knob.light_blocks_per_cu;
-    const size_t val_bytes = p.val_type == MI355_VAL_F64 ? 8 : 4;
-    const size_t lds = chunk_lds_bytes(p.window_elems, int(rows), val_bytes) + 1024;
-    int64_t per_cu = int64_t(160 * 1024 / lds);
-    // registers: the kernels are bounded to 3 waves per SIMD (256 threads) / 4 (512 threads), see the kernel
-    const int64_t reg_bound = workgroups_per_cu_by_registers(p);
-    if (per_cu > reg_bound) per_cu = reg_bound;
-    if (per_cu < 1) per_cu = 1;
-    return int64_t(kCus) * per_cu;
-}
-
-// Workgroups to launch: a persistent grid (what stays resident) that dequeues chunks when there are several
-// chunks per workgroup to balance; one workgroup per chunk, taken by index, when there are at most two per slot
-// (the dequeue — two dependent atomics and a poll per workgroup — then costs more than it can balance away).
-static int64_t light_grid(const Plan& p, int64_t n_chunks, int64_t resident) {
-    // equal-row chunks: one workgroup (and one dequeue) per chunk; weight-cut chunks: the persistent grid
-    int64_t blocks = (!p.balanced || n_chunks <= 2 * resident) ? n_chunks : resident;
-    return blocks < 1 ? 1 : blocks;
-}
-// equal-row chunks: take the chunk by index (no counter) when there are at most two per workgroup slot
-static bool light_dequeue_once(const Plan& p, int64_t n_chunks, int64_t resident) {
-    return !p.balanced && n_chunks > 2 * resident;
-}
-
-void shape_light(Plan& p) {
-    p.lanes_per_row = pick_lanes_per_row(p.nnz - p.nnz_begin, p.n_rows, p.elems_per_lane);
-    const int R = p.val_type == MI355_VAL_F64 ? light_rows_in_flight<double>() : light_rows_in_flight<float>();
-    {                                                          // tuning knob (as the CSR-vector kind)
-        const int t = p.knob.lanes;
-        if (t == 2 || t == 4 || t == 8 || t == 16 || t == 32 || t == 64) p.lanes_per_row = t;
+// LIGHT's kernels for the launch path it shares with VECTOR (row_launch.hpp): chunks handed out by the counters
+struct LightRows {
+    static constexpr const char* name = "light_rows";
+    static constexpr bool kCounters = true;
+    static constexpr bool kPlainKnob = false;
+    template <int BLOCK, int T, int R, int NSEG, bool ADAPT, typename val_t>
+    static auto window() { return light_rows_window_kernel<BLOCK, T, R, NSEG, ADAPT, val_t>; }
+    template <int T, int R, typename val_t>
+    static auto sweep() { return light_rows_sweep_kernel<T, R, val_t>; }
+    // unaligned operands: light_rows_kernel on the plan's grid, a dequeue of rows_per_chunk rows per wave
+    template <typename off_t, typename val_t>
+    static int plain(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s) {
+        return with_lanes(p, name, [&](auto lanes) -> int {
+            constexpr int T = decltype(lanes)::value;
+            hipLaunchKernelGGL((light_rows_kernel<T, off_t, val_t>), dim3((unsigned)p.grid_blocks), dim3(kBlock), 0, s, p.n_rows,
+                               (off_t)p.nnz, Ap, p.Aj, Ax, x, y, p.counters, (int32_t)p.rows_per_chunk, (val_t)p.alpha,
+                               (val_t)p.beta);
+            MI355_HIP_TRY(hipGetLastError());
+            return MI355_SPMV_OK;
+        });
     }
-    const int div = p.knob.light_chunk_div;
-    // chunks: the static kind's size (halving them cost 6 % on the S32-band target: the
-    // window of x is staged per chunk), never below one pass of the workgroup
-    shape_chunks(p, R, div > 0 ? div : 1, true, true);
-    p.n_tiles = (int64_t(p.n_rows) + p.rows_per_chunk - 1) / p.rows_per_chunk;
-    p.grid_blocks = light_grid(p, p.n_tiles, light_resident(p, p.rows_per_chunk));
-    p.light_dequeue_once = light_dequeue_once(p, p.n_tiles, light_resident(p, p.rows_per_chunk));
-    p.n_kernels = 1;
-    snprintf(p.main_kernel, sizeof(p.main_kernel), "light_rows_window_kernel");
-}
-
-// after decide_balance: the persistent grid is sized by the chunks there are, window by the rows a chunk may hold
-void reshape_light_balanced(Plan& p) {
-    if (!p.balanced) return;
-    p.n_tiles = p.n_chunks;
-    p.block_threads = kBlock;          // (weight-cut chunks are sized for 256 threads)
-    p.window_bytes = kWindowBytes;
-    p.window_elems = pick_window_elems(p, p.rows_cap);
-    if (p.n_seg >= 2) { p.window_elems = 0; p.n_seg = 0; }
-    p.grid_blocks = light_grid(p, p.n_chunks, light_resident(p, p.rows_cap));
-    p.light_dequeue_once = false;
-}
-
-void block_grid_light(Plan& p) {
-    p.n_tiles = p.n_chunks;
-    const int64_t resident = p.sweep ? int64_t(kCus) : light_resident(p, p.balanced ? p.rows_cap : p.rows_per_chunk);
-    p.grid_blocks = light_grid(p, p.n_chunks, resident);
-    p.light_dequeue_once = light_dequeue_once(p, p.n_chunks, resident);
-    snprintf(p.main_kernel, sizeof(p.main_kernel), p.sweep ? "light_rows_sweep_kernel" : "light_rows_window_kernel");
-}
-
-// after shape_sweep said yes (analyze.hip): one workgroup per chunk, one per CU resident
-void reshape_light_sweep(Plan& p) {
-    if (!p.sweep) return;
-    block_grid_light(p);
-}
-
-#endif  // MI355_TU_F64
-
-template <int BLOCK, typename val_t>
-static int launch_light_window(const Plan& p, const ApView Ap, const val_t* Ax, const val_t* x, val_t* y,
-                               hipStream_t s) {
-    if constexpr (BLOCK >= kWideBlock) {
-        // (see launch_vector_window: no 512- / 1 024-thread kernel without ONE window of x)
-        if (p.window_elems <= 0 || p.n_seg >= 2) return launch_light_window<kBlock, val_t>(p, Ap, Ax, x, y, s);
-    }
-    constexpr int R = light_rows_in_flight<val_t>();
-    const BandHint hint{p.band_lo, p.band_hi, p.window_from_band};
-    const dim3 grid((unsigned)p.grid_blocks), block(BLOCK);
-    const int64_t nnz = p.nnz_read;
-    const ChunkMap cmap{p.balanced ? p.chunk_row : nullptr, (int32_t)p.rows_per_chunk, (int32_t)p.rows_cap, p.n_chunks,
-                        long_steps_for(p), p.n_giant > 0 ? p.giant_len : int64_t(0),
-                        p.knob.rel32_limit > 0 ? p.knob.rel32_limit : kRel32Limit,
-                        p.light_dequeue_once ? 1 : 0};
-    const size_t lds = chunk_lds_bytes(p.window_elems, p.rows_cap, sizeof(val_t));
-    SegmentPlan segs;
-    segs.n = p.n_seg;
-    for (int i = 0; i < kMaxSegments; ++i) { segs.lo[i] = p.seg_lo[i]; segs.hi[i] = p.seg_hi[i]; }
-#define MI355_LIGHT_ARGS s, p.n_rows, p.n_cols, nnz, Ap, p.Aj, Ax, x, y, p.counters, cmap, (int32_t)p.window_elems, hint, segs, (val_t)p.alpha, (val_t)p.beta
-    // rows a vector keeps in flight: fp32 with 16 or more lanes per row (rows of 33+ nonzeros) runs with 2 instead of
-    // 4 - a long row keeps its lanes' loads busy by itself, and the body then needs ~95 VGPRs instead of ~135 (four
-    // 256-thread workgroups per CU instead of three: what a small matrix's single round of chunks is sized for)
-    constexpr auto wide_r = [](int tt) constexpr { return (sizeof(val_t) == 4 && tt >= 16) ? 2 : R; };
-#define MI355_LIGHT_LAUNCH(TT, NSEG_, ADAPT_)                                                                  \
-    do {                                                                                                       \
-        if (const int st = allow_dynamic_lds((const void*)light_rows_window_kernel<BLOCK, TT, (wide_r(TT)), NSEG_, ADAPT_, val_t>, lds)) return st; \
-        hipLaunchKernelGGL((light_rows_window_kernel<BLOCK, TT, (wide_r(TT)), NSEG_, ADAPT_, val_t>), grid, block, lds, MI355_LIGHT_ARGS); \
-    } while (0)
-#define MI355_LIGHT_CASE(TT)                                                                                   \
-    case TT:                                                                                                   \
-        if (p.window_elems > 0 && p.n_seg >= 2) {                                                              \
-            /* (several bands: shape_chunks keeps those plans on 256 threads) */                               \
-            if constexpr (BLOCK == kBlock) MI355_LIGHT_LAUNCH(TT, kMaxSegments, false);                        \
-            else { set_error("light_rows: no 512-thread kernel for a multi-band window"); return MI355_SPMV_EINVAL; } \
-        }                                                                                                      \
-        else if (p.window_elems > 0) MI355_LIGHT_LAUNCH(TT, 1, false);                                         \
-        else if constexpr (BLOCK == kBlock) MI355_LIGHT_LAUNCH(TT, 0, false);                                  \
-        break;
-    if constexpr (BLOCK == kBlock) if (p.balanced) {   // vector width per chunk (chunk_rows_any); the T of the template is not used
-        // (the weight-cut layout holds up to 2 K rows of bounds and results next to the window: may pass 64 KB)
-        if (p.window_elems > 0) MI355_LIGHT_LAUNCH(2, 1, true);
-        else MI355_LIGHT_LAUNCH(2, 0, true);
-        MI355_HIP_TRY(hipGetLastError());
-        return p.off_type == MI355_OFF_I64
-                   ? launch_giant_rows<int64_t, val_t>(p, static_cast<const int64_t*>(Ap.p), Ax, x, y, s)
-                   : launch_giant_rows<int32_t, val_t>(p, static_cast<const int32_t*>(Ap.p), Ax, x, y, s);   // (rows too long for one workgroup, if any)
-    }
-    switch (p.lanes_per_row) {
-        MI355_LIGHT_CASE(2)
-        MI355_LIGHT_CASE(4)
-        MI355_LIGHT_CASE(8)
-        MI355_LIGHT_CASE(16)
-        MI355_LIGHT_CASE(32)
-        MI355_LIGHT_CASE(64)
-        default:
-            set_error("light_rows: bad lanes_per_row %d", p.lanes_per_row);
-            return MI355_SPMV_EINVAL;
-    }
-#undef MI355_LIGHT_CASE
-#undef MI355_LIGHT_LAUNCH
-    MI355_HIP_TRY(hipGetLastError());
-    return MI355_SPMV_OK;
-}
-
-template <typename val_t>
-static int launch_light_sweep(const Plan& p, const ApView Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s) {
-    const BandHint hint{p.band_lo, p.band_hi, true};
-    const dim3 grid((unsigned)p.grid_blocks), block(kHugeBlock);
-    const size_t lds = chunk_lds_bytes(p.window_elems, p.rows_cap, sizeof(val_t));
-    const ChunkMap cmap{nullptr, (int32_t)p.rows_per_chunk, (int32_t)p.rows_cap, p.n_chunks, 0, int64_t(0),
-                        p.knob.rel32_limit > 0 ? p.knob.rel32_limit : kRel32Limit, p.light_dequeue_once ? 1 : 0};
-    const int64_t vectors = kHugeBlock / p.lanes_per_row;     // (rows a vector holds: 4, or 8 in fp32 — csr_vector.hip, sweep_rows_for)
-    const int held = int(p.rows_per_chunk / vectors);
-    constexpr bool kHasEight = sizeof(val_t) == 4;
-    if (p.rows_per_chunk != vectors * held || !(held == kSweepRows || (kHasEight && held == 8 && p.lanes_per_row >= 4)) ||
-        p.rows_cap < p.rows_per_chunk || p.window_elems < int(kHugeBlock * 16 / sizeof(val_t))) {
-        set_error("light_rows: sweep plan with %lld rows per chunk at %d lanes per row", (long long)p.rows_per_chunk, p.lanes_per_row);
-        return MI355_SPMV_EINVAL;
-    }
-#define MI355_LIGHT_SWEEP(TT, RR)                                                                              \
-    do {                                                                                                       \
-        if (const int st = allow_dynamic_lds((const void*)light_rows_sweep_kernel<TT, RR, val_t>, lds)) return st; \
-        hipLaunchKernelGGL((light_rows_sweep_kernel<TT, RR, val_t>), grid, block, lds, s, p.n_rows, p.n_cols, p.nnz_read, Ap, \
-                           p.Aj, Ax, x, y, p.counters, cmap, (int32_t)p.window_elems, hint, (val_t)p.alpha, (val_t)p.beta); \
-    } while (0)
-#define MI355_LIGHT_CASE(TT)                                                                                   \
-    case TT:                                                                                                   \
-        if constexpr (kHasEight && TT >= 4) { if (held == 8) { MI355_LIGHT_SWEEP(TT, 8); break; } }             \
-        MI355_LIGHT_SWEEP(TT, kSweepRows);                                                                     \
-        break;
-    switch (p.lanes_per_row) {
-        MI355_LIGHT_CASE(2)
-        MI355_LIGHT_CASE(4)
-        MI355_LIGHT_CASE(8)
-        MI355_LIGHT_CASE(16)
-        MI355_LIGHT_CASE(32)
-        MI355_LIGHT_CASE(64)
-        default:
-            set_error("light_rows: bad lanes_per_row %d", p.lanes_per_row);
-            return MI355_SPMV_EINVAL;
-    }
-#undef MI355_LIGHT_CASE
-    MI355_HIP_TRY(hipGetLastError());
-    return MI355_SPMV_OK;
-}
-
-template <typename off_t, typename val_t>
-static int launch_light_plain(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y,
-                              hipStream_t s) {
-    const dim3 grid((unsigned)p.grid_blocks), block(kBlock);
-    const off_t nnz = (off_t)p.nnz;
-    const int32_t chunk = (int32_t)p.rows_per_chunk;
-#define MI355_LIGHT_CASE(TT)                                                                          \
-    case TT:                                                                                          \
-        hipLaunchKernelGGL((light_rows_kernel<TT, off_t, val_t>), grid, block, 0, s, p.n_rows, nnz, Ap, \
-                           p.Aj, Ax, x, y, p.counters, chunk, (val_t)p.alpha, (val_t)p.beta);         \
-        break;
-    switch (p.lanes_per_row) {
-        MI355_LIGHT_CASE(2)
-        MI355_LIGHT_CASE(4)
-        MI355_LIGHT_CASE(8)
-        MI355_LIGHT_CASE(16)
-        MI355_LIGHT_CASE(32)
-        MI355_LIGHT_CASE(64)
-        default:
-            set_error("light_rows: bad lanes_per_row %d", p.lanes_per_row);
-            return MI355_SPMV_EINVAL;
-    }
-#undef MI355_LIGHT_CASE
-    MI355_HIP_TRY(hipGetLastError());
-    return MI355_SPMV_OK;
-}
-
-template <typename off_t, typename val_t>
-int launch_light(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s) {
-    if (p.n_rows == 0) return MI355_SPMV_OK;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(p.Aj) | reinterpret_cast<uintptr_t>(Ax) |
-                           reinterpret_cast<uintptr_t>(x)) & 15u) == 0;
-    if (aligned && p.nnz >= 4) {
-        const ApView view{Ap, sizeof(off_t) == 8 ? 1 : 0};
-        if (p.sweep) return launch_light_sweep<val_t>(p, view, Ax, x, y, s);
-        return p.block_threads == kHugeBlock   ? launch_light_window<kHugeBlock, val_t>(p, view, Ax, x, y, s)
-               : p.block_threads == kWideBlock ? launch_light_window<kWideBlock, val_t>(p, view, Ax, x, y, s)
-                                               : launch_light_window<kBlock, val_t>(p, view, Ax, x, y, s);
-    }
-    return launch_light_plain<off_t, val_t>(p, Ap, Ax, x, y, s);
-}
+};
 
 // One translation unit per value type (light_rows_f64.hip includes this file with MI355_TU_F64).
 #ifdef MI355_TU_PROBE      // (scripts: one kernel instantiated on its own to read its register use quickly)
 #elif !defined(MI355_TU_F64)
-template int launch_light<int32_t, float>(const Plan&, const int32_t*, const float*, const float*, float*, hipStream_t);
-template int launch_light<int64_t, float>(const Plan&, const int64_t*, const float*, const float*, float*, hipStream_t);
+template int launch_rows<LightRows, int32_t, float>(const Plan&, const int32_t*, const float*, const float*, float*, hipStream_t);
+template int launch_rows<LightRows, int64_t, float>(const Plan&, const int64_t*, const float*, const float*, float*, hipStream_t);
 #else
-template int launch_light<int32_t, double>(const Plan&, const int32_t*, const double*, const double*, double*, hipStream_t);
-template int launch_light<int64_t, double>(const Plan&, const int64_t*, const double*, const double*, double*, hipStream_t);
+template int launch_rows<LightRows, int32_t, double>(const Plan&, const int32_t*, const double*, const double*, double*, hipStream_t);
+template int launch_rows<LightRows, int64_t, double>(const Plan&, const int64_t*, const double*, const double*, double*, hipStream_t);
 #endif
 
 }  // namespace mi355
