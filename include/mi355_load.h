@@ -38,6 +38,20 @@ const void* mi355_csr_host_Ap(const mi355_csr_host* csr);
 const int32_t* mi355_csr_host_Aj(const mi355_csr_host* csr);
 const void* mi355_csr_host_Ax(const mi355_csr_host* csr);
 void mi355_csr_host_free(mi355_csr_host* csr);
+
+/* The COO that LoadCoo produces, before ToCsr (main.cu:32-39 runs the two in a row): entries in file order, 0-based,
+ * `symmetric` expanded entry-then-mirror with the diagonal once, pattern values 1.0 — for callers that build the CSR
+ * elsewhere (mi355_spmv_coo_to_csr in include/mi355_spmv.h, on the device).  Same types and error codes as
+ * mi355_load_mtx: off_type only decides which sizes fit.  *out owns the arrays until mi355_load_coo_free.          */
+typedef struct mi355_coo_host mi355_coo_host;
+int mi355_load_mtx_coo(const char* path, int off_type, int val_type, mi355_coo_host** out);
+int mi355_load_coo_dims(const mi355_coo_host* coo, int64_t* n_rows, int64_t* n_cols, int64_t* nnz);
+/* nnz row and column indices (int32) and values (float or double, as loaded): host memory, valid until free        */
+const int32_t* mi355_load_coo_rows(const mi355_coo_host* coo);
+const int32_t* mi355_load_coo_cols(const mi355_coo_host* coo);
+const void* mi355_load_coo_vals(const mi355_coo_host* coo);
+void mi355_load_coo_free(mi355_coo_host* coo);
+
 /* Message of the last failing call on this thread ("" if none).                                                    */
 const char* mi355_load_last_error(void);
 

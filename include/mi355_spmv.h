@@ -368,6 +368,27 @@ int mi355_spmv_plan_release(mi355_spmv_plan* plan, int executed_ok);
  * of thread_search.cuh:15-49.                                                  */
 int mi355_spmv_plan_merge_coords(mi355_spmv_plan* plan, int64_t* tile_row, int64_t* tile_nnz);
 
+/* ---- COO -> CSR on the device --------------------------------------------------
+ * The result of the reference's ToCsr (include/load.hpp:420-474), bit for bit: Ap[r] = number of entries whose row
+ * is below r; inside a row the entries keep their input order; duplicates are kept; columns are not sorted.  The
+ * order is the input's, never that of atomics: two calls give identical outputs.
+ *   rows, cols    nnz device int32 indices (any order: file order, an edge list, ...)
+ *   vals          nnz device values of val_type (F32, F64 or I32: only the element size matters), or NULL
+ *   Ap            n_rows + 1 device offsets of off_type;  Aj: nnz int32;  Ax: nnz values, NULL exactly when vals is
+ *   perm          NULL, or nnz int64: perm[k] = the source index of CSR slot k (re-value later: Ax = vals[perm])
+ *   workspace     NULL: *workspace_bytes = the bytes needed, return OK (touches no device, needs no GPU);
+ *                 otherwise device memory of *workspace_bytes >= that many bytes; the call allocates nothing
+ * Sizes follow plan_create: with MI355_OFF_I32 nnz <= INT32_MAX (else EINVAL).  nnz >= 2^32 returns
+ * MI355_SPMV_ENOTSUP (the sort carries 32-bit source indices).  n_rows == 0 and nnz == 0 writes Ap = [0].
+ * Every entry is checked first: a row outside [0, n_rows) or a column outside [0, n_cols) returns MI355_SPMV_EINVAL,
+ * mi355_spmv_last_error() names the first such entry (index, row, col), and no output is written.
+ * The work is enqueued on `stream`, which is then synchronised once (to read the check's result); nothing is kept
+ * between calls.  Kernels and traffic: DESIGN.md §3.7.                                                               */
+int mi355_spmv_coo_to_csr(int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+                          const int32_t* rows, const int32_t* cols, const void* vals,
+                          void* Ap, int32_t* Aj, void* Ax, int64_t* perm,
+                          void* workspace, size_t* workspace_bytes, void* stream);
+
 /* ---- a generalized SpMV whose functor is the CALLER'S code --------------------
  * The reference's SpMV_merge_based_generalized is a template over a functor_t with three static members
  * (include/spmv/merge_genl/merge_genl.cuh:19-38; CPU twin include/spmv/cpu_navie.hpp:20-34)

@@ -40,6 +40,7 @@ EXPORTS = (
                                         "set_alpha_beta", "parts", "cuts", "part_info", "device_y", "device_x",
                                         "destroy")]
     + ["mi355_spmv_functor_" + n for n in ("compile", "compile_log", "spmv", "destroy")]
+    + ["mi355_spmv_coo_to_csr"]
 )
 
 
@@ -136,6 +137,9 @@ def lib():
         L.mi355_spmv_dist_device_x.argtypes = [C.c_void_p, C.c_int]
         L.mi355_spmv_dist_device_x.restype = C.c_void_p
         L.mi355_spmv_dist_destroy.argtypes = [C.c_void_p]
+        L.mi355_spmv_coo_to_csr.argtypes = [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_size_t), C.c_void_p]
         _lib = L
     return _lib
 
@@ -220,6 +224,49 @@ def spmv_genl(semiring, n_rows, n_cols, nnz, Ap, Aj, Ax, x, y, stream=None):
             C.c_void_p(y.data_ptr()), _stream_ptr(stream))
     _check(st, "mi355_spmv_merge_genl_%s_%s" % (o, v))
     return y
+
+
+def coo_to_csr_workspace_bytes(n_rows, nnz, off_dtype=torch.int32, val_dtype=None):
+    """Device workspace mi355_spmv_coo_to_csr needs (the size query: no device is touched)."""
+    ws = C.c_size_t(0)
+    st = lib().mi355_spmv_coo_to_csr(OFF_TYPES[off_dtype][0], VAL_TYPES[val_dtype or torch.float32][0],
+                                     C.c_int32(n_rows), C.c_int32(0), C.c_int64(nnz), None, None, None, None, None,
+                                     None, None, None, C.byref(ws), None)
+    _check(st, "mi355_spmv_coo_to_csr (size query)")
+    return ws.value
+
+
+def coo_to_csr(n_rows, n_cols, rows, cols, vals=None, off_dtype=torch.int32, return_perm=False, stream=None):
+    """COO -> CSR on the device (mi355_spmv_coo_to_csr): the reference's ToCsr result (include/load.hpp:420-474) —
+    entries of a row in input order, duplicates kept, columns not sorted.  rows / cols: int32 device tensors; vals:
+    a float32 / float64 / int32 device tensor or None (then Ax is None).  Returns a synth.Csr, or (Csr, perm) with
+    perm[k] = the source index of CSR slot k (int64) when return_perm.  Synchronises the stream."""
+    from .synth import Csr
+    _require_device(rows, cols, *([vals] if vals is not None else []))
+    if rows.dtype != torch.int32 or cols.dtype != torch.int32:
+        raise TypeError("rows and cols must be int32")
+    nnz = rows.numel()
+    if cols.numel() != nnz or (vals is not None and vals.numel() != nnz):
+        raise ValueError("rows, cols and vals must have the same length")
+    if vals is not None and vals.dtype not in VAL_TYPES:
+        raise TypeError("vals must be float32, float64 or int32")
+    dev = rows.device
+    Ap = torch.empty(n_rows + 1, dtype=off_dtype, device=dev)
+    Aj = torch.empty(nnz, dtype=torch.int32, device=dev)
+    Ax = torch.empty(nnz, dtype=vals.dtype, device=dev) if vals is not None else None
+    perm = torch.empty(nnz, dtype=torch.int64, device=dev) if return_perm else None
+    val_dtype = vals.dtype if vals is not None else torch.float32
+    nbytes = coo_to_csr_workspace_bytes(n_rows, nnz, off_dtype, val_dtype)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    size = C.c_size_t(nbytes)
+    st = lib().mi355_spmv_coo_to_csr(OFF_TYPES[off_dtype][0], VAL_TYPES[val_dtype][0], C.c_int32(n_rows),
+                                     C.c_int32(n_cols), C.c_int64(nnz), ptr(rows), ptr(cols), ptr(vals), ptr(Ap),
+                                     ptr(Aj), ptr(Ax), ptr(perm), C.c_void_p(ws.data_ptr()), C.byref(size),
+                                     _stream_ptr(stream))
+    _check(st, "mi355_spmv_coo_to_csr")
+    csr = Csr(n_rows, n_cols, nnz, Ap, Aj, Ax, "coo_to_csr", {"synthetic": False})
+    return (csr, perm) if return_perm else csr
 
 
 class Plan:

@@ -1,0 +1,367 @@
+// coo_csr.hip — COO -> CSR on the device with the result of the reference's ToCsr (include/load.hpp:420-474; the
+// product's host twin is host/load.hpp ToCsr): Ap[r] = entries whose row is below r, entries of a row in their input
+// order, duplicates kept, columns not sorted.  mi355_spmv_coo_to_csr (include/mi355_spmv.h) is the entry point.
+//
+// The row is the key of an LSD radix sort with the source index as its payload; the sort is stable, so the sorted
+// payload is the CSR slot -> source index map (`perm`) and everything else is a gather through it.  Per pass of
+// 8 bits (ceil(bit_width(n_rows - 1) / 8) passes: 0 for one row, 3 up to 2^24 rows) it is reduce-then-scan:
+//   count_digits  each tile counts its 256 digits                          -> counts[digit][tile]
+//   scan_*        an exclusive scan over that array, digit-major            -> where (digit, tile) starts
+//   scatter       stable ranks inside the tile, the tile in digit order in LDS, then key and payload to their places
+// Every kernel finishes on its own: no workgroup waits for another (no look-back, no grid barrier).  Stable ranks:
+// the four waves of a tile each walk a contiguous quarter in steps of 64 entries, so (wave, step, lane) is source
+// order; the lanes of one step that share a digit are found with 8 ballots, a lane's rank among them is the popcount
+// of the peers below it, and a running count per (wave, digit) in LDS carries it from step to step.  No atomics: the
+// order in which they land cannot reach the result.
+//
+// Validation runs first and records the smallest entry whose row or column is out of range; every later kernel reads
+// that word and returns at once if it is set, so no index that failed the check is ever used as an address and the
+// caller's output buffers are not written.
+#include "common.hpp"
+
+namespace mi355 {
+namespace coo {
+
+constexpr int kSteps = 16;                        // 64-entry steps a wave walks per tile
+constexpr int kTile = kBlock * kSteps;             // 4 096 entries per tile
+constexpr int kScanItems = 16;                     // counts a thread of the scan kernels sums
+constexpr int kScanChunk = kBlock * kScanItems;   // counts per workgroup of the scan kernels
+constexpr unsigned long long kNoBad = ~0ull;
+
+constexpr size_t align_up(size_t v) { return (v + 255) / 256 * 256; }
+
+inline int radix_passes(int32_t n_rows) {
+    int bits = 0;
+    for (uint32_t m = n_rows > 1 ? uint32_t(n_rows - 1) : 0u; m; m >>= 1) ++bits;
+    return (bits + 7) / 8;
+}
+
+// Workspace: the validation word, two key and two payload buffers (one of each for a single pass), the tile counts
+// and the scan's per-workgroup sums.
+struct Layout {
+    int passes = 0;
+    uint64_t n_tiles = 0, n_counts = 0, n_scan_blocks = 0;
+    size_t o_keys[2] = {0, 0}, o_pay[2] = {0, 0}, o_counts = 0, o_bsum = 0, bytes = 0;
+};
+
+inline Layout layout(int32_t n_rows, uint64_t nnz) {
+    Layout L;
+    L.passes = nnz ? radix_passes(n_rows) : 0;
+    size_t off = 256;   // the validation word
+    if (L.passes > 0) {
+        L.n_tiles = (nnz + kTile - 1) / kTile;
+        L.n_counts = 256 * L.n_tiles;
+        L.n_scan_blocks = (L.n_counts + kScanChunk - 1) / kScanChunk;
+        const int bufs = L.passes > 1 ? 2 : 1;
+        for (int b = 0; b < bufs; ++b) {
+            L.o_keys[b] = off; off = align_up(off + 4 * nnz);
+            L.o_pay[b] = off;  off = align_up(off + 4 * nnz);
+        }
+        L.o_counts = off; off = align_up(off + 4 * L.n_counts);
+        L.o_bsum = off;   off = align_up(off + 4 * L.n_scan_blocks);
+    }
+    L.bytes = off;
+    return L;
+}
+
+__global__ void __launch_bounds__(kBlock) validate(const int32_t* __restrict__ rows, const int32_t* __restrict__ cols,
+                                                   uint64_t nnz, uint32_t n_rows, uint32_t n_cols,
+                                                   unsigned long long* bad) {
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    for (uint64_t k = uint64_t(blockIdx.x) * kBlock + threadIdx.x; k < nnz; k += stride)
+        if (uint32_t(rows[k]) >= n_rows || uint32_t(cols[k]) >= n_cols) atomicMin(bad, (unsigned long long)k);
+}
+
+// Digits of one wave's quarter of a tile: cnt[wave][digit] ends as the wave's count of each digit.  With RANKS, rank[s]
+// is the entry's place among the wave's entries of its digit, in source order.  `keys` is the tile's first entry.
+template <bool RANKS>
+__device__ inline void wave_digits(const uint32_t* __restrict__ keys, uint64_t n_left, int shift, uint32_t (*cnt)[256],
+                                   uint32_t* key, uint32_t* rank) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1;
+    const uint64_t first = uint64_t(wave) * kSteps * 64 + lane;
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        const uint64_t i = first + uint64_t(s) * 64;
+        key[s] = i < n_left ? keys[i] : 0u;
+    }
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        const bool valid = first + uint64_t(s) * 64 < n_left;
+        const uint32_t d = (key[s] >> shift) & 255u;
+        unsigned long long peers = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const unsigned long long m = __ballot((d >> b) & 1u);
+            peers &= ((d >> b) & 1u) ? m : ~m;
+        }
+        const uint32_t before = cnt[wave][d];
+        const uint32_t r = uint32_t(__popcll(peers & below));
+        if (RANKS) rank[s] = before + r;
+        // the last of the peers advances the count; every lane has read it above, in this wave's program order
+        if (valid && (peers >> lane) == 1ull) cnt[wave][d] = before + r + 1;
+    }
+}
+
+// Upsweep: counts[digit * n_tiles + tile] = entries of the tile with that digit.
+__global__ void __launch_bounds__(kBlock) count_digits(const uint32_t* __restrict__ keys, uint64_t nnz, int shift,
+                                                       uint64_t n_tiles, uint32_t* __restrict__ counts,
+                                                       const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    __shared__ uint32_t cnt[4][256];
+    for (int i = threadIdx.x; i < 4 * 256; i += kBlock) cnt[i >> 8][i & 255] = 0;
+    __syncthreads();
+    const uint64_t base = uint64_t(blockIdx.x) * kTile;
+    uint32_t key[kSteps];
+    wave_digits<false>(keys + base, nnz - base, shift, cnt, key, nullptr);
+    __syncthreads();
+    const int d = threadIdx.x;
+    counts[uint64_t(d) * n_tiles + blockIdx.x] = cnt[0][d] + cnt[1][d] + cnt[2][d] + cnt[3][d];
+}
+
+// Exclusive scan of `count` per-thread items held in v[], over the workgroup; returns the workgroup total.
+__device__ inline uint32_t block_exclusive_scan(uint32_t* v, int count) {
+    __shared__ uint32_t wave_sum[4];
+    uint32_t own = 0;
+    for (int i = 0; i < count; ++i) { const uint32_t t = v[i]; v[i] = own; own += t; }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) wave_sum[wave] = inc;
+    __syncthreads();
+    uint32_t before = inc - own, total = 0;
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) before += wave_sum[w];
+        total += wave_sum[w];
+    }
+    __syncthreads();   // wave_sum is reused by the next call
+    for (int i = 0; i < count; ++i) v[i] += before;
+    return total;
+}
+
+// Reduce: bsum[b] = sum of the counts of scan workgroup b.
+__global__ void __launch_bounds__(kBlock) scan_reduce(const uint32_t* __restrict__ counts, uint64_t n,
+                                                      uint32_t* __restrict__ bsum, const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    __shared__ uint32_t part[kBlock / 64];
+    const uint64_t base = uint64_t(blockIdx.x) * kScanChunk;
+    uint32_t s = 0;
+    for (int i = 0; i < kScanItems; ++i) {
+        const uint64_t k = base + uint64_t(i) * kBlock + threadIdx.x;
+        if (k < n) s += counts[k];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) bsum[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// One workgroup: exclusive scan of the per-workgroup sums, in place, in chunks with a running carry.
+__global__ void __launch_bounds__(kBlock) scan_sums(uint32_t* bsum, uint64_t n, const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    uint32_t carry = 0;
+    for (uint64_t base = 0; base < n; base += kScanChunk) {
+        uint32_t v[kScanItems];
+        const uint64_t first = base + uint64_t(threadIdx.x) * kScanItems;
+        for (int i = 0; i < kScanItems; ++i) v[i] = first + i < n ? bsum[first + i] : 0u;
+        const uint32_t total = block_exclusive_scan(v, kScanItems);
+        for (int i = 0; i < kScanItems; ++i)
+            if (first + i < n) bsum[first + i] = v[i] + carry;
+        carry += total;
+    }
+}
+
+// Apply: the counts of scan workgroup b become their exclusive prefix, starting at bsum[b].
+__global__ void __launch_bounds__(kBlock) scan_apply(uint32_t* counts, uint64_t n, const uint32_t* __restrict__ bsum,
+                                                     const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    const uint64_t first = uint64_t(blockIdx.x) * kScanChunk + uint64_t(threadIdx.x) * kScanItems;
+    uint32_t v[kScanItems];
+    for (int i = 0; i < kScanItems; ++i) v[i] = first + i < n ? counts[first + i] : 0u;
+    (void)block_exclusive_scan(v, kScanItems);
+    const uint32_t carry = bsum[blockIdx.x];
+    for (int i = 0; i < kScanItems; ++i)
+        if (first + i < n) counts[first + i] = v[i] + carry;
+}
+
+// Downsweep: each entry of the tile goes to start(digit, tile) + entries of that digit before it in the tile.  The
+// tile is first put in digit order in LDS, so that consecutive lanes write consecutive places of a digit's run (a
+// store instruction then touches a few runs, not up to 64 of them).  pay_in == nullptr: the payload is the source
+// index (the first pass).
+__global__ void __launch_bounds__(kBlock) scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ pay_in,
+                                                  uint64_t nnz, int shift, uint64_t n_tiles,
+                                                  const uint32_t* __restrict__ starts, uint32_t* __restrict__ keys_out,
+                                                  uint32_t* __restrict__ pay_out, const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    __shared__ uint32_t cnt[4][256];
+    __shared__ uint32_t digit_at[256];    // where digit d's run starts in the tile, in digit order
+    __shared__ uint32_t digit_out[256];   // ... and in the output
+    __shared__ uint32_t staged_key[kTile], staged_pay[kTile];
+    for (int i = threadIdx.x; i < 4 * 256; i += kBlock) cnt[i >> 8][i & 255] = 0;
+    __syncthreads();
+    const uint64_t base = uint64_t(blockIdx.x) * kTile;
+    const uint64_t n_left = nnz - base;
+    uint32_t key[kSteps], rank[kSteps];
+    wave_digits<true>(keys_in + base, n_left, shift, cnt, key, rank);
+    __syncthreads();
+    {   // cnt[w][d] becomes where wave w's entries of digit d start inside the digit's run
+        const int d = threadIdx.x;
+        uint32_t total = 0;
+        for (int w = 0; w < 4; ++w) { const uint32_t c = cnt[w][d]; cnt[w][d] = total; total += c; }
+        (void)block_exclusive_scan(&total, 1);
+        digit_at[d] = total;
+        digit_out[d] = starts[uint64_t(d) * n_tiles + blockIdx.x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t first = uint64_t(wave) * kSteps * 64 + lane;
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        const uint64_t i = first + uint64_t(s) * 64;
+        if (i < n_left) {
+            const uint32_t d = (key[s] >> shift) & 255u;
+            const uint32_t at = digit_at[d] + cnt[wave][d] + rank[s];
+            staged_key[at] = key[s];
+            staged_pay[at] = pay_in ? pay_in[base + i] : uint32_t(base + i);
+        }
+    }
+    __syncthreads();
+    const uint32_t n_here = n_left < kTile ? uint32_t(n_left) : uint32_t(kTile);
+    for (uint32_t i = threadIdx.x; i < n_here; i += kBlock) {
+        const uint32_t k = staged_key[i];
+        const uint32_t d = (k >> shift) & 255u;
+        const uint32_t dst = digit_out[d] + (i - digit_at[d]);
+        keys_out[dst] = k;
+        pay_out[dst] = staged_pay[i];
+    }
+}
+
+// Ap[r] = first place of a key >= r in the sorted keys (keys == nullptr: every key is 0, one row).
+template <typename off_t>
+__global__ void __launch_bounds__(kBlock) row_offsets(const uint32_t* __restrict__ keys, uint64_t nnz, uint32_t n_rows,
+                                                      off_t* __restrict__ Ap, const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    for (uint64_t r = uint64_t(blockIdx.x) * kBlock + threadIdx.x; r <= n_rows; r += stride) {
+        uint64_t lo = 0, hi = nnz;
+        if (!keys) {
+            lo = r == 0 ? 0 : nnz;
+        } else {
+            while (lo < hi) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (keys[mid] < r) lo = mid + 1; else hi = mid;
+            }
+        }
+        Ap[r] = off_t(lo);
+    }
+}
+
+// Aj[k] = cols[perm[k]], Ax[k] = vals[perm[k]] (elem_t: the value's bits), perm out as int64 if asked for.
+// pay == nullptr: the identity (no pass ran).
+template <typename elem_t>
+__global__ void __launch_bounds__(kBlock) gather(const uint32_t* __restrict__ pay, uint64_t nnz,
+                                                 const int32_t* __restrict__ cols, const elem_t* __restrict__ vals,
+                                                 int32_t* __restrict__ Aj, elem_t* __restrict__ Ax,
+                                                 int64_t* __restrict__ perm, const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    for (uint64_t k = uint64_t(blockIdx.x) * kBlock + threadIdx.x; k < nnz; k += stride) {
+        const uint64_t p = pay ? pay[k] : k;
+        Aj[k] = cols[p];
+        if (Ax) Ax[k] = vals[p];
+        if (perm) perm[k] = int64_t(p);
+    }
+}
+
+inline unsigned grid_for(uint64_t items) {
+    const uint64_t g = (items + kBlock - 1) / kBlock;
+    return unsigned(g < 8192 ? (g ? g : 1) : 8192);
+}
+
+#define MI355_COO_LAUNCH(kernel, grid, ...)                     \
+    do {                                                        \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, __VA_ARGS__); \
+        MI355_HIP_TRY(hipGetLastError());                       \
+    } while (0)
+
+template <typename off_t>
+static int run(const Layout& L, int val_bytes, int32_t n_rows, int32_t n_cols, uint64_t nnz, const int32_t* rows,
+               const int32_t* cols, const void* vals, void* Ap, int32_t* Aj, void* Ax, int64_t* perm, char* ws,
+               hipStream_t s) {
+    auto* bad = reinterpret_cast<unsigned long long*>(ws);
+    MI355_HIP_TRY(hipMemsetAsync(bad, 0xff, sizeof(unsigned long long), s));
+    if (nnz) MI355_COO_LAUNCH(validate, grid_for(nnz), rows, cols, nnz, uint32_t(n_rows), uint32_t(n_cols), bad);
+    const uint32_t* keys = nullptr;
+    const uint32_t* pay = nullptr;
+    uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.o_counts);
+    uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + L.o_bsum);
+    for (int p = 0; p < L.passes; ++p) {
+        const int shift = 8 * p;
+        const uint32_t* keys_in = p == 0 ? reinterpret_cast<const uint32_t*>(rows) : keys;
+        uint32_t* keys_out = reinterpret_cast<uint32_t*>(ws + L.o_keys[p & 1]);
+        uint32_t* pay_out = reinterpret_cast<uint32_t*>(ws + L.o_pay[p & 1]);
+        MI355_COO_LAUNCH(count_digits, unsigned(L.n_tiles), keys_in, nnz, shift, L.n_tiles, counts, bad);
+        MI355_COO_LAUNCH(scan_reduce, unsigned(L.n_scan_blocks), counts, L.n_counts, bsum, bad);
+        MI355_COO_LAUNCH(scan_sums, 1u, bsum, L.n_scan_blocks, bad);
+        MI355_COO_LAUNCH(scan_apply, unsigned(L.n_scan_blocks), counts, L.n_counts, bsum, bad);
+        MI355_COO_LAUNCH(scatter, unsigned(L.n_tiles), keys_in, pay, nnz, shift, L.n_tiles, counts, keys_out, pay_out, bad);
+        keys = keys_out;
+        pay = pay_out;
+    }
+    MI355_COO_LAUNCH(row_offsets<off_t>, grid_for(uint64_t(n_rows) + 1), keys, nnz, uint32_t(n_rows),
+                     static_cast<off_t*>(Ap), bad);
+    if (nnz) {
+        if (val_bytes == 8)
+            MI355_COO_LAUNCH(gather<uint64_t>, grid_for(nnz), pay, nnz, cols, static_cast<const uint64_t*>(vals), Aj,
+                             static_cast<uint64_t*>(Ax), perm, bad);
+        else
+            MI355_COO_LAUNCH(gather<uint32_t>, grid_for(nnz), pay, nnz, cols, static_cast<const uint32_t*>(vals), Aj,
+                             static_cast<uint32_t*>(Ax), perm, bad);
+    }
+    // the one synchronisation: the validation word
+    unsigned long long first_bad = kNoBad;
+    MI355_HIP_TRY(hipMemcpyAsync(&first_bad, bad, sizeof(first_bad), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if (first_bad != kNoBad) {
+        int32_t r = 0, c = 0;
+        MI355_HIP_TRY(hipMemcpy(&r, rows + first_bad, sizeof(r), hipMemcpyDeviceToHost));
+        MI355_HIP_TRY(hipMemcpy(&c, cols + first_bad, sizeof(c), hipMemcpyDeviceToHost));
+        set_error("coo_to_csr: entry %llu is (row %d, col %d), outside the %d x %d matrix", first_bad, r, c, n_rows,
+                  n_cols);
+        return MI355_SPMV_EINVAL;
+    }
+    return MI355_SPMV_OK;
+}
+
+}  // namespace coo
+}  // namespace mi355
+
+extern "C" int mi355_spmv_coo_to_csr(int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+                                     const int32_t* rows, const int32_t* cols, const void* vals, void* Ap, int32_t* Aj,
+                                     void* Ax, int64_t* perm, void* workspace, size_t* workspace_bytes, void* stream) {
+    using namespace mi355;
+    set_error("%s", "");
+    if (off_type != MI355_OFF_I32 && off_type != MI355_OFF_I64) { set_error("coo_to_csr: unknown offset type %d", off_type); return MI355_SPMV_EINVAL; }
+    if (val_type != MI355_VAL_F32 && val_type != MI355_VAL_F64 && val_type != MI355_VAL_I32) { set_error("coo_to_csr: unknown value type %d", val_type); return MI355_SPMV_EINVAL; }
+    if (n_rows < 0 || n_cols < 0 || nnz < 0) { set_error("coo_to_csr: negative size"); return MI355_SPMV_EINVAL; }
+    if (off_type == MI355_OFF_I32 && nnz > INT32_MAX) { set_error("coo_to_csr: nnz does not fit 32-bit offsets (use 64-bit offsets)"); return MI355_SPMV_EINVAL; }
+    if (uint64_t(nnz) >= (1ull << 32)) { set_error("coo_to_csr: 2^32 or more entries (the sort's payload is 32-bit)"); return MI355_SPMV_ENOTSUP; }
+    if (!workspace_bytes) { set_error("coo_to_csr: null workspace_bytes"); return MI355_SPMV_EINVAL; }
+    const coo::Layout L = coo::layout(n_rows, uint64_t(nnz));
+    if (!workspace) { *workspace_bytes = L.bytes; return MI355_SPMV_OK; }
+    if (*workspace_bytes < L.bytes) { set_error("coo_to_csr: workspace of %zu bytes, %zu needed", *workspace_bytes, L.bytes); return MI355_SPMV_EINVAL; }
+    if (!Ap) { set_error("coo_to_csr: null Ap"); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && (!rows || !cols || !Aj)) { set_error("coo_to_csr: null rows, cols or Aj"); return MI355_SPMV_EINVAL; }
+    if ((vals == nullptr) != (Ax == nullptr)) { set_error("coo_to_csr: Ax and vals must be both given or both null"); return MI355_SPMV_EINVAL; }
+    const int val_bytes = val_type == MI355_VAL_F64 ? 8 : 4;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    return off_type == MI355_OFF_I32
+               ? coo::run<int32_t>(L, val_bytes, n_rows, n_cols, uint64_t(nnz), rows, cols, vals, Ap, Aj, Ax, perm, ws, s)
+               : coo::run<int64_t>(L, val_bytes, n_rows, n_cols, uint64_t(nnz), rows, cols, vals, Ap, Aj, Ax, perm, ws, s);
+}

@@ -1,7 +1,9 @@
 """ctypes binding of libmi355load.so (include/mi355_load.h): Matrix Market file -> CSR, through the product loader
-(host/load.hpp: the reference's LoadCoo + ToCsr, include/load.hpp:268-474, main.cu:32-39).  Host code only."""
+(host/load.hpp: the reference's LoadCoo + ToCsr, include/load.hpp:268-474, main.cu:32-39), or -> the COO before
+ToCsr (load_mtx_coo).  Host code only."""
 import ctypes as C
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -11,7 +13,9 @@ from .synth import Csr
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI355_LOAD_LIB") or os.path.join(_HERE, "lib", "libmi355load.so")
 EXPORTS = ["mi355_load_mtx", "mi355_csr_host_dims", "mi355_csr_host_Ap", "mi355_csr_host_Aj", "mi355_csr_host_Ax",
-           "mi355_csr_host_free", "mi355_load_last_error"]
+           "mi355_csr_host_free", "mi355_load_last_error",
+           "mi355_load_mtx_coo", "mi355_load_coo_dims", "mi355_load_coo_rows", "mi355_load_coo_cols",
+           "mi355_load_coo_vals", "mi355_load_coo_free"]
 STATUS = {1: "invalid argument", 2: "not a usable Matrix Market coordinate file", 3: "malformed entry",
           4: "does not fit the index / offset types"}
 _lib = None
@@ -31,8 +35,57 @@ def lib():
         L.mi355_csr_host_free.argtypes = [C.c_void_p]
         L.mi355_csr_host_free.restype = None
         L.mi355_load_last_error.restype = C.c_char_p
+        L.mi355_load_mtx_coo.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.mi355_load_coo_dims.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        for f in (L.mi355_load_coo_rows, L.mi355_load_coo_cols, L.mi355_load_coo_vals):
+            f.argtypes = [C.c_void_p]
+            f.restype = C.c_void_p
+        L.mi355_load_coo_free.argtypes = [C.c_void_p]
+        L.mi355_load_coo_free.restype = None
         _lib = L
     return _lib
+
+
+def _view(ptr, count, dt):
+    """A copy of `count` elements of dtype `dt` at host address `ptr`."""
+    if count == 0 or not ptr:
+        return np.zeros(count, dtype=dt)
+    buf = (C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr)
+    return np.frombuffer(buf, dtype=dt, count=count).copy()
+
+
+@dataclass
+class Coo:
+    """A Matrix Market file as LoadCoo leaves it: entries in file order (`symmetric` expanded entry-then-mirror)."""
+    n_rows: int
+    n_cols: int
+    nnz: int
+    rows: torch.Tensor   # int32
+    cols: torch.Tensor   # int32
+    vals: torch.Tensor   # float32 or float64
+
+
+def load_mtx_coo(path, off_dtype=torch.int32, val_dtype=torch.float32, device="cpu"):
+    """The file as the reference's LoadCoo gives it, before ToCsr (mi355_load_mtx_coo), as a Coo on `device`;
+    sp.coo_to_csr then builds the CSR on the GPU.  off_dtype only decides which sizes fit, as for load_mtx."""
+    L = lib()
+    h = C.c_void_p()
+    st = L.mi355_load_mtx_coo(os.fsencode(path), 1 if off_dtype == torch.int64 else 0,
+                              1 if val_dtype == torch.float64 else 0, C.byref(h))
+    if st != 0:
+        raise RuntimeError("mi355_load_mtx_coo(%s): %s (%s)" % (path, STATUS.get(st, st),
+                                                                L.mi355_load_last_error().decode()))
+    try:
+        nr, nc, nnz = C.c_int64(), C.c_int64(), C.c_int64()
+        L.mi355_load_coo_dims(h, C.byref(nr), C.byref(nc), C.byref(nnz))
+        n = nnz.value
+        rows = _view(L.mi355_load_coo_rows(h), n, np.int32)
+        cols = _view(L.mi355_load_coo_cols(h), n, np.int32)
+        vals = _view(L.mi355_load_coo_vals(h), n, np.float64 if val_dtype == torch.float64 else np.float32)
+    finally:
+        L.mi355_load_coo_free(h)
+    t = lambda a: torch.from_numpy(a).to(device)
+    return Coo(nr.value, nc.value, n, t(rows), t(cols), t(vals))
 
 
 def load_mtx(path, off_dtype=torch.int32, val_dtype=torch.float32, device="cpu"):
