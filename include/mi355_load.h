@@ -52,6 +52,16 @@ const int32_t* mi355_load_coo_cols(const mi355_coo_host* coo);
 const void* mi355_load_coo_vals(const mi355_coo_host* coo);
 void mi355_load_coo_free(mi355_coo_host* coo);
 
+/* The file AS STORED, before LoadCoo's expansion: entries in file order, 0-based, pattern values 1.0, a `symmetric`
+ * file's entries NOT mirrored — what mi355_spmv_coo_to_csr_symmetric (include/mi355_spmv.h) takes, so that only the
+ * stored half crosses the bus.  The handle is a mi355_coo_host (dims: nnz = the stored entries; rows / cols / vals
+ * and free as above).  *symmetric = 1 exactly when the banner says `symmetric`; *nnz_expanded = the entries
+ * mi355_load_mtx_coo would return: nnz + the off-diagonal entries for a symmetric file, nnz otherwise
+ * (skew-symmetric and hermitian files are not expanded, as in LoadCoo).  Same types, checks and error codes as
+ * mi355_load_mtx_coo (a symmetric file's indices must fit both dimensions).                                          */
+int mi355_load_mtx_stored(const char* path, int off_type, int val_type, mi355_coo_host** out, int* symmetric,
+                          int64_t* nnz_expanded);
+
 /* Message of the last failing call on this thread ("" if none).                                                    */
 const char* mi355_load_last_error(void);
 

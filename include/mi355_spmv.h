@@ -389,6 +389,38 @@ int mi355_spmv_coo_to_csr(int off_type, int val_type, int32_t n_rows, int32_t n_
                           void* Ap, int32_t* Aj, void* Ax, int64_t* perm,
                           void* workspace, size_t* workspace_bytes, void* stream);
 
+/* The same for the STORED entries of a `symmetric` Matrix Market file (the lower or upper triangle, as the file lists
+ * them): the outputs equal, bit for bit, ToCsr of the COO that the reference's LoadCoo makes of such a file
+ * (include/load.hpp:362-403): for stored entry i in order, (r, c, v), then (c, r, v) right after it if r != c — the
+ * diagonal once — then the stable sort by row.  So inside a CSR row the entries keep the order of that expanded
+ * sequence, duplicates are kept, columns are not sorted, and a list that holds both (i, j) and (j, i) gives four
+ * entries.  The expanded COO is never built and never crosses the bus: the caller uploads the stored entries only.
+ *   mi355_spmv_coo_symmetric_nnz   *nnz_expanded = nnz_stored + the number of entries with rows[i] != cols[i]: a
+ *                 device reduction on `stream`, which is synchronised once; it sizes Aj / Ax / perm.
+ *   rows, cols    nnz_stored device int32 indices;  vals: nnz_stored device values or NULL
+ *   nnz_expanded  what Aj / Ax / perm were allocated for.  The call checks it on the device against the true count
+ *                 before anything is sized by it; a mismatch returns MI355_SPMV_EINVAL, mi355_spmv_last_error()
+ *                 holds both numbers, and nothing is written to Ap / Aj / Ax / perm.
+ *   Ap            n_rows + 1 offsets of off_type;  Aj: nnz_expanded int32;  Ax: nnz_expanded values, NULL exactly
+ *                 when vals is
+ *   perm          NULL, or nnz_expanded int64: perm[k] = the index of the STORED entry behind CSR slot k.  An entry
+ *                 and its mirror share one index, so Ax = vals[perm] re-values the expanded matrix from the file's
+ *                 value list (rows[perm[k]] is slot k's row, or its column when slot k is a mirror).
+ *   workspace     as above: NULL is the size query (no device is touched); it depends on both counts.
+ * Every stored entry is checked first: row and col must BOTH be inside [0, n_rows) and inside [0, n_cols), because
+ * the mirror is stored too (the loader's rule for symmetric files).  The first bad entry is named in the error, no
+ * output is written, and the stream is still synchronised exactly once.
+ * Sizes: with MI355_OFF_I32 nnz_expanded <= INT32_MAX (else EINVAL); nnz_expanded outside
+ * [nnz_stored, 2 nnz_stored] is EINVAL; nnz_expanded >= 2^32 returns MI355_SPMV_ENOTSUP, and so does
+ * nnz_stored >= 2^31: the sort's 32-bit payload carries the stored index and a mirror bit.                          */
+int mi355_spmv_coo_symmetric_nnz(int64_t nnz_stored, const int32_t* rows, const int32_t* cols, void* stream,
+                                 int64_t* nnz_expanded);
+int mi355_spmv_coo_to_csr_symmetric(int off_type, int val_type, int32_t n_rows, int32_t n_cols,
+                                    int64_t nnz_stored, int64_t nnz_expanded,
+                                    const int32_t* rows, const int32_t* cols, const void* vals,
+                                    void* Ap, int32_t* Aj, void* Ax, int64_t* perm,
+                                    void* workspace, size_t* workspace_bytes, void* stream);
+
 /* ---- a generalized SpMV whose functor is the CALLER'S code --------------------
  * The reference's SpMV_merge_based_generalized is a template over a functor_t with three static members
  * (include/spmv/merge_genl/merge_genl.cuh:19-38; CPU twin include/spmv/cpu_navie.hpp:20-34)

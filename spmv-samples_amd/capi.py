@@ -40,7 +40,7 @@ EXPORTS = (
                                         "set_alpha_beta", "parts", "cuts", "part_info", "device_y", "device_x",
                                         "destroy")]
     + ["mi355_spmv_functor_" + n for n in ("compile", "compile_log", "spmv", "destroy")]
-    + ["mi355_spmv_coo_to_csr"]
+    + ["mi355_spmv_coo_to_csr", "mi355_spmv_coo_symmetric_nnz", "mi355_spmv_coo_to_csr_symmetric"]
 )
 
 
@@ -140,6 +140,11 @@ def lib():
         L.mi355_spmv_coo_to_csr.argtypes = [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_size_t), C.c_void_p]
+        L.mi355_spmv_coo_symmetric_nnz.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.mi355_spmv_coo_to_csr_symmetric.argtypes = [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t),
+                                                      C.c_void_p]
         _lib = L
     return _lib
 
@@ -236,29 +241,73 @@ def coo_to_csr_workspace_bytes(n_rows, nnz, off_dtype=torch.int32, val_dtype=Non
     return ws.value
 
 
-def coo_to_csr(n_rows, n_cols, rows, cols, vals=None, off_dtype=torch.int32, return_perm=False, stream=None):
+def coo_to_csr_symmetric_workspace_bytes(n_rows, nnz_stored, nnz_expanded, off_dtype=torch.int32, val_dtype=None):
+    """Device workspace mi355_spmv_coo_to_csr_symmetric needs (the size query: no device is touched)."""
+    ws = C.c_size_t(0)
+    st = lib().mi355_spmv_coo_to_csr_symmetric(OFF_TYPES[off_dtype][0], VAL_TYPES[val_dtype or torch.float32][0],
+                                               C.c_int32(n_rows), C.c_int32(0), C.c_int64(nnz_stored),
+                                               C.c_int64(nnz_expanded), None, None, None, None, None, None, None, None,
+                                               C.byref(ws), None)
+    _check(st, "mi355_spmv_coo_to_csr_symmetric (size query)")
+    return ws.value
+
+
+def coo_symmetric_nnz(rows, cols, stream=None):
+    """Entries the stored entries (rows, cols) of a symmetric matrix expand to: their number plus the off-diagonal
+    ones (mi355_spmv_coo_symmetric_nnz, a device reduction).  Synchronises the stream."""
+    _require_device(rows, cols)
+    if rows.dtype != torch.int32 or cols.dtype != torch.int32:
+        raise TypeError("rows and cols must be int32")
+    if cols.numel() != rows.numel():
+        raise ValueError("rows and cols must have the same length")
+    out = C.c_int64(0)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+    with torch.cuda.device(rows.device):
+        st = lib().mi355_spmv_coo_symmetric_nnz(C.c_int64(rows.numel()), ptr(rows), ptr(cols), _stream_ptr(stream),
+                                                C.byref(out))
+    _check(st, "mi355_spmv_coo_symmetric_nnz")
+    return out.value
+
+
+def coo_to_csr(n_rows, n_cols, rows, cols, vals=None, off_dtype=torch.int32, return_perm=False, stream=None,
+               symmetric=False):
     """COO -> CSR on the device (mi355_spmv_coo_to_csr): the reference's ToCsr result (include/load.hpp:420-474) —
     entries of a row in input order, duplicates kept, columns not sorted.  rows / cols: int32 device tensors; vals:
     a float32 / float64 / int32 device tensor or None (then Ax is None).  Returns a synth.Csr, or (Csr, perm) with
-    perm[k] = the source index of CSR slot k (int64) when return_perm.  Synchronises the stream."""
+    perm[k] = the source index of CSR slot k (int64) when return_perm.  Synchronises the stream.
+    symmetric=True: rows / cols / vals are the STORED entries of a symmetric file; the result is ToCsr of LoadCoo's
+    expansion (entry, then its mirror if off the diagonal), built by mi355_spmv_coo_to_csr_symmetric after
+    coo_symmetric_nnz has sized it; perm[k] is then the index of the stored entry behind slot k."""
     from .synth import Csr
     _require_device(rows, cols, *([vals] if vals is not None else []))
     if rows.dtype != torch.int32 or cols.dtype != torch.int32:
         raise TypeError("rows and cols must be int32")
-    nnz = rows.numel()
-    if cols.numel() != nnz or (vals is not None and vals.numel() != nnz):
+    n_in = rows.numel()
+    if cols.numel() != n_in or (vals is not None and vals.numel() != n_in):
         raise ValueError("rows, cols and vals must have the same length")
     if vals is not None and vals.dtype not in VAL_TYPES:
         raise TypeError("vals must be float32, float64 or int32")
     dev = rows.device
+    nnz = coo_symmetric_nnz(rows, cols, stream) if symmetric else n_in
     Ap = torch.empty(n_rows + 1, dtype=off_dtype, device=dev)
     Aj = torch.empty(nnz, dtype=torch.int32, device=dev)
     Ax = torch.empty(nnz, dtype=vals.dtype, device=dev) if vals is not None else None
     perm = torch.empty(nnz, dtype=torch.int64, device=dev) if return_perm else None
     val_dtype = vals.dtype if vals is not None else torch.float32
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    if symmetric:
+        nbytes = coo_to_csr_symmetric_workspace_bytes(n_rows, n_in, nnz, off_dtype, val_dtype)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        size = C.c_size_t(nbytes)
+        st = lib().mi355_spmv_coo_to_csr_symmetric(OFF_TYPES[off_dtype][0], VAL_TYPES[val_dtype][0], C.c_int32(n_rows),
+                                                   C.c_int32(n_cols), C.c_int64(n_in), C.c_int64(nnz), ptr(rows),
+                                                   ptr(cols), ptr(vals), ptr(Ap), ptr(Aj), ptr(Ax), ptr(perm),
+                                                   C.c_void_p(ws.data_ptr()), C.byref(size), _stream_ptr(stream))
+        _check(st, "mi355_spmv_coo_to_csr_symmetric")
+        csr = Csr(n_rows, n_cols, nnz, Ap, Aj, Ax, "coo_to_csr_symmetric", {"synthetic": False})
+        return (csr, perm) if return_perm else csr
     nbytes = coo_to_csr_workspace_bytes(n_rows, nnz, off_dtype, val_dtype)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
     size = C.c_size_t(nbytes)
     st = lib().mi355_spmv_coo_to_csr(OFF_TYPES[off_dtype][0], VAL_TYPES[val_dtype][0], C.c_int32(n_rows),
                                      C.c_int32(n_cols), C.c_int64(nnz), ptr(rows), ptr(cols), ptr(vals), ptr(Ap),

@@ -17,6 +17,15 @@
 // Validation runs first and records the smallest entry whose row or column is out of range; every later kernel reads
 // that word and returns at once if it is set, so no index that failed the check is ever used as an address and the
 // caller's output buffers are not written.
+//
+// mi355_spmv_coo_to_csr_symmetric takes the STORED entries of a `symmetric` Matrix Market file and gives ToCsr of what
+// LoadCoo makes of them (reference include/load.hpp:362-403; host/load.hpp ExpandSymmetric): entry i, then its mirror
+// if it is off the diagonal.  The expanded COO is never built: stored entry i goes to expanded place
+// i + (off-diagonal entries before i), found by reduce-then-scan over tiles of stored entries (offdiag_count ->
+// scan_sums -> expand), and only the sort's key (the row) and payload (2 i + mirror bit) are written there; the last
+// gather reads cols[i] or rows[i] by the bit, and vals[i], from the stored arrays.  check_count compares the true
+// expanded count with the caller's before anything is sized by it and stops every later kernel through the same word
+// the validation uses.
 #include "common.hpp"
 
 namespace mi355 {
@@ -27,6 +36,7 @@ constexpr int kTile = kBlock * kSteps;             // 4 096 entries per tile
 constexpr int kScanItems = 16;                     // counts a thread of the scan kernels sums
 constexpr int kScanChunk = kBlock * kScanItems;   // counts per workgroup of the scan kernels
 constexpr unsigned long long kNoBad = ~0ull;
+constexpr unsigned long long kBadCount = ~0ull - 1;   // symmetric: nnz_expanded is not the true count (no entry index gets here: nnz < 2^32)
 
 constexpr size_t align_up(size_t v) { return (v + 255) / 256 * 256; }
 
@@ -44,7 +54,8 @@ struct Layout {
     size_t o_keys[2] = {0, 0}, o_pay[2] = {0, 0}, o_counts = 0, o_bsum = 0, bytes = 0;
 };
 
-inline Layout layout(int32_t n_rows, uint64_t nnz) {
+// both_pairs: two buffer pairs for a single pass too (the symmetric call sorts out of a buffer of its own making).
+inline Layout layout(int32_t n_rows, uint64_t nnz, bool both_pairs = false) {
     Layout L;
     L.passes = nnz ? radix_passes(n_rows) : 0;
     size_t off = 256;   // the validation word
@@ -52,7 +63,7 @@ inline Layout layout(int32_t n_rows, uint64_t nnz) {
         L.n_tiles = (nnz + kTile - 1) / kTile;
         L.n_counts = 256 * L.n_tiles;
         L.n_scan_blocks = (L.n_counts + kScanChunk - 1) / kScanChunk;
-        const int bufs = L.passes > 1 ? 2 : 1;
+        const int bufs = L.passes > 1 || both_pairs ? 2 : 1;
         for (int b = 0; b < bufs; ++b) {
             L.o_keys[b] = off; off = align_up(off + 4 * nnz);
             L.o_pay[b] = off;  off = align_up(off + 4 * nnz);
@@ -278,6 +289,141 @@ __global__ void __launch_bounds__(kBlock) gather(const uint32_t* __restrict__ pa
     }
 }
 
+// ---- symmetric: the stored entries of a `symmetric` file -------------------------------------------------------
+// The sort's workspace for nnz_expanded entries, then one count per tile of stored entries (+ 1: the total).
+struct SymLayout {
+    Layout sort;
+    uint64_t n_etiles = 0;
+    size_t o_esum = 0, bytes = 0;
+};
+
+inline SymLayout sym_layout(int32_t n_rows, uint64_t nnz_stored, uint64_t nnz_expanded) {
+    SymLayout S;
+    S.sort = layout(n_rows, nnz_expanded, true);
+    S.n_etiles = (nnz_stored + kTile - 1) / kTile;
+    S.o_esum = S.sort.bytes;
+    S.bytes = align_up(S.o_esum + 4 * (S.n_etiles + 1));
+    return S;
+}
+
+// The mirror (col, row) is stored too: both indices inside both dimensions (the loader's rule, host/load.hpp).
+__global__ void __launch_bounds__(kBlock) validate_symmetric(const int32_t* __restrict__ rows,
+                                                             const int32_t* __restrict__ cols, uint64_t nnz,
+                                                             uint32_t n_square, unsigned long long* bad) {
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    for (uint64_t k = uint64_t(blockIdx.x) * kBlock + threadIdx.x; k < nnz; k += stride)
+        if (uint32_t(rows[k]) >= n_square || uint32_t(cols[k]) >= n_square) atomicMin(bad, (unsigned long long)k);
+}
+
+// Reduce: esum[t] = off-diagonal entries of tile t of the stored entries (0 for the one workgroup past the last tile,
+// which the exclusive scan turns into the total).  Compares only: no index is used as an address.
+__global__ void __launch_bounds__(kBlock) offdiag_count(const int32_t* __restrict__ rows, const int32_t* __restrict__ cols,
+                                                        uint64_t nnz, uint32_t* __restrict__ esum) {
+    __shared__ uint32_t part[kBlock / 64];
+    const uint64_t base = uint64_t(blockIdx.x) * kTile;
+    uint32_t s = 0;
+    for (int i = 0; i < kSteps; ++i) {
+        const uint64_t k = base + uint64_t(i) * kBlock + threadIdx.x;
+        if (k < nnz) s += rows[k] != cols[k];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) esum[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// After the scan esum[n_etiles] is the number of off-diagonal entries.  word[1] = the true expanded count; if it is
+// not the caller's, word[0] (the validation word) stops everything that follows.
+__global__ void __launch_bounds__(kBlock) check_count(const uint32_t* __restrict__ esum, uint64_t n_etiles,
+                                                      uint64_t nnz_stored, uint64_t nnz_expanded,
+                                                      unsigned long long* word) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || word[0] != kNoBad) return;
+    const unsigned long long expanded = nnz_stored + esum[n_etiles];
+    word[1] = expanded;
+    if (expanded != nnz_expanded) word[0] = kBadCount;
+}
+
+// Downsweep: stored entry i goes to expanded place i + (off-diagonal entries before it), its mirror right after it.
+// The four waves each walk a contiguous quarter of the tile in steps of 64, as the sort does, so one ballot per step
+// counts the off-diagonal entries before a lane.  Key = the row of the expanded entry, payload = 2 i + mirror.
+__global__ void __launch_bounds__(kBlock) expand(const int32_t* __restrict__ rows, const int32_t* __restrict__ cols,
+                                                 uint64_t nnz, const uint32_t* __restrict__ esum,
+                                                 uint32_t* __restrict__ keys_out, uint32_t* __restrict__ pay_out,
+                                                 const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    __shared__ uint32_t wave_total[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1;
+    const uint64_t base = uint64_t(blockIdx.x) * kTile;
+    const uint64_t n_left = nnz - base;
+    const uint64_t first = uint64_t(wave) * kSteps * 64 + lane;
+    uint32_t r[kSteps], c[kSteps], before[kSteps];
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        const uint64_t i = first + uint64_t(s) * 64;
+        r[s] = i < n_left ? uint32_t(rows[base + i]) : 0u;
+        c[s] = i < n_left ? uint32_t(cols[base + i]) : 0u;   // (past the end: r == c, counts as nothing)
+    }
+    uint32_t run = 0;
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        const unsigned long long m = __ballot(r[s] != c[s]);
+        before[s] = run + uint32_t(__popcll(m & below));
+        run += uint32_t(__popcll(m));
+    }
+    if (lane == 0) wave_total[wave] = run;
+    __syncthreads();
+    uint64_t shift = base + esum[blockIdx.x];   // expanded place of the tile's first entry, minus its stored place
+    for (int w = 0; w < wave; ++w) shift += wave_total[w];
+#pragma unroll
+    for (int s = 0; s < kSteps; ++s) {
+        const uint64_t i = first + uint64_t(s) * 64;
+        if (i < n_left) {
+            const uint64_t at = shift + i + before[s];
+            const uint32_t p = uint32_t(base + i) << 1;
+            keys_out[at] = r[s];
+            pay_out[at] = p;
+            if (r[s] != c[s]) {
+                keys_out[at + 1] = c[s];
+                pay_out[at + 1] = p | 1u;
+            }
+        }
+    }
+}
+
+// Aj[k] = cols[i] (rows[i] for a mirror), Ax[k] = vals[i], perm[k] = i, with 2 i + mirror = the sorted payload.
+// pay == nullptr: the identity (no pass ran: at most one row, so no entry has a mirror).
+template <typename elem_t>
+__global__ void __launch_bounds__(kBlock) gather_symmetric(const uint32_t* __restrict__ pay, uint64_t nnz,
+                                                           const int32_t* __restrict__ rows,
+                                                           const int32_t* __restrict__ cols,
+                                                           const elem_t* __restrict__ vals, int32_t* __restrict__ Aj,
+                                                           elem_t* __restrict__ Ax, int64_t* __restrict__ perm,
+                                                           const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    for (uint64_t k = uint64_t(blockIdx.x) * kBlock + threadIdx.x; k < nnz; k += stride) {
+        const uint64_t p = pay ? pay[k] : k << 1;
+        const uint64_t i = p >> 1;
+        Aj[k] = (p & 1) ? rows[i] : cols[i];
+        if (Ax) Ax[k] = vals[i];
+        if (perm) perm[k] = int64_t(i);
+    }
+}
+
+// Off-diagonal entries of the whole list (mi355_spmv_coo_symmetric_nnz): one integer add per wave, so the total does
+// not depend on the order in which they land.
+__global__ void __launch_bounds__(kBlock) offdiag_total(const int32_t* __restrict__ rows, const int32_t* __restrict__ cols,
+                                                        uint64_t nnz, unsigned long long* total) {
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    uint32_t s = 0;
+    for (uint64_t k = uint64_t(blockIdx.x) * kBlock + threadIdx.x; k < nnz; k += stride) s += rows[k] != cols[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(total, (unsigned long long)s);
+}
+
 inline unsigned grid_for(uint64_t items) {
     const uint64_t g = (items + kBlock - 1) / kBlock;
     return unsigned(g < 8192 ? (g ? g : 1) : 8192);
@@ -338,6 +484,73 @@ static int run(const Layout& L, int val_bytes, int32_t n_rows, int32_t n_cols, u
     return MI355_SPMV_OK;
 }
 
+template <typename off_t>
+static int run_symmetric(const SymLayout& S, int val_bytes, int32_t n_rows, int32_t n_cols, uint64_t nnz_stored,
+                         uint64_t nnz_expanded, const int32_t* rows, const int32_t* cols, const void* vals, void* Ap,
+                         int32_t* Aj, void* Ax, int64_t* perm, char* ws, hipStream_t s) {
+    const Layout& L = S.sort;
+    auto* bad = reinterpret_cast<unsigned long long*>(ws);   // [0] the validation word, [1] the true expanded count
+    uint32_t* esum = reinterpret_cast<uint32_t*>(ws + S.o_esum);
+    MI355_HIP_TRY(hipMemsetAsync(bad, 0xff, 2 * sizeof(unsigned long long), s));
+    if (nnz_stored)
+        MI355_COO_LAUNCH(validate_symmetric, grid_for(nnz_stored), rows, cols, nnz_stored,
+                         uint32_t(n_rows < n_cols ? n_rows : n_cols), bad);
+    MI355_COO_LAUNCH(offdiag_count, unsigned(S.n_etiles + 1), rows, cols, nnz_stored, esum);
+    MI355_COO_LAUNCH(scan_sums, 1u, esum, S.n_etiles + 1, bad);
+    MI355_COO_LAUNCH(check_count, 1u, esum, S.n_etiles, nnz_stored, nnz_expanded, bad);
+    uint32_t* keys_buf[2] = {reinterpret_cast<uint32_t*>(ws + L.o_keys[0]), reinterpret_cast<uint32_t*>(ws + L.o_keys[1])};
+    uint32_t* pay_buf[2] = {reinterpret_cast<uint32_t*>(ws + L.o_pay[0]), reinterpret_cast<uint32_t*>(ws + L.o_pay[1])};
+    const uint32_t* keys = nullptr;
+    const uint32_t* pay = nullptr;
+    if (L.passes > 0) {
+        MI355_COO_LAUNCH(expand, unsigned(S.n_etiles), rows, cols, nnz_stored, esum, keys_buf[0], pay_buf[0], bad);
+        keys = keys_buf[0];
+        pay = pay_buf[0];
+    }
+    uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.o_counts);
+    uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + L.o_bsum);
+    for (int p = 0; p < L.passes; ++p) {
+        const int shift = 8 * p;
+        uint32_t* keys_out = keys_buf[(p + 1) & 1];
+        uint32_t* pay_out = pay_buf[(p + 1) & 1];
+        MI355_COO_LAUNCH(count_digits, unsigned(L.n_tiles), keys, nnz_expanded, shift, L.n_tiles, counts, bad);
+        MI355_COO_LAUNCH(scan_reduce, unsigned(L.n_scan_blocks), counts, L.n_counts, bsum, bad);
+        MI355_COO_LAUNCH(scan_sums, 1u, bsum, L.n_scan_blocks, bad);
+        MI355_COO_LAUNCH(scan_apply, unsigned(L.n_scan_blocks), counts, L.n_counts, bsum, bad);
+        MI355_COO_LAUNCH(scatter, unsigned(L.n_tiles), keys, pay, nnz_expanded, shift, L.n_tiles, counts, keys_out, pay_out, bad);
+        keys = keys_out;
+        pay = pay_out;
+    }
+    MI355_COO_LAUNCH(row_offsets<off_t>, grid_for(uint64_t(n_rows) + 1), keys, nnz_expanded, uint32_t(n_rows),
+                     static_cast<off_t*>(Ap), bad);
+    if (nnz_expanded) {
+        if (val_bytes == 8)
+            MI355_COO_LAUNCH(gather_symmetric<uint64_t>, grid_for(nnz_expanded), pay, nnz_expanded, rows, cols,
+                             static_cast<const uint64_t*>(vals), Aj, static_cast<uint64_t*>(Ax), perm, bad);
+        else
+            MI355_COO_LAUNCH(gather_symmetric<uint32_t>, grid_for(nnz_expanded), pay, nnz_expanded, rows, cols,
+                             static_cast<const uint32_t*>(vals), Aj, static_cast<uint32_t*>(Ax), perm, bad);
+    }
+    // the one synchronisation: the validation word and the true count
+    unsigned long long word[2] = {kNoBad, 0};
+    MI355_HIP_TRY(hipMemcpyAsync(word, bad, sizeof(word), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if (word[0] == kBadCount) {
+        set_error("coo_to_csr_symmetric: nnz_expanded is %llu, the stored entries expand to %llu",
+                  (unsigned long long)nnz_expanded, word[1]);
+        return MI355_SPMV_EINVAL;
+    }
+    if (word[0] != kNoBad) {
+        int32_t r = 0, c = 0;
+        MI355_HIP_TRY(hipMemcpy(&r, rows + word[0], sizeof(r), hipMemcpyDeviceToHost));
+        MI355_HIP_TRY(hipMemcpy(&c, cols + word[0], sizeof(c), hipMemcpyDeviceToHost));
+        set_error("coo_to_csr_symmetric: entry %llu is (row %d, col %d); it or its mirror is outside the %d x %d matrix",
+                  word[0], r, c, n_rows, n_cols);
+        return MI355_SPMV_EINVAL;
+    }
+    return MI355_SPMV_OK;
+}
+
 }  // namespace coo
 }  // namespace mi355
 
@@ -364,4 +577,60 @@ extern "C" int mi355_spmv_coo_to_csr(int off_type, int val_type, int32_t n_rows,
     return off_type == MI355_OFF_I32
                ? coo::run<int32_t>(L, val_bytes, n_rows, n_cols, uint64_t(nnz), rows, cols, vals, Ap, Aj, Ax, perm, ws, s)
                : coo::run<int64_t>(L, val_bytes, n_rows, n_cols, uint64_t(nnz), rows, cols, vals, Ap, Aj, Ax, perm, ws, s);
+}
+
+extern "C" int mi355_spmv_coo_symmetric_nnz(int64_t nnz_stored, const int32_t* rows, const int32_t* cols, void* stream,
+                                            int64_t* nnz_expanded) {
+    using namespace mi355;
+    using namespace mi355::coo;   // (MI355_COO_LAUNCH names the kernels unqualified)
+    set_error("%s", "");
+    if (!nnz_expanded) { set_error("coo_symmetric_nnz: null nnz_expanded"); return MI355_SPMV_EINVAL; }
+    if (nnz_stored < 0) { set_error("coo_symmetric_nnz: negative size"); return MI355_SPMV_EINVAL; }
+    if (nnz_stored > 0 && (!rows || !cols)) { set_error("coo_symmetric_nnz: null rows or cols"); return MI355_SPMV_EINVAL; }
+    *nnz_expanded = 0;
+    if (nnz_stored == 0) return MI355_SPMV_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned long long* total = nullptr;
+    MI355_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&total), sizeof(*total)));
+    unsigned long long off_diag = 0;
+    const int st = [&]() -> int {
+        MI355_HIP_TRY(hipMemsetAsync(total, 0, sizeof(*total), s));
+        MI355_COO_LAUNCH(offdiag_total, grid_for(uint64_t(nnz_stored)), rows, cols, uint64_t(nnz_stored), total);
+        MI355_HIP_TRY(hipMemcpyAsync(&off_diag, total, sizeof(off_diag), hipMemcpyDeviceToHost, s));
+        MI355_HIP_TRY(hipStreamSynchronize(s));
+        return MI355_SPMV_OK;
+    }();
+    (void)hipFree(total);
+    if (st != MI355_SPMV_OK) return st;
+    *nnz_expanded = nnz_stored + int64_t(off_diag);
+    return MI355_SPMV_OK;
+}
+
+extern "C" int mi355_spmv_coo_to_csr_symmetric(int off_type, int val_type, int32_t n_rows, int32_t n_cols,
+                                               int64_t nnz_stored, int64_t nnz_expanded, const int32_t* rows,
+                                               const int32_t* cols, const void* vals, void* Ap, int32_t* Aj, void* Ax,
+                                               int64_t* perm, void* workspace, size_t* workspace_bytes, void* stream) {
+    using namespace mi355;
+    const char* const fn = "coo_to_csr_symmetric";
+    set_error("%s", "");
+    if (off_type != MI355_OFF_I32 && off_type != MI355_OFF_I64) { set_error("%s: unknown offset type %d", fn, off_type); return MI355_SPMV_EINVAL; }
+    if (val_type != MI355_VAL_F32 && val_type != MI355_VAL_F64 && val_type != MI355_VAL_I32) { set_error("%s: unknown value type %d", fn, val_type); return MI355_SPMV_EINVAL; }
+    if (n_rows < 0 || n_cols < 0 || nnz_stored < 0 || nnz_expanded < 0) { set_error("%s: negative size", fn); return MI355_SPMV_EINVAL; }
+    if (nnz_expanded < nnz_stored || uint64_t(nnz_expanded) > 2 * uint64_t(nnz_stored)) { set_error("%s: nnz_expanded %lld is not between nnz_stored %lld and twice that", fn, (long long)nnz_expanded, (long long)nnz_stored); return MI355_SPMV_EINVAL; }
+    if (off_type == MI355_OFF_I32 && nnz_expanded > INT32_MAX) { set_error("%s: nnz_expanded does not fit 32-bit offsets (use 64-bit offsets)", fn); return MI355_SPMV_EINVAL; }
+    if (uint64_t(nnz_expanded) >= (1ull << 32)) { set_error("%s: 2^32 or more expanded entries (the sort's counters are 32-bit)", fn); return MI355_SPMV_ENOTSUP; }
+    if (uint64_t(nnz_stored) >= (1ull << 31)) { set_error("%s: 2^31 or more stored entries (the sort's 32-bit payload holds the stored index and the mirror bit)", fn); return MI355_SPMV_ENOTSUP; }
+    if (!workspace_bytes) { set_error("%s: null workspace_bytes", fn); return MI355_SPMV_EINVAL; }
+    const coo::SymLayout S = coo::sym_layout(n_rows, uint64_t(nnz_stored), uint64_t(nnz_expanded));
+    if (!workspace) { *workspace_bytes = S.bytes; return MI355_SPMV_OK; }
+    if (*workspace_bytes < S.bytes) { set_error("%s: workspace of %zu bytes, %zu needed", fn, *workspace_bytes, S.bytes); return MI355_SPMV_EINVAL; }
+    if (!Ap) { set_error("%s: null Ap", fn); return MI355_SPMV_EINVAL; }
+    if (nnz_stored > 0 && (!rows || !cols || !Aj)) { set_error("%s: null rows, cols or Aj", fn); return MI355_SPMV_EINVAL; }
+    if ((vals == nullptr) != (Ax == nullptr)) { set_error("%s: Ax and vals must be both given or both null", fn); return MI355_SPMV_EINVAL; }
+    const int val_bytes = val_type == MI355_VAL_F64 ? 8 : 4;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    return off_type == MI355_OFF_I32
+               ? coo::run_symmetric<int32_t>(S, val_bytes, n_rows, n_cols, uint64_t(nnz_stored), uint64_t(nnz_expanded), rows, cols, vals, Ap, Aj, Ax, perm, ws, s)
+               : coo::run_symmetric<int64_t>(S, val_bytes, n_rows, n_cols, uint64_t(nnz_stored), uint64_t(nnz_expanded), rows, cols, vals, Ap, Aj, Ax, perm, ws, s);
 }

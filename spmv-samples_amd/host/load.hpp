@@ -2,7 +2,7 @@
 //
 // Same public surface and the same results as the reference's include/load.hpp:
 //   coo_t / csr_t                      load.hpp:131-161  (same member names)
-//   LoadCoo<index_t,offset_t,value_t>  load.hpp:268-408
+//   LoadCoo<index_t,offset_t,value_t>  load.hpp:268-408  (= LoadCooStored, the file as stored, then ExpandSymmetric)
 //   ToCsr                              load.hpp:420-474
 // "Same results" is meant entry for entry (tests/test_host_loader.py compares with the
 // reference build and with tests/golden/golden.json): 1-based -> 0-based; pattern -> 1.0;
@@ -236,8 +236,11 @@ inline unsigned parse_threads() {
 
 }  // namespace mm_detail
 
+// The file as stored: entries in file order, nothing mirrored.  *symmetric = the banner says `symmetric`;
+// *off_diagonal = its entries with row != column (counted inside the parallel parse; 0 for other symmetries) — what
+// the expansion adds.  LoadCoo is this, then ExpandSymmetric.
 template <typename index_t, typename offset_t, typename value_t>
-coo_t<index_t, offset_t, value_t> LoadCoo(std::string filename) {
+coo_t<index_t, offset_t, value_t> LoadCooStored(std::string filename, bool* symmetric, uint64_t* off_diagonal) {
     using namespace mm_detail;
     Mapped f;
     if (!f.open(filename)) fatal("File could not be opened: " + filename);
@@ -306,6 +309,7 @@ coo_t<index_t, offset_t, value_t> LoadCoo(std::string filename) {
     for (size_t c = 0; c < n_chunks; ++c) tok_begin[c + 1] += tok_begin[c];
 
     std::vector<int> status(n_chunks, 0);   // 0 ok, 1 short read, 2 zero index, 3 index beyond the header's size
+    std::vector<uint64_t> chunk_off_diag(n_chunks, 0);
     for_chunks([&](size_t c) {
         const char* q = body + c * chunk;
         const char* e = std::min(q + chunk, end);
@@ -333,6 +337,7 @@ coo_t<index_t, offset_t, value_t> LoadCoo(std::string filename) {
             coo.row_indices[entry] = index_t(r) - 1;
             coo.column_indices[entry] = index_t(cidx) - 1;
             coo.nonzero_values[entry] = pattern ? value_t(1.0) : value_t(w);
+            chunk_off_diag[c] += mirror && r != cidx;
             ++entry;
             tok += tokens_per_entry;
         }
@@ -348,25 +353,39 @@ coo_t<index_t, offset_t, value_t> LoadCoo(std::string filename) {
     }
     throw_if_exception(total_tokens / tokens_per_entry < n_entries, short_msg);
 
-    // ---- symmetric: entry, then its mirror, in file order; diagonal once
-    if (symmetry == "symmetric") {
-        uint64_t off_diag = 0;
-        for (size_t i = 0; i < n_entries; ++i) off_diag += coo.row_indices[i] != coo.column_indices[i];
-        const uint64_t total = uint64_t(n_entries) + off_diag;
-        std::vector<index_t> I(total), J(total);
-        std::vector<value_t> V(total);
-        uint64_t k = 0;
-        for (size_t i = 0; i < n_entries; ++i) {
-            const index_t r = coo.row_indices[i], c = coo.column_indices[i];
-            const value_t v = coo.nonzero_values[i];
-            I[k] = r; J[k] = c; V[k] = v; ++k;
-            if (r != c) { I[k] = c; J[k] = r; V[k] = v; ++k; }
-        }
-        coo.row_indices.swap(I);
-        coo.column_indices.swap(J);
-        coo.nonzero_values.swap(V);
-        coo.number_of_nonzeros = offset_t(total);
+    *symmetric = mirror;
+    *off_diagonal = 0;
+    for (size_t c = 0; c < n_chunks; ++c) *off_diagonal += chunk_off_diag[c];
+    return coo;
+}
+
+// symmetric: entry, then its mirror, in file order; diagonal once (reference load.hpp:362-403).  off_diagonal = the
+// stored entries with row != column.
+template <typename index_t, typename offset_t, typename value_t>
+void ExpandSymmetric(coo_t<index_t, offset_t, value_t>& coo, uint64_t off_diagonal) {
+    const size_t n_entries = size_t(coo.number_of_nonzeros);
+    const uint64_t total = uint64_t(n_entries) + off_diagonal;
+    std::vector<index_t> I(total), J(total);
+    std::vector<value_t> V(total);
+    uint64_t k = 0;
+    for (size_t i = 0; i < n_entries; ++i) {
+        const index_t r = coo.row_indices[i], c = coo.column_indices[i];
+        const value_t v = coo.nonzero_values[i];
+        I[k] = r; J[k] = c; V[k] = v; ++k;
+        if (r != c) { I[k] = c; J[k] = r; V[k] = v; ++k; }
     }
+    coo.row_indices.swap(I);
+    coo.column_indices.swap(J);
+    coo.nonzero_values.swap(V);
+    coo.number_of_nonzeros = offset_t(total);
+}
+
+template <typename index_t, typename offset_t, typename value_t>
+coo_t<index_t, offset_t, value_t> LoadCoo(std::string filename) {
+    bool symmetric = false;
+    uint64_t off_diagonal = 0;
+    coo_t<index_t, offset_t, value_t> coo = LoadCooStored<index_t, offset_t, value_t>(filename, &symmetric, &off_diagonal);
+    if (symmetric) ExpandSymmetric(coo, off_diagonal);
     return coo;
 }
 

@@ -1,6 +1,7 @@
 // load_capi.cpp — the extern "C" surface of include/mi355_load.h around host/load.hpp (LoadCoo + ToCsr, the
 // reference's include/load.hpp:268-474 restated for speed): what bench.py --mtx and other non-C++ callers bind; and
-// LoadCoo alone (mi355_load_mtx_coo), for callers that build the CSR on the device.
+// LoadCoo alone (mi355_load_mtx_coo) and the file as stored (mi355_load_mtx_stored), for callers that build the CSR on
+// the device.
 // The reference exits the process on a bad file (load.hpp:278-300); a library must not, so the loader runs with
 // its exit-on-error switched to exceptions (MI355_LOAD_NO_EXIT) and everything becomes a status + message.
 #include <cstdint>
@@ -76,6 +77,11 @@ template <typename off_t, typename val_t>
 int fill_coo(mi355_coo_host& into, const char* path) {
     return guarded([&] { take_coo(into, LoadCoo<int, off_t, val_t>(std::string(path))); });
 }
+
+template <typename off_t, typename val_t>
+int fill_stored(mi355_coo_host& into, const char* path, bool* symmetric, uint64_t* off_diagonal) {
+    return guarded([&] { take_coo(into, LoadCooStored<int, off_t, val_t>(std::string(path), symmetric, off_diagonal)); });
+}
 }  // namespace
 
 extern "C" {
@@ -139,6 +145,30 @@ int mi355_load_mtx_coo(const char* path, int off_type, int val_type, mi355_coo_h
                                                   : fill_coo<long long, double>(*h, path));
     if (st != MI355_LOAD_OK) { delete h; return st; }
     *out = h;
+    return MI355_LOAD_OK;
+}
+int mi355_load_mtx_stored(const char* path, int off_type, int val_type, mi355_coo_host** out, int* symmetric,
+                          int64_t* nnz_expanded) {
+    g_err[0] = 0;
+    if (!path || !out || !symmetric || !nnz_expanded || (off_type != 0 && off_type != 1) ||
+        (val_type != 0 && val_type != 1)) {
+        set_err("mi355_load_mtx_stored: null pointer or unknown type");
+        return MI355_LOAD_EINVAL;
+    }
+    *out = nullptr;
+    mi355_coo_host* h = new (std::nothrow) mi355_coo_host();
+    if (!h) { set_err("out of host memory"); return MI355_LOAD_ERANGE; }
+    h->val_type = val_type;
+    bool sym = false;
+    uint64_t off_diag = 0;
+    const int st = off_type == 0 ? (val_type == 0 ? fill_stored<int, float>(*h, path, &sym, &off_diag)
+                                                  : fill_stored<int, double>(*h, path, &sym, &off_diag))
+                                 : (val_type == 0 ? fill_stored<long long, float>(*h, path, &sym, &off_diag)
+                                                  : fill_stored<long long, double>(*h, path, &sym, &off_diag));
+    if (st != MI355_LOAD_OK) { delete h; return st; }
+    *out = h;
+    *symmetric = sym ? 1 : 0;
+    *nnz_expanded = h->nnz + int64_t(off_diag);
     return MI355_LOAD_OK;
 }
 int mi355_load_coo_dims(const mi355_coo_host* h, int64_t* n_rows, int64_t* n_cols, int64_t* nnz) {

@@ -28,6 +28,10 @@
 //                    an "ms" label (timer.hpp:10 vs main.cu:111-112); default keeps its label
 //   --ngpu N         GPUs the hip_dist_* kinds spread the rows over (default 1; the reference is
 //                    single-device, main.cu:53); --sub-blocks S = row blocks per GPU (default 4 when N > 1)
+//   --csr-on-device  build the device CSR on the GPU: the file's STORED entries are uploaded (a `symmetric` file's
+//                    half, not its expansion) and mi355_spmv_coo_to_csr / mi355_spmv_coo_to_csr_symmetric make
+//                    Ap / Aj / Ax there.  The CPU check still runs on the host-made CSR, so the delta table also
+//                    compares the two builds.  Default: ToCsr(LoadCoo(...)) on the host, uploaded (main.cu:32-74)
 // and, since no SuiteSparse file is at hand offline (SURVEY §5 "config / flags", §8(d)), a seeded matrix in the file's place:
 //     ./bin/spmv --synthetic band:n=4194304,k=32,w=4096 hip_vector hip_merge --seed 1
 //     ./bin/spmv synthetic:rand:n=1048576,k=16 hip_merge
@@ -49,6 +53,8 @@
 #include "spmv.h"
 #include "spmv/cpu_check.hpp"
 
+#include "../../include/mi355_spmv.h"
+
 #define checkHipErr(val) CheckHipErr((val), #val, __FILE__, __LINE__)
 static void CheckHipErr(hipError_t result, const char* func, const char* file, int line) {
     if (result != hipSuccess) {
@@ -63,6 +69,7 @@ struct Options {
     bool poison = true;
     bool unit_us = false;
     unsigned long long seed = 1;
+    bool csr_on_device = false;
 };
 
 // ---- seeded synthetic matrices (in the place of a Matrix Market file) ----------------------------------------
@@ -137,8 +144,22 @@ static csr_t<index_t, offset_t, value_t> make_synthetic(const std::string& spec,
 template <typename index_t, typename offset_t, typename value_t>
 static int run(const char* path, const std::vector<std::string>& kinds, const Options& opt) {
     const bool synthetic = std::strncmp(path, "synthetic:", 10) == 0;
-    csr_t<index_t, offset_t, value_t> csr = synthetic ? make_synthetic<index_t, offset_t, value_t>(path + 10, opt.seed)
-                                                      : ToCsr(LoadCoo<index_t, offset_t, value_t>(path));
+    if (synthetic && opt.csr_on_device) { std::cerr << "--csr-on-device needs a Matrix Market file" << std::endl; std::exit(1); }
+    // --csr-on-device: the entries as the file stores them, kept for the upload; the host CSR below is made from a copy
+    coo_t<index_t, offset_t, value_t> stored(0, 0, 0);
+    bool symmetric = false;
+    uint64_t off_diagonal = 0;
+    csr_t<index_t, offset_t, value_t> csr;
+    if (synthetic) {
+        csr = make_synthetic<index_t, offset_t, value_t>(path + 10, opt.seed);
+    } else if (opt.csr_on_device) {
+        stored = LoadCooStored<index_t, offset_t, value_t>(path, &symmetric, &off_diagonal);
+        coo_t<index_t, offset_t, value_t> coo = stored;
+        if (symmetric) ExpandSymmetric(coo, off_diagonal);
+        csr = ToCsr(coo);
+    } else {
+        csr = ToCsr(LoadCoo<index_t, offset_t, value_t>(path));
+    }
     const index_t n_rows = csr.number_of_rows, n_cols = csr.number_of_columns;
     const offset_t nnz = csr.number_of_nonzeros;
     std::cout << "Dataset: " << (synthetic ? std::string(path) + " seed=" + std::to_string(opt.seed) : std::filesystem::path(path).filename().string()) << std::endl
@@ -154,9 +175,41 @@ static int run(const char* path, const std::vector<std::string>& kinds, const Op
     checkHipErr(hipMalloc((void**)&dAx, (size_t(nnz) + 1) * sizeof(value_t)));
     checkHipErr(hipMalloc((void**)&dX, (size_t(n_cols) + 1) * sizeof(value_t)));
     checkHipErr(hipMalloc((void**)&dY, (size_t(n_rows) + 1) * sizeof(value_t)));
-    checkHipErr(hipMemcpy(dAp, csr.row_offsets.data(), (size_t(n_rows) + 1) * sizeof(offset_t), hipMemcpyHostToDevice));
-    checkHipErr(hipMemcpy(dAj, csr.column_indices.data(), size_t(nnz) * sizeof(index_t), hipMemcpyHostToDevice));
-    checkHipErr(hipMemcpy(dAx, csr.nonzero_values.data(), size_t(nnz) * sizeof(value_t), hipMemcpyHostToDevice));
+    if (opt.csr_on_device) {
+        const size_t n_stored = size_t(stored.number_of_nonzeros);
+        const int off_type = sizeof(offset_t) == 8 ? MI355_OFF_I64 : MI355_OFF_I32;
+        const int val_type = sizeof(value_t) == 8 ? MI355_VAL_F64 : MI355_VAL_F32;
+        index_t *dRows, *dCols; value_t* dVals; void* dWs;
+        checkHipErr(hipMalloc((void**)&dRows, (n_stored + 1) * sizeof(index_t)));
+        checkHipErr(hipMalloc((void**)&dCols, (n_stored + 1) * sizeof(index_t)));
+        checkHipErr(hipMalloc((void**)&dVals, (n_stored + 1) * sizeof(value_t)));
+        checkHipErr(hipMemcpy(dRows, stored.row_indices.data(), n_stored * sizeof(index_t), hipMemcpyHostToDevice));
+        checkHipErr(hipMemcpy(dCols, stored.column_indices.data(), n_stored * sizeof(index_t), hipMemcpyHostToDevice));
+        checkHipErr(hipMemcpy(dVals, stored.nonzero_values.data(), n_stored * sizeof(value_t), hipMemcpyHostToDevice));
+        auto to_csr = [&](void* ws, size_t* ws_bytes) {
+            return symmetric ? mi355_spmv_coo_to_csr_symmetric(off_type, val_type, n_rows, n_cols, int64_t(n_stored),
+                                                               int64_t(nnz), dRows, dCols, dVals, dAp, dAj, dAx, nullptr,
+                                                               ws, ws_bytes, nullptr)
+                             : mi355_spmv_coo_to_csr(off_type, val_type, n_rows, n_cols, int64_t(n_stored), dRows, dCols,
+                                                     dVals, dAp, dAj, dAx, nullptr, ws, ws_bytes, nullptr);
+        };
+        size_t ws_bytes = 0;
+        int st = to_csr(nullptr, &ws_bytes);
+        if (st == MI355_SPMV_OK) {
+            checkHipErr(hipMalloc(&dWs, ws_bytes));
+            st = to_csr(dWs, &ws_bytes);
+            checkHipErr(hipFree(dWs));
+        }
+        if (st != MI355_SPMV_OK) {
+            std::fprintf(stderr, "--csr-on-device: %s (%s)\n", mi355_spmv_status_string(st), mi355_spmv_last_error());
+            std::abort();
+        }
+        checkHipErr(hipFree(dRows)); checkHipErr(hipFree(dCols)); checkHipErr(hipFree(dVals));
+    } else {
+        checkHipErr(hipMemcpy(dAp, csr.row_offsets.data(), (size_t(n_rows) + 1) * sizeof(offset_t), hipMemcpyHostToDevice));
+        checkHipErr(hipMemcpy(dAj, csr.column_indices.data(), size_t(nnz) * sizeof(index_t), hipMemcpyHostToDevice));
+        checkHipErr(hipMemcpy(dAx, csr.nonzero_values.data(), size_t(nnz) * sizeof(value_t), hipMemcpyHostToDevice));
+    }
     checkHipErr(hipMemcpy(dX, vec_x.data(), size_t(n_cols) * sizeof(value_t), hipMemcpyHostToDevice));
     checkHipErr(hipMemcpy(dY, vec_y.data(), size_t(n_rows) * sizeof(value_t), hipMemcpyHostToDevice));
 
@@ -222,11 +275,13 @@ int main(int argc, char** argv) {
         else if (a == "--sub-blocks") mi355_host::dist_sub_blocks() = std::max(1, std::atoi(value("--sub-blocks").c_str()));
         else if (a == "--no-poison") opt.poison = false;
         else if (a == "--unit-us") opt.unit_us = true;
+        else if (a == "--csr-on-device") opt.csr_on_device = true;
         else if (a == "--seed") opt.seed = std::strtoull(value("--seed").c_str(), nullptr, 10);
         else kinds.push_back(a);
     }
     if (argc < 3 || kinds.empty()) {
-        std::cerr << "usage: ./bin/<program-name>  <filename.mtx>  <SpMV_kind_string>..." << std::endl;
+        std::cerr << "usage: ./bin/<program-name>  <filename.mtx>  <SpMV_kind_string>..." << std::endl
+                  << "       options after the kinds: --iters N  --dtype f64  --offset 64  --csr-on-device  (see main.cpp)" << std::endl;
         std::exit(1);
     }
     const bool f64 = dtype == "f64", o64 = offset == "64";
