@@ -104,6 +104,9 @@ def lib():
                                                    C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
         L.mi355_spmv_plan_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355_spmv_plan_destroy.argtypes = [C.c_void_p]
+        L.mi355_spmv_plan_acquire.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32,
+                                              C.c_int64, C.c_void_p, C.c_void_p]
+        L.mi355_spmv_plan_release.argtypes = [C.c_void_p, C.c_int]
         L.mi355_spmv_plan_set_semiring.argtypes = [C.c_void_p, C.c_int]
         L.mi355_spmv_plan_set_alpha_beta.argtypes = [C.c_void_p, C.c_double, C.c_double]
         L.mi355_spmv_plan_get_info.argtypes = [C.c_void_p, C.POINTER(PlanInfo)]
@@ -406,6 +409,36 @@ class Plan:
             C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
         _check(st, "mi355_spmv_plan_create_block")
         return self
+
+    @classmethod
+    def acquire(cls, kind, n_rows, n_cols, nnz, Ap, Aj, val_dtype):
+        """The plan a one-shot call on these arrays would run (mi355_spmv_plan_acquire): the one kept from the previous
+        call on the same pointers, sizes, types, kind and device, else a new one.  Give it back with release() once
+        the stream it ran on has been synchronised; destroy() instead drops it without keeping it."""
+        kind = LABELS.get(kind, kind)
+        if kind not in KINDS:
+            raise ValueError('SpMV kind "%s" is NOT SUPPORTED' % kind)
+        _require_device(Ap, Aj)
+        if Aj.dtype != torch.int32:
+            raise TypeError("Aj must be int32")
+        self = cls.__new__(cls)
+        self.kind, self.n_rows, self.n_cols, self.nnz = kind, n_rows, n_cols, nnz
+        self.Ap, self.Aj, self.val_dtype, self.mat_dtype = Ap, Aj, val_dtype, val_dtype
+        self._h = C.c_void_p()
+        with torch.cuda.device(Ap.device):
+            st = lib().mi355_spmv_plan_acquire(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0],
+                                               VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz,
+                                               C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()))
+        _check(st, "mi355_spmv_plan_acquire")
+        return self
+
+    def release(self, executed_ok=True):
+        """Hand an acquired plan back (mi355_spmv_plan_release): kept for the next acquire / one-shot call on the same
+        arrays when that is safe, destroyed otherwise.  The handle is gone either way."""
+        if self._h:
+            h, self._h = self._h, C.c_void_p()
+            with torch.cuda.device(self.Ap.device):
+                _check(lib().mi355_spmv_plan_release(h, 1 if executed_ok else 0), "mi355_spmv_plan_release")
 
     def merge_coords(self):
         import numpy as np

@@ -116,6 +116,22 @@ def test_binding_refuses_host_tensors_and_unknown_kinds(sp):
         sp.spmv("cusparse", 1, 1, 1, Ap, Aj, Ax, Ax, Ax.clone())
 
 
+def test_plan_acquire_and_release_check_their_arguments_without_touching_the_device(sp):
+    """mi355_spmv_plan_acquire / _release (what Plan.acquire / plan.release bind): a null handle pointer is refused,
+    releasing nothing is fine, and the binding refuses host tensors and unknown kinds like the other entry points."""
+    lib = sp.capi.lib()
+    dummy = C.c_void_p(256)
+    assert lib.mi355_spmv_plan_acquire(None, 0, 0, 0, 4, 4, 4, dummy, dummy) == 1
+    assert lib.mi355_spmv_last_error() != b""
+    assert lib.mi355_spmv_plan_release(None, 1) == 0
+    Ap = torch.tensor([0, 1], dtype=torch.int32)
+    Aj = torch.tensor([0], dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="device tensors only"):
+        sp.Plan.acquire("vector", 1, 1, 1, Ap, Aj, torch.float32)
+    with pytest.raises(ValueError, match="NOT SUPPORTED"):
+        sp.Plan.acquire("cusparse", 1, 1, 1, Ap, Aj, torch.float32)
+
+
 def test_missing_library_fails_loudly(sp, monkeypatch):
     monkeypatch.setattr(sp.capi, "_lib", None)
     monkeypatch.setattr(sp.capi, "LIB_PATH", "/nonexistent/libmi355spmv.so")
