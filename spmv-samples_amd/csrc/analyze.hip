@@ -401,6 +401,9 @@ int find_giant_rows(Plan& p) {
     p.n_giant_slices = 0;
     // (a row-block plan does what the whole matrix's plan decided: p.giant_enabled / p.giant_len are inherited)
     if (!p.balanced || (p.is_block ? !p.giant_enabled : p.knob.giant == 0)) { p.giant_enabled = false; return MI355_SPMV_OK; }
+    // an empty row block of a weight-cut plan (a row heavier than a block's share of the nonzeros leaves the cuts behind
+    // it without rows): nothing to scan, and a grid of no workgroups is not a launch
+    if (p.n_rows <= 0) return MI355_SPMV_OK;
     // A row is giant when it alone is more than an eighth of a CU's fair share of the matrix (a hub of 30 K nonzeros in a
     // 4 M-nonzero R-MAT kept ONE workgroup busy for most of the kernel: 75 us against merge's 30), between 4 K and 64 K.
     if (!p.is_block) {

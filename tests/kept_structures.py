@@ -234,6 +234,15 @@ def values(g):
     return (rng.random(g.nnz) * 2 - 1).astype(g.val), (rng.random(g.n_cols) * 2 - 1).astype(g.val)
 
 
+def real_values(g):
+    """(Ax, x) of the row-block tests (tests/test_gpu_block_shapes.py): uniform reals in (-1, 1) in the group's value
+    type, the fp32 groups included — two orders of summation then give different bits — from a seed of its own."""
+    rng = np.random.default_rng([9, g.n_rows, g.per_row])
+    lim = np.nextafter(g.val.type(1), g.val.type(0))              # (the cast to fp32 may round up to 1)
+    draw = lambda n: np.clip((rng.random(n) * 2 - 1).astype(g.val), -lim, lim)
+    return draw(g.nnz), draw(g.n_cols)
+
+
 def nan_values(g):
     """(Ax, x) of the NaN / Inf test: Ax in {1, 2, 3}; x = 1 except NaN at one column and +Inf at another."""
     rng = np.random.default_rng([8, g.n_rows, g.per_row])
@@ -241,6 +250,36 @@ def nan_values(g):
     x[g.nan_col] = np.nan
     x[g.inf_col] = np.inf
     return rng.integers(1, 4, size=g.nnz).astype(g.val), x
+
+
+# Phase variants.  A row block is a 16-byte-aligned view of the whole arrays that starts at element Ap[first row] & ~3, so
+# its Ap[0] is that row's position modulo 4, its phase.  The structures with rows of one length — a multiple of 4 —
+# start every row, and so every block, at phase 0; with the first d entries of row 1 gone every later row starts at
+# phase (-d) & 3.  Row 1 is neither probed nor planted.  The structures of UNALIGNED have row starts of every phase as
+# they are (and a row 1 that may be short or empty).
+UNALIGNED = ("ragged", "giant", "liar")
+SHIFT_ROW = 1
+
+
+def phase_shifts(g, name):
+    """The shifts d the row-block tests run a structure at: all four on the small groups, 0 and one odd d on the big
+    ones (a different one each), 0 alone for the structures that are unaligned already."""
+    if name in UNALIGNED:
+        return (0,)
+    if g.nnz <= 4_100_000:
+        return (0, 1, 2, 3)
+    return (0, 1) if g.val == np.float32 else (0, 3)
+
+
+def phase_shifted(Ap, Aj, d):
+    """(Ap, Aj) with the first d entries of row 1 deleted: n_rows as before, nnz - d nonzeros."""
+    if d == 0:
+        return Ap, Aj
+    a = int(Ap[SHIFT_ROW])
+    assert int(Ap[SHIFT_ROW + 1]) - a >= d
+    Ap = Ap.copy()
+    Ap[SHIFT_ROW + 1:] -= d
+    return Ap, np.concatenate([Aj[:a], Aj[a + d:]])
 
 
 def rows_referencing(Ap, Aj, col):

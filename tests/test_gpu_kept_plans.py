@@ -21,6 +21,8 @@ import torch
 
 import kept_structures as ks
 from conftest import parity_bound
+from plan_census import REPORT, has_giant_list, merge_lines, plain_lanes, row_kind_lines
+from plan_census import describe as describe_plan
 from small_path import forced, small_choice
 
 pytestmark = pytest.mark.gpu
@@ -28,9 +30,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 KINDS = ["vector", "merge", "light"]
 TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
-REPORT = ("main_kernel", "block_threads", "lanes_per_row", "window_elems", "window_segments", "balanced_chunks",
-          "grid_blocks", "n_chunks", "n_kernels")
-PLAIN, TILE, RUNS = "csr_vector_kernel", "merge_tile_kernel", "merge_rows_kernel"
 
 # (group, arm of the small-matrix choice or None): the small groups run under the library's default, where the plain
 # kernel is among the kept plans, and again under the chunked kernels; merge ignores that choice
@@ -112,17 +111,7 @@ def arm_of(sp, arm):
 
 
 def describe(sp, plan):
-    """What a plan is, as plain data: its info, its shape as bytes, and the few shape fields the census reads."""
-    info, sh = plan.info(), plan.shape()
-    extra = {"window_from_band": sh.window_from_band, "window_sweep": sh.window_sweep, "small_plain": sh.small_plain,
-             "band": int(sh.band_hi - sh.band_lo + 1), "probe_ok": sh.probe_ok}
-    return info, bytes(sh), extra
-
-
-def has_giant_list(kind, info):
-    """VECTOR / LIGHT run one kernel, plus two for the slices of giant rows (analyze.hip, set_rows_launch); the merge
-    kind has no such list."""
-    return kind != "merge" and info["n_kernels"] == 3
+    return describe_plan(plan)
 
 
 def acquire(sp, st, kind):
@@ -222,52 +211,8 @@ def test_nan_and_inf_reach_only_their_rows_under_staged_windows(sp, oracle, gnam
 
 
 def census_lines():
-    """(label, predicate over (kind, info, extra)) — every shape the plans kept as A must include."""
-    window = {"vector": "csr_vector_window_kernel", "light": "light_rows_window_kernel"}
-    sweep = {"vector": "csr_vector_sweep_kernel", "light": "light_rows_sweep_kernel"}
-    lines = []
-    for kind in ("vector", "light"):
-        def one_band(threads, kind=kind):
-            return lambda k, i, e: (k == kind and i["main_kernel"] == window[kind] and i["window_segments"] == 1 and
-                                    i["window_elems"] > 0 and e["window_from_band"] == 1 and i["balanced_chunks"] == 0 and
-                                    i["block_threads"] == threads)
-        lines += [
-            ("%s: one band-placed window, 256 threads" % kind, one_band(256)),
-            ("%s: one band-placed window, 512 threads" % kind, one_band(512)),
-            ("%s: one band-placed window, 1024 threads" % kind, one_band(1024)),
-            ("%s: window kernel, window_segments >= 2" % kind,
-             lambda k, i, e, kind=kind: k == kind and i["main_kernel"] == window[kind] and i["window_segments"] >= 2),
-            ("%s: window kernel, window_elems == 0" % kind,
-             lambda k, i, e, kind=kind: k == kind and i["main_kernel"] == window[kind] and i["window_elems"] == 0 and
-             i["balanced_chunks"] == 0),
-            ("%s: sweep kernel" % kind, lambda k, i, e, kind=kind: k == kind and i["main_kernel"] == sweep[kind]),
-            ("%s: weight-cut chunks with a window" % kind,
-             lambda k, i, e, kind=kind: k == kind and i["balanced_chunks"] == 1 and i["window_elems"] > 0),
-            ("%s: weight-cut chunks without a window" % kind,
-             lambda k, i, e, kind=kind: k == kind and i["balanced_chunks"] == 1 and i["window_elems"] == 0),
-        ]
-    lines += [
-        ("light: grid_blocks < n_chunks", lambda k, i, e: k == "light" and i["grid_blocks"] < i["n_chunks"]),
-        ("light: grid_blocks == n_chunks",
-         lambda k, i, e: k == "light" and i["main_kernel"] != PLAIN and i["grid_blocks"] == i["n_chunks"]),
-    ]
-    # merge: n_kernels = the main kernel, the carry fix-up when there is more than one run, and the search kernel in
-    # front unless the main kernel searches its own coordinates (merge_path.hip, shape_merge)
-    searches_itself = lambda i: i["n_kernels"] == (2 if i["grid_blocks"] > 1 else 1)
-    runs = lambda k, i: k == "merge" and i["main_kernel"] == RUNS
-    sweeping = lambda i, e: i["block_threads"] == 1024 and 0 < i["window_elems"] < e["band"]
-    lines += [
-        ("merge: tile kernel, the search inside", lambda k, i, e: k == "merge" and i["main_kernel"] == TILE and searches_itself(i)),
-        ("merge: tile kernel, the search kernel in front",
-         lambda k, i, e: k == "merge" and i["main_kernel"] == TILE and not searches_itself(i)),
-        ("merge: run kernel, 256 threads", lambda k, i, e: runs(k, i) and i["block_threads"] == 256),
-        ("merge: run kernel, 512 threads", lambda k, i, e: runs(k, i) and i["block_threads"] == 512),
-        ("merge: run kernel, 1024 threads, one band-placed window",
-         lambda k, i, e: runs(k, i) and i["block_threads"] == 1024 and not sweeping(i, e)),
-        ("merge: run kernel, window_segments >= 2", lambda k, i, e: runs(k, i) and i["window_segments"] >= 2),
-        ("merge: run kernel, sweeping", lambda k, i, e: runs(k, i) and sweeping(i, e)),
-    ]
-    return lines
+    """(label, predicate over (kind, info, extra)) — every shape the plans kept as A must include (plan_census.py)."""
+    return row_kind_lines() + merge_lines()
 
 
 def test_census_of_the_plans_kept_as_a(sp, oracle):
@@ -283,8 +228,8 @@ def test_census_of_the_plans_kept_as_a(sp, oracle):
                 with arm_of(sp, arm):
                     plan, _ = keep_as_a(sp, state(oracle, gname), gname, arm, kind, a)
                     plan.destroy()
-    lanes = {kind: sorted({i["lanes_per_row"] for (g_, arm, k, a), (i, e) in _KEPT.items()
-                           if k == kind and i["main_kernel"] == PLAIN}) for kind in ("vector", "light")}
+    lanes = {kind: plain_lanes(kind, [(k, i) for (g_, arm, k, a), (i, e) in _KEPT.items()])
+             for kind in ("vector", "light")}
     missing = ["%s: the plain kernel with two lane widths (have %s)" % (kind, lanes[kind])
                for kind in ("vector", "light") if len(lanes[kind]) < 2]
     print("census of the plans kept as A (%d pairs run in this session)" % _PAIRS[0])

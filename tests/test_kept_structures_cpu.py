@@ -1,5 +1,6 @@
 """The structure catalogue of tests/kept_structures.py, checked without a GPU: what the GPU tests of kept one-shot
-plans (tests/test_gpu_kept_plans.py) assume about their inputs holds before anything goes to a device."""
+plans (tests/test_gpu_kept_plans.py) and of row-block plans (tests/test_gpu_block_shapes.py) assume about their inputs
+holds before anything goes to a device."""
 import numpy as np
 import pytest
 
@@ -40,6 +41,72 @@ def test_groups_hold_what_the_gpu_tests_need():
         assert not set(ks.hub_rows(n)) & (set(ks.probed_rows(n)) | set(ks.planted_rows(n)))
         assert ks.giant_row(n) not in set(ks.probed_rows(n)) | set(ks.planted_rows(n))
         assert g.nan_col != g.inf_col and 0 <= g.nan_col < g.n_cols and 0 <= g.inf_col < g.n_cols
+
+
+@pytest.mark.parametrize("group", list(ks.GROUPS))
+def test_real_values_are_reals_in_every_group(group):
+    """The values of the row-block tests: reals strictly inside (-1, 1) in the group's type — the fp32 groups too, whose
+    cross-product values are integers that sum to the same bits in any order — deterministic, of a seed of their own."""
+    g = ks.GROUPS[group]
+    Ax, x = ks.real_values(g)
+    assert Ax.dtype == g.val and x.dtype == g.val and Ax.shape == (g.nnz,) and x.shape == (g.n_cols,)
+    for a in (Ax, x):
+        assert np.abs(a).max() < 1 and a.min() < -0.99 and a.max() > 0.99 and abs(float(a.mean(dtype=np.float64))) < 0.01
+        assert np.unique(a[:1000]).size > 990 and np.count_nonzero(a[:1000] == np.round(a[:1000])) == 0
+    Ax2, x2 = ks.real_values(g)
+    assert np.array_equal(Ax, Ax2) and np.array_equal(x, x2)
+    del Ax2, x2
+    old_Ax, old_x = ks.values(g)
+    assert not np.array_equal(Ax[:1000], old_Ax[:1000]) and not np.array_equal(x[:1000], old_x[:1000])
+    # what the integers cannot show: one row of per_row products summed forwards and backwards differs in some row
+    k = g.per_row
+    prod = (Ax[:1000 * k] * x[np.arange(1000 * k) % g.n_cols]).reshape(1000, k)
+    fwd, bwd = np.zeros(1000, dtype=g.val), np.zeros(1000, dtype=g.val)
+    for j in range(k):
+        fwd += prod[:, j]
+        bwd += prod[:, k - 1 - j]
+    assert np.count_nonzero(fwd != bwd) > 100
+
+
+def check_phase_shifts(g, name, Ap, Aj):
+    """ks.phase_shifted at every shift the row-block tests use for this structure: row 1 loses its first d entries and
+    nothing else changes — not the sizes but for d, not a probed or planted row — and every later row start, so every cut
+    a partition can make, has phase (its old phase - d) & 3."""
+    from small_path import SMALL_PLAIN_NNZ
+    n = g.n_rows
+    Ap64 = Ap.astype(np.int64)
+    lens = np.diff(Ap64)
+    shifts = ks.phase_shifts(g, name)
+    special = np.concatenate([ks.probed_rows(n), ks.planted_rows(n)])
+    assert ks.SHIFT_ROW == 1 and ks.SHIFT_ROW not in set(special.tolist()) and shifts[0] == 0
+    starts = Ap64[:-1][lens > 0]
+    if name in ks.UNALIGNED:
+        assert shifts == (0,)
+        assert set((starts & 3).tolist()) == {0, 1, 2, 3}           # unaligned as they are
+    else:
+        assert lens[ks.SHIFT_ROW] >= 8
+        assert set(shifts) == {0, 1, 2, 3} if g.nnz <= SMALL_PLAIN_NNZ else (len(shifts) >= 2 and all(0 <= d <= 3 for d in shifts))
+    if name in ("band_narrow", "band_1024", "band_sweep", "stencil", "scatter"):
+        assert not np.any(starts & 3)                               # rows of one length, a multiple of 4: phase 0 only
+    sample = np.concatenate([special, np.arange(0, n, max(1, n // 500)), [0, 1, 2, n - 1]])
+    for d in shifts[1:]:
+        Ap_d, Aj_d = ks.phase_shifted(Ap, Aj, d)
+        assert Ap_d.dtype == Ap.dtype and Aj_d.dtype == Aj.dtype and Ap_d.shape == Ap.shape
+        assert int(Ap_d[0]) == 0 and int(Ap_d[-1]) == g.nnz - d == Aj_d.size
+        assert (g.nnz - d <= SMALL_PLAIN_NNZ) == (g.nnz <= SMALL_PLAIN_NNZ)  # a small group stays one, a big one big
+        Ad64 = Ap_d.astype(np.int64)
+        lens_d = np.diff(Ad64)
+        assert lens_d[ks.SHIFT_ROW] == lens[ks.SHIFT_ROW] - d and np.count_nonzero(lens_d != lens) == 1
+        assert np.array_equal(Ad64[:2], Ap64[:2]) and np.array_equal(Ad64[2:], Ap64[2:] - d)
+        if name not in ks.UNALIGNED and name in ("band_narrow", "band_1024", "band_sweep", "stencil", "scatter"):
+            assert set((Ad64[2:-1] & 3).tolist()) == {(-d) & 3}       # every row start after row 1: one non-zero phase
+        assert np.array_equal(Aj_d[:Ad64[1]], Aj[:Ap64[1]]) and np.array_equal(Aj_d[Ad64[2]:], Aj[Ap64[2]:])
+        assert np.array_equal(Aj_d[Ad64[1]:Ad64[2]], Aj[Ap64[1] + d:Ap64[2]])
+        for r in sample:                                            # the probed and planted rows: as they were
+            if r != ks.SHIFT_ROW:
+                assert np.array_equal(Aj_d[Ad64[r]:Ad64[r + 1]], Aj[Ap64[r]:Ap64[r + 1]]), (name, d, r)
+    Ap_0, Aj_0 = ks.phase_shifted(Ap, Aj, 0)
+    assert Ap_0 is Ap and Aj_0 is Aj
 
 
 @pytest.mark.parametrize("group,name", CASES)
@@ -105,6 +172,7 @@ def test_structure(group, name, group_values):
         others = others[lens[others] > 0]
         assert np.mean(np.abs(offsets_of(others)) > 10 * g.band_hw) > 0.5
         assert lens.min() == 0 and 150 <= lens.max() <= 200 and np.count_nonzero(lens == 0) > n // 200
+    check_phase_shifts(g, name, Ap, Aj)
     # the NaN and Inf columns: referenced, from far away at least (the planted rows), and in the banded structures
     # from the rows around them too
     for col in (g.nan_col, g.inf_col):
