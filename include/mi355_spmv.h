@@ -94,9 +94,27 @@ enum {
     MI355_PLAN_DEFAULT = 0,
     /* Keep results that depend only on Ap (merge-path tile coordinates) across
      * executes instead of recomputing them every call.  Valid while the caller
-     * leaves Ap unchanged.  Off by default: a default plan holds scratch memory
-     * and launch shapes only, and every execute runs every kernel of the kind. */
-    MI355_PLAN_REUSE_STRUCTURE = 1
+     * leaves Ap unchanged.  Off by default: every execute runs every kernel of
+     * the kind.                                                                */
+    MI355_PLAN_REUSE_STRUCTURE = 1,
+    /* What a default plan holds: scratch memory, launch shapes, and — a VECTOR plan
+     * of a banded matrix — a PACKED INDEX: one 16-bit number per nonzero, the
+     * column's position inside the LDS window of x that its chunk of rows stages
+     * (0xFFFF: outside it).  The banded kernel streams that instead of Aj, i.e. 2
+     * instead of 4 bytes per nonzero of index on every execute (the S32-band
+     * target reads 0.76 of the bytes).  Cost: 2 bytes per nonzero of device memory
+     * for the life of the plan and one extra pass over Aj at create.  It is built
+     * when the plan runs csr_vector_window_kernel with one window of at most
+     * 65 535 elements placed from the band the structure probe saw, equal-row
+     * chunks, and Aj is 16-byte aligned; if the memory cannot
+     * be had the plan is created without it.  plan_info reports its size.  It IS
+     * derived from the contents of Aj — which a plan's caller may not change
+     * anyway (see create below).
+     * With this flag the plan holds nothing derived from the contents of Aj.  The
+     * one-shot entry points and plan_acquire always set it: their plans are found
+     * again by pointer and stay right for arrays rewritten in place.
+     * MI355_SPMV_PACK=0 in the environment has the same effect on every plan.   */
+    MI355_PLAN_NO_INDEX_COPY = 2
 };
 
 /* ---- one-shot entry points -------------------------------------------------
@@ -137,15 +155,18 @@ MI355_SPMV_DECLARE_GENL(i64_i32, int64_t, int32_t)
  * The reference re-creates scratch on every call (quirks 7-9 of SURVEY.md §2c);
  * a plan keeps scratch and launch shapes across the timing loop of main.cu:102-113.
  * create: sizes + structure pointers (Ap/Aj are retained, not copied, and must
- *         outlive the plan; their CONTENTS are read here — a structure probe and,
- *         for VECTOR / LIGHT, the chunk boundaries — so they must already be valid
- *         and must not change while the plan lives).  Synchronises the device.
+ *         outlive the plan; their CONTENTS are read here — a structure probe,
+ *         for VECTOR / LIGHT the chunk boundaries, and for a banded VECTOR plan
+ *         one pass over all of Aj that builds its packed index (plan flags above;
+ *         not with MI355_PLAN_NO_INDEX_COPY) — so they must already be valid
+ *         and must not change while the plan lives: executes of a plan with a
+ *         packed index read the columns from that copy).  Synchronises the device.
  * execute: asynchronous on `stream`, no host sync, no allocation, kernels only
  *         (hipGraph-capturable: tests/test_gpu_parity.py).  A plan serves ONE
  *         stream at a time (its scratch — merge coordinates and carries, the LIGHT
  *         counters — belongs to the execute in flight); concurrent executes need
  *         one plan each.
- * destroy: frees scratch (hipFree: waits for the device).                      */
+ * destroy: frees scratch and the packed index (hipFree: waits for the device). */
 typedef struct mi355_spmv_plan mi355_spmv_plan;
 
 int mi355_spmv_plan_create(mi355_spmv_plan** plan, int kind, int off_type, int val_type,
@@ -189,7 +210,7 @@ typedef struct mi355_spmv_plan_info {
     int64_t tile_items;       /* MERGE: merge items per tile                       */
     int64_t n_tiles;          /* MERGE: tiles; LIGHT: row chunks                   */
     int64_t rows_per_chunk;   /* LIGHT: rows per dequeue                           */
-    int64_t scratch_bytes;    /* device scratch held by the plan                   */
+    int64_t scratch_bytes;    /* device memory held by the plan: scratch + packed index */
     int32_t n_kernels;        /* kernels launched per execute                      */
     int32_t window_elems;     /* elements of x staged through LDS per workgroup (0 = none) */
     int32_t window_segments;  /* 1 = one window; 2..4 = that many column bands staged side by side */
@@ -199,6 +220,8 @@ typedef struct mi355_spmv_plan_info {
     int32_t rows_cap;         /* VECTOR, LIGHT: most rows a chunk can hold                                 */
     int64_t n_chunks;         /* VECTOR, LIGHT: row chunks                                                 */
     char knobs[160];          /* the MI355_* tuning variables that were set when the plan was created, "NAME=value ..." */
+    int64_t packed_index_bytes;   /* VECTOR: bytes of the plan's packed index (2 per nonzero + padding); 0 = the plan reads Aj */
+    int64_t packed_index_escapes; /* ... and how many nonzeros lie outside their chunk's window (their columns are read from Aj) */
 } mi355_spmv_plan_info;
 int mi355_spmv_plan_get_info(const mi355_spmv_plan* plan, mi355_spmv_plan_info* info);
 
@@ -351,11 +374,12 @@ int mi355_spmv_knobs_reload(void);
 /* The one-shot entry points keep their last few plans, found again by the pointers and sizes of Ap / Aj, the types, the
  * kind and the device (the reference's harness calls a kind 2 000 times in a row on one matrix, main.cu:102-113; plan
  * creation is a third of such a call on the target).  Safe if the arrays were rewritten in place: a kept plan holds
- * launch-shape decisions only (plans with giant rows, whose row list is structure, are never kept).
+ * launch-shape decisions only (it is created with MI355_PLAN_NO_INDEX_COPY, so it has no packed index; plans with giant
+ * rows, whose row list is structure, are never kept).
  * MI355_SPMV_PLAN_CACHE=0 disables it; this call destroys the kept plans and frees their scratch.                  */
 int mi355_spmv_cache_release(void);
 /* The same for a caller that wants its own timer between the steps (the C++ mirror of the reference boundary,
- * host/spmv/mi355.hpp): acquire = a kept plan for this matrix or a new default plan; release = hand it back after the
+ * host/spmv/mi355.hpp): acquire = a kept plan for this matrix or a new one (MI355_PLAN_NO_INDEX_COPY); release = hand it back after the
  * stream it ran on has been synchronised (executed_ok = 0 after a failed execute: the plan is destroyed).  A plan whose
  * semiring was changed is handed back with it (the next acquirer sets its own); alpha / beta other than 1 / 0 are not kept. */
 int mi355_spmv_plan_acquire(mi355_spmv_plan** plan, int kind, int off_type, int val_type, int32_t n_rows,

@@ -22,6 +22,7 @@ LABELS = {"hip_vector": "vector", "hip_merge": "merge", "hip_light": "light", "h
 OFF_TYPES = {torch.int32: (0, "i32"), torch.int64: (1, "i64")}
 VAL_TYPES = {torch.float32: (0, "f32"), torch.float64: (1, "f64"), torch.int32: (2, "i32")}   # (int32 values: the merge kind only)
 PLAN_REUSE_STRUCTURE = 1
+PLAN_NO_INDEX_COPY = 2       # the plan holds nothing derived from the contents of Aj (no packed index)
 SEMIRINGS = {"plus_times": 0, "min_plus": 1, "max_times": 2, "max_plus": 3, "or_and": 4}
 
 EXPORTS = (
@@ -51,7 +52,7 @@ class PlanInfo(C.Structure):
                 ("rows_per_chunk", C.c_int64), ("scratch_bytes", C.c_int64), ("n_kernels", C.c_int32),
                 ("window_elems", C.c_int32), ("window_segments", C.c_int32), ("main_kernel", C.c_char * 64),
                 ("balanced_chunks", C.c_int32), ("rows_cap", C.c_int32), ("n_chunks", C.c_int64),
-                ("knobs", C.c_char * 160)]
+                ("knobs", C.c_char * 160), ("packed_index_bytes", C.c_int64), ("packed_index_escapes", C.c_int64)]
 
     def as_dict(self):
         d = {n: getattr(self, n) for n, _ in self._fields_}

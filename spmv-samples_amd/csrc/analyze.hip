@@ -56,6 +56,7 @@ static void parse_knobs(Knobs& k) {
     getl("MI355_SPMV_GIANT_ROW", k.giant_row);
     geti("MI355_SPMV_PLAIN", k.plain);
     geti("MI355_SPMV_SMALL", k.small);
+    geti("MI355_SPMV_PACK", k.pack);
     getl("MI355_SPMV_REL32_LIMIT", k.rel32_limit);
     geti("MI355_LIGHT_BLOCKS_PER_CU", k.light_blocks_per_cu);
     geti("MI355_LIGHT_CHUNK_DIV", k.light_chunk_div);
@@ -490,6 +491,99 @@ int build_chunk_table(Plan& p) {
                            p.is_block ? p.block_weight_off : -p.nnz_begin, p.is_block ? p.block_chunk_begin : int64_t(0));
     MI355_HIP_TRY(hipGetLastError());
     MI355_HIP_TRY(hipStreamSynchronize(nullptr));   // the first execute may come on any stream
+    return MI355_SPMV_OK;
+}
+
+// ---- the packed index of a banded VECTOR plan -----------------------------------------------------------
+// On the flagship (S32-band, 2^22 rows x 32, fp32) Aj is 537 MB of the 1 124 MB an execute reads, and all the kernel
+// does with a column is subtract the start of its chunk's window and range-check the difference (XWindow::find).  When
+// every chunk's window is placed from the plan's band — a function of the chunk's rows and the plan alone
+// (xwindow.hpp, band_window) — that difference can be stored once: 16 bits per nonzero, kPackedEscape for a column
+// outside the window (the kernel then reads the real column from Aj, as it reads x from memory for it today).
+// One workgroup per chunk of the plan's ChunkMap; it writes exactly the elements [Ap[rb], Ap[re]) of its rows.
+template <typename val_t>
+__global__ __launch_bounds__(kBlock) void pack_index_kernel(int32_t n_rows, int32_t n_cols, const ApView Ap,
+                                                            const int32_t* __restrict__ Aj, uint16_t* __restrict__ out,
+                                                            ChunkMap cmap, int32_t window_cap, BandHint hint,
+                                                            unsigned long long* escapes) {
+    int64_t rb, re;
+    cmap.range(blockIdx.x, n_rows, rb, re);
+    if (rb >= re) return;
+    const int64_t s = Ap.at(rb), e = Ap.at(re);
+    const WindowSpan w = band_window<val_t>(rb, re, n_cols, window_cap, hint);
+    unsigned escaped = 0;
+    auto encode = [&](int32_t col) -> unsigned {
+        const unsigned rel = unsigned(col - w.lo);
+        const bool in = rel < unsigned(w.len);
+        escaped += in ? 0u : 1u;
+        return in ? rel : kPackedEscape;
+    };
+    // whole 16-byte groups of Aj -> 8-byte groups of the index; the elements before the first and after the last singly
+    const int64_t s4 = min((s + 3) & ~int64_t(3), e), e4 = max(e & ~int64_t(3), s4);
+    const int tid = threadIdx.x;
+    if (tid < s4 - s) out[s + tid] = uint16_t(encode(Aj[s + tid]));
+    if (tid < e - e4) out[e4 + tid] = uint16_t(encode(Aj[e4 + tid]));
+    for (int64_t k = s4 + int64_t(tid) * 4; k < e4; k += int64_t(kBlock) * 4) {
+        const int4v c = stream_load(reinterpret_cast<const int4v*>(Aj + k));
+        uint2v v;
+        v[0] = encode(c[0]) | (encode(c[1]) << 16);
+        v[1] = encode(c[2]) | (encode(c[3]) << 16);
+        *reinterpret_cast<uint2v*>(out + k) = v;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) escaped += __shfl_xor(escaped, o, kWave);
+    if ((tid & (kWave - 1)) == 0 && escaped) atomicAdd(escapes, (unsigned long long)escaped);
+}
+
+// Which plans hold one: kind VECTOR on the chunked kernels with ONE window of at most 65 535 elements that every chunk
+// places from the band, equal-row chunks, a 16-byte-aligned Aj, and neither MI355_PLAN_NO_INDEX_COPY nor
+// MI355_SPMV_PACK=0.  No device memory for it: the plan stays unpacked, which is not an error.  Synchronises (the first
+// execute may come on any stream; the escape count comes back with it).
+int build_packed_index(Plan& p) {
+    p.packed_index = nullptr;
+    p.packed_bytes = 0;
+    p.packed_escapes = 0;
+    if (p.kind != MI355_KIND_VECTOR || (p.flags & MI355_PLAN_NO_INDEX_COPY) || p.knob.pack == 0) return MI355_SPMV_OK;
+    if (p.small_plain || p.sweep || p.balanced || (p.knob.plain != 0 && !p.is_block)) return MI355_SPMV_OK;
+    if (p.window_elems <= 0 || p.window_elems > 65535 || p.n_seg >= 2 || !p.window_from_band) return MI355_SPMV_OK;
+    if (p.n_rows <= 0 || p.nnz < 4 || p.nnz <= p.nnz_begin || p.n_chunks < 1 || p.n_chunks > int64_t(UINT32_MAX)) return MI355_SPMV_OK;
+    if ((reinterpret_cast<uintptr_t>(p.Aj) & 15u) != 0) return MI355_SPMV_OK;
+    // every 8-byte group the kernels address lies below nnz_read rounded up to a group (their clamped loads included:
+    // j_max = the last whole group); one group more, and the allocation is 256-byte aligned
+    const size_t bytes = (((size_t(p.nnz_read) + 3) & ~size_t(3)) + 4) * sizeof(uint16_t);
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return MI355_SPMV_OK;
+    }
+    std::lock_guard<std::mutex> lock(g_analysis_mutex);
+    unsigned long long* d_escapes = reinterpret_cast<unsigned long long*>(analysis_buffer());
+    hipError_t e = d_escapes ? hipSuccess : hipErrorOutOfMemory;
+    // elements that belong to no row of this plan (a block's phase, the tail of its last group, the padding) escape
+    if (e == hipSuccess) e = hipMemsetAsync(ptr, 0xFF, bytes, nullptr);
+    if (e == hipSuccess) e = hipMemsetAsync(d_escapes, 0, sizeof(unsigned long long), nullptr);
+    if (e == hipSuccess) {
+        const ApView Ap{p.Ap, p.off_type == MI355_OFF_I64 ? 1 : 0};
+        const BandHint hint{p.band_lo, p.band_hi, true};
+        const dim3 grid((unsigned)p.n_chunks), block(kBlock);
+        if (p.val_type == MI355_VAL_F64)
+            hipLaunchKernelGGL((pack_index_kernel<double>), grid, block, 0, nullptr, p.n_rows, p.n_cols, Ap, p.Aj,
+                               static_cast<uint16_t*>(ptr), chunk_map_of(p), (int32_t)p.window_elems, hint, d_escapes);
+        else
+            hipLaunchKernelGGL((pack_index_kernel<float>), grid, block, 0, nullptr, p.n_rows, p.n_cols, Ap, p.Aj,
+                               static_cast<uint16_t*>(ptr), chunk_map_of(p), (int32_t)p.window_elems, hint, d_escapes);
+        e = hipGetLastError();
+    }
+    unsigned long long escaped = 0;
+    if (e == hipSuccess) e = hipMemcpy(&escaped, d_escapes, sizeof(escaped), hipMemcpyDeviceToHost);   // synchronises
+    if (e != hipSuccess) {
+        (void)hipFree(ptr);
+        set_error("build_packed_index: %s", hipGetErrorString(e));
+        return MI355_SPMV_EHIP;
+    }
+    p.packed_index = static_cast<uint16_t*>(ptr);
+    p.packed_bytes = bytes;
+    p.packed_escapes = int64_t(escaped);
     return MI355_SPMV_OK;
 }
 

@@ -202,7 +202,9 @@ static int plan_acquire(mi355_spmv_plan** out, int kind, int off_type, int val_t
     const bool cache = oneshot_cache_enabled() && nnz > 0 && hipGetDevice(&key.device) == hipSuccess;
     *out = cache ? oneshot_take(key) : nullptr;
     if (*out) return MI355_SPMV_OK;
-    const int st = mi355_spmv_plan_create(out, kind, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, MI355_PLAN_DEFAULT);
+    // (NO_INDEX_COPY: a kept plan is found again by pointers and must stay right for arrays rewritten in place, so it may
+    // hold nothing derived from the contents of Aj)
+    const int st = mi355_spmv_plan_create(out, kind, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, MI355_PLAN_NO_INDEX_COPY);
     if (st == MI355_SPMV_OK && cache) (*out)->acquired_on = key.device;
     return st;
 }
@@ -383,7 +385,9 @@ static int plan_create_impl(mi355_spmv_plan** out, int kind, int off_type, int v
     }
     int st = plan_alloc_scratch(p);
     if (st == MI355_SPMV_OK) st = build_chunk_table(p);
+    if (st == MI355_SPMV_OK) st = build_packed_index(p);
     if (st != MI355_SPMV_OK) {
+        if (p.packed_index) (void)hipFree(p.packed_index);
         if (p.scratch) (void)hipFree(p.scratch);
         delete h;
         return st;
@@ -527,6 +531,10 @@ int mi355_spmv_plan_destroy(mi355_spmv_plan* h) {
         hipError_t e = hipFree(h->p.scratch);
         if (e != hipSuccess) { set_error("hipFree -> %s", hipGetErrorString(e)); st = MI355_SPMV_EHIP; }
     }
+    if (h->p.packed_index) {
+        hipError_t e = hipFree(h->p.packed_index);
+        if (e != hipSuccess) { set_error("hipFree -> %s", hipGetErrorString(e)); st = MI355_SPMV_EHIP; }
+    }
     delete h;
     return st;
 }
@@ -581,7 +589,9 @@ int mi355_spmv_plan_get_info(const mi355_spmv_plan* h, mi355_spmv_plan_info* inf
     info->tile_items = p.tile_items;
     info->n_tiles = p.n_tiles;
     info->rows_per_chunk = p.rows_per_chunk;
-    info->scratch_bytes = (int64_t)p.scratch_bytes;
+    info->scratch_bytes = (int64_t)(p.scratch_bytes + p.packed_bytes);
+    info->packed_index_bytes = (int64_t)p.packed_bytes;
+    info->packed_index_escapes = p.packed_escapes;
     info->n_kernels = p.n_kernels;
     info->window_elems = p.window_elems;
     info->window_segments = p.window_elems > 0 ? (p.n_seg >= 2 ? p.n_seg : 1) : 0;

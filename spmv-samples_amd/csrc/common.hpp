@@ -97,6 +97,7 @@ struct Knobs {
     int64_t giant_row = 0;     // MI355_SPMV_GIANT_ROW        nonzeros beyond which a row is giant (>= 4096)
     int plain = 0;             // MI355_SPMV_PLAIN            1 = the 4-byte-per-lane fallback kernels
     int small = -1;            // MI355_SPMV_SMALL            0 = small matrices keep the chunked kernels too (VECTOR / LIGHT)
+    int pack = -1;             // MI355_SPMV_PACK             0 = no plan holds a packed index (1 = the default: banded VECTOR plans do)
     int64_t rel32_limit = 0;   // MI355_SPMV_REL32_LIMIT      tests: nonzero span beyond which a chunk leaves the 32-bit path
     int light_blocks_per_cu = 0;   // MI355_LIGHT_BLOCKS_PER_CU
     int light_chunk_div = 0;   // MI355_LIGHT_CHUNK_DIV
@@ -192,6 +193,11 @@ struct Plan {
     int32_t* carry_row;    // [n_super]
     void* carry_val;       // [n_super] of value type
     unsigned long long* counters;  // LIGHT: kXcds shards, one 128-B line each
+    // VECTOR, one window placed from the band, equal-row chunks: a 16-bit window-relative copy of Aj (build_packed_index).
+    // An allocation of its own — never part of `scratch`, which a released one-shot plan hands on to the next plan.
+    uint16_t* packed_index;        // [nnz_read + padding] in the numbering of Aj, or nullptr
+    size_t packed_bytes;           // bytes of that allocation (0 = none)
+    int64_t packed_escapes;        // nonzeros whose column lies outside their chunk's window (stored as kPackedEscape)
     bool light_dequeue_once;       // LIGHT, equal-row chunks: one workgroup and one dequeue per chunk (else by index)
     int n_kernels;
     bool small_plain = false;   // VECTOR / LIGHT: a matrix small enough for the plain one-pass kernel to win (analyze.hip, shape_rows)
@@ -219,6 +225,7 @@ int pick_window_elems(Plan& p, int64_t rows_per_workgroup);
 int64_t segment_rows_fit(const Plan& p);
 int long_steps_for(const Plan& p);   // steps of its vector after which a row is left to the long-row pass
 int build_chunk_table(Plan& p);    // after the scratch is allocated
+int build_packed_index(Plan& p);   // after the shape is final: the packed index of a plan that qualifies (synchronises)
 int find_giant_rows(Plan& p);      // balanced plans: rows beyond kGiantRow nonzeros (synchronises)
 void shape_merge(Plan& p);
 int shape_rows(Plan& p);           // VECTOR / LIGHT, whole plans: the shape, then set_rows_launch (synchronises)

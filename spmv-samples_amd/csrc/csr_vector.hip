@@ -29,11 +29,14 @@ namespace mi355 {
 // by the same numbers: a kernel that silently needs a few more registers than its plan assumed loses 30-40 %
 // there — cant stand-in: 14.7 -> 19-21 us when its body went from 127 to 139 VGPRs.)  The kernel does not depend on the width
 // of the row offsets: a chunk is walked with 32-bit offsets relative to its own first nonzero (xwindow.hpp).
-template <int BLOCK, int T, int R, int NSEG, bool ADAPT, typename val_t>
+// PACKED (NSEG == 1, equal-row chunks, the window placed from the plan's band): the loop streams the plan's 16-bit
+// window indices Aj16 instead of Aj (xwindow.hpp, chunk_rows; analyze.hip, build_packed_index); Aj16 is unused otherwise.
+template <int BLOCK, int T, int R, int NSEG, bool ADAPT, typename val_t, bool PACKED = false>
 __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock || R == 2 ? 4 : 3)) void csr_vector_window_kernel(
     int32_t n_rows, int32_t n_cols, int64_t nnz, const ApView Ap, const int32_t* __restrict__ Aj,
     const val_t* __restrict__ Ax, const val_t* __restrict__ x, val_t* __restrict__ y, ChunkMap cmap,
-    int32_t window_cap, BandHint hint, SegmentPlan segs, val_t alpha, val_t beta) {
+    int32_t window_cap, BandHint hint, SegmentPlan segs, const uint16_t* __restrict__ Aj16, val_t alpha, val_t beta) {
+    static_assert(!PACKED || (NSEG == 1 && !ADAPT), "the packed index exists for one band-placed window and equal-row chunks");
     // NSEG: 0 = no window (plain gathers), 1 = one window of x in LDS, kMaxSegments = several bands
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // window | bounds | y | flags
     __shared__ int s_red[2];
@@ -76,7 +79,11 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock || R == 2 ? 4 : 3)) voi
         auto stage = [&] {
             return stage_x_window<val_t>(rb, re, n_cols, first_last, x, scr.s_x, window_cap, s_red, hint);
         };
-        chunk_rows_any<BLOCK, T, R, NSEG == 1, ADAPT, val_t>(rb, re, nnz_c, Aj_c, Ax_c, x, y, stage, scr);
+        if constexpr (PACKED)   // (hint.use holds: the window staged is the one the index was encoded against)
+            chunk_rows_any<BLOCK, T, R, true, false, val_t, decltype(stage)&, false, true>(rb, re, nnz_c, Aj_c, Ax_c, x, y, stage,
+                                                                                          scr, Aj16 + base);
+        else
+            chunk_rows_any<BLOCK, T, R, NSEG == 1, ADAPT, val_t>(rb, re, nnz_c, Aj_c, Ax_c, x, y, stage, scr);
     }
 }
 
@@ -135,8 +142,9 @@ struct VectorRows {
     static constexpr const char* name = "csr_vector";
     static constexpr bool kCounters = false;   // (LIGHT's kernels take its dequeue counters)
     static constexpr bool kPlainKnob = true;   // MI355_SPMV_PLAIN forces the 4-byte kernel on whole plans (LIGHT ignores it)
-    template <int BLOCK, int T, int R, int NSEG, bool ADAPT, typename val_t>
-    static auto window() { return csr_vector_window_kernel<BLOCK, T, R, NSEG, ADAPT, val_t>; }
+    static constexpr bool kPackedIndex = true; // its window kernels take the plan's packed index and have PACKED twins
+    template <int BLOCK, int T, int R, int NSEG, bool ADAPT, typename val_t, bool PACKED = false>
+    static auto window() { return csr_vector_window_kernel<BLOCK, T, R, NSEG, ADAPT, val_t, PACKED>; }
     template <int T, int R, typename val_t>
     static auto sweep() { return csr_vector_sweep_kernel<T, R, val_t>; }
     template <typename off_t, typename val_t>

@@ -340,6 +340,7 @@ struct LightRows {
     static constexpr bool kPlainKnob = false;
     template <int BLOCK, int T, int R, int NSEG, bool ADAPT, typename val_t>
     static auto window() { return light_rows_window_kernel<BLOCK, T, R, NSEG, ADAPT, val_t>; }
+    static constexpr bool kPackedIndex = false;   // (VECTOR only: LIGHT plans hold no packed index)
     template <int T, int R, typename val_t>
     static auto sweep() { return light_rows_sweep_kernel<T, R, val_t>; }
     // unaligned operands: light_rows_kernel on the plan's grid, a dequeue of rows_per_chunk rows per wave

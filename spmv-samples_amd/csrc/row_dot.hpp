@@ -19,6 +19,8 @@
 namespace mi355 {
 
 typedef int int4v __attribute__((ext_vector_type(4)));
+typedef unsigned uint2v __attribute__((ext_vector_type(2)));   // four 16-bit window indices (xwindow.hpp, PACKED)
+constexpr unsigned kPackedEscape = 0xFFFFu;                    // ... and the one that says "outside the window"
 typedef float float4v __attribute__((ext_vector_type(4)));
 typedef double double4v __attribute__((ext_vector_type(4)));
 

@@ -68,13 +68,16 @@ static int launch_rows_window(const RowOperands<val_t>& o, const off_t* Ap) {
         if (p.window_elems <= 0 || p.n_seg >= 2) return launch_rows_window<Kind, kBlock>(o, Ap);
     }
     const BandHint hint{p.band_lo, p.band_hi, p.window_from_band};
-    const ChunkMap cmap{p.balanced ? p.chunk_row : nullptr, (int32_t)p.rows_per_chunk, (int32_t)p.rows_cap, p.n_chunks,
-                        long_steps_for(p), p.n_giant > 0 ? p.giant_len : int64_t(0),
-                        p.knob.rel32_limit > 0 ? p.knob.rel32_limit : kRel32Limit, p.light_dequeue_once ? 1 : 0};
+    const ChunkMap cmap = chunk_map_of(p);
     SegmentPlan segs;
     segs.n = p.n_seg;
     for (int i = 0; i < kMaxSegments; ++i) { segs.lo[i] = p.seg_lo[i]; segs.hi[i] = p.seg_hi[i]; }
-    auto go = [&](auto kernel) { return launch_chunked<Kind, val_t>(kernel, BLOCK, o, cmap, hint, segs); };
+    auto go = [&](auto kernel) {
+        if constexpr (Kind::kPackedIndex)
+            return launch_chunked<Kind, val_t>(kernel, BLOCK, o, cmap, hint, segs, (const uint16_t*)p.packed_index);
+        else
+            return launch_chunked<Kind, val_t>(kernel, BLOCK, o, cmap, hint, segs);
+    };
     if constexpr (BLOCK == kBlock) if (p.balanced) {   // vector width per chunk (chunk_rows_any); the T of the template is not used
         // (the weight-cut layout holds up to 2 K rows of bounds and results next to the window: may pass 64 KB)
         constexpr int R = rows_in_flight(sizeof(val_t), 2);
@@ -90,6 +93,12 @@ static int launch_rows_window(const RowOperands<val_t>& o, const off_t* Ap) {
             if constexpr (BLOCK == kBlock) return go(Kind::template window<BLOCK, T, R, kMaxSegments, false, val_t>());
             set_error("%s: no 512-thread kernel for a multi-band window", Kind::name);
             return MI355_SPMV_EINVAL;
+        }
+        if constexpr (Kind::kPackedIndex) {
+            // the plan holds 16-bit window indices (build_packed_index made sure of the shape: one window placed from
+            // the band, equal-row chunks; the operands' alignment was checked by launch_rows): the twin that streams them
+            if (p.packed_index && p.window_elems > 0 && p.window_from_band)
+                return go(Kind::template window<BLOCK, T, R, 1, false, val_t, true>());
         }
         if (p.window_elems > 0) return go(Kind::template window<BLOCK, T, R, 1, false, val_t>());
         if constexpr (BLOCK == kBlock) return go(Kind::template window<BLOCK, T, R, 0, false, val_t>());

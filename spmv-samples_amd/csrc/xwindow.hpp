@@ -107,6 +107,42 @@ struct BandHint {
     bool use;
 };
 
+// Where a window sits: x[lo, lo + len), len == 0 = none.
+struct WindowSpan {
+    int32_t lo, len;
+};
+
+// The window for the column span [lo, hi] (0 <= lo <= hi < n_cols) under a capacity of `cap` elements.  A span taken
+// from the plan's band (`from_band`) is taken as it is; a sampled one may miss the extremes and is widened by an eighth
+// (+64) on each side.  A span beyond the capacity gets a window centred on it.
+template <typename val_t>
+__device__ __forceinline__ WindowSpan place_window(int lo, int hi, int32_t n_cols, int32_t cap, bool from_band) {
+    constexpr int PER16 = 16 / int(sizeof(val_t));   // elements per 16-byte load
+    const int span = hi - lo + 1;
+    if (cap <= 0 || span / 16 > cap) return WindowSpan{0, 0};   // columns scattered far beyond what LDS can hold: not worth a window
+    int len = from_band ? span + (PER16 - 1) : span + 2 * (span / 8 + 64);   // (+: the start is rounded down to 16 bytes)
+    if (len > cap) len = cap;
+    if (len > n_cols) len = n_cols;
+    int64_t start = (int64_t(lo) + hi + 1 - len) / 2;
+    if (start + len > n_cols) start = n_cols - len;
+    if (start < 0) start = 0;
+    lo = int(start) & ~(PER16 - 1);                  // x is 16-byte aligned (checked on the host)
+    if (lo + len > n_cols) len = n_cols - lo;
+    return WindowSpan{lo, len};
+}
+
+// The window of the chunk of rows [rb, re), re > rb, placed from the plan's band (hint.use): a function of these five
+// values alone.  stage_x_window stages exactly this window on the hinted path, and the plan's packed index
+// (analyze.hip, pack_index_kernel) encodes every column against it — both call this, so they cannot disagree.
+template <typename val_t>
+__device__ __forceinline__ WindowSpan band_window(int64_t rb, int64_t re, int32_t n_cols, int32_t cap, const BandHint& hint) {
+    const int64_t l = rb + hint.lo, h = re - 1 + hint.hi;
+    const int lo = int(l < 0 ? 0 : (l >= n_cols ? n_cols - 1 : l));
+    const int hi = int(h < 0 ? 0 : (h >= n_cols ? n_cols - 1 : h));
+    if (hi < 0) return WindowSpan{0, 0};             // (no columns at all)
+    return place_window<val_t>(lo, hi, n_cols, cap, true);
+}
+
 // first_last(r, first, last): the first and last stored column of row r (false when the row is empty) — the
 // merge kernel reads them through Ap, the row-chunk kernels through the bounds they already hold in LDS.
 template <typename val_t, typename FirstLast>
@@ -128,10 +164,9 @@ __device__ __forceinline__ XWindow<val_t> stage_x_window(int64_t rb, int64_t re,
         __syncthreads();   // callers rely on this function being a workgroup barrier
         return none;
     }
+    WindowSpan span;
     if (hint.use && re > rb) {
-        const int64_t l = rb + hint.lo, h = re - 1 + hint.hi;
-        lo = int(l < 0 ? 0 : (l >= n_cols ? n_cols - 1 : l));
-        hi = int(h < 0 ? 0 : (h >= n_cols ? n_cols - 1 : h));
+        span = band_window<val_t>(rb, re, n_cols, cap, hint);
     } else {
     // kSamples rows spread evenly over the chunk, first and last row included.  NOT
     // every row: the first and last column of a 32-nonzero row sit in the two cache
@@ -156,35 +191,20 @@ __device__ __forceinline__ XWindow<val_t> stage_x_window(int64_t rb, int64_t re,
     __syncthreads();
     lo = s_red[0];
     hi = s_red[1];
+    // (hi < 0: no sampled row has a nonzero)
+    span = hi < 0 ? WindowSpan{0, 0} : place_window<val_t>(lo, hi, n_cols, cap, hint.use);
     }
     XWindow<val_t> win;
     win.s_x = s_x;
-    if (hi < 0) {          // no sampled row has a nonzero: no window, every gather goes to global
-        win.lo = 0;
-        win.len = 0;
+    win.lo = span.lo;
+    win.len = span.len;
+    if (span.len <= 0) {   // no window: every gather goes to global
         __syncthreads();
         return win;
     }
     constexpr int PER16 = 16 / int(sizeof(val_t));   // elements per 16-byte load
-    // The samples may miss the extremes: widen the sampled span by an eighth (+64) on
-    // each side; if that exceeds the capacity, centre the window on the span.
-    const int span = hi - lo + 1;
-    if (cap <= 0 || span / 16 > cap) {   // columns scattered far beyond what LDS can hold: not worth a window
-        win.lo = 0;
-        win.len = 0;
-        __syncthreads();
-        return win;
-    }
-    int len = hint.use ? span + (PER16 - 1) : span + 2 * (span / 8 + 64);   // (+: the start is rounded down to 16 bytes)
-    if (len > cap) len = cap;
-    if (len > n_cols) len = n_cols;
-    int64_t start = (int64_t(lo) + hi + 1 - len) / 2;
-    if (start + len > n_cols) start = n_cols - len;
-    if (start < 0) start = 0;
-    lo = int(start) & ~(PER16 - 1);                  // x is 16-byte aligned (checked on the host)
-    if (lo + len > n_cols) len = n_cols - lo;
-    win.lo = lo;
-    win.len = len;
+    lo = span.lo;
+    const int len = span.len;
     using v16 = typename std::conditional<sizeof(val_t) == 4, float4v, double __attribute__((ext_vector_type(2)))>::type;
     int full = (min(lo + len, n_cols & ~(PER16 - 1)) - lo) / PER16;   // whole 16-byte groups inside x
     if (full < 0) full = 0;
@@ -304,6 +324,13 @@ struct ChunkMap {
         }
     }
 };
+
+// the chunks of a VECTOR / LIGHT plan, as its kernels take them
+inline ChunkMap chunk_map_of(const Plan& p) {
+    return ChunkMap{p.balanced ? p.chunk_row : nullptr, (int32_t)p.rows_per_chunk, (int32_t)p.rows_cap, p.n_chunks,
+                    long_steps_for(p), p.n_giant > 0 ? p.giant_len : int64_t(0),
+                    p.knob.rel32_limit > 0 ? p.knob.rel32_limit : kRel32Limit, p.light_dequeue_once ? 1 : 0};
+}
 
 __host__ __device__ inline size_t lds_align16(size_t v) { return (v + 15) & ~size_t(15); }
 __host__ __device__ inline size_t chunk_lds_bytes(int window_elems, int rows, size_t val_bytes) {
@@ -429,13 +456,20 @@ __device__ __forceinline__ void store_chunk_results(const ChunkScratch<val_t>& s
 //    are in flight), so a chunk's prologue costs one memory round trip, not two.
 // All BLOCK threads of the workgroup must call (wave-wide shuffles and barriers inside); the caller
 // has run stage_chunk_bounds + a barrier; `stage()` returns the window and ends with a barrier.
-template <int BLOCK, int T, int R, bool WINDOW, typename val_t, typename StageFn>
+// PACKED (the plan's packed index, analyze.hip build_packed_index; WINDOW only): Aj16[k] is the 16-bit index of
+// Aj[k] INSIDE the window of the chunk that owns element k, kPackedEscape when the column is outside it.  The
+// pipelined loop streams 8 bytes of Aj16 per group of four instead of 16 bytes of Aj; Aj itself is read only for an
+// escaped element, in the long-row passes and for the arrays' last, partial group.  Same arithmetic in the same order.
+template <int BLOCK, int T, int R, bool WINDOW, typename val_t, bool PACKED = false, typename StageFn>
 __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_end, int32_t nnz,
                                            const int32_t* __restrict__ Aj,
                                            const val_t* __restrict__ Ax, const val_t* __restrict__ x,
                                            val_t* __restrict__ y, StageFn&& stage,
-                                           const ChunkScratch<val_t>& scr) {
+                                           const ChunkScratch<val_t>& scr,
+                                           const uint16_t* __restrict__ Aj16 = nullptr) {
+    static_assert(!PACKED || WINDOW, "a packed index is window-relative");
     using v4 = typename Vec4<val_t>::type;
+    using col4 = typename std::conditional<PACKED, uint2v, int4v>::type;   // four columns as a group is loaded
     using off_t = int32_t;                                 // chunk-relative offsets
     constexpr int VECS = BLOCK / T;
     constexpr int WAVES = BLOCK / kWave;
@@ -465,8 +499,12 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
     // is consumed (2 R ds_reads) instead of riding along through the previous group's arithmetic — 2 R registers per
     // set that the wide fp32 bodies, held to 128, do not have (they spilled).
     struct Group {
-        int4v c[R];
+        col4 c[R];
         v4 a[R];
+    };
+    auto load_cols = [&](off_t jl) {
+        if constexpr (PACKED) return stream_load(reinterpret_cast<const uint2v*>(Aj16 + jl));
+        else return stream_load(reinterpret_cast<const int4v*>(Aj + jl));
     };
     struct Bounds { off_t lo[R], hi[R]; };
     auto read_bounds = [&](int g, Bounds& B) {
@@ -488,7 +526,7 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
             off_t jl = j0 < B.hi[r] ? j0 : (B.lo[r] & ~off_t(3));
             jl = jl < j_max ? jl : j_max;
             // straight-line, branch-free: hipcc serialises (vmcnt(0)) around loads in branches
-            G.c[r] = stream_load(reinterpret_cast<const int4v*>(Aj + jl));
+            G.c[r] = load_cols(jl);
             G.a[r] = stream_load(reinterpret_cast<const v4*>(Ax + jl));
         }
         // (nothing of the consume that follows may be scheduled above these loads: its first instructions wait for the
@@ -518,8 +556,26 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
     // so the address is always in range), pinned the same way.
     auto pin4 = [](val_t (&v)[4]) { asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3])); };
     // the window part of a step: lookups and reads only (no use of the values) ...
-    auto gather4 = [&](const int4v& c, val_t (&xv)[4], bool (&in)[4]) {
-        if constexpr (WINDOW) {
+    auto gather4 = [&](const auto& c, val_t (&xv)[4], bool (&in)[4]) {
+        constexpr bool packed_group = std::is_same<std::decay_t<decltype(c)>, uint2v>::value;
+        if constexpr (PACKED) {
+            // a packed group: the index is already window-relative.  The escape value and an element of a neighbouring
+            // chunk (encoded against that chunk's window; always masked) fail the one compare, so no address leaves the
+            // window.  (The long-row passes still come with the columns themselves.)
+            unsigned idx[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (packed_group) {
+                    const unsigned rel = (e & 1) ? (c[e >> 1] >> 16) : (c[e >> 1] & 0xFFFFu);
+                    in[e] = rel < unsigned(win.len);
+                    idx[e] = in[e] ? rel : 0u;
+                } else {
+                    in[e] = win.find(c[e], idx[e]);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xv[e] = win.s_x[idx[e]];
+        } else if constexpr (WINDOW) {
             unsigned idx[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) in[e] = win.find(c[e], idx[e]);
@@ -534,7 +590,9 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
     // (branch-free on purpose: masks are combined with & / |, never && / ||, and every product is formed
     // unconditionally and pinned before its select — written as `(valid && in) ? sum + a * xv : sum` hipcc lowers each
     // element to exec-mask control flow, ~10 scalar instructions around one v_fma)
-    auto fold4 = [&](val_t& sum, const int4v& c, const v4& a, const val_t (&xv)[4], const bool (&in)[4], off_t j, off_t lo, off_t hi) {
+    // (c: the four columns as loaded; a packed group has lost them, and the rare element outside the window reads its
+    // column from Aj[j + e] — wherever an element is valid, j is the address its group was loaded from)
+    auto fold4 = [&](val_t& sum, const auto& c, const v4& a, const val_t (&xv)[4], const bool (&in)[4], off_t j, off_t lo, off_t hi) {
         const off_t d_lo = lo - j, d_hi = hi - j;
         const int e_lo = d_lo > 0 ? int(d_lo) : 0;                 // lo - j <= 3 wherever this is called
         const int e_hi = d_hi < 4 ? (d_hi > 0 ? int(d_hi) : 0) : 4;
@@ -554,12 +612,16 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
             if (need_any) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    if (need[e]) sum += a[e] * x[c[e]];
+                    if constexpr (std::is_same<std::decay_t<decltype(c)>, uint2v>::value) {
+                        if (need[e]) sum += a[e] * x[Aj[j + e]];
+                    } else {
+                        if (need[e]) sum += a[e] * x[c[e]];
+                    }
                 }
             }
         }
     };
-    auto accumulate = [&](val_t& sum, const int4v& c, const v4& a, off_t j, off_t lo, off_t hi) {
+    auto accumulate = [&](val_t& sum, const auto& c, const v4& a, off_t j, off_t lo, off_t hi) {
         val_t xv[4];
         bool in[4];
         gather4(c, xv, in);
@@ -603,13 +665,13 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
             }
         }
         while (more) {                                     // rows longer than one step (4T nonzeros)
-            int4v c2[R];
+            col4 c2[R];
             v4 a2[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 off_t jl = jn[r] < hi[r] ? jn[r] : (B.lo[r] & ~off_t(3));
                 jl = jl < j_max ? jl : j_max;
-                c2[r] = stream_load(reinterpret_cast<const int4v*>(Aj + jl));
+                c2[r] = load_cols(jl);
                 a2[r] = stream_load(reinterpret_cast<const v4*>(Ax + jl));
             }
             more = false;
@@ -775,14 +837,17 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
 // REGULAR (the merge kind's row-parallel runs: rows alike): the width that takes a mean row in ONE step (8 / 16 / 32 /
 // 64 / 128 nonzeros) — a second, dependent step per row costs such a matrix more than idle lanes do (rows of 64 +- 16 with 8
 // lanes: three steps, 740 us; with 32 lanes: see merge_path.hip).
-template <int BLOCK, int T, int R, bool WINDOW, bool ADAPT, typename val_t, typename StageFn, bool REGULAR = false>
+template <int BLOCK, int T, int R, bool WINDOW, bool ADAPT, typename val_t, typename StageFn, bool REGULAR = false,
+          bool PACKED = false>
 __device__ __forceinline__ void chunk_rows_any(int64_t chunk_begin, int64_t chunk_end, int32_t nnz,
                                                const int32_t* __restrict__ Aj,
                                                const val_t* __restrict__ Ax, const val_t* __restrict__ x,
                                                val_t* __restrict__ y, StageFn&& stage,
-                                               const ChunkScratch<val_t>& scr) {
+                                               const ChunkScratch<val_t>& scr,
+                                               const uint16_t* __restrict__ Aj16 = nullptr) {
+    static_assert(!PACKED || !ADAPT, "packed plans have equal-row chunks of one vector width");
     if constexpr (!ADAPT) {
-        chunk_rows<BLOCK, T, R, WINDOW, val_t>(chunk_begin, chunk_end, nnz, Aj, Ax, x, y, stage, scr);
+        chunk_rows<BLOCK, T, R, WINDOW, val_t, PACKED>(chunk_begin, chunk_end, nnz, Aj, Ax, x, y, stage, scr, Aj16);
     } else {
         const int rows = int(chunk_end - chunk_begin);
         const int32_t mean = (scr.s_b[rows] - scr.s_b[0]) / int32_t(rows > 0 ? rows : 1);   // uniform over the workgroup
