@@ -38,6 +38,10 @@ extern "C" {
 #endif
 
 #define MI355_SPMV_VERSION 310 /* 0.3.1 */
+/* Additions since 310 that a caller can test for at compile time (the entry points themselves: dlsym).  The number
+ * above did NOT move with them: MI355_SPMV_VERSION / mi355_spmv_version() alone do not tell a library that has the
+ * pattern entry points from one that has not — test this macro, or look the symbols up.                          */
+#define MI355_SPMV_HAS_PATTERN 1 /* MI355_VAL_PATTERN, mi355_spmv_merge_pattern_*, mi355_spmv_plan_get_mat_type */
 
 /* status codes */
 enum {
@@ -73,7 +77,11 @@ enum { MI355_VAL_F32 = 0, MI355_VAL_F64 = 1,
         * reduction order).  The reference's generalized merge kind is a template over the value types and its
         * functor (merge_genl.cuh:19-38, :134-150); this is the integer / boolean instance of it.  VECTOR / LIGHT
         * plans and alpha / beta return MI355_SPMV_ENOTSUP for it.                                              */
-       MI355_VAL_I32 = 2 };
+       MI355_VAL_I32 = 2,
+       /* A PATTERN matrix: no stored values, every entry is one in the type of x and y (a Matrix Market `pattern`
+        * file, an unweighted graph).  Valid ONLY as the mat_type of mi355_spmv_plan_create_typed, MERGE kind: as
+        * x_type / y_type and as the val_type of every other entry point it is an error.                        */
+       MI355_VAL_PATTERN = 3 };
 
 /* semirings of the generalized merge kind.  The reference's
  * SpMV_merge_based_generalized takes a functor_t with initialize / combine / reduce
@@ -177,9 +185,31 @@ int mi355_spmv_plan_create(mi355_spmv_plan** plan, int kind, int off_type, int v
  * MATRIX under fp64 x and y for the MERGE kind — values are widened as they meet x, products and sums are fp64
  * (the mixed-precision case that halves the matrix stream).  Other combinations return MI355_SPMV_ENOTSUP.
  * execute then takes Ax as float*, x / y as double*.                                                         */
+/* mat_type = MI355_VAL_PATTERN, x_type = y_type = F32 / F64 / I32, kind MERGE (AUTO becomes MERGE; VECTOR / LIGHT return
+ * MI355_SPMV_ENOTSUP): the matrix has a structure and no values.  The plan is shaped exactly as the valued MERGE plan
+ * of that vector type (same tiles and runs, same window of x); its executes always walk the tiles (merge_tile_kernel)
+ * with every product combine(1, x[col]), and IGNORE Ax: it may be NULL, and no kernel reads or forms an address from
+ * it.  4 bytes per nonzero cross HBM instead of 8 (fp32) or 12 (fp64), and Ax need not exist.  All five semirings;
+ * alpha / beta under (+, *) for the float types.  The sums are those of the valued plan executed with Ax = ones, bit
+ * for bit, whenever that plan walks its tiles too.                                                                   */
 int mi355_spmv_plan_create_typed(mi355_spmv_plan** plan, int kind, int off_type, int mat_type, int x_type,
                                  int y_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
                                  const int32_t* Aj, int flags);
+/* The mat_type a plan was created with (= its val_type unless plan_create_typed said otherwise).                    */
+int mi355_spmv_plan_get_mat_type(const mi355_spmv_plan* plan, int* mat_type);
+/* One-shot SpMV with a pattern matrix: the arguments of mi355_spmv_merge_genl_* without Ax.  A plan per call.       */
+int mi355_spmv_merge_pattern_i32_f32(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap,
+                                    const int32_t* Aj, const float* x, float* y, void* stream);
+int mi355_spmv_merge_pattern_i32_f64(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap,
+                                    const int32_t* Aj, const double* x, double* y, void* stream);
+int mi355_spmv_merge_pattern_i32_i32(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap,
+                                    const int32_t* Aj, const int32_t* x, int32_t* y, void* stream);
+int mi355_spmv_merge_pattern_i64_f32(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap,
+                                    const int32_t* Aj, const float* x, float* y, void* stream);
+int mi355_spmv_merge_pattern_i64_f64(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap,
+                                    const int32_t* Aj, const double* x, double* y, void* stream);
+int mi355_spmv_merge_pattern_i64_i32(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap,
+                                    const int32_t* Aj, const int32_t* x, int32_t* y, void* stream);
 int mi355_spmv_merge_f32mat_f64vec_i32(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap,
                                        const int32_t* Aj, const float* Ax, const double* x, double* y, void* stream);
 int mi355_spmv_merge_f32mat_f64vec_i64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """hipcc -Rpass-analysis=kernel-resource-usage over every translation unit of the library: one line per kernel
-(VGPRs, SGPRs, scratch bytes per lane, occupancy, static LDS); exit status 1 if any kernel uses scratch."""
+(VGPRs, SGPRs, scratch bytes per lane, occupancy, static LDS); exit status 1 if any kernel uses scratch.
+  check_spills.py [tag] [--tu a.hip,b.hip]     --tu: only these translation units (the record's header names them)"""
 import os
 import re
 import subprocess
@@ -10,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "spmv-samples_amd", "csrc")
 TUS = ["csr_vector.hip", "csr_vector_f64.hip", "light_rows.hip", "light_rows_f64.hip", "merge_path.hip", "merge_path_f64.hip",
-       "merge_path_i32.hip", "analyze.hip",
+       "merge_path_i32.hip", "merge_path_pattern.hip", "analyze.hip",
        "dist.hip", "coo_csr.hip"]
 
 
@@ -48,9 +49,18 @@ def short(name):
 
 
 def main():
-    tag = sys.argv[1] if len(sys.argv) > 1 else None
+    args = sys.argv[1:]
+    tus = TUS
+    if "--tu" in args:
+        i = args.index("--tu")
+        tus = args[i + 1].split(",")
+        unknown = [t for t in tus if t not in TUS]
+        if unknown:
+            sys.exit("unknown translation unit(s): %s" % ", ".join(unknown))
+        del args[i:i + 2]
+    tag = args[0] if args else None
     with ThreadPoolExecutor(max_workers=4) as ex:
-        rows = [r for rs in ex.map(analyse, TUS) for r in rs]
+        rows = [r for rs in ex.map(analyse, tus) for r in rs]
     rows = [r for r in rows if "vgpr" in r]
     names = demangle([r["name"] for r in rows])
     lines = []
@@ -66,7 +76,10 @@ def main():
     sys.stdout.write(text)
     if tag:
         with open(os.path.join(ROOT, "profiles", "%s_kernel_resources.txt" % tag), "w") as f:
-            f.write("# scripts/check_spills.sh %s  (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage)\n" % tag)
+            only = "" if tus is TUS else " --tu %s" % ",".join(tus)
+            f.write("# scripts/check_spills.sh %s%s  (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage)\n" % (tag, only))
+            if tus is not TUS:
+                f.write("# these translation units only; every kernel they instantiate, shared helper kernels included\n")
             f.write(text)
     sys.exit(1 if bad else 0)
 

@@ -18,4 +18,4 @@ Contents (only what the hot path needs):
 """
 from . import capi, dist, load, synth  # noqa: F401
 from .capi import (DistPlan, Functor, Plan, PlanShape, coo_symmetric_nnz, coo_to_csr, spmv, spmv_genl,  # noqa: F401
-                   spmv_mixed)
+                   spmv_mixed, spmv_pattern)

@@ -21,6 +21,7 @@ KIND_NAMES = {0: "vector", 1: "merge", 2: "light"}
 LABELS = {"hip_vector": "vector", "hip_merge": "merge", "hip_light": "light", "hip_auto": "auto"}
 OFF_TYPES = {torch.int32: (0, "i32"), torch.int64: (1, "i64")}
 VAL_TYPES = {torch.float32: (0, "f32"), torch.float64: (1, "f64"), torch.int32: (2, "i32")}   # (int32 values: the merge kind only)
+VAL_PATTERN = 3              # MI355_VAL_PATTERN: a matrix type only (Plan(..., mat_dtype="pattern"), spmv_pattern)
 PLAN_REUSE_STRUCTURE = 1
 PLAN_NO_INDEX_COPY = 2       # the plan holds nothing derived from the contents of Aj (no packed index)
 SEMIRINGS = {"plus_times": 0, "min_plus": 1, "max_times": 2, "max_plus": 3, "or_and": 4}
@@ -42,6 +43,8 @@ EXPORTS = (
                                         "destroy")]
     + ["mi355_spmv_functor_" + n for n in ("compile", "compile_log", "spmv", "destroy")]
     + ["mi355_spmv_coo_to_csr", "mi355_spmv_coo_symmetric_nnz", "mi355_spmv_coo_to_csr_symmetric"]
+    + ["mi355_spmv_merge_pattern_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64", "i32")]
+    + ["mi355_spmv_plan_get_mat_type"]
 )
 
 
@@ -112,6 +115,7 @@ def lib():
         L.mi355_spmv_plan_set_alpha_beta.argtypes = [C.c_void_p, C.c_double, C.c_double]
         L.mi355_spmv_plan_get_info.argtypes = [C.c_void_p, C.POINTER(PlanInfo)]
         L.mi355_spmv_plan_merge_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355_spmv_plan_get_mat_type.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.mi355_spmv_plan_get_shape.argtypes = [C.c_void_p, C.POINTER(PlanShape)]
         L.mi355_spmv_plan_partition.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355_spmv_plan_create_block.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -235,6 +239,23 @@ def spmv_genl(semiring, n_rows, n_cols, nnz, Ap, Aj, Ax, x, y, stream=None):
     return y
 
 
+def spmv_pattern(semiring, n_rows, n_cols, nnz, Ap, Aj, x, y, stream=None):
+    """One-shot generalized merge-path SpMV with a PATTERN matrix — a structure and no values, every entry one
+    (mi355_spmv_merge_pattern_*): the arguments of spmv_genl without Ax.  Synchronises the stream."""
+    sr = SEMIRINGS[semiring] if isinstance(semiring, str) else int(semiring)
+    _require_device(Ap, Aj, x, y)
+    if Aj.dtype != torch.int32 or x.dtype != y.dtype:
+        raise TypeError("Aj must be int32 and x, y one value type")
+    o = OFF_TYPES[Ap.dtype][1]
+    v = VAL_TYPES[x.dtype][1]
+    fn = getattr(lib(), "mi355_spmv_merge_pattern_%s_%s" % (o, v))
+    nnz_c = C.c_int32(nnz) if o == "i32" else C.c_int64(nnz)
+    st = fn(C.c_int(sr), C.c_int32(n_rows), C.c_int32(n_cols), nnz_c, C.c_void_p(Ap.data_ptr()),
+            C.c_void_p(Aj.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), _stream_ptr(stream))
+    _check(st, "mi355_spmv_merge_pattern_%s_%s" % (o, v))
+    return y
+
+
 def coo_to_csr_workspace_bytes(n_rows, nnz, off_dtype=torch.int32, val_dtype=None):
     """Device workspace mi355_spmv_coo_to_csr needs (the size query: no device is touched)."""
     ws = C.c_size_t(0)
@@ -329,7 +350,9 @@ class Plan:
     def __init__(self, kind, n_rows, n_cols, nnz, Ap, Aj, val_dtype, flags=0, mat_dtype=None):
         """val_dtype: the type of x and y (and of all arithmetic).  mat_dtype: the type the matrix values are stored
         in — None = val_dtype; torch.float32 under torch.float64 vectors is built for the merge kind
-        (mi355_spmv_plan_create_typed; the reference's operator keeps the three value types apart, spmv.h:29-34)."""
+        (mi355_spmv_plan_create_typed; the reference's operator keeps the three value types apart, spmv.h:29-34).
+        mat_dtype="pattern": the matrix stores no values, every entry is one (MI355_VAL_PATTERN; merge kind, float32 /
+        float64 / int32 vectors) — execute() then ignores Ax, which may be None."""
         kind = LABELS.get(kind, kind)
         if kind not in KINDS:
             raise ValueError('SpMV kind "%s" is NOT SUPPORTED' % kind)
@@ -340,7 +363,16 @@ class Plan:
         self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
         self.mat_dtype = mat_dtype if mat_dtype is not None else val_dtype
         self._h = C.c_void_p()
-        if self.mat_dtype == val_dtype:
+        if isinstance(self.mat_dtype, str):
+            if self.mat_dtype != "pattern":
+                raise ValueError('mat_dtype is a torch dtype or "pattern"')
+            if val_dtype not in VAL_TYPES:
+                raise TypeError("val_dtype must be float32, float64 or int32")
+            st = lib().mi355_spmv_plan_create_typed(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0], VAL_PATTERN,
+                                                    VAL_TYPES[val_dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols,
+                                                    nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
+            _check(st, "mi355_spmv_plan_create_typed")
+        elif self.mat_dtype == val_dtype:
             st = lib().mi355_spmv_plan_create(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0],
                                               VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz,
                                               C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
@@ -353,7 +385,17 @@ class Plan:
             _check(st, "mi355_spmv_plan_create_typed")
 
     def execute(self, Ax, x, y, stream=None):
-        """Asynchronous on `stream` (default: torch's current stream)."""
+        """Asynchronous on `stream` (default: torch's current stream).  A pattern plan ignores Ax: None or any tensor."""
+        if getattr(self, "mat_dtype", None) == "pattern":
+            _require_device(x, y)
+            if x.dtype != self.val_dtype or y.dtype != self.val_dtype:
+                raise TypeError("value type differs from the plan's")
+            if x.numel() < self.n_cols or y.numel() < self.n_rows:
+                raise ValueError("operand shorter than the plan's sizes")
+            st = lib().mi355_spmv_plan_execute(self._h, None, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
+                                               _stream_ptr(stream))
+            _check(st, "mi355_spmv_plan_execute")
+            return y
         _require_device(Ax, x, y)
         if Ax.dtype != getattr(self, "mat_dtype", self.val_dtype) or x.dtype != self.val_dtype or y.dtype != self.val_dtype:
             raise TypeError("value type differs from the plan's")
@@ -372,6 +414,12 @@ class Plan:
         """y = alpha * A x + beta * y for the following executes (default 1, 0)."""
         _check(lib().mi355_spmv_plan_set_alpha_beta(self._h, C.c_double(alpha), C.c_double(beta)),
                "mi355_spmv_plan_set_alpha_beta")
+
+    def mat_type(self):
+        """The MI355_VAL_* the plan's matrix values are stored in (3 = VAL_PATTERN: none)."""
+        out = C.c_int(-1)
+        _check(lib().mi355_spmv_plan_get_mat_type(self._h, C.byref(out)), "mi355_spmv_plan_get_mat_type")
+        return out.value
 
     def info(self):
         pi = PlanInfo()

@@ -115,6 +115,7 @@ static int execute_typed(Plan& p, const void* Ax, const void* x, void* y, hipStr
     switch (p.kind) {
         case MI355_KIND_VECTOR: return launch_rows<VectorRows, off_t, val_t>(p, Ap, ax, xx, yy, s);
         case MI355_KIND_MERGE:
+            if (p.mat_type == MI355_VAL_PATTERN) return launch_merge<off_t, val_t, PatternOnes>(p, Ap, nullptr, xx, yy, s);
             if constexpr (sizeof(val_t) == 8)
                 if (p.mat_type == MI355_VAL_F32) return launch_merge<off_t, val_t, float>(p, Ap, static_cast<const float*>(Ax), xx, yy, s);
             return launch_merge<off_t, val_t, val_t>(p, Ap, ax, xx, yy, s);
@@ -430,8 +431,26 @@ int mi355_spmv_plan_create_typed(mi355_spmv_plan** out, int kind, int off_type, 
     g_err[0] = 0;
     if (out) *out = nullptr;
     const auto known = [](int t) { return t == MI355_VAL_F32 || t == MI355_VAL_F64 || t == MI355_VAL_I32; };
-    if (!known(mat_type) || !known(x_type) || !known(y_type)) { set_error("plan_create_typed: unknown value type"); return MI355_SPMV_EINVAL; }
+    const bool pattern = mat_type == MI355_VAL_PATTERN;        // (a matrix type only: never the type of x or y)
+    if ((!known(mat_type) && !pattern) || !known(x_type) || !known(y_type)) { set_error("plan_create_typed: unknown value type"); return MI355_SPMV_EINVAL; }
     if (x_type != y_type) { set_error("plan_create_typed: x and y of different types are not built"); return MI355_SPMV_ENOTSUP; }
+    if (pattern) {
+        if (kind == MI355_KIND_AUTO) kind = MI355_KIND_MERGE;
+        if (kind != MI355_KIND_MERGE) {
+            if (kind < 0 || kind >= MI355_KIND_COUNT) { set_error("plan_create_typed: unknown kind %d", kind); return MI355_SPMV_EINVAL; }
+            set_error("plan_create_typed: pattern matrices are built for the merge kind only (as integers, semirings and mixed value types are)");
+            return MI355_SPMV_ENOTSUP;
+        }
+        // shaped exactly as the valued plan of x's type (same tiles, runs and window) ...
+        const int st = plan_create_impl(out, kind, off_type, x_type, n_rows, n_cols, nnz, Ap, Aj, flags, nullptr);
+        if (st != MI355_SPMV_OK) return st;
+        Plan& p = (*out)->p;
+        p.mat_type = MI355_VAL_PATTERN;
+        (*out)->asked_kind = kind;
+        // ... but every execute walks the tiles: the row-parallel run kernel such a shape may name has no pattern form
+        merge_report_tile_walk(p);
+        return st;
+    }
     if (mat_type == x_type) return mi355_spmv_plan_create(out, kind, off_type, x_type, n_rows, n_cols, nnz, Ap, Aj, flags);
     if (!(mat_type == MI355_VAL_F32 && x_type == MI355_VAL_F64)) {
         set_error("plan_create_typed: the only mixed combination built is an fp32 matrix under fp64 vectors");
@@ -505,13 +524,18 @@ int mi355_spmv_plan_execute(mi355_spmv_plan* h, const void* Ax, const void* x, v
     g_err[0] = 0;
     if (!h) { set_error("plan_execute: null plan"); return MI355_SPMV_EINVAL; }
     Plan& p = h->p;
-    if (p.nnz > 0 && (!Ax || !x)) { set_error("plan_execute: null Ax or x"); return MI355_SPMV_EINVAL; }
+    const bool pattern = p.mat_type == MI355_VAL_PATTERN;      // (MERGE only: Ax is ignored and may be NULL)
+    if (p.nnz > 0 && ((!Ax && !pattern) || !x)) { set_error("plan_execute: null Ax or x"); return MI355_SPMV_EINVAL; }
     if (p.n_rows > 0 && !y) { set_error("plan_execute: null y"); return MI355_SPMV_EINVAL; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (p.val_type == MI355_VAL_I32) {      // (MERGE only: plan_create refuses the other kinds)
         const int32_t* ax = static_cast<const int32_t*>(Ax);
         const int32_t* xx = static_cast<const int32_t*>(x);
         int32_t* yy = static_cast<int32_t*>(y);
+        if (pattern)
+            return p.off_type == MI355_OFF_I32
+                       ? launch_merge<int32_t, int32_t, PatternOnes>(p, static_cast<const int32_t*>(p.Ap), nullptr, xx, yy, s)
+                       : launch_merge<int64_t, int32_t, PatternOnes>(p, static_cast<const int64_t*>(p.Ap), nullptr, xx, yy, s);
         return p.off_type == MI355_OFF_I32
                    ? launch_merge<int32_t, int32_t, int32_t>(p, static_cast<const int32_t*>(p.Ap), ax, xx, yy, s)
                    : launch_merge<int64_t, int32_t, int32_t>(p, static_cast<const int64_t*>(p.Ap), ax, xx, yy, s);
@@ -584,7 +608,8 @@ int mi355_spmv_plan_get_info(const mi355_spmv_plan* h, mi355_spmv_plan_info* inf
     info->kind = p.kind; info->off_type = p.off_type; info->val_type = p.val_type;
     info->lanes_per_row = p.lanes_per_row;
     info->elems_per_lane = p.elems_per_lane;
-    info->block_threads = (p.kind == MI355_KIND_MERGE && p.merge_rows) ? p.mr_block : (p.block_threads > 0 ? p.block_threads : kBlock);
+    info->block_threads = (p.kind == MI355_KIND_MERGE && p.merge_rows && p.mat_type != MI355_VAL_PATTERN)
+                              ? p.mr_block : (p.block_threads > 0 ? p.block_threads : kBlock);
     info->grid_blocks = p.grid_blocks;
     info->tile_items = p.tile_items;
     info->n_tiles = p.n_tiles;
@@ -600,6 +625,12 @@ int mi355_spmv_plan_get_info(const mi355_spmv_plan* h, mi355_spmv_plan_info* inf
     info->rows_cap = p.rows_cap;
     info->n_chunks = p.n_chunks;
     snprintf(info->knobs, sizeof(info->knobs), "%s", p.knob.text);
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_plan_get_mat_type(const mi355_spmv_plan* h, int* mat_type) {
+    if (!h || !mat_type) { set_error("plan_get_mat_type: null argument"); return MI355_SPMV_EINVAL; }
+    *mat_type = h->p.mat_type;
     return MI355_SPMV_OK;
 }
 
@@ -664,6 +695,32 @@ MI355_SPMV_DEFINE_GENL(i64_i32, int64_t, MI355_OFF_I64, int32_t, MI355_VAL_I32)
     }
 MI355_SPMV_DEFINE_MIXED(i32, int32_t, MI355_OFF_I32)
 MI355_SPMV_DEFINE_MIXED(i64, int64_t, MI355_OFF_I64)
+
+// pattern matrices: the arguments of merge_genl without Ax.  A plan per call, as the mixed entry points above: the kept
+// one-shot plans are keyed by the vector type alone, and a valued call on the same Ap / Aj must never get this plan.
+#define MI355_SPMV_DEFINE_PATTERN(SUF, OFF, OFFENUM, VAL, VALENUM)                                               \
+    int mi355_spmv_merge_pattern_##SUF(int semiring, int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap,     \
+                                       const int32_t* Aj, const VAL* x, VAL* y, void* st) {                      \
+        if (semiring < 0 || semiring >= MI355_SEMIRING_COUNT) {                                                  \
+            set_error("merge_pattern: unknown semiring %d", semiring);                                           \
+            return MI355_SPMV_EINVAL;                                                                            \
+        }                                                                                                        \
+        mi355_spmv_plan* plan = nullptr;                                                                         \
+        int rc = mi355_spmv_plan_create_typed(&plan, MI355_KIND_MERGE, OFFENUM, MI355_VAL_PATTERN, VALENUM,      \
+                                              VALENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, MI355_PLAN_DEFAULT); \
+        if (rc != MI355_SPMV_OK) return rc;                                                                      \
+        rc = mi355_spmv_plan_set_semiring(plan, semiring);                                                       \
+        if (rc == MI355_SPMV_OK) rc = mi355_spmv_plan_execute(plan, nullptr, x, y, st);                          \
+        if (rc == MI355_SPMV_OK) rc = mi355_spmv_stream_synchronize(st);                                         \
+        const int rc2 = mi355_spmv_plan_destroy(plan);                                                           \
+        return rc != MI355_SPMV_OK ? rc : rc2;                                                                   \
+    }
+MI355_SPMV_DEFINE_PATTERN(i32_f32, int32_t, MI355_OFF_I32, float, MI355_VAL_F32)
+MI355_SPMV_DEFINE_PATTERN(i32_f64, int32_t, MI355_OFF_I32, double, MI355_VAL_F64)
+MI355_SPMV_DEFINE_PATTERN(i32_i32, int32_t, MI355_OFF_I32, int32_t, MI355_VAL_I32)
+MI355_SPMV_DEFINE_PATTERN(i64_f32, int64_t, MI355_OFF_I64, float, MI355_VAL_F32)
+MI355_SPMV_DEFINE_PATTERN(i64_f64, int64_t, MI355_OFF_I64, double, MI355_VAL_F64)
+MI355_SPMV_DEFINE_PATTERN(i64_i32, int64_t, MI355_OFF_I64, int32_t, MI355_VAL_I32)
 
 MI355_SPMV_DEFINE_KIND(vector, MI355_KIND_VECTOR)
 MI355_SPMV_DEFINE_KIND(merge, MI355_KIND_MERGE)

@@ -57,6 +57,11 @@ constexpr int kCus = 256;            // compute units per MI355X
 
 void set_error(const char* fmt, ...);
 
+// mat_t of a PATTERN matrix (MI355_VAL_PATTERN: every stored entry is one, in the type of x and y): a tag that takes
+// no storage.  The merge kind's tile kernel and launch_merge are instantiated with it in the place of the stored
+// value type; the kernel then issues no Ax load at all and no address is ever formed from the pointer.
+struct PatternOnes {};
+
 #define MI355_HIP_TRY(expr)                                                              \
     do {                                                                                 \
         hipError_t _e = (expr);                                                          \
@@ -120,7 +125,8 @@ void knobs_reload();
 
 struct Plan {
     int kind, off_type, val_type, flags;   // val_type: the type of x, y and of all arithmetic
-    int mat_type;              // the type the matrix values are stored in (= val_type, or F32 under F64 vectors: MERGE)
+    int mat_type;              // the type the matrix values are stored in (= val_type; F32 under F64 vectors, or
+                               // MI355_VAL_PATTERN = no stored values, every entry is one: MERGE)
     int32_t n_rows, n_cols;
     int64_t nnz;               // END offset of the nonzeros: Ap[n_rows] (= their count unless nnz_begin > 0)
     int64_t nnz_read;          // elements of Aj / Ax the 16-byte loads may touch: nnz, or nnz rounded up to a multiple
@@ -228,6 +234,7 @@ int build_chunk_table(Plan& p);    // after the scratch is allocated
 int build_packed_index(Plan& p);   // after the shape is final: the packed index of a plan that qualifies (synchronises)
 int find_giant_rows(Plan& p);      // balanced plans: rows beyond kGiantRow nonzeros (synchronises)
 void shape_merge(Plan& p);
+void merge_report_tile_walk(Plan& p);   // MERGE: n_kernels / main_kernel of a plan whose executes all take the tile kernel
 int shape_rows(Plan& p);           // VECTOR / LIGHT, whole plans: the shape, then set_rows_launch (synchronises)
 void set_rows_launch(Plan& p);     // VECTOR / LIGHT: kernel, grid and kernel count from the plan's shape
 // nnz-balanced cuts on the plan's chunk boundaries (analyze.hip; reads Ap on the device, synchronises)

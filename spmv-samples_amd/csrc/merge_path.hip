@@ -161,6 +161,19 @@ __global__ __launch_bounds__(kBlock) void merge_search_kernel(
     }
 }
 
+// The stored value of a nonzero as val_t: element e of a prefetched 16-byte group, or entry k of Ax.  A pattern matrix
+// (mat_t = PatternOnes, common.hpp) stores none: the value is one and neither the group nor the pointer is touched.
+template <typename val_t, typename m4>
+__device__ __forceinline__ val_t mat_elem(const m4& a, int e) {
+    if constexpr (std::is_same<m4, PatternOnes>::value) return val_t(1);
+    else return val_t(a[e]);
+}
+template <typename val_t, typename mat_t>
+__device__ __forceinline__ val_t mat_at(const mat_t* __restrict__ Ax, int64_t k) {
+    if constexpr (std::is_same<mat_t, PatternOnes>::value) return val_t(1);
+    else return val_t(Ax[k]);
+}
+
 // ---- K7: one run of consecutive tiles per workgroup ---------------------------------
 // SEARCH: the run's tile coordinates are found HERE (16 lanes per diagonal, up to 16 diagonals at once by the
 // whole workgroup) instead of by a search kernel in front: one launch and one kernel boundary fewer per SpMV
@@ -168,7 +181,9 @@ __global__ __launch_bounds__(kBlock) void merge_search_kernel(
 // them where the search kernel would have, so plan_merge_coords / MI355_PLAN_REUSE_STRUCTURE see the same arrays.
 // mat_t: the type the matrix values are STORED in — val_t, or float under double vectors (the reference keeps the
 // matrix / x / y types apart, include/spmv.h:29-34; its generalized merge kind computes in the y type,
-// merge_genl.cuh:29-31): a value is widened when it meets x, products and sums are val_t throughout.
+// merge_genl.cuh:29-31): a value is widened when it meets x, products and sums are val_t throughout.  PatternOnes: the
+// matrix stores no values (MI355_VAL_PATTERN) — the Ax stream is not issued, a[] takes no registers and every product is
+// combine(1, x); tiles, walk, scan and carries are those of the valued kernel, so the sums come out in the same order.
 template <int BLOCK, int IPT, bool VEC, bool WINDOW, int S, bool SEARCH, typename off_t, typename val_t, typename mat_t = val_t>
 __global__ __launch_bounds__(BLOCK) void merge_tile_kernel(
     int32_t n_rows, int32_t n_cols, int64_t nnz_begin, int64_t nnz, const off_t* __restrict__ Ap, const int32_t* __restrict__ Aj,
@@ -232,7 +247,7 @@ __global__ __launch_bounds__(BLOCK) void merge_tile_kernel(
 
     // registers holding the Aj/Ax groups of the tile about to be processed
     int4v c[G];
-    m4 a[G];
+    [[maybe_unused]] m4 a[G];
     // branch-free: addresses are clamped below the last whole 16-byte group of the arrays (hipcc
     // serialises loads it finds in branches); the few nonzeros at or past nnz_vec are redone below
     const int64_t nnz_vec = nnz & ~int64_t(3);
@@ -244,7 +259,7 @@ __global__ __launch_bounds__(BLOCK) void merge_tile_kernel(
             int64_t j = base + 4 * int64_t(tid + g * BLOCK);
             j = j < j_max ? j : j_max;
             c[g] = stream_load(reinterpret_cast<const int4v*>(Aj + j));
-            a[g] = stream_load(reinterpret_cast<const m4*>(Ax + j));
+            if constexpr (!std::is_same<mat_t, PatternOnes>::value) a[g] = stream_load(reinterpret_cast<const m4*>(Ax + j));
         }
     };
     if constexpr (VEC) issue(y0);
@@ -302,14 +317,14 @@ __global__ __launch_bounds__(BLOCK) void merge_tile_kernel(
                     for (int e = 0; e < 4; ++e) {
                         const unsigned rel = unsigned(c[g][e] - win.lo);
                         any_out |= rel >= unsigned(win.len);
-                        p[e] = SR::combine(val_t(a[g][e]), win.s_x[min(rel, len_m1)]);
+                        p[e] = SR::combine(mat_elem<val_t>(a[g], e), win.s_x[min(rel, len_m1)]);
                     }
                     if (any_out) {                       // rare: loaded and consumed inside the branch
                         const int rel0 = 4 * (tid + g * BLOCK) - shift;   // tile-relative index of element 0
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const bool out = unsigned(c[g][e] - win.lo) >= unsigned(win.len);
-                            if (out && (rel0 + e >= 0) && (rel0 + e < tn)) p[e] = SR::combine(val_t(a[g][e]), x[c[g][e]]);
+                            if (out && (rel0 + e >= 0) && (rel0 + e < tn)) p[e] = SR::combine(mat_elem<val_t>(a[g], e), x[c[g][e]]);
                         }
                     }
                     *reinterpret_cast<v4*>(&s_nz[4 * (tid + g * BLOCK)]) = p;
@@ -324,7 +339,7 @@ __global__ __launch_bounds__(BLOCK) void merge_tile_kernel(
                 for (int g = 0; g < G; ++g) {
                     v4 p;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) p[e] = SR::combine(val_t(a[g][e]), xv[g][e]);
+                    for (int e = 0; e < 4; ++e) p[e] = SR::combine(mat_elem<val_t>(a[g], e), xv[g][e]);
                     *reinterpret_cast<v4*>(&s_nz[4 * (tid + g * BLOCK)]) = p;
                 }
             }
@@ -335,7 +350,7 @@ __global__ __launch_bounds__(BLOCK) void merge_tile_kernel(
                 // wrong about once in 25 processes).
                 __syncthreads();
                 const int64_t k = (y0 > nnz_vec ? y0 : nnz_vec) + tid;
-                if (k < y1) s_nz[int(k - y0) + shift] = SR::combine(val_t(Ax[k]), x[Aj[k]]);
+                if (k < y1) s_nz[int(k - y0) + shift] = SR::combine(mat_at<val_t>(Ax, k), x[Aj[k]]);
             }
             // the next tile's stream goes in flight now and lands while this tile is walked
             if (t + 1 < last) issue(y1);
@@ -343,7 +358,7 @@ __global__ __launch_bounds__(BLOCK) void merge_tile_kernel(
             // Aj / Ax not 16-byte aligned (an offset view): 4-byte-per-lane form
             for (int i = tid; i < tn; i += BLOCK) {
                 const int32_t col = Aj[y0 + i];
-                s_nz[i] = SR::combine(val_t(Ax[y0 + i]), window_gather<val_t>(win, x, col, true));
+                s_nz[i] = SR::combine(mat_at<val_t>(Ax, y0 + i), window_gather<val_t>(win, x, col, true));
             }
         }
         // (2) row ends, relative to y0; the row still open at the tile end never ends here
@@ -657,7 +672,7 @@ static bool merge_search_in_kernel(const Plan& p) {
     return false;
 }
 
-#if !defined(MI355_TU_F64) && !defined(MI355_TU_I32)   // the host-side shape functions live in the fp32 translation unit only
+#if !defined(MI355_TU_F64) && !defined(MI355_TU_I32) && !defined(MI355_TU_PATTERN)   // the host-side shape functions live in the fp32 translation unit only
 void shape_merge(Plan& p) {
     // tuning knobs: MI355_MERGE_TPS = tiles per run (and MI355_SPMV_WINDOW = 0|1, analyze.hip)
     // 256 threads x 8 items or (MI355_MERGE_BLOCK=512) 512 threads x 4 items: the same 2 044-item tiles
@@ -822,6 +837,13 @@ void shape_merge(Plan& p) {
     snprintf(p.main_kernel, sizeof(p.main_kernel), "merge_tile_kernel");
 }
 
+// What a plan reports when every one of its executes walks the tiles whatever shape_merge shaped it around (a pattern
+// matrix: merge_rows_kernel has no pattern form).  The shape itself — tiles, runs, window — stays as it is.
+void merge_report_tile_walk(Plan& p) {
+    p.n_kernels = (p.n_super > 1 ? 2 : 1) + ((merge_search_in_kernel(p) && p.block_threads == kBlock) ? 0 : 1);
+    snprintf(p.main_kernel, sizeof(p.main_kernel), "merge_tile_kernel");
+}
+
 // The tile coordinates on demand (mi355_spmv_plan_merge_coords on a plan whose executes do not produce them: the
 // row-parallel run kernel only ever finds its own two diagonals).
 int merge_compute_coords(Plan& p) {
@@ -843,8 +865,9 @@ int merge_compute_coords(Plan& p) {
 template <typename off_t, typename val_t, typename mat_t>
 int launch_merge(Plan& p, const off_t* Ap, const mat_t* Ax, const val_t* x, val_t* y, hipStream_t s) {
     if (p.n_rows == 0 || p.n_tiles == 0) return MI355_SPMV_OK;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(p.Aj) | reinterpret_cast<uintptr_t>(Ax) |
-                           reinterpret_cast<uintptr_t>(x)) & 15u) == 0;
+    // (a pattern matrix has no Ax: whatever the caller passed, NULL included, is neither read nor counted here)
+    const uintptr_t ax_bits = std::is_same<mat_t, PatternOnes>::value ? uintptr_t(0) : reinterpret_cast<uintptr_t>(Ax);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(p.Aj) | ax_bits | reinterpret_cast<uintptr_t>(x)) & 15u) == 0;
     const bool reuse = (p.flags & MI355_PLAN_REUSE_STRUCTURE) && p.coords_valid;
     const bool vec = aligned && p.nnz >= 4;
     const bool wide = p.block_threads == kWideBlock && p.semiring == MI355_SEMIRING_PLUS_TIMES;
@@ -1013,8 +1036,16 @@ int launch_merge(Plan& p, const off_t* Ap, const mat_t* Ax, const val_t* x, val_
 }
 
 // One translation unit per value type (merge_path_f64.hip / merge_path_i32.hip include this file with MI355_TU_F64 /
-// MI355_TU_I32): the three thirds of the instantiations compile side by side.
-#if defined(MI355_TU_F64)
+// MI355_TU_I32): the three thirds of the instantiations compile side by side.  merge_path_pattern.hip (MI355_TU_PATTERN)
+// holds the tile kernels of pattern matrices, for all three vector types.
+#if defined(MI355_TU_PATTERN)
+template int launch_merge<int32_t, float, PatternOnes>(Plan&, const int32_t*, const PatternOnes*, const float*, float*, hipStream_t);
+template int launch_merge<int64_t, float, PatternOnes>(Plan&, const int64_t*, const PatternOnes*, const float*, float*, hipStream_t);
+template int launch_merge<int32_t, double, PatternOnes>(Plan&, const int32_t*, const PatternOnes*, const double*, double*, hipStream_t);
+template int launch_merge<int64_t, double, PatternOnes>(Plan&, const int64_t*, const PatternOnes*, const double*, double*, hipStream_t);
+template int launch_merge<int32_t, int32_t, PatternOnes>(Plan&, const int32_t*, const PatternOnes*, const int32_t*, int32_t*, hipStream_t);
+template int launch_merge<int64_t, int32_t, PatternOnes>(Plan&, const int64_t*, const PatternOnes*, const int32_t*, int32_t*, hipStream_t);
+#elif defined(MI355_TU_F64)
 template int launch_merge<int32_t, double, double>(Plan&, const int32_t*, const double*, const double*, double*, hipStream_t);
 template int launch_merge<int64_t, double, double>(Plan&, const int64_t*, const double*, const double*, double*, hipStream_t);
 // fp32 matrix under fp64 vectors (mi355_spmv_plan_create_typed)

@@ -59,6 +59,13 @@ void SpMV_hip_functor_times_plus(index_t n_rows, index_t n_cols, offset_t nnz, c
     X("merge", SpMV_hip_merge)                        \
     X("merge_genl", SpMV_hip_merge_generalized)
 
+// "hip_merge_pattern": the merge kind on the matrix's STRUCTURE, every stored value taken as one (SpMV_hip_merge_pattern,
+// spmv/mi355.hpp): for a Matrix Market `pattern` file or an unweighted graph.  It computes another product than the
+// other rows do unless the values are all one, so it is a row of its own list: SpMV() below finds it like any other
+// label, while code that runs every row of SPMV_KINDS on one matrix and expects one answer is not handed it.
+#define SPMV_KINDS_PATTERN                            \
+    X("hip_merge_pattern", SpMV_hip_merge_pattern)
+
 /// SPMV kind strings and its function
 #define SPMV_KINDS                                    \
     X("hip_vector", SpMV_hip_vector)                  \
@@ -88,6 +95,7 @@ void SpMV(const std::string& kind_str, index_t n_rows, index_t n_cols, offset_t 
     {label, [](index_t r, index_t c, offset_t z, const offset_t* p, const index_t* j, const mat_value_t* a, \
                const vec_x_value_t* xv, vec_y_value_t* yv) { func(r, c, z, p, j, a, xv, yv); }},
         SPMV_KINDS
+        SPMV_KINDS_PATTERN
 #undef X
     };
     for (const kind_row& row : rows) {

@@ -229,6 +229,36 @@ void SpMV_hip_merge_generalized(index_t n_rows, index_t n_cols, offset_t nnz, co
     ::mi355_host::run_kind(MI355_KIND_MERGE, n_rows, n_cols, nnz, Ap, Aj, Ax, x, y, functor_t::id);
 }
 
+/// merge-path SpMV of a PATTERN matrix: the structure with every stored value taken as one (MI355_VAL_PATTERN,
+/// include/mi355_spmv.h).  The reference's eight arguments, and Ax handed to nobody: a Matrix Market `pattern` file — the
+/// loader gives its entries the value 1 — or an unweighted graph runs without its ones crossing HBM.  On a matrix whose
+/// values are not all one this computes another product, and a check against the CPU result fails: that is the label's
+/// meaning.  Values and vectors of one type (float, double or int); a plan per call.
+template <typename index_t, typename offset_t, typename mat_value_t, typename vec_x_value_t, typename vec_y_value_t>
+void SpMV_hip_merge_pattern(index_t n_rows, index_t n_cols, offset_t nnz, const offset_t* Ap, const index_t* Aj,
+                            const mat_value_t* /*Ax: not read*/, const vec_x_value_t* x, vec_y_value_t* y) {
+    static_assert(std::is_same<index_t, int>::value || std::is_same<index_t, int32_t>::value,
+                  "mi355 kinds: index_t must be a 32-bit int (reference main.cu:15)");
+    static_assert(std::is_integral<offset_t>::value && std::is_signed<offset_t>::value && (sizeof(offset_t) == 4 || sizeof(offset_t) == 8),
+                  "mi355 kinds: offset_t must be a signed 32- or 64-bit integer");
+    static_assert(std::is_same<vec_x_value_t, vec_y_value_t>::value &&
+                      (std::is_same<vec_x_value_t, float>::value || std::is_same<vec_x_value_t, double>::value ||
+                       std::is_same<vec_x_value_t, int>::value),
+                  "mi355 pattern kind: x and y share one type, float, double or int");
+    const int off_type = sizeof(offset_t) == 8 ? MI355_OFF_I64 : MI355_OFF_I32;
+    const int vec_type = std::is_same<vec_x_value_t, int>::value ? MI355_VAL_I32
+                         : std::is_same<vec_x_value_t, double>::value ? MI355_VAL_F64 : MI355_VAL_F32;
+    mi355_spmv_plan* plan = nullptr;
+    MI355_CHECK(mi355_spmv_plan_create_typed(&plan, MI355_KIND_MERGE, off_type, MI355_VAL_PATTERN, vec_type, vec_type,
+                                             (int32_t)n_rows, (int32_t)n_cols, (int64_t)nnz, Ap,
+                                             reinterpret_cast<const int32_t*>(Aj), MI355_PLAN_DEFAULT));
+    Timer::kernel_start();
+    MI355_CHECK(mi355_spmv_plan_execute(plan, /*Ax=*/nullptr, x, y, /*stream=*/nullptr));
+    MI355_CHECK(mi355_spmv_stream_synchronize(/*stream=*/nullptr));
+    Timer::kernel_stop();
+    MI355_CHECK(mi355_spmv_plan_destroy(plan));
+}
+
 // ---- a functor of the caller's own (the reference's functor_t, merge_genl.cuh:19-38) -------------------------------
 // The reference hands SpMV_merge_based_generalized a C++ type.  Here the kernels are compiled at run time from the
 // functor's TEXT (mi355_spmv_functor_*, include/mi355_spmv.h): MI355_FUNCTOR(Name, definition...) keeps the definition
