@@ -152,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void probe_kernel(int32_t n_rows, const off
     }
     // how many of the sampled rows fill less than three quarters of the step (8, 16, 32, 64 or 128 nonzeros: the widths
     // a vector of lanes covers at once) that the longest of them needs: a stencil's boundary rows are a few per cent
-    // of the sample, a matrix of VARYING row lengths half of it (merge_path.hip, merge_rows_wanted)
+    // of the sample, a matrix of VARYING row lengths half of it (merge_plan.hip, merge_rows_wanted)
     __syncthreads();
     {
         const long long longest = s_lmax[0];

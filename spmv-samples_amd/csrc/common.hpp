@@ -235,6 +235,18 @@ int build_packed_index(Plan& p);   // after the shape is final: the packed index
 int find_giant_rows(Plan& p);      // balanced plans: rows beyond kGiantRow nonzeros (synchronises)
 void shape_merge(Plan& p);
 void merge_report_tile_walk(Plan& p);   // MERGE: n_kernels / main_kernel of a plan whose executes all take the tile kernel
+// MERGE, what the shaper and the launcher must agree on (merge_plan.hip): whether the main kernel searches its own
+// coordinates; whether the runs are summed row-parallel, and the regular row lengths that takes
+bool merge_search_in_kernel(const Plan& p);
+bool merge_rows_wanted(const Plan& p);
+bool merge_rows_regular(const Plan& p);
+// MERGE, the kernels that do not depend on the matrix type (merge_plan.hip).  The search: `diagonals` diagonals,
+// tile_items apart, `lanes` lanes each (16 | 4 | 1), into the plan's tile_row / tile_nnz.  The fix-up: the carries of the
+// plan's runs into y (nothing to add on a plan of one run).
+int launch_merge_search(int off_type, int lanes, int64_t diagonals, int64_t tile_items, const Plan& p, const void* Ap,
+                        hipStream_t s);
+template <typename val_t>
+int launch_merge_fixup(int semiring, const Plan& p, val_t* y, hipStream_t s);
 int shape_rows(Plan& p);           // VECTOR / LIGHT, whole plans: the shape, then set_rows_launch (synchronises)
 void set_rows_launch(Plan& p);     // VECTOR / LIGHT: kernel, grid and kernel count from the plan's shape
 // nnz-balanced cuts on the plan's chunk boundaries (analyze.hip; reads Ap on the device, synchronises)

@@ -42,6 +42,12 @@
 //
 // n_cols == 1 (the reference's special kernel, dispatch_spmv_orig.cuh:68-96,
 // :572-597) needs no special case here.
+//
+// This file is a header: the device code a value-type translation unit instantiates (merge_path_*.hip, through
+// merge_launch.hpp).  The search and fix-up kernels, which do not depend on the matrix type, and the plan's shape:
+// merge_plan.hip.
+
+#pragma once
 
 #include <climits>
 #include <cmath>
@@ -101,6 +107,19 @@ template <typename val_t> struct Semiring<MI355_SEMIRING_OR_AND, val_t> {   // b
     __device__ static __forceinline__ val_t combine(val_t a, val_t x) { return (a != val_t(0) && x != val_t(0)) ? val_t(1) : val_t(0); }
     __device__ static __forceinline__ val_t reduce(val_t u, val_t v) { return (u != val_t(0) || v != val_t(0)) ? val_t(1) : val_t(0); }
 };
+// host: f(std::integral_constant<int, S>()) for a plan's semiring S, which the kernels take as a template argument
+template <typename F>
+static int with_semiring(int semiring, F&& f) {
+    switch (semiring) {
+        case MI355_SEMIRING_PLUS_TIMES: return f(std::integral_constant<int, MI355_SEMIRING_PLUS_TIMES>());
+        case MI355_SEMIRING_MIN_PLUS: return f(std::integral_constant<int, MI355_SEMIRING_MIN_PLUS>());
+        case MI355_SEMIRING_MAX_TIMES: return f(std::integral_constant<int, MI355_SEMIRING_MAX_TIMES>());
+        case MI355_SEMIRING_MAX_PLUS: return f(std::integral_constant<int, MI355_SEMIRING_MAX_PLUS>());
+        case MI355_SEMIRING_OR_AND: return f(std::integral_constant<int, MI355_SEMIRING_OR_AND>());
+    }
+    set_error("merge: unknown semiring %d", semiring);
+    return MI355_SPMV_EINVAL;
+}
 
 // ---- K6: tile start coordinates ------------------------------------------------
 // The split of diagonal d is the first p in [lo, hi] with Ap[p + 1] > d - p - 1.  The reference finds it
@@ -138,27 +157,6 @@ __device__ __forceinline__ int64_t merge_search_group(int64_t diag, int32_t n_ro
         }
     }
     return lo;
-}
-
-template <int kSearchLanes, typename off_t>
-__global__ __launch_bounds__(kBlock) void merge_search_kernel(
-    int32_t n_rows, int64_t nnz_begin, int64_t nnz, const off_t* __restrict__ Ap, int64_t tile_items, int64_t n_tiles,
-    int32_t* __restrict__ tile_row, int64_t* __restrict__ tile_nnz) {
-    // (nnz_begin = Ap[0], nnz = Ap[n_rows]: the counting sequence of the merge is nnz_begin .. nnz - 1; a
-    // row-block view of a larger CSR starts at 1..3, everything else at 0)
-    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-    const int64_t t_raw = gid / kSearchLanes;
-    const int64_t t = t_raw <= n_tiles ? t_raw : n_tiles;       // surplus groups repeat the last diagonal
-    const int k = int(gid) & (kSearchLanes - 1);
-    const int shift = (threadIdx.x & (kWave - 1)) & ~(kSearchLanes - 1);
-    const int64_t items = int64_t(n_rows) + (nnz - nnz_begin);
-    int64_t diag = t * tile_items;
-    if (diag > items) diag = items;
-    const int64_t lo = merge_search_group<kSearchLanes, off_t>(diag, n_rows, nnz_begin, nnz, Ap, k, shift);
-    if (k == 0 && t_raw <= n_tiles) {
-        tile_row[t] = int32_t(lo);
-        tile_nnz[t] = nnz_begin + diag - lo;
-    }
 }
 
 // The stored value of a nonzero as val_t: element e of a prefetched 16-byte group, or entry k of Ax.  A pattern matrix
@@ -502,9 +500,7 @@ constexpr int kMergeRowsCap = 1984;    // rows per piece: bounds + results fit 1
 // (xwindow.hpp, chunk_rows_sweep: the CSR-vector kind's body for such bands; plain gathers ran the run at 1.6 TB/s).
 // NSEG > 1: the columns sit in several far-apart bands (the 3-D stencil) — each band gets its own segment of the window,
 // staged per piece of the run (xwindow.hpp, stage_x_segments: the CSR-vector kind's multi-band plan).
-template <int NSEG> struct SegmentArg { static const SegmentPlan& pick(const SegmentPlan& s, const struct NoSegments&) { return s; } };
 struct NoSegments {};   // (the one-window variants take no segment list: 68 bytes of kernel arguments cost the sweep variants their last scalar registers)
-template <> struct SegmentArg<1> { static const NoSegments& pick(const SegmentPlan&, const NoSegments& n) { return n; } };
 template <int BLOCK, int R, bool WINDOW, bool SEARCH, typename off_t, typename val_t, int TS = 0, int NSEG = 1>
 __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock ? 4 : 3)) void merge_rows_kernel(
     int32_t n_rows, int32_t n_cols, int64_t nnz_begin, int64_t nnz, const off_t* __restrict__ Ap,
@@ -613,451 +609,5 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock ? 4 : 3)) void merge_ro
         carry_val[sup] = carry;
     }
 }
-
-// ---- K8: add the carries of rows that straddle runs ------------------------------------
-template <int S, typename val_t>
-__global__ __launch_bounds__(kBlock) void merge_fixup_kernel(
-    int64_t n_carries, int32_t n_rows, const int32_t* __restrict__ carry_row,
-    const val_t* __restrict__ carry_val, val_t* __restrict__ y, val_t alpha) {
-    const int64_t t = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-    if (t >= n_carries) return;
-    // the neighbours and the value are fetched with carry_row[t]: two dependent round trips (then y[r]), not four
-    const int32_t r = carry_row[t];
-    const int32_t r_prev = t > 0 ? carry_row[t - 1] : -1;
-    const int32_t r_next = t + 1 < n_carries ? carry_row[t + 1] : -1;
-    val_t s = carry_val[t];
-    if (r >= n_rows || r_prev == r) return;      // no carry, or not the first run carrying row r
-    using SR = Semiring<S, val_t>;
-    if (r_next == r)
-        for (int64_t u = t + 1; u < n_carries && carry_row[u] == r; ++u) s = SR::reduce(s, carry_val[u]);
-    if constexpr (S == MI355_SEMIRING_PLUS_TIMES) s = alpha * s;
-    y[r] = SR::reduce(y[r], s);
-}
-
-// ---- host side -----------------------------------------------------------------------
-// Whether the tile kernel searches its own coordinates (MI355_MERGE_FUSED = 0 | 1 overrides): always, when a run
-// is short enough for the workgroup to search all its diagonals in two passes.
-static bool merge_search_in_kernel(const Plan& p) {
-    if (p.knob.merge_fused == 0) return false;
-    if (p.tiles_per_super + 1 > 32) return false;         // (one pass of 256 threads searches 32 diagonals)
-    if (p.knob.merge_fused > 0) return true;
-    // Measured (us, fused / search kernel in front): web-Google stand-in (1 473 runs) 46.6 / 49.5, cant stand-in 19.3 /
-    // 20.3 — but S32-band (4 233 runs of 16 tiles) 282 / 258 and R-MAT-24 (8 700 runs) 2 516 / 2 483: on a grid of
-    // many rounds every workgroup pays the search's chain of dependent loads at its start, and the search kernel's
-    // ~9 us are a few per cent.  Fused where the grid is at most ~two rounds of the chip.
-    return p.n_super <= int64_t(kCus) * 8;
-}
-
-// Row-parallel runs (merge_rows_kernel) for a matrix whose rows all but fill ONE step of a vector of 2, 4, 8, 16 or 32
-// lanes (the widths the run body picks from: 8, 16, 32, 64, 128 nonzeros per step) — the probe's 256 sampled rows all
-// hold between three quarters of such a step and the whole of it — and big enough for runs of 16 K+ items (on a small
-// matrix a run is a tile or two: the window and the two diagonals cost more than they are worth — cant stand-in 40.6 us
-// against 19.5 with the item walk).  Measured on 2^27 nonzeros (us, runs / item walk; scripts/gpu_r02_merge_regular.py,
-// profiles/r02_row_length_scan.txt): fixed 8 per row 347 / 410, 16: 285 / 315, 27: 251 / 275, 32: 218 / 257, 48: 239 / 256,
-// 64: 205 / 245, 100: 229 / 242, 128: 195 / 237 — but 40: 262 / 256 (a step of 64 is 62 % full), and rows of VARYING length
-// lose at every mean (24 +- 6: 415 / 341, 64 +- 16: 479 / 381, 128 +- 32: 502 / 380): those keep the item walk, at
-// 4.8-5.5 TB/s.  MI355_MERGE_ROWS = 0 | 1 overrides.
-[[maybe_unused]] static bool merge_rows_regular(const Plan& p);
-[[maybe_unused]] static bool merge_rows_wanted(const Plan& p) {
-    if (p.knob.merge_rows >= 0) return p.knob.merge_rows != 0;
-    if (p.tiles_per_super * p.tile_items < 16000) return false;      // (8 tiles of 2 044 items and up)
-    return merge_rows_regular(p);
-}
-[[maybe_unused]] static bool merge_rows_regular(const Plan& p) {
-    if (!p.probe_ok || p.n_rows <= 0 || p.val_type == MI355_VAL_I32) return false;
-    // (... or all but an eighth of them do: the boundary rows of a stencil — the nlpkkt stand-in's 27-point rows are
-    // 18, 12 or 8 long on the faces, edges and corners of its box — cost their vectors a few idle lanes, nothing more)
-    for (const int64_t step : {8, 16, 32, 64, 128})
-        if (p.probe_len_max <= step && (p.probe_len_min * 4 >= step * 3 || p.probe_short_rows * 8 <= kBlock)) return true;
-    return false;
-}
-
-#if !defined(MI355_TU_F64) && !defined(MI355_TU_I32) && !defined(MI355_TU_PATTERN)   // the host-side shape functions live in the fp32 translation unit only
-void shape_merge(Plan& p) {
-    // tuning knobs: MI355_MERGE_TPS = tiles per run (and MI355_SPMV_WINDOW = 0|1, analyze.hip)
-    // 256 threads x 8 items or (MI355_MERGE_BLOCK=512) 512 threads x 4 items: the same 2 044-item tiles
-    p.block_threads = p.knob.merge_block == kWideBlock ? kWideBlock : kBlock;
-    const int ipt = p.block_threads == kWideBlock ? 4 : 8;   // (16: S32-band 251 vs 259 us, web-Google stand-in 52.4 vs 46.4: not kept)
-    p.lanes_per_row = 0;
-    p.elems_per_lane = ipt;            // reported as items per thread for this kind
-    p.tile_items = int64_t(p.block_threads) * ipt - 4;
-    const int64_t items = int64_t(p.n_rows) + (p.nnz - p.nnz_begin);
-    p.n_tiles = (items + p.tile_items - 1) / p.tile_items;
-    // runs of up to ~32 K items, but at least ~4 runs per CU when the matrix allows
-    int64_t tps = p.n_tiles / (int64_t(kCus) * 4);
-    const int64_t cap = kMergeSuperItems / p.tile_items;
-    if (tps > cap) tps = cap;
-    if (p.knob.merge_tps > 0) tps = p.knob.merge_tps;
-    if (tps < 1) tps = 1;
-    // A REGULAR mid-size matrix (one to four runs of 8 tiles per CU) takes runs of 8 tiles rather than the two to seven
-    // the rule above gives it: 16 K items are what the row-parallel runs and their window of x need to pay
-    // (S32-band shape, us, before / after: 2^17 rows 20.5 / 19.4, 2^18 37.0 / 25.1, 2^19 47.7 / 41.3 — that one by the
-    // threshold in merge_rows_wanted alone).  Taken back below if no window placed from the band serves such a run.
-    const int64_t tps_small = tps;
-    const bool bumped = p.knob.merge_tps <= 0 && p.knob.merge_rows < 0 && tps < 8 && p.n_tiles >= 8 * int64_t(kCus) &&
-                        p.block_threads == kBlock && merge_rows_regular(p);
-    if (bumped) tps = 8;
-    p.tiles_per_super = tps;
-    p.n_super = (p.n_tiles + tps - 1) / tps;
-    p.grid_blocks = p.n_super;
-    // a window of x only pays when a run is long enough to amortise staging it, and
-    // when the band the probe saw (plus the rows of a run) fits
-    bool several_bands = false;
-    int segment_piece = 0;             // rows per piece of a row-parallel run with one window segment per band (0: not that plan)
-    {
-        const int64_t mean1 = 1 + (p.n_rows > 0 ? (p.nnz - p.nnz_begin) / p.n_rows : 0);
-        const int64_t rows_per_run = tps * p.tile_items / mean1 + 1;
-        p.window_elems = (tps * p.tile_items >= 8192) ? pick_window_elems(p, rows_per_run) : 0;
-        // fp64 halves what the 36 KB budget (three workgroups per CU) holds: the S32-band shape in fp64 ran on plain
-        // gathers at 2.4 TB/s.  Second try with 56 KB (two workgroups per CU next to the kernel's 16-24 KB of own LDS).
-        if (p.window_elems == 0 && p.n_seg < 2 && p.val_type == MI355_VAL_F64 && p.knob.window < 0 && tps * p.tile_items >= 8192 &&
-            p.knob.merge_wide_window != 0) {
-            p.window_bytes = 56 * 1024;
-            p.window_elems = pick_window_elems(p, rows_per_run);
-            if (p.window_elems == 0 || p.n_seg >= 2) p.window_bytes = 0;
-        }
-        // Several far-apart bands (the 3-D stencil).  A REGULAR matrix of that kind takes row-parallel runs with a segment
-        // of the window per band, staged per piece of a run — the CSR-vector kind's multi-band plan: the piece is as many
-        // rows as the bands leave room for, a run is one piece.  (Round 2 had this at 681 us against the item walk's 727
-        // on the C4 stand-in, with spilling kernels, and dropped it; the chunk body of round 3 fits its registers.)
-        // MI355_MERGE_SEGMENTS=0 keeps the item walk on plain gathers, as every other several-band matrix does.
-        if (p.n_seg >= 2 && p.block_threads == kBlock && p.knob.merge_segments != 0 && p.knob.merge_tps <= 0 &&
-            p.knob.window < 0 && merge_rows_wanted(p)) {
-            int64_t piece = segment_rows_fit(p);
-            if (piece > kMergeRowsCap) piece = kMergeRowsCap;
-            piece &= ~int64_t(3);
-            int64_t t2 = piece * mean1 / p.tile_items;
-            if (t2 > kMergeSuperItems / p.tile_items) t2 = kMergeSuperItems / p.tile_items;
-            const int64_t n_super = t2 >= 1 ? (p.n_tiles + t2 - 1) / t2 : 0;
-            if (piece >= 256 && t2 >= 1 && n_super >= int64_t(kCus) * 2) {
-                int64_t need = 0;                         // (LDS is occupancy: what the bands need with that many rows)
-                for (int i = 0; i < p.n_seg; ++i) need += p.seg_hi[i] - p.seg_lo[i] + 1 + 4 + piece;
-                need = (need + 3) & ~int64_t(3);
-                if (need < p.window_elems) p.window_elems = int(need);
-                p.tiles_per_super = t2;
-                p.n_super = n_super;
-                p.grid_blocks = n_super;
-                segment_piece = int(piece);
-            }
-        }
-        if (bumped && !(p.window_elems > 0 && p.n_seg < 2 && p.window_from_band)) {   // no window for runs of 8 tiles: the shorter runs
-            tps = tps_small;
-            p.tiles_per_super = tps;
-            p.n_super = (p.n_tiles + tps - 1) / tps;
-            p.grid_blocks = p.n_super;
-            p.window_bytes = 0;
-            p.window_elems = (tps * p.tile_items >= 8192) ? pick_window_elems(p, tps * p.tile_items / mean1 + 1) : 0;
-            segment_piece = 0;
-        }
-        several_bands = p.n_seg >= 2 && segment_piece == 0;
-        if (several_bands) { p.window_elems = 0; p.n_seg = 0; }   // several bands: the item walk keeps to global gathers
-    }
-    p.n_kernels = (p.n_super > 1 ? 2 : 1) + ((merge_search_in_kernel(p) && p.block_threads == kBlock) ? 0 : 1);
-    // (a matrix whose columns sit in several far-apart bands — the 3-D stencil — keeps the item walk: row-parallel runs
-    // on plain gathers measured 720 us against 650-700 on the C4 stand-in, and with the bands staged per piece of a run
-    // 681 against 727 on one box, with four spilling kernels: not kept)
-    p.merge_rows = p.block_threads == kBlock && !several_bands && merge_rows_wanted(p);
-    p.mr_block = kBlock;
-    p.mr_piece_rows = segment_piece > 0 ? segment_piece : kMergeRowsCap;
-    if (segment_piece > 0 && !p.merge_rows) { p.window_elems = 0; p.n_seg = 0; }   // (cannot happen: merge_rows_wanted held above)
-    // The band does not fit the window of a 256-thread workgroup (fp64 on the S32-band shape: 8 193 columns + the rows of a run):
-    // two workgroups of 512 threads per CU may take ~78 KB each, as the CSR-vector kind's wide plan does; the run is then
-    // as long as the rows the band leaves room for, and walked in one piece.
-    if (p.merge_rows && segment_piece == 0 && p.knob.merge_wide_window != 0 && p.knob.window < 0 && p.knob.merge_tps <= 0 && p.probe_ok &&
-        !(p.window_elems > 0 && p.window_from_band)) {
-        const int64_t vb = p.val_type == MI355_VAL_F64 ? 8 : 4;
-        const int64_t band = p.band_hi - p.band_lo + 1;
-        const int64_t mean1 = 1 + (p.n_rows > 0 ? (p.nnz - p.nnz_begin) / p.n_rows : 0);
-        // ... and a band too wide for that gets ONE workgroup of 1 024 threads per CU with ~155 KB (the CSR-vector kind's
-        // third plan): fp32, 32 769 columns, 32 per row: 343 -> see profiles/r02_shape_sweep.txt
-        const struct { int block; int64_t lds; int64_t min_piece; } tries[2] = {{kWideBlock, 78 * 1024, 256}, {kHugeBlock, 155 * 1024, 512}};
-        for (const auto& t : tries) {
-            int64_t piece = (t.lds - vb * (band + 8) - 4) * 8 / (8 * (2 * vb + 4) + 1);   // val (band + rows + 8) + 4 (rows + 1) + val rows + rows / 8
-            piece &= ~int64_t(3);
-            if (piece > kMergeRowsCap) piece = kMergeRowsCap;
-            if (!(band > 0 && piece >= t.min_piece)) continue;
-            const Plan saved = p;
-            int64_t t2 = piece * mean1 / p.tile_items;
-            if (t2 > kMergeSuperItems / p.tile_items) t2 = kMergeSuperItems / p.tile_items;
-            if (t2 < 1) t2 = 1;
-            p.tiles_per_super = t2;
-            p.n_super = (p.n_tiles + t2 - 1) / t2;
-            p.grid_blocks = p.n_super;
-            p.window_bytes = int(vb * (band + piece + 8));
-            p.window_elems = pick_window_elems(p, piece);
-            if (p.window_elems > 0 && p.n_seg < 2 && p.window_from_band && p.n_super >= int64_t(kCus) * 2) {
-                p.mr_block = t.block;
-                p.mr_piece_rows = int(piece);
-                break;
-            }
-            p = saved;
-        }
-    }
-    // Still no window: the band is wider than one CU's LDS.  The CSR-vector kind sweeps such a band with the window
-    // (analyze.hip, shape_sweep); a run here does the same — a piece = one group of rows of a 1 024-thread workgroup held in
-    // registers, 4 T nonzeros per row in one step — under the same rule: the staged bytes of a piece stay below half the
-    // line fills its nonzeros would cost as plain gathers.  Rows of up to 8 nonzeros (T = 2) keep the gathers.
-    p.mr_sweep_lanes = 0;
-    if (p.merge_rows && p.window_elems == 0 && p.probe_ok && p.knob.sweep != 0 && p.knob.window < 0 && p.knob.merge_tps <= 0 &&
-        p.knob.merge_wide_window != 0 && p.probe_len_max > 8 && p.probe_len_max <= 128) {
-        const int64_t vb = p.val_type == MI355_VAL_F64 ? 8 : 4;
-        const int64_t band = p.band_hi - p.band_lo + 1;
-        const int64_t mean1 = 1 + (p.n_rows > 0 ? (p.nnz - p.nnz_begin) / p.n_rows : 0);
-        int t = 4;
-        while (t < 32 && 4 * t < p.probe_len_max) t *= 2;
-        const int64_t piece = int64_t(kHugeBlock / t) * sweep_rows_for(p.val_type, t);
-        const int64_t fixed = int64_t(chunk_lds_bytes(0, int(piece), size_t(vb)));
-        const int64_t cap = sweep_window_cap(vb, fixed);
-        const int64_t span = band + piece + 8;
-        const int64_t passes = cap > 0 ? (span + cap - 1) / cap : 0;
-        int64_t t2 = piece * mean1 / p.tile_items;
-        if (t2 > kMergeSuperItems / p.tile_items) t2 = kMergeSuperItems / p.tile_items;
-        if (t2 < 1) t2 = 1;
-        const int64_t n_super = (p.n_tiles + t2 - 1) / t2;
-        const bool pays = span * vb <= 64 * (mean1 - 1) * piece;
-        if (band > 0 && passes >= 1 && passes <= 16 && n_super >= int64_t(kCus) * 2 && (pays || p.knob.sweep == 1)) {
-            p.tiles_per_super = t2;
-            p.n_super = n_super;
-            p.grid_blocks = n_super;
-            p.mr_block = kHugeBlock;
-            p.mr_piece_rows = int(piece);
-            p.mr_sweep_lanes = t;
-            p.window_bytes = int(cap * vb);
-            p.window_elems = int(cap);
-            p.window_from_band = true;
-            p.n_seg = 0;
-        }
-    }
-    if (p.merge_rows) {
-        p.n_kernels = (p.n_super > 1 ? 2 : 1) + (merge_search_in_kernel(p) ? 0 : 1);
-        snprintf(p.main_kernel, sizeof(p.main_kernel), "merge_rows_kernel");
-        return;
-    }
-    p.coords_valid = false;
-    snprintf(p.main_kernel, sizeof(p.main_kernel), "merge_tile_kernel");
-}
-
-// What a plan reports when every one of its executes walks the tiles whatever shape_merge shaped it around (a pattern
-// matrix: merge_rows_kernel has no pattern form).  The shape itself — tiles, runs, window — stays as it is.
-void merge_report_tile_walk(Plan& p) {
-    p.n_kernels = (p.n_super > 1 ? 2 : 1) + ((merge_search_in_kernel(p) && p.block_threads == kBlock) ? 0 : 1);
-    snprintf(p.main_kernel, sizeof(p.main_kernel), "merge_tile_kernel");
-}
-
-// The tile coordinates on demand (mi355_spmv_plan_merge_coords on a plan whose executes do not produce them: the
-// row-parallel run kernel only ever finds its own two diagonals).
-int merge_compute_coords(Plan& p) {
-    if (p.n_rows == 0 || p.n_tiles == 0) return MI355_SPMV_OK;
-    const unsigned g = unsigned(((p.n_tiles + 1) * 4 + kBlock - 1) / kBlock);
-    if (p.off_type == MI355_OFF_I32)
-        hipLaunchKernelGGL((merge_search_kernel<4, int32_t>), dim3(g), dim3(kBlock), 0, nullptr, p.n_rows, p.nnz_begin, p.nnz,
-                           static_cast<const int32_t*>(p.Ap), p.tile_items, p.n_tiles, p.tile_row, p.tile_nnz);
-    else
-        hipLaunchKernelGGL((merge_search_kernel<4, int64_t>), dim3(g), dim3(kBlock), 0, nullptr, p.n_rows, p.nnz_begin, p.nnz,
-                           static_cast<const int64_t*>(p.Ap), p.tile_items, p.n_tiles, p.tile_row, p.tile_nnz);
-    MI355_HIP_TRY(hipGetLastError());
-    MI355_HIP_TRY(hipStreamSynchronize(nullptr));
-    return MI355_SPMV_OK;
-}
-
-#endif
-
-template <typename off_t, typename val_t, typename mat_t>
-int launch_merge(Plan& p, const off_t* Ap, const mat_t* Ax, const val_t* x, val_t* y, hipStream_t s) {
-    if (p.n_rows == 0 || p.n_tiles == 0) return MI355_SPMV_OK;
-    // (a pattern matrix has no Ax: whatever the caller passed, NULL included, is neither read nor counted here)
-    const uintptr_t ax_bits = std::is_same<mat_t, PatternOnes>::value ? uintptr_t(0) : reinterpret_cast<uintptr_t>(Ax);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(p.Aj) | ax_bits | reinterpret_cast<uintptr_t>(x)) & 15u) == 0;
-    const bool reuse = (p.flags & MI355_PLAN_REUSE_STRUCTURE) && p.coords_valid;
-    const bool vec = aligned && p.nnz >= 4;
-    const bool wide = p.block_threads == kWideBlock && p.semiring == MI355_SEMIRING_PLUS_TIMES;
-    // the tile kernel finds its run's coordinates itself (no search kernel in front) on the 16-byte path with 256 threads
-    // regular matrix: row-parallel runs (plus-times, one value type, 16-byte path); the kernel searches its own diagonals
-    if constexpr (std::is_same<val_t, mat_t>::value && std::is_floating_point<val_t>::value) {
-        if (p.merge_rows && vec && p.semiring == MI355_SEMIRING_PLUS_TIMES) {
-            constexpr int RR = sizeof(val_t) == 4 ? 4 : 2;
-            const int32_t capw = (int32_t)p.window_elems;
-            const size_t lds = chunk_lds_bytes(capw, p.mr_piece_rows, sizeof(val_t));
-            const BandHint hint_r{p.band_lo, p.band_hi, p.window_from_band};
-            const dim3 grid_r((unsigned)p.n_super);
-            // run boundaries: searched in the kernel on small grids, by the search kernel (n_super + 1 diagonals of
-            // tiles_per_super tiles each; the last one clamps to the end of the merge) on big ones
-            const bool in_kernel = merge_search_in_kernel(p);
-            if (!in_kernel) {
-                const int64_t diagonals = p.n_super + 1;
-                const unsigned gs = unsigned((diagonals * 4 + kBlock - 1) / kBlock);
-                hipLaunchKernelGGL((merge_search_kernel<4, off_t>), dim3(gs), dim3(kBlock), 0, s, p.n_rows, p.nnz_begin, p.nnz, Ap,
-                                   p.tile_items * p.tiles_per_super, p.n_super, p.tile_row, p.tile_nnz);
-                MI355_HIP_TRY(hipGetLastError());
-                p.coords_valid = false;       // (the arrays now hold RUN boundaries, not tile coordinates)
-            }
-            // (rows a vector keeps in flight: the 512-thread kernel is held to 128 VGPRs, which the fp32 body with 4 rows exceeds)
-            SegmentPlan segs;
-            segs.n = p.n_seg;
-            for (int i = 0; i < kMaxSegments; ++i) { segs.lo[i] = p.seg_lo[i]; segs.hi[i] = p.seg_hi[i]; }
-            const NoSegments no_segs;
-#define MI355_MERGE_ROWS_LAUNCH_N(BLOCK_, WIN_, SEARCH_, NSEG_)                                                    \
-    do {                                                                                                           \
-        constexpr int RR_ = (BLOCK_ >= kWideBlock || NSEG_ > 1) ? 2 : RR;   /* (several bands: the fp32 body with 4 rows spills) */ \
-        const auto& segs_ = SegmentArg<NSEG_>::pick(segs, no_segs);                                                 \
-        if (const int st = allow_dynamic_lds((const void*)merge_rows_kernel<BLOCK_, RR_, WIN_, SEARCH_, off_t, val_t, 0, NSEG_>, lds + 1024)) return st; \
-        hipLaunchKernelGGL((merge_rows_kernel<BLOCK_, RR_, WIN_, SEARCH_, off_t, val_t, 0, NSEG_>), grid_r, dim3(BLOCK_), lds, s, p.n_rows, \
-                           p.n_cols, p.nnz_begin, p.nnz, Ap, p.Aj, Ax, x, y, p.tile_items, p.tile_row, p.tile_nnz,   \
-                           p.carry_row, static_cast<val_t*>(p.carry_val), p.n_tiles, (int32_t)p.tiles_per_super,    \
-                           capw, hint_r, (val_t)p.alpha, (val_t)p.beta, (int32_t)p.mr_piece_rows, segs_);           \
-    } while (0)
-#define MI355_MERGE_ROWS_LAUNCH(BLOCK_, WIN_, SEARCH_) MI355_MERGE_ROWS_LAUNCH_N(BLOCK_, WIN_, SEARCH_, 1)
-            if (p.mr_sweep_lanes > 0 && capw > 0) {           // the window sweeps the band: one group of rows per piece
-                constexpr int RS = sizeof(val_t) == 4 ? 8 : kSweepRows;
-                const BandHint hint_s{p.band_lo, p.band_hi, true};
-                if (p.mr_piece_rows != (kHugeBlock / p.mr_sweep_lanes) * RS || capw < int32_t(kHugeBlock * 16 / sizeof(val_t))) {
-                    set_error("merge: sweep plan with %d rows per piece at %d lanes per row", p.mr_piece_rows, p.mr_sweep_lanes);
-                    return MI355_SPMV_EINVAL;
-                }
-#define MI355_MERGE_SWEEP_LAUNCH(TS_, SEARCH_)                                                                     \
-    do {                                                                                                           \
-        if (const int st = allow_dynamic_lds((const void*)merge_rows_kernel<kHugeBlock, RS, true, SEARCH_, off_t, val_t, TS_>, lds + 1024)) return st; \
-        hipLaunchKernelGGL((merge_rows_kernel<kHugeBlock, RS, true, SEARCH_, off_t, val_t, TS_>), grid_r, dim3(kHugeBlock), lds, s, p.n_rows, \
-                           p.n_cols, p.nnz_begin, p.nnz, Ap, p.Aj, Ax, x, y, p.tile_items, p.tile_row, p.tile_nnz,   \
-                           p.carry_row, static_cast<val_t*>(p.carry_val), p.n_tiles, (int32_t)p.tiles_per_super,    \
-                           capw, hint_s, (val_t)p.alpha, (val_t)p.beta, (int32_t)p.mr_piece_rows, no_segs);         \
-    } while (0)
-                switch (p.mr_sweep_lanes) {
-                    case 4:  if (in_kernel) MI355_MERGE_SWEEP_LAUNCH(4, true); else MI355_MERGE_SWEEP_LAUNCH(4, false); break;
-                    case 8:  if (in_kernel) MI355_MERGE_SWEEP_LAUNCH(8, true); else MI355_MERGE_SWEEP_LAUNCH(8, false); break;
-                    case 16: if (in_kernel) MI355_MERGE_SWEEP_LAUNCH(16, true); else MI355_MERGE_SWEEP_LAUNCH(16, false); break;
-                    case 32: if (in_kernel) MI355_MERGE_SWEEP_LAUNCH(32, true); else MI355_MERGE_SWEEP_LAUNCH(32, false); break;
-                    default: set_error("merge: bad sweep width %d", p.mr_sweep_lanes); return MI355_SPMV_EINVAL;
-                }
-#undef MI355_MERGE_SWEEP_LAUNCH
-            }
-            else if (p.mr_block == kHugeBlock && capw > 0) {       // (the wide run kernels exist around ONE window of x)
-                if (in_kernel) MI355_MERGE_ROWS_LAUNCH(kHugeBlock, true, true); else MI355_MERGE_ROWS_LAUNCH(kHugeBlock, true, false);
-            }
-            else if (p.mr_block == kWideBlock && capw > 0) {
-                if (in_kernel) MI355_MERGE_ROWS_LAUNCH(kWideBlock, true, true); else MI355_MERGE_ROWS_LAUNCH(kWideBlock, true, false);
-            }
-            else if (capw > 0 && p.n_seg >= 2) {                   // several bands: a segment of the window each
-                if (in_kernel) MI355_MERGE_ROWS_LAUNCH_N(kBlock, true, true, kMaxSegments); else MI355_MERGE_ROWS_LAUNCH_N(kBlock, true, false, kMaxSegments);
-            }
-            else if (capw > 0) { if (in_kernel) MI355_MERGE_ROWS_LAUNCH(kBlock, true, true); else MI355_MERGE_ROWS_LAUNCH(kBlock, true, false); }
-            else { if (in_kernel) MI355_MERGE_ROWS_LAUNCH(kBlock, false, true); else MI355_MERGE_ROWS_LAUNCH(kBlock, false, false); }
-#undef MI355_MERGE_ROWS_LAUNCH
-#undef MI355_MERGE_ROWS_LAUNCH_N
-            MI355_HIP_TRY(hipGetLastError());
-            if (p.n_super > 1) {
-                const unsigned g = unsigned((p.n_super + kBlock - 1) / kBlock);
-                hipLaunchKernelGGL((merge_fixup_kernel<MI355_SEMIRING_PLUS_TIMES, val_t>), dim3(g), dim3(kBlock), 0, s, p.n_super,
-                                   p.n_rows, p.carry_row, static_cast<const val_t*>(p.carry_val), y, (val_t)p.alpha);
-                MI355_HIP_TRY(hipGetLastError());
-            }
-            return MI355_SPMV_OK;
-        }
-    }
-    const bool fused = !reuse && vec && !wide && merge_search_in_kernel(p);
-    if (!reuse && !fused) {
-        const int64_t diagonals = p.n_tiles + 1;
-        // measured (us, L = 1 / 4 / 16): 2 946 diagonals 7.3 / 6.0 / 4.4, 68 K 11.9 / 8.5 / 13.3, 139 K 14.0 / 16.0 / 30.9
-        const int forced = p.knob.merge_search_lanes;
-        const int lanes = forced > 0 ? forced : diagonals <= 16384 ? 16 : diagonals <= 98304 ? 4 : 1;
-        const unsigned g = unsigned((diagonals * lanes + kBlock - 1) / kBlock);
-        if (lanes >= 16)
-            hipLaunchKernelGGL((merge_search_kernel<16, off_t>), dim3(g), dim3(kBlock), 0, s, p.n_rows, p.nnz_begin, p.nnz, Ap,
-                               p.tile_items, p.n_tiles, p.tile_row, p.tile_nnz);
-        else if (lanes >= 4)
-            hipLaunchKernelGGL((merge_search_kernel<4, off_t>), dim3(g), dim3(kBlock), 0, s, p.n_rows, p.nnz_begin, p.nnz, Ap,
-                               p.tile_items, p.n_tiles, p.tile_row, p.tile_nnz);
-        else
-            hipLaunchKernelGGL((merge_search_kernel<1, off_t>), dim3(g), dim3(kBlock), 0, s, p.n_rows, p.nnz_begin, p.nnz, Ap,
-                               p.tile_items, p.n_tiles, p.tile_row, p.tile_nnz);
-        MI355_HIP_TRY(hipGetLastError());
-    }
-    if (!reuse) p.coords_valid = true;
-    // a window sized for the row-parallel run kernel (512 / 1 024 threads, a swept band, a segment per band: up to
-    // ~155 KB) is not one for the tile kernel, which needs its own ~24 KB next to it: those plans' other executes
-    // (another semiring, an fp32 matrix under fp64 vectors) walk their tiles on plain gathers
-    const bool rows_window = p.merge_rows && (p.mr_block != kBlock || p.mr_sweep_lanes > 0 || p.n_seg >= 2);
-    const int32_t cap = (aligned && p.nnz >= 4 && !rows_window) ? (int32_t)p.window_elems : 0;
-    const size_t dyn = size_t(cap) * sizeof(val_t);
-    const BandHint hint{p.band_lo, p.band_hi, p.window_from_band};
-    const dim3 grid((unsigned)p.n_super);
-#define MI355_MERGE_ARGS dyn, s, p.n_rows, p.n_cols, p.nnz_begin, p.nnz, Ap, p.Aj, Ax, x, y, p.tile_row, p.tile_nnz, p.tile_items, p.carry_row, \
-                       static_cast<val_t*>(p.carry_val), p.n_tiles, (int32_t)p.tiles_per_super, cap, hint, (val_t)p.alpha, (val_t)p.beta
-#define MI355_MERGE_ALLOW(K_)                                                                                 \
-    if (dyn > 40 * 1024)                                                                                      \
-        if (const int st_ = allow_dynamic_lds((const void*)K_, dyn + 24 * 1024)) return st_;   /* (dynamic + the kernel's own LDS may pass 64 KB) */
-#define MI355_MERGE_LAUNCH(VEC_, WIN_, S_)                                                                    \
-    do {                                                                                                      \
-        if constexpr (S_ == MI355_SEMIRING_PLUS_TIMES) {                                                      \
-            if (wide) {                                                                                       \
-                MI355_MERGE_ALLOW((merge_tile_kernel<kWideBlock, 4, VEC_, WIN_, S_, false, off_t, val_t, mat_t>)) \
-                hipLaunchKernelGGL((merge_tile_kernel<kWideBlock, 4, VEC_, WIN_, S_, false, off_t, val_t, mat_t>), grid, dim3(kWideBlock), MI355_MERGE_ARGS); \
-                break;                                                                                        \
-            }                                                                                                 \
-        }                                                                                                     \
-        if constexpr (VEC_) {                                                                                 \
-            if (fused) {                                                                                      \
-                MI355_MERGE_ALLOW((merge_tile_kernel<kBlock, 8, VEC_, WIN_, S_, true, off_t, val_t, mat_t>))  \
-                hipLaunchKernelGGL((merge_tile_kernel<kBlock, 8, VEC_, WIN_, S_, true, off_t, val_t, mat_t>), grid, dim3(kBlock), MI355_MERGE_ARGS); \
-                break;                                                                                        \
-            }                                                                                                 \
-        }                                                                                                     \
-        MI355_MERGE_ALLOW((merge_tile_kernel<kBlock, 8, VEC_, WIN_, S_, false, off_t, val_t, mat_t>))         \
-        hipLaunchKernelGGL((merge_tile_kernel<kBlock, 8, VEC_, WIN_, S_, false, off_t, val_t, mat_t>), grid, dim3(kBlock), MI355_MERGE_ARGS); \
-    } while (0)
-#define MI355_MERGE_SEMIRING(S_)                                                    \
-    do {                                                                            \
-        if (!vec) MI355_MERGE_LAUNCH(false, false, S_);                             \
-        else if (cap > 0) MI355_MERGE_LAUNCH(true, true, S_);                       \
-        else MI355_MERGE_LAUNCH(true, false, S_);                                   \
-        MI355_HIP_TRY(hipGetLastError());                                           \
-        if (p.n_super > 1) {                                                        \
-            const unsigned g = unsigned((p.n_super + kBlock - 1) / kBlock);         \
-            hipLaunchKernelGGL((merge_fixup_kernel<S_, val_t>), dim3(g), dim3(kBlock), 0, s, p.n_super, p.n_rows, \
-                               p.carry_row, static_cast<const val_t*>(p.carry_val), y, (val_t)p.alpha);      \
-            MI355_HIP_TRY(hipGetLastError());                                       \
-        }                                                                           \
-    } while (0)
-    switch (p.semiring) {
-        case MI355_SEMIRING_PLUS_TIMES: MI355_MERGE_SEMIRING(MI355_SEMIRING_PLUS_TIMES); break;
-        case MI355_SEMIRING_MIN_PLUS:   MI355_MERGE_SEMIRING(MI355_SEMIRING_MIN_PLUS); break;
-        case MI355_SEMIRING_MAX_TIMES:  MI355_MERGE_SEMIRING(MI355_SEMIRING_MAX_TIMES); break;
-        case MI355_SEMIRING_MAX_PLUS:   MI355_MERGE_SEMIRING(MI355_SEMIRING_MAX_PLUS); break;
-        case MI355_SEMIRING_OR_AND:     MI355_MERGE_SEMIRING(MI355_SEMIRING_OR_AND); break;
-        default:
-            set_error("merge: unknown semiring %d", p.semiring);
-            return MI355_SPMV_EINVAL;
-    }
-#undef MI355_MERGE_SEMIRING
-#undef MI355_MERGE_LAUNCH
-#undef MI355_MERGE_ALLOW
-#undef MI355_MERGE_ARGS
-    return MI355_SPMV_OK;
-}
-
-// One translation unit per value type (merge_path_f64.hip / merge_path_i32.hip include this file with MI355_TU_F64 /
-// MI355_TU_I32): the three thirds of the instantiations compile side by side.  merge_path_pattern.hip (MI355_TU_PATTERN)
-// holds the tile kernels of pattern matrices, for all three vector types.
-#if defined(MI355_TU_PATTERN)
-template int launch_merge<int32_t, float, PatternOnes>(Plan&, const int32_t*, const PatternOnes*, const float*, float*, hipStream_t);
-template int launch_merge<int64_t, float, PatternOnes>(Plan&, const int64_t*, const PatternOnes*, const float*, float*, hipStream_t);
-template int launch_merge<int32_t, double, PatternOnes>(Plan&, const int32_t*, const PatternOnes*, const double*, double*, hipStream_t);
-template int launch_merge<int64_t, double, PatternOnes>(Plan&, const int64_t*, const PatternOnes*, const double*, double*, hipStream_t);
-template int launch_merge<int32_t, int32_t, PatternOnes>(Plan&, const int32_t*, const PatternOnes*, const int32_t*, int32_t*, hipStream_t);
-template int launch_merge<int64_t, int32_t, PatternOnes>(Plan&, const int64_t*, const PatternOnes*, const int32_t*, int32_t*, hipStream_t);
-#elif defined(MI355_TU_F64)
-template int launch_merge<int32_t, double, double>(Plan&, const int32_t*, const double*, const double*, double*, hipStream_t);
-template int launch_merge<int64_t, double, double>(Plan&, const int64_t*, const double*, const double*, double*, hipStream_t);
-// fp32 matrix under fp64 vectors (mi355_spmv_plan_create_typed)
-template int launch_merge<int32_t, double, float>(Plan&, const int32_t*, const float*, const double*, double*, hipStream_t);
-template int launch_merge<int64_t, double, float>(Plan&, const int64_t*, const float*, const double*, double*, hipStream_t);
-#elif defined(MI355_TU_I32)
-// 32-bit integer values (MI355_VAL_I32: every semiring, exact)
-template int launch_merge<int32_t, int32_t, int32_t>(Plan&, const int32_t*, const int32_t*, const int32_t*, int32_t*, hipStream_t);
-template int launch_merge<int64_t, int32_t, int32_t>(Plan&, const int64_t*, const int32_t*, const int32_t*, int32_t*, hipStream_t);
-#else
-template int launch_merge<int32_t, float, float>(Plan&, const int32_t*, const float*, const float*, float*, hipStream_t);
-template int launch_merge<int64_t, float, float>(Plan&, const int64_t*, const float*, const float*, float*, hipStream_t);
-#endif
 
 }  // namespace mi355

@@ -836,7 +836,7 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
 // one step) from the chunk's own mean row length, read from the bounds already in LDS.
 // REGULAR (the merge kind's row-parallel runs: rows alike): the width that takes a mean row in ONE step (8 / 16 / 32 /
 // 64 / 128 nonzeros) — a second, dependent step per row costs such a matrix more than idle lanes do (rows of 64 +- 16 with 8
-// lanes: three steps, 740 us; with 32 lanes: see merge_path.hip).
+// lanes: three steps, 740 us; with 32 lanes: see merge_plan.hip).
 template <int BLOCK, int T, int R, bool WINDOW, bool ADAPT, typename val_t, typename StageFn, bool REGULAR = false,
           bool PACKED = false>
 __device__ __forceinline__ void chunk_rows_any(int64_t chunk_begin, int64_t chunk_end, int32_t nnz,

@@ -36,7 +36,7 @@ class Group:
 
 # Sizes.  large: the 512- and 1 024-thread plans, the sweep, and — the reason it has 2.2 M rows rather than 1.5 M — a
 # merge grid of more than 2 048 runs of 16 tiles (69 M+ items), the size from which merge_tile_kernel takes its
-# coordinates from a search kernel in front (merge_path.hip, merge_search_in_kernel).  f64: 1.2 M rows, so that the
+# coordinates from a search kernel in front (merge_plan.hip, merge_search_in_kernel).  f64: 1.2 M rows, so that the
 # weight-cut plan is cut into 2 x 1 024 chunks, more than twice what stays resident: LIGHT's persistent grid.
 # small32 / small8: under SMALL_PLAIN_NNZ nonzeros with two mean row lengths, i.e. two lane widths of the plain kernel.
 LARGE = ("band_narrow", "band_1024", "band_sweep", "stencil", "scatter", "powerlaw", "powerlaw_band", "ragged", "giant",

@@ -59,7 +59,7 @@ def row_kind_lines():
 
 def merge_lines():
     # merge: n_kernels = the main kernel, the carry fix-up when there is more than one run, and the search kernel in
-    # front unless the main kernel searches its own coordinates (merge_path.hip, shape_merge)
+    # front unless the main kernel searches its own coordinates (merge_plan.hip, shape_merge)
     searches_itself = lambda i: i["n_kernels"] == (2 if i["grid_blocks"] > 1 else 1)
     runs = lambda k, i: k == "merge" and i["main_kernel"] == RUNS
     sweeping = lambda i, e: i["block_threads"] == 1024 and 0 < i["window_elems"] < e["band"]

@@ -1,6 +1,6 @@
 """GPU suite: the executes of a merge plan built for its row-parallel run kernel (merge_rows_kernel) that the run kernel
 does not serve — another semiring, the one-shot generalized entry points, an fp32 matrix under fp64 vectors, unaligned
-views — and that walk the plan's tiles with merge_tile_kernel instead (merge_path.hip, launch_merge).  The plans are
+views — and that walk the plan's tiles with merge_tile_kernel instead (merge_launch.hpp, launch_merge).  The plans are
 the wide ones of tests/test_gpu_parity.py: 512- and 1 024-thread runs with one window of x, runs that sweep a band
 wider than any window, and runs that stage a window segment per band.  Their window was sized for the run kernel
 (up to ~155 KB of LDS): the tile kernel must not inherit it.
