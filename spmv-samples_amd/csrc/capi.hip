@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <mutex>
 #include <new>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -106,9 +107,8 @@ static int plan_alloc_scratch(Plan& p) {
     return MI355_SPMV_OK;
 }
 
-template <typename off_t, typename val_t>
-static int execute_typed(Plan& p, const void* Ax, const void* x, void* y, hipStream_t s) {
-    const off_t* Ap = static_cast<const off_t*>(p.Ap);
+template <typename val_t, typename off_t>
+static int execute_typed(Plan& p, const off_t* Ap, const void* Ax, const void* x, void* y, hipStream_t s) {
     const val_t* ax = static_cast<const val_t*>(Ax);
     const val_t* xx = static_cast<const val_t*>(x);
     val_t* yy = static_cast<val_t*>(y);
@@ -285,13 +285,7 @@ int mi355_spmv_device_count(void) {
 
 // Common body of plan_create / plan_create_block.  blk == nullptr: an ordinary plan (Ap[0] == 0).
 // blk != nullptr: rows of a larger CSR (Ap[0] = blk->phase in 0..3, nnz = END offset); VECTOR / LIGHT blocks
-// inherit the launch shape of the whole matrix's plan so that every row is summed exactly as there.
-struct BlockSpec {
-    const mi355_spmv_plan_shape* whole;   // may be null (MERGE, or an independent block)
-    int64_t row_begin, chunk_begin, n_chunks, nnz_begin_whole;
-    int phase;
-};
-
+// inherit the launch shape of the whole matrix's plan (rows_plan.hip, inherit_rows_shape).
 static int plan_create_impl(mi355_spmv_plan** out, int kind, int off_type, int val_type, int32_t n_rows,
                             int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj, int flags,
                             const BlockSpec* blk) {
@@ -313,10 +307,9 @@ static int plan_create_impl(mi355_spmv_plan** out, int kind, int off_type, int v
     if (nnz > 0 && n_cols == 0) { set_error("plan_create: nonzeros but no columns"); return MI355_SPMV_EINVAL; }
     if (blk && (blk->phase < 0 || blk->phase > 3 || blk->phase > nnz)) { set_error("plan_create_block: Ap[0] must be 0..3"); return MI355_SPMV_EINVAL; }
 
-    mi355_spmv_plan* h = new (std::nothrow) mi355_spmv_plan();
+    mi355_spmv_plan* h = new (std::nothrow) mi355_spmv_plan();   // (the plan value-initialised: common.hpp)
     if (!h) { set_error("plan_create: host allocation failed"); return MI355_SPMV_ENOMEM; }
     Plan& p = h->p;
-    memset(static_cast<void*>(&p), 0, sizeof(p));
     p.knob = knobs();
     p.kind = kind; p.off_type = off_type; p.val_type = val_type; p.flags = flags;
     p.mat_type = val_type;
@@ -326,66 +319,23 @@ static int plan_create_impl(mi355_spmv_plan** out, int kind, int off_type, int v
     p.elems_per_lane = 4;
     p.alpha = 1.0;
     p.beta = 0.0;
-    const mi355_spmv_plan_shape* w = (blk && kind != MI355_KIND_MERGE) ? blk->whole : nullptr;
-    if (w) {
-        if (w->struct_bytes != int32_t(sizeof(mi355_spmv_plan_shape)) || w->kind != kind || w->off_type != off_type ||
-            w->val_type != val_type) {
-            set_error("plan_create_block: the shape is of another kind / type / library version");
-            delete h;
-            return MI355_SPMV_EINVAL;
-        }
-        if (n_rows > 0 && ((blk->row_begin & 3) != 0 ||
-                           (w->balanced_chunks == 0 && w->rows_per_chunk > 0 && blk->row_begin % w->rows_per_chunk != 0))) {
-            set_error("plan_create_block: row_begin is not a chunk boundary of the whole plan");
-            delete h;
-            return MI355_SPMV_EINVAL;
-        }
-        p.is_block = true;
-        // not the last block: the tail of its last row is read in whole 16-byte groups, as the whole plan reads it — but
-        // never past the end of the whole arrays (a block that ends inside their last, partial group)
-        if ((blk->nnz_begin_whole & ~int64_t(3)) + nnz < w->nnz)
-            p.nnz_read = std::min((nnz + 3) & ~int64_t(3), w->nnz - (blk->nnz_begin_whole & ~int64_t(3)));
-        p.block_row_begin = blk->row_begin;
-        p.block_chunk_begin = blk->chunk_begin;
-        p.lanes_per_row = w->lanes_per_row;
-        p.elems_per_lane = w->elems_per_lane;
-        p.block_threads = w->block_threads;
-        p.rows_per_chunk = w->rows_per_chunk;
-        p.rows_cap = w->rows_cap;
-        p.balanced = w->balanced_chunks != 0;
-        p.bal_k = w->bal_k;
-        p.bal_q = w->bal_q;
-        p.block_weight_off = (blk->nnz_begin_whole - blk->phase) + w->bal_k * blk->row_begin;
-        p.giant_enabled = w->giant_rows_enabled != 0;
-        p.giant_len = w->giant_len;
-        p.knob.long_steps = w->long_steps;          // (0 = the default rule, which depends on `balanced` only)
-        p.window_elems = w->window_elems;
-        p.window_bytes = w->window_bytes;
-        p.window_from_band = w->window_from_band != 0;
-        p.sweep = w->window_sweep != 0;
-        p.small_plain = w->small_plain != 0;
-        p.n_seg = w->window_segments >= 2 ? w->window_segments : 0;
-        p.probe_ok = w->probe_ok != 0;
-        // (column - row) bands were measured with whole-matrix row numbers; this plan's rows start at 0
-        p.band_lo = w->band_lo + blk->row_begin;
-        p.band_hi = w->band_hi + blk->row_begin;
-        for (int i = 0; i < 4; ++i) { p.seg_lo[i] = w->seg_lo[i] + blk->row_begin; p.seg_hi[i] = w->seg_hi[i] + blk->row_begin; }
-        p.n_chunks = p.balanced ? blk->n_chunks
-                                : (p.rows_per_chunk > 0 ? (int64_t(n_rows) + p.rows_per_chunk - 1) / p.rows_per_chunk : 0);
-        if (p.n_chunks < 1) p.n_chunks = 1;
-        const int st2 = find_giant_rows(p);
-        if (st2 != MI355_SPMV_OK) { delete h; return st2; }
-        set_rows_launch(p);
+    ProbeSamples probe;     // plan-time data: dropped when the create returns
+    GiantRowList giants;
+    int st;
+    if (blk && kind != MI355_KIND_MERGE && blk->whole) {
+        st = inherit_rows_shape(p, *blk->whole, *blk);
+        if (st == MI355_SPMV_OK) st = find_giant_rows(p, giants);
+        if (st == MI355_SPMV_OK) set_rows_launch(p);
     } else {
-        int st = probe_structure(p);             // one tiny kernel + one 16-byte copy (synchronises)
+        st = probe_structure(p, probe);          // one tiny kernel + one 16-byte copy (synchronises)
         if (st == MI355_SPMV_OK) {
-            if (kind == MI355_KIND_MERGE) shape_merge(p);
-            else st = shape_rows(p);             // (synchronises)
+            if (kind == MI355_KIND_MERGE) shape_merge(p, probe);
+            else st = shape_rows(p, probe, giants);   // (synchronises)
         }
-        if (st != MI355_SPMV_OK) { delete h; return st; }
     }
-    int st = plan_alloc_scratch(p);
-    if (st == MI355_SPMV_OK) st = build_chunk_table(p);
+    if (st != MI355_SPMV_OK) { delete h; return st; }
+    st = plan_alloc_scratch(p);
+    if (st == MI355_SPMV_OK) st = build_chunk_table(p, giants);
     if (st == MI355_SPMV_OK) st = build_packed_index(p);
     if (st != MI355_SPMV_OK) {
         if (p.packed_index) (void)hipFree(p.packed_index);
@@ -468,28 +418,7 @@ int mi355_spmv_plan_create_typed(mi355_spmv_plan** out, int kind, int off_type, 
 
 int mi355_spmv_plan_get_shape(const mi355_spmv_plan* h, mi355_spmv_plan_shape* sh) {
     if (!h || !sh) { set_error("plan_get_shape: null argument"); return MI355_SPMV_EINVAL; }
-    const Plan& p = h->p;
-    memset(sh, 0, sizeof(*sh));
-    sh->struct_bytes = int32_t(sizeof(*sh));
-    sh->kind = p.kind; sh->off_type = p.off_type; sh->val_type = p.val_type;
-    sh->n_rows = p.n_rows; sh->n_cols = p.n_cols; sh->nnz = p.nnz;
-    sh->lanes_per_row = p.lanes_per_row; sh->elems_per_lane = p.elems_per_lane;
-    sh->block_threads = p.block_threads > 0 ? p.block_threads : kBlock;
-    sh->balanced_chunks = p.balanced ? 1 : 0;
-    sh->rows_cap = p.rows_cap;
-    sh->giant_rows_enabled = p.giant_enabled ? 1 : 0;
-    sh->rows_per_chunk = p.rows_per_chunk; sh->n_chunks = p.n_chunks;
-    sh->bal_k = p.bal_k; sh->bal_q = p.bal_q; sh->giant_len = p.giant_len;
-    sh->window_elems = p.window_elems; sh->window_bytes = p.window_bytes;
-    sh->window_from_band = p.window_from_band ? 1 : 0;
-    sh->window_sweep = p.sweep ? 1 : 0;
-    sh->small_plain = p.small_plain ? 1 : 0;
-    sh->window_segments = p.n_seg >= 2 ? p.n_seg : (p.window_elems > 0 ? 1 : 0);
-    sh->probe_ok = p.probe_ok ? 1 : 0;
-    sh->long_steps = p.knob.long_steps;
-    // bands in whole-matrix row numbering (a block plan stores them shifted by its first row)
-    sh->band_lo = p.band_lo - p.block_row_begin; sh->band_hi = p.band_hi - p.block_row_begin;
-    for (int i = 0; i < 4; ++i) { sh->seg_lo[i] = p.seg_lo[i] - p.block_row_begin; sh->seg_hi[i] = p.seg_hi[i] - p.block_row_begin; }
+    export_rows_shape(h->p, sh);
     return MI355_SPMV_OK;
 }
 
@@ -528,24 +457,16 @@ int mi355_spmv_plan_execute(mi355_spmv_plan* h, const void* Ax, const void* x, v
     if (p.nnz > 0 && ((!Ax && !pattern) || !x)) { set_error("plan_execute: null Ax or x"); return MI355_SPMV_EINVAL; }
     if (p.n_rows > 0 && !y) { set_error("plan_execute: null y"); return MI355_SPMV_EINVAL; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.val_type == MI355_VAL_I32) {      // (MERGE only: plan_create refuses the other kinds)
-        const int32_t* ax = static_cast<const int32_t*>(Ax);
-        const int32_t* xx = static_cast<const int32_t*>(x);
-        int32_t* yy = static_cast<int32_t*>(y);
-        if (pattern)
-            return p.off_type == MI355_OFF_I32
-                       ? launch_merge<int32_t, int32_t, PatternOnes>(p, static_cast<const int32_t*>(p.Ap), nullptr, xx, yy, s)
-                       : launch_merge<int64_t, int32_t, PatternOnes>(p, static_cast<const int64_t*>(p.Ap), nullptr, xx, yy, s);
-        return p.off_type == MI355_OFF_I32
-                   ? launch_merge<int32_t, int32_t, int32_t>(p, static_cast<const int32_t*>(p.Ap), ax, xx, yy, s)
-                   : launch_merge<int64_t, int32_t, int32_t>(p, static_cast<const int64_t*>(p.Ap), ax, xx, yy, s);
-    }
-    if (p.off_type == MI355_OFF_I32) {
-        return p.val_type == MI355_VAL_F32 ? execute_typed<int32_t, float>(p, Ax, x, y, s)
-                                           : execute_typed<int32_t, double>(p, Ax, x, y, s);
-    }
-    return p.val_type == MI355_VAL_F32 ? execute_typed<int64_t, float>(p, Ax, x, y, s)
-                                       : execute_typed<int64_t, double>(p, Ax, x, y, s);
+    return with_offsets(p, [&](auto* Ap) -> int {
+        using off_t = std::remove_cv_t<std::remove_pointer_t<decltype(Ap)>>;
+        if (p.val_type == MI355_VAL_I32) {      // (MERGE only: plan_create refuses the other kinds)
+            const int32_t* xx = static_cast<const int32_t*>(x);
+            int32_t* yy = static_cast<int32_t*>(y);
+            if (pattern) return launch_merge<off_t, int32_t, PatternOnes>(p, Ap, nullptr, xx, yy, s);
+            return launch_merge<off_t, int32_t, int32_t>(p, Ap, static_cast<const int32_t*>(Ax), xx, yy, s);
+        }
+        return p.val_type == MI355_VAL_F32 ? execute_typed<float>(p, Ap, Ax, x, y, s) : execute_typed<double>(p, Ap, Ax, x, y, s);
+    });
 }
 
 int mi355_spmv_plan_destroy(mi355_spmv_plan* h) {

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 
 #include "../../include/mi355_spmv.h"
 
@@ -17,7 +18,7 @@ constexpr int kMaxGiantRows = 1024;   // giant rows a plan handles (more: they s
 constexpr int64_t kGiantRow = 65536;   // a row beyond this many nonzeros is cut into slices of kGiantSlice
 constexpr int64_t kGiantSlice = 32768;
 // slice of a giant row when the plan's threshold is below the default (small power-law matrices: the threshold follows the
-// matrix, analyze.hip find_giant_rows): half the threshold, so that a row just beyond it is already shared by two workgroups
+// matrix, rows_plan.hip find_giant_rows): half the threshold, so that a row just beyond it is already shared by two workgroups
 inline int64_t giant_slice_for(int64_t giant_len) {
     int64_t s = (giant_len / 2) & ~int64_t(1023);
     if (s < 2048) s = 2048;
@@ -28,7 +29,7 @@ constexpr int kHugeBlock = 1024;     // VECTOR, band too wide for two workgroups
 // Rows a vector of the chunked VECTOR / LIGHT kernels keeps in flight: 4, or 2 for fp64 and for fp32 with 16 or more lanes
 // per row (rows of 33+ nonzeros) — a long row keeps its lanes' loads busy by itself, and the body then needs ~95 VGPRs
 // instead of ~135 (four 256-thread workgroups per CU instead of three: what a small matrix's single round of chunks is
-// sized for).  The plan's chunks (analyze.hip, shape_chunks) and the kernel launched (row_launch.hpp) both follow it.
+// sized for).  The plan's chunks (rows_plan.hip, shape_chunks) and the kernel launched (row_launch.hpp) both follow it.
 constexpr int rows_in_flight(size_t val_bytes, int lanes_per_row) { return (val_bytes == 4 && lanes_per_row < 16) ? 4 : 2; }
 constexpr int kSweepRows = 4;        // rows a vector of the sweep kernel holds at least (its whole chunk stays in registers)
 // ... and 8 for fp32 where a chunk of 8 rows per vector stays within the 2 048 rows a chunk may have (T >= 4): the
@@ -123,92 +124,128 @@ struct Knobs {
 const Knobs& knobs();          // parsed on first use
 void knobs_reload();
 
-struct Plan {
-    int kind, off_type, val_type, flags;   // val_type: the type of x, y and of all arithmetic
-    int mat_type;              // the type the matrix values are stored in (= val_type; F32 under F64 vectors, or
+struct Plan {   // only what an execute or a report reads: what a create needs and then drops are locals of the create path
+    int kind = 0, off_type = 0, val_type = 0, flags = 0;   // val_type: the type of x, y and of all arithmetic
+    int mat_type = 0;          // the type the matrix values are stored in (= val_type; F32 under F64 vectors, or
                                // MI355_VAL_PATTERN = no stored values, every entry is one: MERGE)
-    int32_t n_rows, n_cols;
-    int64_t nnz;               // END offset of the nonzeros: Ap[n_rows] (= their count unless nnz_begin > 0)
-    int64_t nnz_read;          // elements of Aj / Ax the 16-byte loads may touch: nnz, or nnz rounded up to a multiple
+    int32_t n_rows = 0, n_cols = 0;
+    int64_t nnz = 0;           // END offset of the nonzeros: Ap[n_rows] (= their count unless nnz_begin > 0)
+    int64_t nnz_read = 0;      // elements of Aj / Ax the 16-byte loads may touch: nnz, or nnz rounded up to a multiple
                                // of 4 in a row-block plan that is not the last block (the view continues into the
                                // next block, so the tail of its last row is read by whole groups exactly as the
                                // whole matrix's plan reads it: same summation order)
-    int64_t nnz_begin;         // Ap[0]: 0, or 1..3 in a row-block plan whose arrays are a 16-byte-aligned view
+    int64_t nnz_begin = 0;     // Ap[0]: 0, or 1..3 in a row-block plan whose arrays are a 16-byte-aligned view
                                // of a larger CSR (plan_create_block): elements below it belong to no row
     Knobs knob;                // the knobs this plan was shaped under
     // row-block plans (mi355_spmv_plan_create_block): launch shape inherited from the whole matrix's plan
-    bool is_block;
-    int64_t block_row_begin;   // first row of the block in the whole matrix
-    int64_t block_chunk_begin; // first chunk of the block in the whole plan's chunk numbering
-    int64_t block_weight_off;  // weight-cut plans: (global nnz offset of the block - nnz_begin) + bal_k * block_row_begin
-    bool giant_enabled;        // weight-cut plans: whether rows beyond giant_len are cut into slices
-    const void* Ap;
-    const int32_t* Aj;
+    bool is_block = false;
+    int64_t block_row_begin = 0;   // first row of the block in the whole matrix
+    int64_t block_chunk_begin = 0; // first chunk of the block in the whole plan's chunk numbering
+    int64_t block_weight_off = 0;  // weight-cut plans: (global nnz offset of the block - nnz_begin) + bal_k * block_row_begin
+    bool giant_enabled = false;    // weight-cut plans: whether rows beyond giant_len are cut into slices
+    const void* Ap = nullptr;
+    const int32_t* Aj = nullptr;
     // launch shape
-    int lanes_per_row;     // T
-    int elems_per_lane;    // 1 or 4
-    int64_t grid_blocks;
+    int lanes_per_row = 0;     // T
+    int elems_per_lane = 0;    // 1 or 4
+    int64_t grid_blocks = 0;
     // merge-path
-    int64_t tile_items, n_tiles;
-    int64_t tiles_per_super, n_super;   // consecutive tiles one workgroup walks; number of such groups
-    bool coords_valid;
-    bool merge_rows;            // MERGE: regular matrix -> runs are summed row-parallel (merge_rows_kernel)
-    int64_t probe_len_min, probe_len_max;   // shortest / longest of the probe's sampled rows (valid when probe_ok)
+    int64_t tile_items = 0, n_tiles = 0;
+    int64_t tiles_per_super = 0, n_super = 0;   // consecutive tiles one workgroup walks; number of such groups
+    bool coords_valid = false;
+    bool merge_rows = false;    // MERGE: regular matrix -> runs are summed row-parallel (merge_rows_kernel)
+    int64_t probe_len_min = 0, probe_len_max = 0;   // shortest / longest of the probe's sampled rows (valid when probe_ok)
     int probe_short_rows = 0;               // ... and how many of the 256 fill less than 3/4 of the step the longest needs
-    int semiring;               // MERGE: MI355_SEMIRING_* (0 = plus-times)
-    double alpha, beta;         // y = alpha * A x + beta * y (1, 0 by default)
+    int semiring = 0;           // MERGE: MI355_SEMIRING_* (0 = plus-times)
+    double alpha = 0, beta = 0; // y = alpha * A x + beta * y (plan_create sets 1, 0)
     // structure probe (plan creation): band of (column - row) seen on sampled rows
-    int64_t band_lo, band_hi;   // valid when probe_ok
-    bool probe_ok;
-    int block_threads;          // VECTOR / LIGHT: 256, or 512 for big uniform matrices (chunks twice as long)
-    int window_bytes;           // LDS budget of the x window per workgroup (pick_window_elems)
-    int window_elems;           // LDS window of x per workgroup, in elements; 0 = no window
-    bool window_from_band;      // place the window from band_lo/band_hi instead of sampling per chunk
-    int mr_block = 256;         // MERGE, row-parallel runs: workgroup size (512: the band needs ~78 KB of LDS) and rows per piece of a run
-    int mr_piece_rows = 1984;
+    int64_t band_lo = 0, band_hi = 0;   // valid when probe_ok
+    bool probe_ok = false;
+    int block_threads = 0;      // VECTOR / LIGHT: 256, or 512 for big uniform matrices (chunks twice as long)
+    int window_bytes = 0;       // LDS budget of the x window per workgroup (pick_window_elems)
+    int window_elems = 0;       // LDS window of x per workgroup, in elements; 0 = no window
+    bool window_from_band = false;   // place the window from band_lo/band_hi instead of sampling per chunk
+    int mr_block = 0;           // MERGE, row-parallel runs: workgroup size (512: the band needs ~78 KB of LDS) and rows per piece
+    int mr_piece_rows = 0;      // of a run (shape_merge writes both on every path)
     int mr_sweep_lanes = 0;     // MERGE, row-parallel runs on a band wider than any window: lanes per row of the sweeping body (0 = not swept)
     bool sweep = false;         // VECTOR: the band is wider than any window — one group of rows per chunk, the window sweeps the band (chunk_rows_sweep)
     // multi-band plan: up to 4 bands of (column - row) found by clustering the probe's samples
-    int n_seg;
-    int64_t seg_lo[4], seg_hi[4];
-    int probe_n;                 // sampled (column - row) offsets (sorted ascending once probe_sorted)
-    bool probe_sorted;
-    int64_t probe_off[8192];
+    int n_seg = 0;
+    int64_t seg_lo[4] = {}, seg_hi[4] = {};
     // row chunks of VECTOR / LIGHT
-    int64_t rows_per_chunk;     // uniform plan: every chunk has this many rows
-    bool balanced;              // nnz-balanced plan: chunk c = rows [chunk_row[c], chunk_row[c+1])
-    int64_t n_chunks;
-    int rows_cap;               // rows the LDS layout of a workgroup holds (>= any chunk)
-    int64_t bal_k, bal_q;       // a row weighs (its nonzeros + bal_k), a chunk holds <= bal_q of weight
-    int32_t* chunk_row;         // [n_chunks + 1], device (balanced plans only)
+    int64_t rows_per_chunk = 0; // uniform plan: every chunk has this many rows
+    bool balanced = false;      // nnz-balanced plan: chunk c = rows [chunk_row[c], chunk_row[c+1])
+    int64_t n_chunks = 0;
+    int rows_cap = 0;           // rows the LDS layout of a workgroup holds (>= any chunk)
+    int64_t bal_k = 0, bal_q = 0;   // a row weighs (its nonzeros + bal_k), a chunk holds <= bal_q of weight
+    int32_t* chunk_row = nullptr;   // [n_chunks + 1], device (balanced plans only)
     // giant rows (balanced plans): rows beyond kGiantRow nonzeros are cut into slices summed by separate workgroups
-    int n_giant;                // 0 = none
-    int64_t giant_len;          // rows beyond this many nonzeros are giant (kGiantRow, or MI355_SPMV_GIANT_ROW)
-    int64_t n_giant_slices;
-    int32_t giant_row_host[kMaxGiantRows];
-    int64_t giant_slice_first_host[kMaxGiantRows + 1];
-    int32_t* giant_row;         // [n_giant], device
-    int64_t* giant_slice_first; // [n_giant + 1], device
-    void* giant_partial;        // [n_giant_slices] of value type, device
+    int n_giant = 0;            // 0 = none
+    int64_t giant_len = 0;      // rows beyond this many nonzeros are giant (kGiantRow, or MI355_SPMV_GIANT_ROW)
+    int64_t n_giant_slices = 0;
+    int32_t* giant_row = nullptr;           // [n_giant], device
+    int64_t* giant_slice_first = nullptr;   // [n_giant + 1], device
+    void* giant_partial = nullptr;          // [n_giant_slices] of value type, device
     // scratch
-    void* scratch;
-    size_t scratch_bytes;
-    size_t scratch_capacity;   // bytes of the allocation behind `scratch` (>= scratch_bytes when reused)
-    int32_t* tile_row;     // [n_tiles + 1]
-    int64_t* tile_nnz;     // [n_tiles + 1]
-    int32_t* carry_row;    // [n_super]
-    void* carry_val;       // [n_super] of value type
-    unsigned long long* counters;  // LIGHT: kXcds shards, one 128-B line each
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    size_t scratch_capacity = 0;   // bytes of the allocation behind `scratch` (>= scratch_bytes when reused)
+    int32_t* tile_row = nullptr;   // [n_tiles + 1]
+    int64_t* tile_nnz = nullptr;   // [n_tiles + 1]
+    int32_t* carry_row = nullptr;  // [n_super]
+    void* carry_val = nullptr;     // [n_super] of value type
+    unsigned long long* counters = nullptr;  // LIGHT: kXcds shards, one 128-B line each
     // VECTOR, one window placed from the band, equal-row chunks: a 16-bit window-relative copy of Aj (build_packed_index).
     // An allocation of its own — never part of `scratch`, which a released one-shot plan hands on to the next plan.
-    uint16_t* packed_index;        // [nnz_read + padding] in the numbering of Aj, or nullptr
-    size_t packed_bytes;           // bytes of that allocation (0 = none)
-    int64_t packed_escapes;        // nonzeros whose column lies outside their chunk's window (stored as kPackedEscape)
-    bool light_dequeue_once;       // LIGHT, equal-row chunks: one workgroup and one dequeue per chunk (else by index)
-    int n_kernels;
-    bool small_plain = false;   // VECTOR / LIGHT: a matrix small enough for the plain one-pass kernel to win (analyze.hip, shape_rows)
-    char main_kernel[64];
+    uint16_t* packed_index = nullptr;   // [nnz_read + padding] in the numbering of Aj, or nullptr
+    size_t packed_bytes = 0;            // bytes of that allocation (0 = none)
+    int64_t packed_escapes = 0;         // nonzeros whose column lies outside their chunk's window (stored as kPackedEscape)
+    bool light_dequeue_once = false;    // LIGHT, equal-row chunks: one workgroup and one dequeue per chunk (else by index)
+    int n_kernels = 0;
+    bool small_plain = false;   // VECTOR / LIGHT: a matrix small enough for the plain one-pass kernel to win (rows_plan.hip, shape_rows)
+    char main_kernel[64] = "";
 };
+static_assert(sizeof(Plan) <= 2048, "Plan (1 096 bytes) holds what executes and reports read; plan-time buffers are locals of plan_create");
+
+// ---- what lives for the duration of one plan_create ----------------------------------------------------------
+constexpr int kProbePerRow = 32;   // (column - row) samples per probed row
+// the structure probe's samples: (column - row) at kProbePerRow positions of each of kBlock rows, sorted on first use
+// (cluster_bands): most plans never need them
+struct ProbeSamples {
+    int n = 0;
+    bool sorted = false;
+    int64_t off[kBlock * kProbePerRow];
+};
+// the giant rows of a weight-cut plan, ascending, and the first slice of each: find_giant_rows -> build_chunk_table
+struct GiantRowList {
+    int32_t row[kMaxGiantRows];
+    int64_t slice_first[kMaxGiantRows + 1];
+};
+// a row block (plan_create_block): where it lies in the whole matrix's plan.  phase = its Ap[0], 0..3
+struct BlockSpec {
+    const mi355_spmv_plan_shape* whole;   // may be null (MERGE, or an independent block)
+    int64_t row_begin, chunk_begin, n_chunks, nnz_begin_whole;
+    int phase;
+};
+
+// Device scratch of the plan-time kernels (probe samples, heaviest-chunk word, giant rows, partition cuts): one
+// allocation per device for the life of the process instead of a hipMalloc + hipFree (an implicit device
+// synchronisation) per plan — the one-shot entry points create a plan per call, like the reference's kinds.
+// The holder keeps the buffer locked for as long as it lives; words is null when the device has none to give.
+constexpr size_t kAnalysisWords = 2 + size_t(kBlock) * kProbePerRow + 2 + 2;   // band, samples, row lengths, 2 spare words
+static_assert(1 + 2 * size_t(kMaxGiantRows) <= kAnalysisWords, "analysis buffer");
+class AnalysisBuffer {
+    std::lock_guard<std::mutex> lock_;
+public:
+    AnalysisBuffer();
+    long long* const words;
+};
+
+// f(Ap) with the plan's row offsets as a pointer of their own type (host side: the kernels take off_t as a template argument)
+template <typename F>
+static auto with_offsets(const Plan& p, F&& f) {
+    return p.off_type == MI355_OFF_I32 ? f(static_cast<const int32_t*>(p.Ap)) : f(static_cast<const int64_t*>(p.Ap));
+}
 
 // A launch that asks for more dynamic LDS than the default 64 KB cap must raise the kernel's limit first
 // (gfx950: up to 160 KB per workgroup).  Remembered per kernel, so the call happens once.
@@ -226,14 +263,21 @@ template <typename off_t, typename val_t, typename mat_t>
 int launch_merge(Plan& p, const off_t* Ap, const mat_t* Ax, const val_t* x, val_t* y, hipStream_t s);
 
 int merge_compute_coords(Plan& p);   // MERGE: run the search kernel now (null stream, synchronises)
-int probe_structure(Plan& p);
-int pick_window_elems(Plan& p, int64_t rows_per_workgroup);
+// what both planners use (analyze.hip)
+int probe_structure(Plan& p, ProbeSamples& probe);
+int pick_window_elems(Plan& p, ProbeSamples& probe, int64_t rows_per_workgroup);
 int64_t segment_rows_fit(const Plan& p);
+// the row kinds' plan unit (rows_plan.hip)
 int long_steps_for(const Plan& p);   // steps of its vector after which a row is left to the long-row pass
-int build_chunk_table(Plan& p);    // after the scratch is allocated
+int shape_rows(Plan& p, ProbeSamples& probe, GiantRowList& giants);   // VECTOR / LIGHT, whole plans: the shape, then set_rows_launch (synchronises)
+void set_rows_launch(Plan& p);     // VECTOR / LIGHT: kernel, grid and kernel count from the plan's shape
+int find_giant_rows(Plan& p, GiantRowList& giants);          // balanced plans: rows beyond giant_len nonzeros (synchronises)
+int build_chunk_table(Plan& p, const GiantRowList& giants);  // after the scratch is allocated
 int build_packed_index(Plan& p);   // after the shape is final: the packed index of a plan that qualifies (synchronises)
-int find_giant_rows(Plan& p);      // balanced plans: rows beyond kGiantRow nonzeros (synchronises)
-void shape_merge(Plan& p);
+// the two directions of a row block's inherited shape: whole plan -> shape -> block plan (then find_giant_rows, set_rows_launch)
+void export_rows_shape(const Plan& p, mi355_spmv_plan_shape* sh);
+int inherit_rows_shape(Plan& p, const mi355_spmv_plan_shape& w, const BlockSpec& blk);
+void shape_merge(Plan& p, ProbeSamples& probe);
 void merge_report_tile_walk(Plan& p);   // MERGE: n_kernels / main_kernel of a plan whose executes all take the tile kernel
 // MERGE, what the shaper and the launcher must agree on (merge_plan.hip): whether the main kernel searches its own
 // coordinates; whether the runs are summed row-parallel, and the regular row lengths that takes
@@ -247,8 +291,6 @@ int launch_merge_search(int off_type, int lanes, int64_t diagonals, int64_t tile
                         hipStream_t s);
 template <typename val_t>
 int launch_merge_fixup(int semiring, const Plan& p, val_t* y, hipStream_t s);
-int shape_rows(Plan& p);           // VECTOR / LIGHT, whole plans: the shape, then set_rows_launch (synchronises)
-void set_rows_launch(Plan& p);     // VECTOR / LIGHT: kernel, grid and kernel count from the plan's shape
 // nnz-balanced cuts on the plan's chunk boundaries (analyze.hip; reads Ap on the device, synchronises)
 int partition_plan(const Plan& p, int parts, int64_t* row_cuts, int64_t* chunk_cuts, int64_t* nnz_cuts);
 

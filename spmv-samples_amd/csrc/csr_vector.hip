@@ -12,7 +12,7 @@
 //     neighbouring windows of x hit that XCD's L2.
 // The 4-byte-per-lane kernel csr_vector_kernel is the form of the reference
 // (one row per vector, grid = ceil(rows / vectors per block), cusp_warp_reduce.cuh:70-87);
-// it runs small matrices of either kind (analyze.hip, shape_rows) and operands that are not 16-byte aligned.
+// it runs small matrices of either kind (rows_plan.hip, shape_rows) and operands that are not 16-byte aligned.
 
 #include <cstdlib>
 
@@ -30,7 +30,7 @@ namespace mi355 {
 // there — cant stand-in: 14.7 -> 19-21 us when its body went from 127 to 139 VGPRs.)  The kernel does not depend on the width
 // of the row offsets: a chunk is walked with 32-bit offsets relative to its own first nonzero (xwindow.hpp).
 // PACKED (NSEG == 1, equal-row chunks, the window placed from the plan's band): the loop streams the plan's 16-bit
-// window indices Aj16 instead of Aj (xwindow.hpp, chunk_rows; analyze.hip, build_packed_index); Aj16 is unused otherwise.
+// window indices Aj16 instead of Aj (xwindow.hpp, chunk_rows; rows_plan.hip, build_packed_index); Aj16 is unused otherwise.
 template <int BLOCK, int T, int R, int NSEG, bool ADAPT, typename val_t, bool PACKED = false>
 __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock || R == 2 ? 4 : 3)) void csr_vector_window_kernel(
     int32_t n_rows, int32_t n_cols, int64_t nnz, const ApView Ap, const int32_t* __restrict__ Aj,
@@ -153,7 +153,7 @@ struct VectorRows {
     }
 };
 
-// the plain kernel over the plan's rows, its grid from the row count (both kinds' small matrices: analyze.hip, shape_rows)
+// the plain kernel over the plan's rows, its grid from the row count (both kinds' small matrices: rows_plan.hip, shape_rows)
 template <typename off_t, typename val_t>
 int launch_vector_plain(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s) {
     return with_lanes(p, VectorRows::name, [&](auto lanes) -> int {

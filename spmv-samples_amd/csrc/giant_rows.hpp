@@ -3,7 +3,7 @@
 // A row is summed by one workgroup, however the chunks are cut; for a row of millions of nonzeros (a dense
 // row in an otherwise banded matrix) that workgroup streams alone while the chip idles (2^21 banded rows + one
 // row of 4 M entries: 5.8 ms, merge 0.33 ms).  Plans with weight-cut chunks therefore list such rows at
-// creation (find_giant_rows, analyze.hip); the chunk kernel stores 0 for them, and two small kernels follow:
+// creation (find_giant_rows, rows_plan.hip); the chunk kernel stores 0 for them, and two small kernels follow:
 //   giant_slices_kernel   one workgroup per slice of giant_slice_for(giant_len) nonzeros: partial sum -> scratch
 //   giant_final_kernel    one thread per giant row: adds the row's partials IN SLICE ORDER into y
 // so the result does not depend on which workgroup finishes first (no float atomics: run-to-run bitwise

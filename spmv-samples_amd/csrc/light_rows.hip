@@ -7,7 +7,7 @@
 //
 // What changes for MI355X:
 //  * the unit handed out by one atomic is a CHUNK of consecutive rows (equal row counts,
-//    or equal weight on a power-law matrix: analyze.hip, decide_balance) taken by a
+//    or equal weight on a power-law matrix: rows_plan.hip, decide_balance) taken by a
 //    whole workgroup (the reference hands 1 row to a vector or 32/T rows to a warp,
 //    LightSpMV.cuh:128-132, :205-209).  One returning device-scope atomic on a
 //    single word saturates near 88 dequeues/us on this chip; 1 row per atomic would

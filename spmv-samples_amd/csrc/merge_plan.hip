@@ -138,8 +138,8 @@ static int merge_kernel_count(const Plan& p) {
 
 // a window of x only pays when a run is long enough to amortise staging it, and
 // when the band the probe saw (plus the rows of a run) fits
-static int run_window_elems(Plan& p, int64_t tps, int64_t mean1) {
-    return (tps * p.tile_items >= 8192) ? pick_window_elems(p, tps * p.tile_items / mean1 + 1) : 0;
+static int run_window_elems(Plan& p, ProbeSamples& probe, int64_t tps, int64_t mean1) {
+    return (tps * p.tile_items >= 8192) ? pick_window_elems(p, probe, tps * p.tile_items / mean1 + 1) : 0;
 }
 
 // Several far-apart bands (the 3-D stencil).  A REGULAR matrix of that kind takes row-parallel runs with a segment
@@ -171,7 +171,7 @@ static int try_segmented_runs(Plan& p, int64_t mean1) {
 // ... and a band too wide for that gets ONE workgroup of 1 024 threads per CU with ~155 KB (the CSR-vector kind's
 // third plan): fp32, 32 769 columns, 32 per row: 343 -> see profiles/r02_shape_sweep.txt
 // One such try: true when the plan is taken; else p is as it was.
-static bool try_wide_window(Plan& p, int block, int64_t lds, int64_t min_piece, int64_t mean1) {
+static bool try_wide_window(Plan& p, ProbeSamples& probe, int block, int64_t lds, int64_t min_piece, int64_t mean1) {
     const int64_t vb = p.val_type == MI355_VAL_F64 ? 8 : 4;
     const int64_t band = p.band_hi - p.band_lo + 1;
     int64_t piece = (lds - vb * (band + 8) - 4) * 8 / (8 * (2 * vb + 4) + 1);   // val (band + rows + 8) + 4 (rows + 1) + val rows + rows / 8
@@ -184,7 +184,7 @@ static bool try_wide_window(Plan& p, int block, int64_t lds, int64_t min_piece, 
     const int bytes = p.window_bytes, elems = p.window_elems, n_seg = p.n_seg;
     const bool from_band = p.window_from_band;
     p.window_bytes = int(vb * (band + piece + 8));
-    p.window_elems = pick_window_elems(p, piece);
+    p.window_elems = pick_window_elems(p, probe, piece);
     if (!(p.window_elems > 0 && p.n_seg < 2 && p.window_from_band && (p.n_tiles + tps - 1) / tps >= int64_t(kCus) * 2)) {
         p.window_bytes = bytes; p.window_elems = elems; p.n_seg = n_seg; p.window_from_band = from_band;
         return false;
@@ -196,7 +196,7 @@ static bool try_wide_window(Plan& p, int block, int64_t lds, int64_t min_piece, 
 }
 
 // Still no window: the band is wider than one CU's LDS.  The CSR-vector kind sweeps such a band with the window
-// (analyze.hip, shape_sweep); a run here does the same — a piece = one group of rows of a 1 024-thread workgroup held in
+// (rows_plan.hip, shape_sweep); a run here does the same — a piece = one group of rows of a 1 024-thread workgroup held in
 // registers, 4 T nonzeros per row in one step — under the same rule: the staged bytes of a piece stay below half the
 // line fills its nonzeros would cost as plain gathers.  Rows of up to 8 nonzeros (T = 2) keep the gathers.
 static void try_sweep(Plan& p, int64_t mean1) {
@@ -226,7 +226,7 @@ static void try_sweep(Plan& p, int64_t mean1) {
     p.n_seg = 0;
 }
 
-void shape_merge(Plan& p) {
+void shape_merge(Plan& p, ProbeSamples& probe) {
     // tuning knobs: MI355_MERGE_TPS = tiles per run (and MI355_SPMV_WINDOW = 0|1, analyze.hip)
     // 256 threads x 8 items or (MI355_MERGE_BLOCK=512) 512 threads x 4 items: the same 2 044-item tiles
     p.block_threads = p.knob.merge_block == kWideBlock ? kWideBlock : kBlock;
@@ -251,20 +251,20 @@ void shape_merge(Plan& p) {
                         p.block_threads == kBlock && merge_rows_regular(p);
     const int64_t tps = bumped ? 8 : tps_small;
     set_runs(p, tps);
-    p.window_elems = run_window_elems(p, tps, mean1);
+    p.window_elems = run_window_elems(p, probe, tps, mean1);
     // fp64 halves what the 36 KB budget (three workgroups per CU) holds: the S32-band shape in fp64 ran on plain
     // gathers at 2.4 TB/s.  Second try with 56 KB (two workgroups per CU next to the kernel's 16-24 KB of own LDS).
     if (p.window_elems == 0 && p.n_seg < 2 && p.val_type == MI355_VAL_F64 && p.knob.window < 0 && tps * p.tile_items >= 8192 &&
         p.knob.merge_wide_window != 0) {
         p.window_bytes = 56 * 1024;
-        p.window_elems = pick_window_elems(p, tps * p.tile_items / mean1 + 1);
+        p.window_elems = pick_window_elems(p, probe, tps * p.tile_items / mean1 + 1);
         if (p.window_elems == 0 || p.n_seg >= 2) p.window_bytes = 0;
     }
     int segment_piece = try_segmented_runs(p, mean1);   // rows per piece of a run with one window segment per band (0: not that plan)
     if (bumped && !(p.window_elems > 0 && p.n_seg < 2 && p.window_from_band)) {   // no window for runs of 8 tiles: the shorter runs
         set_runs(p, tps_small);
         p.window_bytes = 0;
-        p.window_elems = run_window_elems(p, tps_small, mean1);
+        p.window_elems = run_window_elems(p, probe, tps_small, mean1);
         segment_piece = 0;
     }
     const bool several_bands = p.n_seg >= 2 && segment_piece == 0;
@@ -279,7 +279,7 @@ void shape_merge(Plan& p) {
     if (segment_piece > 0 && !p.merge_rows) { p.window_elems = 0; p.n_seg = 0; }   // (cannot happen: merge_rows_wanted held above)
     if (p.merge_rows && segment_piece == 0 && p.knob.merge_wide_window != 0 && p.knob.window < 0 && p.knob.merge_tps <= 0 && p.probe_ok &&
         !(p.window_elems > 0 && p.window_from_band)) {
-        if (!try_wide_window(p, kWideBlock, 78 * 1024, 256, mean1)) try_wide_window(p, kHugeBlock, 155 * 1024, 512, mean1);
+        if (!try_wide_window(p, probe, kWideBlock, 78 * 1024, 256, mean1)) try_wide_window(p, probe, kHugeBlock, 155 * 1024, 512, mean1);
     }
     p.mr_sweep_lanes = 0;
     try_sweep(p, mean1);

@@ -1,6 +1,6 @@
 // row_dot.hpp — small pieces shared by the row-based kernels: vector types, the
-// nontemporal stream load, the sub-wave reduction, the lanes-per-row rule, and the
-// 4-byte-per-lane row dot product of the fallback kernels.
+// nontemporal stream load, the sub-wave reduction, and the 4-byte-per-lane row dot
+// product of the fallback kernels (the lanes-per-row rule: rows_plan.hip).
 //
 // The reference's per-row arithmetic (cusp_warp_reduce.cuh:26-57, LightSpMV.cuh:147-170):
 // lane l of a T-lane vector reads one 4-byte Aj and one Ax element per step, stride T, and
@@ -61,18 +61,6 @@ __device__ __forceinline__ val_t vector_reduce(val_t v) {
         v += __shfl_down(v, o, T);
     }
     return v;
-}
-
-// T (lanes per row) from the mean row length.  With 4 nonzeros per lane per step a T-lane
-// vector covers 4T nonzeros per step; pick the smallest T whose step covers the mean row,
-// so that a typical row is one load per lane and a wave holds 64/T rows in flight.
-// (Reference rule, 1 element per lane and T <= 32: cusp_warp_reduce.cuh:100-127;
-// LightSpMV.cuh:354-370.)
-inline int pick_lanes_per_row(int64_t nnz, int64_t n_rows, int elems) {
-    const int64_t mean = n_rows > 0 ? (nnz + n_rows - 1) / n_rows : 0;
-    int t = 2;
-    while (t < 64 && int64_t(t) * elems < mean) t <<= 1;
-    return t;
 }
 
 }  // namespace mi355

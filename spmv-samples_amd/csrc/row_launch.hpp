@@ -1,5 +1,5 @@
 // row_launch.hpp — the launch path of the chunked row kinds, VECTOR (csr_vector.hip) and LIGHT (light_rows.hip).
-// Both run the same chunk bodies (xwindow.hpp) under the same plan (analyze.hip: shape_rows, set_rows_launch); they
+// Both run the same chunk bodies (xwindow.hpp) under the same plan (rows_plan.hip: shape_rows, set_rows_launch); they
 // differ only in how a workgroup gets its chunk — by block index, or from LIGHT's sharded counters — and so in their
 // kernels.  A kind names those in a traits type (VectorRows, LightRows) and instantiates launch_rows with it in its own
 // translation units, so that each kernel is compiled where it is defined.
@@ -133,7 +133,7 @@ static int launch_rows_sweep(const RowOperands<val_t>& o) {
 template <typename Kind, typename off_t, typename val_t>
 int launch_rows(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s) {
     if (p.n_rows == 0) return MI355_SPMV_OK;
-    // a small matrix: the plain one-pass kernel of the CSR-vector kind, whichever the plan's kind (analyze.hip,
+    // a small matrix: the plain one-pass kernel of the CSR-vector kind, whichever the plan's kind (rows_plan.hip,
     // shape_rows; handing rows out cost LIGHT 29-133 us where this takes 3-6).  A block inherits the choice with its
     // lanes per row: the same sums bit for bit.
     if (p.small_plain) return launch_vector_plain<off_t, val_t>(p, Ap, Ax, x, y, s);

@@ -133,7 +133,7 @@ __device__ __forceinline__ WindowSpan place_window(int lo, int hi, int32_t n_col
 
 // The window of the chunk of rows [rb, re), re > rb, placed from the plan's band (hint.use): a function of these five
 // values alone.  stage_x_window stages exactly this window on the hinted path, and the plan's packed index
-// (analyze.hip, pack_index_kernel) encodes every column against it — both call this, so they cannot disagree.
+// (rows_plan.hip, pack_index_kernel) encodes every column against it — both call this, so they cannot disagree.
 template <typename val_t>
 __device__ __forceinline__ WindowSpan band_window(int64_t rb, int64_t re, int32_t n_cols, int32_t cap, const BandHint& hint) {
     const int64_t l = rb + hint.lo, h = re - 1 + hint.hi;
@@ -303,7 +303,7 @@ struct ApView {
 };
 
 // How chunk ids map to rows.  Uniform plans: chunk c = rows [c * rows_per_chunk, ...).  nnz-balanced plans
-// (analyze.hip, decide_balance): boundaries from a table built at plan creation, so that a chunk of a
+// (rows_plan.hip, decide_balance): boundaries from a table built at plan creation, so that a chunk of a
 // power-law matrix holds a bounded number of nonzeros as well as of rows.
 struct ChunkMap {
     const int32_t* table;     // n_chunks + 1 boundaries, or nullptr
@@ -456,7 +456,7 @@ __device__ __forceinline__ void store_chunk_results(const ChunkScratch<val_t>& s
 //    are in flight), so a chunk's prologue costs one memory round trip, not two.
 // All BLOCK threads of the workgroup must call (wave-wide shuffles and barriers inside); the caller
 // has run stage_chunk_bounds + a barrier; `stage()` returns the window and ends with a barrier.
-// PACKED (the plan's packed index, analyze.hip build_packed_index; WINDOW only): Aj16[k] is the 16-bit index of
+// PACKED (the plan's packed index, rows_plan.hip build_packed_index; WINDOW only): Aj16[k] is the 16-bit index of
 // Aj[k] INSIDE the window of the chunk that owns element k, kPackedEscape when the column is outside it.  The
 // pipelined loop streams 8 bytes of Aj16 per group of four instead of 16 bytes of Aj; Aj itself is read only for an
 // escaped element, in the long-row passes and for the arrays' last, partial group.  Same arithmetic in the same order.
@@ -873,7 +873,7 @@ __device__ __forceinline__ void chunk_rows_any(int64_t chunk_begin, int64_t chun
 // cut into windows of `cap` columns, and for every window in turn the workgroup stages it and each lane adds
 // the elements whose column falls inside.  Per chunk: BLOCK * R * 4 nonzero slots (2 MB of line fills as plain
 // gathers at 16 K slots) against passes * cap * sizeof(val_t) staged bytes — the plan takes this shape only
-// while the second is well below the first (analyze.hip, shape_chunks).
+// while the second is well below the first (rows_plan.hip, shape_chunks).
 // The band is the probe's (a sample): a column outside the swept span is gathered from global memory, a row
 // longer than one step (4 T nonzeros; the plan picks T from the longest row it saw) finishes with plain
 // gathers.  With sorted columns a lane adds its elements in the order chunk_rows does.
@@ -955,7 +955,7 @@ __device__ __forceinline__ void chunk_rows_sweep(int64_t chunk_begin, int64_t ch
         // round trips to L2, and staging — not the Aj / Ax stream, which this structure reads at 7.8 TB/s, nor the
         // consume — was more than half the kernel (321 us; 144 without the passes; 338 with the passes and half the
         // consumes).  A wave-instruction writes LDS at a wave-uniform base + 16 bytes x lane, which is the window's
-        // own layout.  cap is a whole number of such rounds of the workgroup (analyze.hip: shape_sweep), so every lane
+        // own layout.  cap is a whole number of such rounds of the workgroup (rows_plan.hip: shape_sweep), so every lane
         // of every instruction has a slot inside the window's LDS: a group past the window's end re-loads the last
         // whole group of x into a slot nothing reads.  The instructions count on vmcnt: the wait + the barrier below
         // order them before every wave's ds_reads.
@@ -1060,22 +1060,6 @@ __device__ __forceinline__ void chunk_rows_wide(int64_t chunk_begin, int64_t chu
         sum = vector_reduce<kWave, val_t>(sum);
         if (lane64 == 0) y[row] = (beta != val_t(0)) ? alpha * sum + beta * y[row] : alpha * sum;
     }
-}
-
-// Rows per workgroup chunk: ~32 K nonzeros (256 KB of fp32 stream) per chunk, a
-// multiple of the rows one pass of the workgroup covers.
-inline int64_t pick_rows_per_chunk(int64_t nnz, int64_t n_rows, int lanes_per_row, int rows_in_flight,
-                                   int block_threads = kBlock, int64_t nnz_per_chunk = 32768, int per_cu = 4) {
-    const int64_t pass = int64_t(block_threads / lanes_per_row) * rows_in_flight;
-    const int64_t mean = n_rows > 0 ? (nnz + n_rows - 1) / n_rows : 1;
-    int64_t rows = nnz_per_chunk / (mean > 0 ? mean : 1);
-    // small matrices: prefer one chunk per workgroup slot (per_cu a CU) over long chunks
-    const int64_t fill = (n_rows + int64_t(kCus) * per_cu - 1) / (int64_t(kCus) * per_cu);
-    if (rows > fill) rows = fill;
-    rows = (rows + pass - 1) / pass * pass;
-    if (rows < pass) rows = pass;
-    if (rows > kMaxChunkRows) rows = kMaxChunkRows / pass * pass > 0 ? kMaxChunkRows / pass * pass : pass;
-    return rows;
 }
 
 constexpr int kWindowBytes = 36 * 1024;   // LDS window of x per workgroup: 4 workgroups per CU

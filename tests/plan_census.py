@@ -19,7 +19,7 @@ def describe(plan):
 
 
 def has_giant_list(kind, info):
-    """VECTOR / LIGHT run one kernel, plus two for the slices of giant rows (analyze.hip, set_rows_launch); the merge
+    """VECTOR / LIGHT run one kernel, plus two for the slices of giant rows (rows_plan.hip, set_rows_launch); the merge
     kind has no such list."""
     return kind != "merge" and info["n_kernels"] == 3
 

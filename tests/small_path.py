@@ -2,7 +2,7 @@
 
 tests/conftest.py switches the product's small-matrix choice off for the whole suite (MI355_SPMV_SMALL=0: the chunked
 kernels); the library's DEFAULT sends every regular VECTOR or LIGHT matrix of up to kSmallPlainNnz nonzeros to the
-plain one-pass kernel csr_vector_kernel (capi.hip, small_plain).  The `path` fixture runs a test under either:
+plain one-pass kernel csr_vector_kernel (rows_plan.hip, shape_rows: small_plain).  The `path` fixture runs a test under either:
   default  MI355_SPMV_SMALL unset, the knobs re-read (which also drops the kept one-shot plans)
   chunked  MI355_SPMV_SMALL=0, the knobs re-read
 and puts the environment back afterwards.  Merge ignores the knob, so `kind_paths` gives it the chunked arm only; the
@@ -16,8 +16,8 @@ KNOB = "MI355_SPMV_SMALL"
 PLAIN = "csr_vector_kernel"
 SMALL_PLAIN_NNZ = 4_100_000        # common.hpp, kSmallPlainNnz
 BLOCK = 256                        # common.hpp, kBlock
-# why a small matrix with a hub row is not on the plain kernel: capi.hip takes it only for chunks of equal rows
-WEIGHT_CUT = "weight-cut chunks (analyze.hip, decide_balance: its chunk weighs more than twice the mean chunk)"
+# why a small matrix with a hub row is not on the plain kernel: shape_rows takes it only for chunks of equal rows
+WEIGHT_CUT = "weight-cut chunks (rows_plan.hip, decide_balance: its chunk weighs more than twice the mean chunk)"
 
 
 def forced():
@@ -68,7 +68,7 @@ def kind_paths(kinds):
 
 
 def plain_lanes(nnz, n_rows):
-    """Lanes per row of the plain kernel: capi.hip's rule restated — two elements per lane up to a mean of 32 per row,
+    """Lanes per row of the plain kernel: shape_rows' rule restated — two elements per lane up to a mean of 32 per row,
     four beyond, the smallest power of two from 2 to 64 that covers the mean row."""
     mean = nnz // n_rows
     per_lane = 2 if mean <= 32 else 4

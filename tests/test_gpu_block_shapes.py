@@ -3,7 +3,7 @@
 The multi-GPU design rests on one claim (README.md; include/mi355_spmv.h, "row-block plans"): for the row-local kinds,
 VECTOR and LIGHT, a plan made by mi355_spmv_plan_create_block sums every row exactly as the whole matrix's plan does,
 so the concatenated y is the one-GPU y bit for bit.  A block plan does not shape itself: it copies the launch shape out
-of mi355_spmv_plan_shape (capi.hip, plan_create_impl) and every copied field belongs to one plan shape.  Here the claim
+of mi355_spmv_plan_shape (rows_plan.hip, inherit_rows_shape) and every copied field belongs to one plan shape.  Here the claim
 is tried on the structure catalogue of tests/kept_structures.py, whose structures are named after the plan shapes they
 produce, the small groups under both arms of the small-matrix choice, and a census at the end asserts that the whole
 plans whose blocks were checked cover the plan space.
@@ -329,6 +329,31 @@ def test_the_librarys_own_cutting(sp, oracle, gname, arm, name, d, kind):
             check("DistPlan.rank", y, y1)
         finally:
             dist.destroy()
+
+
+# a banded, a multi-band and a weight-cut structure, with what the whole plan's shape must show for the case to be that one
+ROUND_TRIP = {"band_narrow": lambda sh: sh.window_segments == 1 and sh.window_from_band == 1 and sh.balanced_chunks == 0,
+              "stencil": lambda sh: sh.window_segments >= 2,
+              "powerlaw": lambda sh: sh.balanced_chunks == 1}
+
+
+@pytest.mark.parametrize("kind", ROW_KINDS)
+@pytest.mark.parametrize("name", sorted(ROUND_TRIP))
+def test_a_block_that_is_the_whole_matrix_has_the_whole_plans_shape(sp, oracle, name, kind):
+    """The two directions of the block shape (rows_plan.hip, export_rows_shape / inherit_rows_shape) undo each other: a
+    block plan over all rows and all chunks of the whole plan, made from the whole plan's shape, reports that shape byte
+    for byte."""
+    gs, c = case(oracle, "large", name, 0)
+    whole = sp.Plan(kind, c.n_rows, c.n_cols, c.nnz, c.Ap, c.Aj, c.dt)
+    shape = whole.shape()
+    whole.destroy()
+    fields = lambda sh: {f: getattr(sh, f) if isinstance(getattr(sh, f), int) else list(getattr(sh, f)) for f, _ in sh._fields_}
+    assert ROUND_TRIP[name](shape), "large/%s %s: not the plan shape the case is about: %s" % (name, kind, fields(shape))
+    block = sp.Plan.block(kind, shape, 0, 0, shape.n_chunks, 0, c.n_rows, c.n_cols, c.nnz, c.Ap, c.Aj, c.dt)
+    again = block.shape()
+    block.destroy()
+    assert bytes(again) == bytes(shape), "large/%s %s: the block's shape differs from the whole plan's: block %s, whole %s" % (
+        name, kind, fields(again), fields(shape))
 
 
 WINDOWED = ("one band-placed window", "window_segments >= 2", "sweep kernel", "chunks with a window")

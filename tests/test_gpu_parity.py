@@ -363,7 +363,7 @@ def test_execute_is_capturable_in_a_hip_graph(sp, oracle, kind, path):
 
 
 def test_chunks_are_cut_by_weight_only_when_rows_are_uneven(sp, oracle):
-    """decide_balance (analyze.hip): equal-row chunks for uniform matrices (no table), weight-cut
+    """decide_balance (rows_plan.hip): equal-row chunks for uniform matrices (no table), weight-cut
     chunks when the heaviest equal-row chunk is more than twice the mean.  Either way every row is
     computed exactly once (integer-valued data: bit-exact), hub rows (summed by a whole workgroup) included."""
     rng = np.random.RandomState(41)

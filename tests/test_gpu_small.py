@@ -1,4 +1,4 @@
-"""GPU suite: the product's DEFAULT on small matrices — the VECTOR kind's plain one-pass kernel (capi.hip, small_plain;
+"""GPU suite: the product's DEFAULT on small matrices — the VECTOR kind's plain one-pass kernel (rows_plan.hip, shape_rows: small_plain;
 common.hpp, kSmallPlainNnz).  tests/conftest.py switches that choice off for the rest of the suite (whose small matrices
 are there to exercise the chunked kernels); here it is switched back on, the knobs re-read, and the same kinds of
 matrices — ragged, empty rows, one long row, one column, every type combination, row blocks — go through it."""

@@ -1,5 +1,5 @@
 """GPU suite: the edges of the plain one-pass kernel (csr_vector_kernel) under the product's default — every lane width
-the small-matrix rule picks (capi.hip, small_plain: 2 elements per lane up to 32 per row, 4 beyond; T = 2 .. 64), the
+the small-matrix rule picks (rows_plan.hip, shape_rows: 2 elements per lane up to 32 per row, 4 beyond; T = 2 .. 64), the
 kSmallPlainNnz boundary itself, hub rows the structure probe does not see, tiny and degenerate matrices, alpha / beta.
 Each case is checked row by row against the oracle (bound of tests/test_gpu_parity.py, bit-exact where integer-valued)."""
 import numpy as np
@@ -138,7 +138,7 @@ HUBS = {5000: WEIGHT_CUT, 50_000: WEIGHT_CUT, 200_000: WEIGHT_CUT}
 @pytest.mark.parametrize("hub", sorted(HUBS))
 def test_hub_rows_the_probe_does_not_see(sp, oracle, small_on, hub):
     """A regular matrix (16 per row) with three rows of `hub` nonzeros placed where the 256-row structure probe does
-    not look (capi.hip, probe_structure samples rows (n - 1) i / 255): the plan it gets, every row, vector = light."""
+    not look (analyze.hip, probe_structure samples rows (n - 1) i / 255): the plan it gets, every row, vector = light."""
     rng = np.random.RandomState(hub % 1000 + 7)
     n = 60_002
     Ap, Aj = regular_csr(rng, 16, n, n)

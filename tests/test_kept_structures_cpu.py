@@ -150,7 +150,7 @@ def test_structure(group, name, group_values):
         hubs = hubs[hubs >= g.head_rows]
         assert hubs.size >= 30 and np.all(lens[hubs] == g.hub_len)
         assert np.all(lens[:g.head_rows] == 8 * k)
-        # below the threshold from which a fresh plan would cut a row into slices (analyze.hip, find_giant_rows)
+        # below the threshold from which a fresh plan would cut a row into slices (rows_plan.hip, find_giant_rows)
         fair = max(4096, min(65536, (g.nnz // 2048 + 1023) & ~1023))
         assert lens.max() == g.hub_len < fair
     if name == "ragged":
