@@ -42,6 +42,7 @@ extern "C" {
  * above did NOT move with them: MI355_SPMV_VERSION / mi355_spmv_version() alone do not tell a library that has the
  * pattern entry points from one that has not — test this macro, or look the symbols up.                          */
 #define MI355_SPMV_HAS_PATTERN 1 /* MI355_VAL_PATTERN, mi355_spmv_merge_pattern_*, mi355_spmv_plan_get_mat_type */
+#define MI355_SPMV_HAS_MULTI 1   /* mi355_spmv_multi_*: Y = A X for k vectors in one pass over A */
 
 /* status codes */
 enum {
@@ -502,6 +503,55 @@ const char* mi355_spmv_functor_compile_log(void);
 int mi355_spmv_functor_spmv(mi355_spmv_functor* functor, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
                             const int32_t* Aj, const void* Ax, const void* x, void* y, void* stream);
 int mi355_spmv_functor_destroy(mi355_spmv_functor* functor);
+
+/* ---- multi-vector SpMV: Y = alpha * A X + beta * Y for k vectors in one pass over A ------------------------------
+ * For callers with several right-hand sides (block Krylov, several loads, GNN features, PageRank batches), who would
+ * otherwise call plan_execute k times and stream the matrix — and waste most of every gathered line of x — k times.
+ * The reference's operator has one x and one y (include/spmv.h:29-34): this has no counterpart there.
+ *   X   n_cols x k, ROW-major: X[c * ldx + j] is element c of vector j, ldx >= k
+ *   Y   n_rows x k, likewise:  Y[r * ldy + j], ldy >= k;  Y[:, j] = alpha * A X[:, j] + beta * Y[:, j] for j < k
+ * Elements j >= k of a row of X are never read, of a row of Y never written; with beta = 0 (the default; alpha = 1)
+ * Y is never read.  Rows of X / Y are accessed 16 bytes per lane when the pointer and ld * sizeof(value) are 16-byte
+ * aligned, else element by element.
+ * Types: {I32, I64} offsets x {F32, F64} values, the (+, *) semiring; MI355_VAL_I32 / MI355_VAL_PATTERN return
+ * MI355_SPMV_ENOTSUP.  Column-major X, mixed precision and the dist_* entry points are not built.
+ * The work is cut by NONZEROS: a wave owns a slice of slice_len merge items (row ends + nonzeros), so empty rows and
+ * hub rows cost what they hold; a row that crosses slices leaves carries in scratch (sized for k_max at create), and
+ * a fix-up kernel adds them in slice order — no float atomics: two executes on the same inputs give the same bits.
+ * Columns are served in tiles of 4 / 8 / 16 / 32 (fp32) or 2 / 4 / 8 / 16 (fp64); another k takes the next width with
+ * the surplus masked; k above the widest takes ceil(k / widest) passes over A inside the one execute.
+ * Life cycle as plan_*: create may allocate and synchronise, retains Ap / Aj (not copied; it does not read them);
+ * execute is asynchronous on `stream`, allocates nothing, never synchronises, launches kernels only (graph-capturable);
+ * one stream at a time per object; 1 <= k <= k_max.  Argument errors are refused before any device call.         */
+typedef struct mi355_spmv_multi mi355_spmv_multi;
+typedef struct mi355_spmv_multi_info {
+    int32_t off_type, val_type, k_max;
+    int32_t slice_len;       /* merge items (row ends + nonzeros) per slice = per wave                    */
+    int32_t block_threads;
+    int32_t widest_tile;     /* columns of the widest tile                                                */
+    int32_t passes;          /* passes over A per execute with k = k_max                                  */
+    int32_t n_kernels;       /* kernels per execute with k = k_max: the passes + the fix-up               */
+    int64_t n_slices;
+    int64_t grid_blocks;     /* workgroups of one pass                                                    */
+    int64_t scratch_bytes;   /* device memory held: the slices' carry rows and carry values for k_max     */
+    char main_kernel[64];
+} mi355_spmv_multi_info;
+int mi355_spmv_multi_create(mi355_spmv_multi** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols,
+                            int64_t nnz, const void* Ap, const int32_t* Aj, int32_t k_max);
+int mi355_spmv_multi_set_alpha_beta(mi355_spmv_multi* multi, double alpha, double beta);
+int mi355_spmv_multi_execute(mi355_spmv_multi* multi, const void* Ax, const void* X, int64_t ldx,
+                             void* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_get_info(const mi355_spmv_multi* multi, mi355_spmv_multi_info* info);
+int mi355_spmv_multi_destroy(mi355_spmv_multi* multi);
+/* One-shots: create (k_max = k), execute, synchronise the stream, destroy.  No plan is kept between calls.       */
+int mi355_spmv_multi_i32_f32(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+                            const float* Ax, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_i32_f64(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+                            const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+                            const float* Ax, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+                            const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

@@ -45,6 +45,8 @@ EXPORTS = (
     + ["mi355_spmv_coo_to_csr", "mi355_spmv_coo_symmetric_nnz", "mi355_spmv_coo_to_csr_symmetric"]
     + ["mi355_spmv_merge_pattern_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64", "i32")]
     + ["mi355_spmv_plan_get_mat_type"]
+    + ["mi355_spmv_multi_" + n for n in ("create", "set_alpha_beta", "execute", "get_info", "destroy")]
+    + ["mi355_spmv_multi_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
 )
 
 
@@ -83,6 +85,13 @@ class DistInfo(C.Structure):
                 ("exchange", C.c_int32), ("auto_picked", C.c_int32), ("allgather_in_place", C.c_int32),
                 ("reserved0", C.c_int32), ("trial_us", C.c_float * 4), ("max_block_rows", C.c_int64),
                 ("staging_bytes", C.c_int64), ("exchange_name", C.c_char * 16)]
+
+
+class MultiInfo(C.Structure):
+    _fields_ = [("off_type", C.c_int32), ("val_type", C.c_int32), ("k_max", C.c_int32), ("slice_len", C.c_int32),
+                ("block_threads", C.c_int32), ("widest_tile", C.c_int32), ("passes", C.c_int32), ("n_kernels", C.c_int32),
+                ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("scratch_bytes", C.c_int64),
+                ("main_kernel", C.c_char * 64)]
 
 
 EXCHANGES = {"auto": 0, "bcast": 1, "sendrecv": 2, "allgather": 3}
@@ -153,6 +162,18 @@ def lib():
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t),
                                                       C.c_void_p]
+        L.mi355_spmv_multi_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_int32]
+        L.mi355_spmv_multi_set_alpha_beta.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        L.mi355_spmv_multi_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                               C.c_int32, C.c_void_p]
+        L.mi355_spmv_multi_get_info.argtypes = [C.c_void_p, C.POINTER(MultiInfo)]
+        L.mi355_spmv_multi_destroy.argtypes = [C.c_void_p]
+        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
+            for v in ("f32", "f64"):
+                getattr(L, "mi355_spmv_multi_%s_%s" % (o, v)).argtypes = [
+                    C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                    C.c_int64, C.c_int32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -508,6 +529,106 @@ class Plan:
             self.destroy()
         except Exception:
             pass
+
+
+def _require_matrix(t, name, rows, dtype):
+    """A 2-D device tensor of `rows` rows whose rows are contiguous (stride(1) == 1); returns its leading dimension."""
+    if not t.is_cuda:
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if t.dim() != 2:
+        raise ValueError("%s must be 2-D (one row per matrix column / row, one column per vector)" % name)
+    if t.dtype != dtype:
+        raise TypeError("value type differs from the plan's")
+    if t.size(0) < rows:
+        raise ValueError("operand shorter than the plan's sizes")
+    if t.size(1) > 1 and t.stride(1) != 1:
+        raise ValueError("%s must be row-major: stride(1) == 1 (column-major operands are not built)" % name)
+    ld = t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
+    if ld < t.size(1):
+        raise ValueError("%s: rows overlap (stride(0) below the number of columns)" % name)
+    return ld
+
+
+class MultiPlan:
+    """mi355_spmv_multi_*: Y = alpha * A X + beta * Y for up to k_max vectors in one pass over A.  X (n_cols x k) and
+    Y (n_rows x k) are 2-D row-major device tensors; views with a larger stride(0) are taken as they are.  Holds
+    references to Ap and Aj so they outlive the object."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max):
+        _require_device(Ap, Aj)
+        if Aj.dtype != torch.int32:
+            raise TypeError("Aj must be int32")
+        if val_dtype not in (torch.float32, torch.float64):
+            raise TypeError("val_dtype must be float32 or float64")
+        self.n_rows, self.n_cols, self.nnz, self.k_max = n_rows, n_cols, nnz, k_max
+        self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
+        self._h = C.c_void_p()
+        with torch.cuda.device(Ap.device):
+            st = lib().mi355_spmv_multi_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows,
+                                               n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), k_max)
+        _check(st, "mi355_spmv_multi_create")
+
+    def execute(self, Ax, X, Y, stream=None):
+        """Asynchronous on `stream` (default: torch's current stream).  k = X.size(1) = Y.size(1)."""
+        _require_device(Ax)
+        if Ax.dtype != self.val_dtype:
+            raise TypeError("value type differs from the plan's")
+        if Ax.numel() < self.nnz:
+            raise ValueError("operand shorter than the plan's sizes")
+        ldx = _require_matrix(X, "X", self.n_cols, self.val_dtype)
+        ldy = _require_matrix(Y, "Y", self.n_rows, self.val_dtype)
+        if X.size(1) != Y.size(1):
+            raise ValueError("X and Y hold different numbers of vectors")
+        st = lib().mi355_spmv_multi_execute(self._h, C.c_void_p(Ax.data_ptr()), C.c_void_p(X.data_ptr()), ldx,
+                                            C.c_void_p(Y.data_ptr()), ldy, X.size(1), _stream_ptr(stream))
+        _check(st, "mi355_spmv_multi_execute")
+        return Y
+
+    def set_alpha_beta(self, alpha, beta):
+        """Y = alpha * A X + beta * Y for the following executes (default 1, 0)."""
+        _check(lib().mi355_spmv_multi_set_alpha_beta(self._h, C.c_double(alpha), C.c_double(beta)),
+               "mi355_spmv_multi_set_alpha_beta")
+
+    def info(self):
+        mi = MultiInfo()
+        _check(lib().mi355_spmv_multi_get_info(self._h, C.byref(mi)), "mi355_spmv_multi_get_info")
+        d = {n: getattr(mi, n) for n, _ in mi._fields_}
+        d["main_kernel"] = d["main_kernel"].decode()
+        return d
+
+    def destroy(self):
+        if self._h:
+            lib().mi355_spmv_multi_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def spmm(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None):
+    """One-shot Y = A X for the k = X.size(1) vectors of a row-major X (mi355_spmv_multi_<off>_<val>): create, execute,
+    synchronise the stream, destroy."""
+    _require_device(Ap, Aj, Ax)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if Ax.dtype not in (torch.float32, torch.float64):
+        raise TypeError("Ax must be float32 or float64")
+    if Ax.numel() < nnz:
+        raise ValueError("operand shorter than the matrix")
+    ldx = _require_matrix(X, "X", n_cols, Ax.dtype)
+    ldy = _require_matrix(Y, "Y", n_rows, Ax.dtype)
+    if X.size(1) != Y.size(1):
+        raise ValueError("X and Y hold different numbers of vectors")
+    o, v = OFF_TYPES[Ap.dtype][1], VAL_TYPES[Ax.dtype][1]
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), "mi355_spmv_multi_%s_%s" % (o, v))(
+            n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), C.c_void_p(Ax.data_ptr()),
+            C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, X.size(1), _stream_ptr(stream))
+    _check(st, "mi355_spmv_multi_%s_%s" % (o, v))
+    return Y
 
 
 C_TYPE_NAMES = {torch.float32: "float", torch.float64: "double", torch.int32: "int", torch.int64: "long long"}
