@@ -43,6 +43,7 @@ extern "C" {
  * pattern entry points from one that has not — test this macro, or look the symbols up.                          */
 #define MI355_SPMV_HAS_PATTERN 1 /* MI355_VAL_PATTERN, mi355_spmv_merge_pattern_*, mi355_spmv_plan_get_mat_type */
 #define MI355_SPMV_HAS_MULTI 1   /* mi355_spmv_multi_*: Y = A X for k vectors in one pass over A */
+#define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
 enum {
@@ -82,7 +83,12 @@ enum { MI355_VAL_F32 = 0, MI355_VAL_F64 = 1,
        /* A PATTERN matrix: no stored values, every entry is one in the type of x and y (a Matrix Market `pattern`
         * file, an unweighted graph).  Valid ONLY as the mat_type of mi355_spmv_plan_create_typed, MERGE kind: as
         * x_type / y_type and as the val_type of every other entry point it is an error.                        */
-       MI355_VAL_PATTERN = 3 };
+       MI355_VAL_PATTERN = 3,
+       /* Matrix values stored in 16 bits — IEEE binary16, or bfloat16 (the upper half of an fp32) — under fp32 x and
+        * y: every value is widened exactly as it meets x, products and sums are fp32.  Valid ONLY as the mat_type of
+        * mi355_spmv_plan_create_typed, VECTOR kind, x_type = y_type = F32: as x_type / y_type and as the val_type of
+        * every other entry point they are MI355_SPMV_EINVAL.  mi355_spmv_narrow_values makes such values.        */
+       MI355_VAL_F16 = 4, MI355_VAL_BF16 = 5 };
 
 /* semirings of the generalized merge kind.  The reference's
  * SpMV_merge_based_generalized takes a functor_t with initialize / combine / reduce
@@ -193,11 +199,25 @@ int mi355_spmv_plan_create(mi355_spmv_plan** plan, int kind, int off_type, int v
  * it.  4 bytes per nonzero cross HBM instead of 8 (fp32) or 12 (fp64), and Ax need not exist.  All five semirings;
  * alpha / beta under (+, *) for the float types.  The sums are those of the valued plan executed with Ax = ones, bit
  * for bit, whenever that plan walks its tiles too.                                                                   */
+/* mat_type = MI355_VAL_F16 / MI355_VAL_BF16, x_type = y_type = F32, kind VECTOR (AUTO becomes VECTOR; MERGE / LIGHT and
+ * any other x / y type return MI355_SPMV_ENOTSUP): execute takes Ax as 16-bit values (8-byte aligned for the fast
+ * path), x / y as float*.  The plan is shaped exactly as the fp32 VECTOR plan of the same structure and flags
+ * (plan_get_shape is byte-identical; plan_get_info().val_type stays F32, plan_get_mat_type says 4 / 5), so a banded
+ * matrix streams 2 + 2 bytes per nonzero with the packed index and 4 + 2 with MI355_PLAN_NO_INDEX_COPY, where fp32
+ * streams 2 + 4 and 4 + 4; a row's products are added in the fp32 plan's order, so y equals the fp32 plan's y on the
+ * widened values bit for bit.  That fast path covers equal-row chunks with one window of x or none.  Weight-cut
+ * chunks, several bands, the swept window, giant rows and small matrices run the plain one-pass kernel instead
+ * (plan_get_info then says main_kernel = "csr_vector_kernel", window_elems = 0, n_kernels = 1), as does an execute
+ * whose Ax is not 8-byte aligned or whose Aj / x are not 16-byte aligned.  alpha / beta work; set_semiring stays
+ * ENOTSUP as for every VECTOR plan; no one-shot entry points, no row blocks, no dist_*.                              */
 int mi355_spmv_plan_create_typed(mi355_spmv_plan** plan, int kind, int off_type, int mat_type, int x_type,
                                  int y_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
                                  const int32_t* Aj, int flags);
 /* The mat_type a plan was created with (= its val_type unless plan_create_typed said otherwise).                    */
 int mi355_spmv_plan_get_mat_type(const mi355_spmv_plan* plan, int* mat_type);
+/* dst[i] = src[i] rounded to dst_type (MI355_VAL_F16 / MI355_VAL_BF16; anything else: MI355_SPMV_EINVAL), i < n, device
+ * pointers: round to nearest even, overflow to +-inf, NaN stays NaN, subnormals kept.  Asynchronous on `stream`.    */
+int mi355_spmv_narrow_values(int dst_type, int64_t n, const float* src, void* dst, void* stream);
 /* One-shot SpMV with a pattern matrix: the arguments of mi355_spmv_merge_genl_* without Ax.  A plan per call.       */
 int mi355_spmv_merge_pattern_i32_f32(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap,
                                     const int32_t* Aj, const float* x, float* y, void* stream);

@@ -22,6 +22,9 @@ LABELS = {"hip_vector": "vector", "hip_merge": "merge", "hip_light": "light", "h
 OFF_TYPES = {torch.int32: (0, "i32"), torch.int64: (1, "i64")}
 VAL_TYPES = {torch.float32: (0, "f32"), torch.float64: (1, "f64"), torch.int32: (2, "i32")}   # (int32 values: the merge kind only)
 VAL_PATTERN = 3              # MI355_VAL_PATTERN: a matrix type only (Plan(..., mat_dtype="pattern"), spmv_pattern)
+# MI355_VAL_F16 / MI355_VAL_BF16: matrix types only — 16-bit values under float32 x and y, the vector kind
+# (Plan("vector", ..., torch.float32, mat_dtype=torch.float16), narrow_values).  Never in VAL_TYPES: that is x's and y's.
+MAT_TYPES = {torch.float16: (4, "f16"), torch.bfloat16: (5, "bf16")}
 PLAN_REUSE_STRUCTURE = 1
 PLAN_NO_INDEX_COPY = 2       # the plan holds nothing derived from the contents of Aj (no packed index)
 SEMIRINGS = {"plus_times": 0, "min_plus": 1, "max_times": 2, "max_plus": 3, "or_and": 4}
@@ -44,7 +47,7 @@ EXPORTS = (
     + ["mi355_spmv_functor_" + n for n in ("compile", "compile_log", "spmv", "destroy")]
     + ["mi355_spmv_coo_to_csr", "mi355_spmv_coo_symmetric_nnz", "mi355_spmv_coo_to_csr_symmetric"]
     + ["mi355_spmv_merge_pattern_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64", "i32")]
-    + ["mi355_spmv_plan_get_mat_type"]
+    + ["mi355_spmv_plan_get_mat_type", "mi355_spmv_narrow_values"]
     + ["mi355_spmv_multi_" + n for n in ("create", "set_alpha_beta", "execute", "get_info", "destroy")]
     + ["mi355_spmv_multi_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
 )
@@ -125,6 +128,7 @@ def lib():
         L.mi355_spmv_plan_get_info.argtypes = [C.c_void_p, C.POINTER(PlanInfo)]
         L.mi355_spmv_plan_merge_coords.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355_spmv_plan_get_mat_type.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.mi355_spmv_narrow_values.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355_spmv_plan_get_shape.argtypes = [C.c_void_p, C.POINTER(PlanShape)]
         L.mi355_spmv_plan_partition.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355_spmv_plan_create_block.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -235,6 +239,26 @@ def spmv_mixed(n_rows, n_cols, nnz, Ap, Aj, Ax, x, y, stream=None):
             C.c_void_p(Ax.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), _stream_ptr(stream))
     _check(st, "mi355_spmv_merge_f32mat_f64vec_%s" % o)
     return y
+
+
+def narrow_values(Ax, dtype, out=None, stream=None):
+    """Device float32 values rounded to torch.float16 / torch.bfloat16 (mi355_spmv_narrow_values: nearest even, overflow
+    to +-inf, NaN stays NaN, subnormals kept): the Ax of a Plan(..., mat_dtype=dtype).  Asynchronous on `stream`."""
+    if dtype not in MAT_TYPES:
+        raise TypeError("narrow_values: dtype is torch.float16 or torch.bfloat16")
+    _require_device(Ax)
+    if Ax.dtype != torch.float32:
+        raise TypeError("narrow_values takes float32 values")
+    if out is None:
+        out = torch.empty(Ax.shape, dtype=dtype, device=Ax.device)
+    else:
+        _require_device(out)
+        if out.dtype != dtype or out.numel() < Ax.numel():
+            raise TypeError("narrow_values: out must hold Ax.numel() values of the asked dtype")
+    st = lib().mi355_spmv_narrow_values(MAT_TYPES[dtype][0], Ax.numel(), C.c_void_p(Ax.data_ptr()),
+                                        C.c_void_p(out.data_ptr()), _stream_ptr(stream))
+    _check(st, "mi355_spmv_narrow_values")
+    return out
 
 
 def cache_release():
@@ -373,7 +397,9 @@ class Plan:
         in — None = val_dtype; torch.float32 under torch.float64 vectors is built for the merge kind
         (mi355_spmv_plan_create_typed; the reference's operator keeps the three value types apart, spmv.h:29-34).
         mat_dtype="pattern": the matrix stores no values, every entry is one (MI355_VAL_PATTERN; merge kind, float32 /
-        float64 / int32 vectors) — execute() then ignores Ax, which may be None."""
+        float64 / int32 vectors) — execute() then ignores Ax, which may be None.
+        mat_dtype=torch.float16 / torch.bfloat16: the matrix values are stored in 16 bits under float32 x and y
+        (MI355_VAL_F16 / MI355_VAL_BF16; kind "vector", or "auto", which becomes it) — execute() takes Ax of that dtype."""
         kind = LABELS.get(kind, kind)
         if kind not in KINDS:
             raise ValueError('SpMV kind "%s" is NOT SUPPORTED' % kind)
@@ -392,6 +418,13 @@ class Plan:
             st = lib().mi355_spmv_plan_create_typed(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0], VAL_PATTERN,
                                                     VAL_TYPES[val_dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols,
                                                     nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
+            _check(st, "mi355_spmv_plan_create_typed")
+        elif self.mat_dtype in MAT_TYPES:
+            if val_dtype != torch.float32:
+                raise TypeError("a float16 / bfloat16 matrix is built under float32 x and y only")
+            st = lib().mi355_spmv_plan_create_typed(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0],
+                                                    MAT_TYPES[self.mat_dtype][0], 0, 0, n_rows, n_cols, nnz,
+                                                    C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
             _check(st, "mi355_spmv_plan_create_typed")
         elif self.mat_dtype == val_dtype:
             st = lib().mi355_spmv_plan_create(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0],

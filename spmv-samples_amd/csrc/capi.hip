@@ -113,7 +113,12 @@ static int execute_typed(Plan& p, const off_t* Ap, const void* Ax, const void* x
     const val_t* xx = static_cast<const val_t*>(x);
     val_t* yy = static_cast<val_t*>(y);
     switch (p.kind) {
-        case MI355_KIND_VECTOR: return launch_rows<VectorRows, off_t, val_t>(p, Ap, ax, xx, yy, s);
+        case MI355_KIND_VECTOR:
+            if constexpr (sizeof(val_t) == 4) {   // (a 16-bit matrix under fp32 vectors: plan_create_typed)
+                if (p.mat_type == MI355_VAL_F16) return launch_vector_half<off_t, _Float16>(p, Ap, static_cast<const _Float16*>(Ax), xx, yy, s);
+                if (p.mat_type == MI355_VAL_BF16) return launch_vector_half<off_t, Bf16>(p, Ap, static_cast<const Bf16*>(Ax), xx, yy, s);
+            }
+            return launch_rows<VectorRows, off_t, val_t>(p, Ap, ax, xx, yy, s);
         case MI355_KIND_MERGE:
             if (p.mat_type == MI355_VAL_PATTERN) return launch_merge<off_t, val_t, PatternOnes>(p, Ap, nullptr, xx, yy, s);
             if constexpr (sizeof(val_t) == 8)
@@ -382,7 +387,8 @@ int mi355_spmv_plan_create_typed(mi355_spmv_plan** out, int kind, int off_type, 
     if (out) *out = nullptr;
     const auto known = [](int t) { return t == MI355_VAL_F32 || t == MI355_VAL_F64 || t == MI355_VAL_I32; };
     const bool pattern = mat_type == MI355_VAL_PATTERN;        // (a matrix type only: never the type of x or y)
-    if ((!known(mat_type) && !pattern) || !known(x_type) || !known(y_type)) { set_error("plan_create_typed: unknown value type"); return MI355_SPMV_EINVAL; }
+    const bool half = is_half_matrix(mat_type);                // (F16 / BF16: matrix types only as well)
+    if ((!known(mat_type) && !pattern && !half) || !known(x_type) || !known(y_type)) { set_error("plan_create_typed: unknown value type"); return MI355_SPMV_EINVAL; }
     if (x_type != y_type) { set_error("plan_create_typed: x and y of different types are not built"); return MI355_SPMV_ENOTSUP; }
     if (pattern) {
         if (kind == MI355_KIND_AUTO) kind = MI355_KIND_MERGE;
@@ -402,6 +408,27 @@ int mi355_spmv_plan_create_typed(mi355_spmv_plan** out, int kind, int off_type, 
         return st;
     }
     if (mat_type == x_type) return mi355_spmv_plan_create(out, kind, off_type, x_type, n_rows, n_cols, nnz, Ap, Aj, flags);
+    if (half) {
+        if (x_type != MI355_VAL_F32) {
+            set_error("plan_create_typed: a 16-bit matrix is built under fp32 x and y only");
+            return MI355_SPMV_ENOTSUP;
+        }
+        if (kind == MI355_KIND_AUTO) kind = MI355_KIND_VECTOR;
+        if (kind != MI355_KIND_VECTOR) {
+            if (kind < 0 || kind >= MI355_KIND_COUNT) { set_error("plan_create_typed: unknown kind %d", kind); return MI355_SPMV_EINVAL; }
+            set_error("plan_create_typed: 16-bit matrix values are built for the vector kind only (the kind whose banded plans are bound by the matrix stream)");
+            return MI355_SPMV_ENOTSUP;
+        }
+        // shaped exactly as the fp32 plan of the same structure and flags, packed index included ...
+        const int st = plan_create_impl(out, kind, off_type, x_type, n_rows, n_cols, nnz, Ap, Aj, flags, nullptr);
+        if (st != MI355_SPMV_OK) return st;
+        Plan& p = (*out)->p;
+        p.mat_type = mat_type;
+        (*out)->asked_kind = kind;
+        // ... and reported as what executes: a shape the 16-bit chunked kernels are not built for runs the plain kernel
+        set_half_matrix_launch(p);
+        return st;
+    }
     if (!(mat_type == MI355_VAL_F32 && x_type == MI355_VAL_F64)) {
         set_error("plan_create_typed: the only mixed combination built is an fp32 matrix under fp64 vectors");
         return MI355_SPMV_ENOTSUP;
@@ -539,8 +566,10 @@ int mi355_spmv_plan_get_info(const mi355_spmv_plan* h, mi355_spmv_plan_info* inf
     info->packed_index_bytes = (int64_t)p.packed_bytes;
     info->packed_index_escapes = p.packed_escapes;
     info->n_kernels = p.n_kernels;
-    info->window_elems = p.window_elems;
-    info->window_segments = p.window_elems > 0 ? (p.n_seg >= 2 ? p.n_seg : 1) : 0;
+    // (a 16-bit-matrix plan on the plain kernel stages no window, whatever the shape it shares with the fp32 plan holds)
+    const bool windowed = p.window_elems > 0 && !(is_half_matrix(p.mat_type) && !half_matrix_chunked(p));
+    info->window_elems = windowed ? p.window_elems : 0;
+    info->window_segments = windowed ? (p.n_seg >= 2 ? p.n_seg : 1) : 0;
     snprintf(info->main_kernel, sizeof(info->main_kernel), "%s", p.main_kernel);
     info->balanced_chunks = p.balanced ? 1 : 0;
     info->rows_cap = p.rows_cap;
@@ -553,6 +582,15 @@ int mi355_spmv_plan_get_mat_type(const mi355_spmv_plan* h, int* mat_type) {
     if (!h || !mat_type) { set_error("plan_get_mat_type: null argument"); return MI355_SPMV_EINVAL; }
     *mat_type = h->p.mat_type;
     return MI355_SPMV_OK;
+}
+
+int mi355_spmv_narrow_values(int dst_type, int64_t n, const float* src, void* dst, void* stream) {
+    g_err[0] = 0;
+    if (!is_half_matrix(dst_type)) { set_error("narrow_values: the destination type is MI355_VAL_F16 or MI355_VAL_BF16, not %d", dst_type); return MI355_SPMV_EINVAL; }
+    if (n < 0) { set_error("narrow_values: negative size"); return MI355_SPMV_EINVAL; }
+    if (n > 0 && (!src || !dst)) { set_error("narrow_values: null src or dst"); return MI355_SPMV_EINVAL; }
+    if (n == 0) return MI355_SPMV_OK;
+    return launch_narrow_values(dst_type, n, src, dst, static_cast<hipStream_t>(stream));
 }
 
 int mi355_spmv_plan_merge_coords(mi355_spmv_plan* h, int64_t* tile_row, int64_t* tile_nnz) {

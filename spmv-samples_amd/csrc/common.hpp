@@ -62,6 +62,10 @@ void set_error(const char* fmt, ...);
 // no storage.  The merge kind's tile kernel and launch_merge are instantiated with it in the place of the stored
 // value type; the kernel then issues no Ax load at all and no address is ever formed from the pointer.
 struct PatternOnes {};
+// mat_t of a MI355_VAL_BF16 matrix: bfloat16 as stored, the upper half of an fp32 (MI355_VAL_F16 is _Float16).  The
+// VECTOR kind's chunk bodies take either under fp32 vectors (row_dot.hpp, csr_vector_h16.hip).
+struct Bf16 { uint16_t bits; };
+inline bool is_half_matrix(int mat_type) { return mat_type == MI355_VAL_F16 || mat_type == MI355_VAL_BF16; }
 
 #define MI355_HIP_TRY(expr)                                                              \
     do {                                                                                 \
@@ -127,7 +131,8 @@ void knobs_reload();
 struct Plan {   // only what an execute or a report reads: what a create needs and then drops are locals of the create path
     int kind = 0, off_type = 0, val_type = 0, flags = 0;   // val_type: the type of x, y and of all arithmetic
     int mat_type = 0;          // the type the matrix values are stored in (= val_type; F32 under F64 vectors, or
-                               // MI355_VAL_PATTERN = no stored values, every entry is one: MERGE)
+                               // MI355_VAL_PATTERN = no stored values, every entry is one: MERGE; F16 / BF16 under
+                               // F32 vectors: VECTOR)
     int32_t n_rows = 0, n_cols = 0;
     int64_t nnz = 0;           // END offset of the nonzeros: Ap[n_rows] (= their count unless nnz_begin > 0)
     int64_t nnz_read = 0;      // elements of Aj / Ax the 16-byte loads may touch: nnz, or nnz rounded up to a multiple
@@ -259,6 +264,11 @@ template <typename Kind, typename off_t, typename val_t>
 int launch_rows(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s);
 template <typename off_t, typename val_t>   // the plain CSR-vector kernel (small matrices of either kind)
 int launch_vector_plain(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s);
+// VECTOR with a 16-bit matrix under fp32 vectors (csr_vector_h16.hip; mat_t = _Float16 | Bf16): the chunked kernels on
+// the shapes they are built for (half_matrix_chunked), the plain kernel otherwise; and the fp32 -> 16-bit conversion
+template <typename off_t, typename mat_t>
+int launch_vector_half(const Plan& p, const off_t* Ap, const mat_t* Ax, const float* x, float* y, hipStream_t s);
+int launch_narrow_values(int dst_type, int64_t n, const float* src, void* dst, hipStream_t s);
 template <typename off_t, typename val_t, typename mat_t>
 int launch_merge(Plan& p, const off_t* Ap, const mat_t* Ax, const val_t* x, val_t* y, hipStream_t s);
 
@@ -274,6 +284,8 @@ void set_rows_launch(Plan& p);     // VECTOR / LIGHT: kernel, grid and kernel co
 int find_giant_rows(Plan& p, GiantRowList& giants);          // balanced plans: rows beyond giant_len nonzeros (synchronises)
 int build_chunk_table(Plan& p, const GiantRowList& giants);  // after the scratch is allocated
 int build_packed_index(Plan& p);   // after the shape is final: the packed index of a plan that qualifies (synchronises)
+bool half_matrix_chunked(const Plan& p);   // a 16-bit-matrix VECTOR plan: whether its shape is one the 16-bit chunked kernels are built for
+void set_half_matrix_launch(Plan& p);      // ... and, where it is not, the report of the plain kernel that runs instead
 // the two directions of a row block's inherited shape: whole plan -> shape -> block plan (then find_giant_rows, set_rows_launch)
 void export_rows_shape(const Plan& p, mi355_spmv_plan_shape* sh);
 int inherit_rows_shape(Plan& p, const mi355_spmv_plan_shape& w, const BlockSpec& blk);

@@ -660,6 +660,10 @@ int mi355_spmv_dist_create_local(mi355_spmv_dist** out, int kind, int off_type, 
                                  const int* devices, int sub_blocks, int flags) {
     if (!out) { set_error("dist_create_local: null pointer"); return MI355_SPMV_EINVAL; }
     *out = nullptr;
+    if (val_type == MI355_VAL_F16 || val_type == MI355_VAL_BF16) {   // (from the arguments alone: no device call yet)
+        set_error("dist_create_local: value type %d is a matrix type of mi355_spmv_plan_create_typed only", val_type);
+        return MI355_SPMV_EINVAL;
+    }
     if (n_devices < 1 || n_devices > kMaxPieces || sub_blocks < 1 || sub_blocks > 64) {
         set_error("dist_create_local: n_devices %d / sub_blocks %d out of range", n_devices, sub_blocks);
         return MI355_SPMV_EINVAL;
@@ -757,6 +761,10 @@ int mi355_spmv_dist_create_rank(mi355_spmv_dist** out, int kind, int off_type, i
                                 int64_t nnz_end_local, const void* Ap_local, const int32_t* Aj_local, int flags) {
     if (!out) { set_error("dist_create_rank: null pointer"); return MI355_SPMV_EINVAL; }
     *out = nullptr;
+    if (val_type == MI355_VAL_F16 || val_type == MI355_VAL_BF16) {
+        set_error("dist_create_rank: value type %d is a matrix type of mi355_spmv_plan_create_typed only", val_type);
+        return MI355_SPMV_EINVAL;
+    }
     if (world < 1 || world > kMaxPieces || rank < 0 || rank >= world || parts_per_rank < 1 || parts_per_rank > 64 || !row_cuts || !nnz_cuts) {
         set_error("dist_create_rank: bad rank / world / cuts");
         return MI355_SPMV_EINVAL;

@@ -14,6 +14,8 @@
 // a shuffle-down tree over T lanes — the shape of SURVEY Appendix A.1 with T up to 64.
 #pragma once
 
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace mi355 {
@@ -30,6 +32,33 @@ template <> struct Vec4<double> { using type = double4v; };
 template <> struct Vec4<int32_t> { using type = int4v; };   // (integer values: the generalized merge kind)
 template <> struct Vec4<PatternOnes> { using type = PatternOnes; };   // (a pattern matrix: nothing to hold)
 
+// 16-bit matrix values under fp32 vectors (MI355_VAL_F16 / MI355_VAL_BF16, kind VECTOR: csr_vector_h16.hip).  The chunk
+// bodies take the stored type as a trailing mat_t (= val_t everywhere else): a group of four is then ONE 8-byte load,
+// held as loaded and widened to four values of val_t where it is consumed; the arithmetic is val_t's.  (Bf16: common.hpp)
+typedef _Float16 half4v __attribute__((ext_vector_type(4)));
+template <> struct Vec4<_Float16> { using type = uint2v; };      // (four of them as loaded)
+template <> struct Vec4<Bf16> { using type = uint2v; };
+
+// one stored value as a val_t: the hardware convert for fp16, a shift for bf16 (both exact)
+template <typename val_t, typename mat_t>
+__device__ __forceinline__ val_t mat_val(mat_t a) {
+    if constexpr (std::is_same<mat_t, Bf16>::value) return __uint_as_float(unsigned(a.bits) << 16);
+    else return val_t(a);
+}
+// ... and a loaded group of four
+template <typename val_t, typename mat_t>
+__device__ __forceinline__ typename Vec4<val_t>::type widen4(const typename Vec4<mat_t>::type& a) {
+    if constexpr (std::is_same<mat_t, val_t>::value) {
+        return a;
+    } else if constexpr (std::is_same<mat_t, _Float16>::value) {
+        return __builtin_convertvector(__builtin_bit_cast(half4v, a), float4v);
+    } else {
+        static_assert(std::is_same<mat_t, Bf16>::value && std::is_same<val_t, float>::value, "no such matrix type");
+        return float4v{__uint_as_float(a[0] << 16), __uint_as_float(a[0] & 0xFFFF0000u), __uint_as_float(a[1] << 16),
+                       __uint_as_float(a[1] & 0xFFFF0000u)};
+    }
+}
+
 // Aj / Ax are read exactly once per SpMV: stream them past the caches (nontemporal) so
 // that the lines of x, which ARE re-used, stay resident.  Measured on the two-stream
 // read pattern of the kernels: 6.9 TB/s nontemporal vs 6.15 TB/s plain.
@@ -44,11 +73,11 @@ __device__ __forceinline__ V stream_load(const V* p) {
 
 // 4-byte-per-lane partial sum of lane `lane` (0..T-1) of the vector that owns [start, end):
 // the reference's form, used only when Aj/Ax/x are not 16-byte aligned.
-template <int T, typename off_t, typename val_t>
+template <int T, typename off_t, typename val_t, typename mat_t = val_t>
 __device__ __forceinline__ val_t row_partial(off_t start, off_t end, int lane, const int32_t* __restrict__ Aj,
-                                             const val_t* __restrict__ Ax, const val_t* __restrict__ x) {
+                                             const mat_t* __restrict__ Ax, const val_t* __restrict__ x) {
     val_t sum = val_t(0);
-    for (off_t j = start + lane; j < end; j += T) sum += Ax[j] * x[Aj[j]];
+    for (off_t j = start + lane; j < end; j += T) sum += mat_val<val_t>(Ax[j]) * x[Aj[j]];
     return sum;
 }
 

@@ -30,11 +30,11 @@ static int with_lanes(const Plan& p, const char* kind, F&& f) {
 }
 
 // what every launch of a chunked kernel of a plan passes
-template <typename val_t>
+template <typename val_t, typename mat_t = val_t>   // (mat_t: the type Ax is stored in, xwindow.hpp chunk_rows)
 struct RowOperands {
     const Plan& p;
     ApView Ap;
-    const val_t* Ax;
+    const mat_t* Ax;
     const val_t* x;
     val_t* y;
     hipStream_t s;
@@ -43,8 +43,8 @@ struct RowOperands {
 
 // One launch of a chunked kernel on the plan's grid (LIGHT's kernels take the counters after y).  A launch that asks for
 // more than the default 64 KB of LDS raises the kernel's limit first.
-template <typename Kind, typename val_t, typename K, typename... Tail>
-static int launch_chunked(K kernel, int threads, const RowOperands<val_t>& o, const ChunkMap& cmap, const BandHint& hint,
+template <typename Kind, typename val_t, typename K, typename mat_t, typename... Tail>
+static int launch_chunked(K kernel, int threads, const RowOperands<val_t, mat_t>& o, const ChunkMap& cmap, const BandHint& hint,
                           Tail... tail) {
     const Plan& p = o.p;
     if (const int st = allow_dynamic_lds((const void*)kernel, o.lds)) return st;

@@ -656,6 +656,23 @@ int shape_rows(Plan& p, ProbeSamples& probe, GiantRowList& giants) {
     return MI355_SPMV_OK;
 }
 
+// A VECTOR plan whose matrix is stored in 16 bits (capi.hip, plan_create_typed) keeps the fp32 plan's shape, but the
+// 16-bit chunked kernels exist only for equal-row chunks with one window of x or none (csr_vector_h16.hip).  Every
+// other shape — weight-cut chunks (with their giant rows), several bands, the swept window, a small matrix — runs the
+// plain one-pass kernel with the shape's lanes per row, and the plan's report says so; the shape itself
+// (export_rows_shape) stays the fp32 plan's.
+bool half_matrix_chunked(const Plan& p) {
+    return !p.small_plain && !p.sweep && !p.balanced && p.n_seg < 2 && p.n_giant == 0;
+}
+
+void set_half_matrix_launch(Plan& p) {
+    if (half_matrix_chunked(p)) return;
+    const int64_t rows_per_block = kBlock / p.lanes_per_row;
+    p.grid_blocks = (int64_t(p.n_rows) + rows_per_block - 1) / rows_per_block;
+    p.n_kernels = 1;
+    snprintf(p.main_kernel, sizeof(p.main_kernel), "%s", "csr_vector_kernel");
+}
+
 // ---- a row block's inherited shape: out of the whole plan, into the block's ---------------------------------
 // The two directions side by side: a field added to one belongs in the other.
 void export_rows_shape(const Plan& p, mi355_spmv_plan_shape* sh) {

@@ -382,21 +382,23 @@ __device__ __forceinline__ int64_t stage_chunk_bounds(const ChunkScratch<val_t>&
     return base;
 }
 
-// One step of 4 nonzeros of one lane: Aj/Ax group at j (16-byte aligned element index).
-template <typename val_t>
+// One step of 4 nonzeros of one lane: Aj/Ax group at j (16-byte aligned element index; a 16-bit mat_t: 8 bytes of Ax).
+template <typename val_t, typename mat_t = val_t>
 __device__ __forceinline__ void load_group(int32_t j, int32_t nnz, const int32_t* __restrict__ Aj,
-                                           const val_t* __restrict__ Ax, int4v& c,
-                                           typename Vec4<val_t>::type& a) {
-    using v4 = typename Vec4<val_t>::type;
+                                           const mat_t* __restrict__ Ax, int4v& c,
+                                           typename Vec4<mat_t>::type& a) {
+    using m4 = typename Vec4<mat_t>::type;
     if (j + 4 <= nnz) {
         c = stream_load(reinterpret_cast<const int4v*>(Aj + j));
-        a = stream_load(reinterpret_cast<const v4*>(Ax + j));
+        a = stream_load(reinterpret_cast<const m4*>(Ax + j));
     } else {   // last, partial group of the arrays: never read past nnz
+        if constexpr (sizeof(mat_t) == 2) a = m4{0u, 0u};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const bool in = (j + e) < nnz;
             c[e] = in ? Aj[j + e] : 0;
-            a[e] = in ? Ax[j + e] : val_t(0);
+            if constexpr (sizeof(mat_t) == 2) a[e >> 1] |= (in ? unsigned(__builtin_bit_cast(uint16_t, Ax[j + e])) : 0u) << (16 * (e & 1));
+            else a[e] = in ? Ax[j + e] : val_t(0);
         }
     }
 }
@@ -460,15 +462,19 @@ __device__ __forceinline__ void store_chunk_results(const ChunkScratch<val_t>& s
 // Aj[k] INSIDE the window of the chunk that owns element k, kPackedEscape when the column is outside it.  The
 // pipelined loop streams 8 bytes of Aj16 per group of four instead of 16 bytes of Aj; Aj itself is read only for an
 // escaped element, in the long-row passes and for the arrays' last, partial group.  Same arithmetic in the same order.
-template <int BLOCK, int T, int R, bool WINDOW, typename val_t, bool PACKED = false, typename StageFn>
+// mat_t (deduced from Ax; = val_t but for the 16-bit matrix types of row_dot.hpp): the type Ax is stored in.  A group's
+// values are held as loaded (m4) and widened to val_t where they are consumed; addresses, masks, the order of a row's
+// additions and the pipeline are the same for every mat_t.
+template <int BLOCK, int T, int R, bool WINDOW, typename val_t, bool PACKED = false, typename StageFn, typename mat_t = val_t>
 __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_end, int32_t nnz,
                                            const int32_t* __restrict__ Aj,
-                                           const val_t* __restrict__ Ax, const val_t* __restrict__ x,
+                                           const mat_t* __restrict__ Ax, const val_t* __restrict__ x,
                                            val_t* __restrict__ y, StageFn&& stage,
                                            const ChunkScratch<val_t>& scr,
                                            const uint16_t* __restrict__ Aj16 = nullptr) {
     static_assert(!PACKED || WINDOW, "a packed index is window-relative");
     using v4 = typename Vec4<val_t>::type;
+    using m4 = typename Vec4<mat_t>::type;                 // four values as a group is loaded
     using col4 = typename std::conditional<PACKED, uint2v, int4v>::type;   // four columns as a group is loaded
     using off_t = int32_t;                                 // chunk-relative offsets
     constexpr int VECS = BLOCK / T;
@@ -500,7 +506,7 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
     // set that the wide fp32 bodies, held to 128, do not have (they spilled).
     struct Group {
         col4 c[R];
-        v4 a[R];
+        m4 a[R];
     };
     auto load_cols = [&](off_t jl) {
         if constexpr (PACKED) return stream_load(reinterpret_cast<const uint2v*>(Aj16 + jl));
@@ -527,7 +533,7 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
             jl = jl < j_max ? jl : j_max;
             // straight-line, branch-free: hipcc serialises (vmcnt(0)) around loads in branches
             G.c[r] = load_cols(jl);
-            G.a[r] = stream_load(reinterpret_cast<const v4*>(Ax + jl));
+            G.a[r] = stream_load(reinterpret_cast<const m4*>(Ax + jl));
         }
         // (nothing of the consume that follows may be scheduled above these loads: its first instructions wait for the
         // PREVIOUS group's data, and a load issued behind that wait has lost its head start — seen as s_waitcnt vmcnt(6)
@@ -621,12 +627,12 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
             }
         }
     };
-    auto accumulate = [&](val_t& sum, const auto& c, const v4& a, off_t j, off_t lo, off_t hi) {
+    auto accumulate = [&](val_t& sum, const auto& c, const m4& a, off_t j, off_t lo, off_t hi) {
         val_t xv[4];
         bool in[4];
         gather4(c, xv, in);
         pin4(xv);
-        fold4(sum, c, a, xv, in, j, lo, hi);
+        fold4(sum, c, widen4<val_t, mat_t>(a), xv, in, j, lo, hi);
     };
     auto consume = [&](int g, const Group& G) {
         Bounds B;
@@ -659,20 +665,20 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
             for (int b = 0; b < XB; ++b) {
                 const int r = r0 + b;
                 const off_t j0 = step0(B.lo[r]);
-                fold4(sum[r], G.c[r], G.a[r], xv[b], in[b], j0, B.lo[r], hi[r]);
+                fold4(sum[r], G.c[r], widen4<val_t, mat_t>(G.a[r]), xv[b], in[b], j0, B.lo[r], hi[r]);
                 jn[r] = j0 + off_t(T) * 4;
                 more |= jn[r] < hi[r];
             }
         }
         while (more) {                                     // rows longer than one step (4T nonzeros)
             col4 c2[R];
-            v4 a2[R];
+            m4 a2[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 off_t jl = jn[r] < hi[r] ? jn[r] : (B.lo[r] & ~off_t(3));
                 jl = jl < j_max ? jl : j_max;
                 c2[r] = load_cols(jl);
-                a2[r] = stream_load(reinterpret_cast<const v4*>(Ax + jl));
+                a2[r] = stream_load(reinterpret_cast<const m4*>(Ax + jl));
             }
             more = false;
 #pragma unroll
@@ -697,7 +703,7 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
                 }
                 if (B.hi[r] > nnz_vec) {                   // the last (partial) group of the arrays
                     for (off_t k = (B.lo[r] > nnz_vec ? B.lo[r] : nnz_vec); k < B.hi[r]; ++k)
-                        sum[r] += Ax[k] * x[Aj[k]];
+                        sum[r] += mat_val<val_t>(Ax[k]) * x[Aj[k]];
                 }
                 scr.s_y[row] = sum[r];
             }
@@ -746,11 +752,11 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
             val_t sum = val_t(0);
             for (off_t j = (start & ~off_t(3)) + off_t(lane64) * 4; j < end; j += off_t(kWave) * 8) {
                 int4v c0, c1;
-                v4 a0, a1;
+                m4 a0, a1;
                 const off_t j1 = j + off_t(kWave) * 4;
                 load_group<val_t>(j, nnz, Aj, Ax, c0, a0);
                 if (j1 < end) load_group<val_t>(j1, nnz, Aj, Ax, c1, a1);
-                else { c1 = int4v{0, 0, 0, 0}; a1 = v4{0, 0, 0, 0}; }
+                else { c1 = int4v{0, 0, 0, 0}; a1 = m4{}; }
                 accumulate(sum, c0, a0, j, start, end);
                 accumulate(sum, c1, a1, j1, start, end);
             }
@@ -782,7 +788,7 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
                 constexpr int64_t SLAB = int64_t(BLOCK) * 4;                    // (64-bit: the steps may pass 2^31)
                 const off_t hi_v = end < nnz_vec ? end : nnz_vec;
                 const off_t first = start & ~off_t(3);
-                struct Slabs { int4v c[R]; v4 a[R]; };
+                struct Slabs { int4v c[R]; m4 a[R]; };
                 auto issue_slabs = [&](int64_t it, Slabs& S) {
 #pragma unroll
                     for (int u = 0; u < R; ++u) {
@@ -790,7 +796,7 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
                         off_t jl = j < int64_t(hi_v) ? off_t(j) : first;
                         jl = jl < j_max ? jl : j_max;
                         S.c[u] = stream_load(reinterpret_cast<const int4v*>(Aj + jl));
-                        S.a[u] = stream_load(reinterpret_cast<const v4*>(Ax + jl));
+                        S.a[u] = stream_load(reinterpret_cast<const m4*>(Ax + jl));
                     }
                 };
                 auto eat_slabs = [&](int64_t it, const Slabs& S) {
@@ -811,7 +817,7 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
                     }
                 }
                 if (tid2 == 0 && end > nnz_vec)                                  // the arrays' last, partial group
-                    for (off_t k = (start > nnz_vec ? start : nnz_vec); k < end; ++k) sum += Ax[k] * x[Aj[k]];
+                    for (off_t k = (start > nnz_vec ? start : nnz_vec); k < end; ++k) sum += mat_val<val_t>(Ax[k]) * x[Aj[k]];
                 sum = vector_reduce<kWave, val_t>(sum);
                 if (lane64 == 0) s_part[wave] = sum;
                 __syncthreads();
@@ -838,10 +844,10 @@ __device__ __forceinline__ void chunk_rows(int64_t chunk_begin, int64_t chunk_en
 // 64 / 128 nonzeros) — a second, dependent step per row costs such a matrix more than idle lanes do (rows of 64 +- 16 with 8
 // lanes: three steps, 740 us; with 32 lanes: see merge_plan.hip).
 template <int BLOCK, int T, int R, bool WINDOW, bool ADAPT, typename val_t, typename StageFn, bool REGULAR = false,
-          bool PACKED = false>
+          bool PACKED = false, typename mat_t = val_t>
 __device__ __forceinline__ void chunk_rows_any(int64_t chunk_begin, int64_t chunk_end, int32_t nnz,
                                                const int32_t* __restrict__ Aj,
-                                               const val_t* __restrict__ Ax, const val_t* __restrict__ x,
+                                               const mat_t* __restrict__ Ax, const val_t* __restrict__ x,
                                                val_t* __restrict__ y, StageFn&& stage,
                                                const ChunkScratch<val_t>& scr,
                                                const uint16_t* __restrict__ Aj16 = nullptr) {
@@ -1046,9 +1052,9 @@ __device__ __forceinline__ void chunk_rows_sweep(int64_t chunk_begin, int64_t ch
 // A chunk whose nonzeros span more than the 32-bit path can index (see kRel32Limit): one wave per row,
 // 4-byte loads, 64-bit indices, results straight to y.  Slow, and only ever reached by matrices with rows
 // of ~10^9 nonzeros; summation order = the fallback kernels' (row_dot.hpp).
-template <int BLOCK, typename val_t>
+template <int BLOCK, typename val_t, typename mat_t = val_t>
 __device__ __forceinline__ void chunk_rows_wide(int64_t chunk_begin, int64_t chunk_end, const ApView Ap,
-                                                const int32_t* __restrict__ Aj, const val_t* __restrict__ Ax,
+                                                const int32_t* __restrict__ Aj, const mat_t* __restrict__ Ax,
                                                 const val_t* __restrict__ x, val_t* __restrict__ y, val_t alpha,
                                                 val_t beta, int64_t giant_len) {
     const int lane64 = threadIdx.x & (kWave - 1);
@@ -1056,7 +1062,7 @@ __device__ __forceinline__ void chunk_rows_wide(int64_t chunk_begin, int64_t chu
         const int64_t start = Ap.at(row), end = Ap.at(row + 1);
         val_t sum = val_t(0);
         if (!(giant_len > 0 && end - start > giant_len))           // (a giant row: 0 here, the slice kernels add it)
-            for (int64_t k = start + lane64; k < end; k += kWave) sum += Ax[k] * x[Aj[k]];
+            for (int64_t k = start + lane64; k < end; k += kWave) sum += mat_val<val_t>(Ax[k]) * x[Aj[k]];
         sum = vector_reduce<kWave, val_t>(sum);
         if (lane64 == 0) y[row] = (beta != val_t(0)) ? alpha * sum + beta * y[row] : alpha * sum;
     }
