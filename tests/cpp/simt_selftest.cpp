@@ -1,0 +1,60 @@
+// simt_selftest — TEST CODE.  What tests/cpp/simt/hip/hip_runtime.h promises, on kernels of a few lines: the host
+// execution of csrc/multi.hip (multi_sim.cpp) means what it says only while these hold.
+//   simt_selftest semantics   shuffles, ballot, barrier, __shared__, block order, the hipMalloc fill: exit status 0
+//   simt_selftest returned    a lane returns while the others of its wave wait in a collective: exit status 3
+//   simt_selftest kind        one lane calls another collective than the others:                exit status 3
+//   simt_selftest size        one lane's operand has another size:                              exit status 3
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+__global__ void semantics(int* ok, int* order) {
+    __shared__ int total[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x / 64;
+    bool good = true;
+    for (unsigned d = 0; d < 64; d = d ? d * 2 : 1)         // __shfl_up: the lane's own value where lane < d
+        good = good && __shfl_up(lane + 100, d) == (unsigned(lane) < d ? lane + 100 : lane + 100 - int(d));
+    good = good && __shfl(lane, 64 + 3) == 3 && __shfl(lane, 63) == 63 && __shfl(lane, -1) == 63;   // src & 63
+    good = good && __shfl_xor(lane, 8) == (lane ^ 8) && __shfl_xor(double(lane), 1) == double(lane ^ 1);
+    good = good && __shfl(int64_t(lane) << 40, 5) == int64_t(5) << 40 && __shfl(float(lane) / 4, 9) == 2.25f;
+    good = good && __ballot(lane & 1) == 0xAAAAAAAAAAAAAAAAull && __ballot(lane == 63) == 1ull << 63 && __ballot(0) == 0;
+    good = good && __clzll(0) == 64 && __clzll(1) == 63;
+    if (lane == 0) total[wave] = int(blockIdx.x) * 10 + wave;
+    __syncthreads();                                        // the waves of a block meet here, and only here
+    for (int w = 0; w < 4; ++w) good = good && total[w] == int(blockIdx.x) * 10 + w;
+    ok[blockIdx.x * blockDim.x + threadIdx.x] = good;
+    if (threadIdx.x == 0) order[blockIdx.x] = order[gridDim.x]++;      // blocks run one after another, in order
+}
+
+__global__ void out_of_step(int mode) {
+    const int lane = threadIdx.x & 63;
+    if (lane == 7) {
+        if (mode == 0) return;
+        if (mode == 1) { __ballot(1); return; }
+        if (mode == 2) { __shfl(double(lane), 0); return; }
+    }
+    __shfl(lane, 0);
+}
+
+int main(int argc, char** argv) {
+    const char* what = argc > 1 ? argv[1] : "";
+    if (!strcmp(what, "semantics")) {
+        unsigned char* fill = nullptr;
+        if (hipMalloc(&fill, 300) != hipSuccess) return 1;
+        for (int i = 0; i < 300; ++i)
+            if (fill[i] != 0x5A) { fprintf(stderr, "hipMalloc: byte %d is not 0x5A\n", i); return 1; }
+        if (reinterpret_cast<uintptr_t>(fill) % 256) { fprintf(stderr, "hipMalloc: not 256-byte aligned\n"); return 1; }
+        hipFree(fill);
+        static int ok[3 * 256], order[3 + 1];
+        hipLaunchKernelGGL(semantics, dim3(3), dim3(256), 0, nullptr, ok, order);
+        for (int i = 0; i < 3 * 256; ++i)
+            if (!ok[i]) { fprintf(stderr, "a collective's result is wrong in thread %d\n", i); return 1; }
+        for (int b = 0; b < 3; ++b)
+            if (order[b] != b) { fprintf(stderr, "block %d ran out of order\n", b); return 1; }
+        return alignof(float4) == 16 && alignof(double2) == 16 ? 0 : 1;
+    }
+    const int mode = !strcmp(what, "returned") ? 0 : !strcmp(what, "kind") ? 1 : !strcmp(what, "size") ? 2 : -1;
+    if (mode < 0) { fprintf(stderr, "usage: simt_selftest semantics | returned | kind | size\n"); return 2; }
+    hipLaunchKernelGGL(out_of_step, dim3(1), dim3(128), 0, nullptr, mode);
+    return 0;   // not reached: the stand-in ends the program with status 3
+}

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import multi_cases as mc
 from conftest import parity_bound, random_csr
 
 pytestmark = pytest.mark.gpu
@@ -323,3 +324,48 @@ def test_info_and_device_side_refusals(sp, plans):
     assert lib.mi355_spmv_multi_execute(p._h, ptr(dAx), None, 4, ptr(Yd), 4, 4, None) == 1
     assert lib.mi355_spmv_multi_execute(p._h, ptr(dAx), ptr(Xd), 4, None, 4, 4, None) == 1
     assert lib.mi355_spmv_multi_execute(p._h, ptr(dAx), ptr(Xd), 3, ptr(Yd), 4, 4, None) == 1  # ldx < k
+
+
+# ---- the table of tests/multi_cases.py: the cases that tests/test_multi_sim_cpu.py executes on the host, on the device ----
+def on_device(flat, shift):
+    """1-D device copy of `flat` whose base lies `shift` elements past a 16-byte boundary (an empty one has no base)."""
+    t = torch.from_numpy(np.ascontiguousarray(flat))
+    es = t.element_size()
+    buf = torch.empty(t.numel() + 16 // es + 1, dtype=t.dtype, device=DEV)
+    base = ((16 - buf.data_ptr() % 16) % 16) // es + shift
+    v = buf[base:base + t.numel()]
+    v.copy_(t)
+    assert t.numel() == 0 or v.data_ptr() % 16 == shift * es
+    return v
+
+
+@pytest.mark.parametrize("family", mc.FAMILIES)
+def test_table(sp, oracle, family):
+    """Every case of the family: plans are made per (structure, types, matrix offsets, k_max) and reused over k,
+    alpha / beta, leading dimensions and the offsets of X and Y.  No case is skipped."""
+    cases = mc.family(family)
+    assert cases
+    key, plan, dAx = None, None, None
+    try:
+        for c in cases:
+            Ap, Aj, Ax, X, Y0 = mc.arrays(c.matrix, c.off, c.val, c.integer)
+            n_rows, n_cols = len(c.matrix.lens), c.matrix.n_cols
+            if mc.plan_key(c) != key:
+                if plan is not None:
+                    plan.destroy()
+                    plan = None
+                key = mc.plan_key(c)
+                dAp, dAj, dAx = on_device(Ap, c.shift[0]), on_device(Aj, c.shift[1]), on_device(Ax, c.shift[2])
+                plan = sp.MultiPlan(n_rows, n_cols, int(Ap[-1]), dAp, dAj, dAx.dtype, c.k_max)
+                mc.assert_geometry(plan.info(), c.val)
+            xh = np.full((n_cols, c.ldx), np.nan, dtype=X.dtype)
+            xh[:, :c.k] = X[:, c.c0:c.c0 + c.k]
+            yh = np.full((n_rows, c.ldy), mc.CANARY, dtype=X.dtype)
+            yh[:, :c.k] = Y0[:, c.c0:c.c0 + c.k] if c.beta != 0.0 else np.nan
+            xf, yf = on_device(xh.ravel(), c.shift[3]), on_device(yh.ravel(), c.shift[4])
+            plan.set_alpha_beta(c.alpha, c.beta)
+            plan.execute(dAx, torch.as_strided(xf, (n_cols, c.k), (c.ldx, 1)), torch.as_strided(yf, (n_rows, c.k), (c.ldy, 1)))
+            mc.check(oracle, c, yf.cpu().numpy())       # (the copy synchronises)
+    finally:
+        if plan is not None:
+            plan.destroy()
