@@ -43,6 +43,7 @@ extern "C" {
  * pattern entry points from one that has not — test this macro, or look the symbols up.                          */
 #define MI355_SPMV_HAS_PATTERN 1 /* MI355_VAL_PATTERN, mi355_spmv_merge_pattern_*, mi355_spmv_plan_get_mat_type */
 #define MI355_SPMV_HAS_MULTI 1   /* mi355_spmv_multi_*: Y = A X for k vectors in one pass over A */
+#define MI355_SPMV_HAS_MULTI_SEMIRING 1 /* mi355_spmv_multi_create_typed / _set_semiring / _get_types / _genl_* / _pattern_* */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -533,8 +534,10 @@ int mi355_spmv_functor_destroy(mi355_spmv_functor* functor);
  * Elements j >= k of a row of X are never read, of a row of Y never written; with beta = 0 (the default; alpha = 1)
  * Y is never read.  Rows of X / Y are accessed 16 bytes per lane when the pointer and ld * sizeof(value) are 16-byte
  * aligned, else element by element.
- * Types: {I32, I64} offsets x {F32, F64} values, the (+, *) semiring; MI355_VAL_I32 / MI355_VAL_PATTERN return
- * MI355_SPMV_ENOTSUP.  Column-major X, mixed precision and the dist_* entry points are not built.
+ * Types: mi355_spmv_multi_create makes {I32, I64} offsets x {F32, F64} values under the (+, *) semiring and returns
+ * MI355_SPMV_ENOTSUP for MI355_VAL_I32 / MI355_VAL_PATTERN; semirings, int32 values and pattern matrices come from
+ * mi355_spmv_multi_create_typed below.  Column-major X, mixed precision and the dist_* entry points are not built
+ * (DESIGN.md 3.10).
  * The work is cut by NONZEROS: a wave owns a slice of slice_len merge items (row ends + nonzeros), so empty rows and
  * hub rows cost what they hold; a row that crosses slices leaves carries in scratch (sized for k_max at create), and
  * a fix-up kernel adds them in slice order — no float atomics: two executes on the same inputs give the same bits.
@@ -572,6 +575,59 @@ int mi355_spmv_multi_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const 
                             const float* Ax, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
 int mi355_spmv_multi_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
                             const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
+
+/* ---- multi-vector SpMV over a semiring, int32 values and pattern matrices (MI355_SPMV_HAS_MULTI_SEMIRING) ----------
+ * For callers with k vectors and a graph: multi-source BFS / reachability ((or, and) on a pattern matrix), batched
+ * SSSP and hop counts ((min, +)), batched Viterbi and widest path ((max, +), (max, *)), integer counting ((+, *) on
+ * int32) — one pass over A instead of k executes of a MERGE plan.
+ *   Y[r, j] = reduce over the nonzeros n of row r of combine(Ax[n], X[Aj[n], j])      for j < k
+ * with (reduce, combine) of MI355_SEMIRING_*; under a PATTERN matrix Ax[n] is one (in the type of X and Y) and Ax is
+ * never read.  An empty row gets the identity of reduce: 0 ((+, *), (or, and)), +inf ((min, +)), -inf ((max, *),
+ * (max, +)); INT32_MAX / INT32_MIN for int32.  Every element j < k of every row is written; elements j >= k are never
+ * touched.  Y is read only under (+, *) with beta != 0.  int32 arithmetic wraps.  No atomics: two executes on the same
+ * inputs give the same bits.  (or, and) takes any non-zero as true and writes 0 / 1.
+ *   create_typed   vec_type (the type of X, Y and of all arithmetic) in {F32, F64, I32}; mat_type = vec_type or
+ *                  MI355_VAL_PATTERN.  PATTERN / F16 / BF16 as vec_type: MI355_SPMV_EINVAL; any other mix (an fp32
+ *                  matrix under fp64 vectors, F16 / BF16 matrices): MI355_SPMV_ENOTSUP.  Everything else as
+ *                  mi355_spmv_multi_create; mi355_spmv_multi_get_info reports vec_type as val_type.
+ *   set_semiring   for the following executes (default MI355_SEMIRING_PLUS_TIMES); nothing is re-sized.  alpha / beta
+ *                  exist for (+, *) on F32 / F64 only, as with plan_set_semiring / plan_set_alpha_beta: a semiring
+ *                  other than PLUS_TIMES while alpha / beta != 1 / 0, or set_alpha_beta to anything but 1 / 0 under
+ *                  such a semiring or on an I32 object, is MI355_SPMV_ENOTSUP; an unknown semiring is EINVAL.
+ *   execute        of a PATTERN object ignores Ax (it may be NULL).
+ * Out of scope: harness labels (the reference's operator has one x), dist_*, mixed precision, column-major X, and
+ * caller-text functors (mi355_spmv_functor_*) on the multi path.                                                   */
+int mi355_spmv_multi_create_typed(mi355_spmv_multi** out, int off_type, int mat_type, int vec_type, int32_t n_rows,
+                                  int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj, int32_t k_max);
+int mi355_spmv_multi_set_semiring(mi355_spmv_multi* multi, int semiring);
+/* Any of the three pointers may be NULL.                                                                         */
+int mi355_spmv_multi_get_types(const mi355_spmv_multi* multi, int* mat_type, int* vec_type, int* semiring);
+/* One-shots under a semiring: create_typed (k_max = k), set_semiring, execute, synchronise the stream, destroy;
+ * mi355_spmv_multi_pattern_* take the same arguments without Ax.  Argument errors are refused before any device call. */
+int mi355_spmv_multi_genl_i32_f32(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const float* Ax, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_genl_i32_f64(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_genl_i32_i32(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const int32_t* Ax, const int32_t* X, int64_t ldx, int32_t* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_genl_i64_f32(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const float* Ax, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_genl_i64_f64(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_genl_i64_i32(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const int32_t* Ax, const int32_t* X, int64_t ldx, int32_t* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_pattern_i32_f32(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_pattern_i32_f64(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_pattern_i32_i32(int semiring, int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const int32_t* X, int64_t ldx, int32_t* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_pattern_i64_f32(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_pattern_i64_f64(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_pattern_i64_i32(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const int32_t* X, int64_t ldx, int32_t* Y, int64_t ldy, int32_t k, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

@@ -50,6 +50,8 @@ EXPORTS = (
     + ["mi355_spmv_plan_get_mat_type", "mi355_spmv_narrow_values"]
     + ["mi355_spmv_multi_" + n for n in ("create", "set_alpha_beta", "execute", "get_info", "destroy")]
     + ["mi355_spmv_multi_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
+    + ["mi355_spmv_multi_" + n for n in ("create_typed", "set_semiring", "get_types")]
+    + ["mi355_spmv_multi_%s_%s_%s" % (g, o, v) for g in ("genl", "pattern") for o in ("i32", "i64") for v in ("f32", "f64", "i32")]
 )
 
 
@@ -177,6 +179,18 @@ def lib():
             for v in ("f32", "f64"):
                 getattr(L, "mi355_spmv_multi_%s_%s" % (o, v)).argtypes = [
                     C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                    C.c_int64, C.c_int32, C.c_void_p]
+        L.mi355_spmv_multi_create_typed.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32,
+                                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
+        L.mi355_spmv_multi_set_semiring.argtypes = [C.c_void_p, C.c_int]
+        L.mi355_spmv_multi_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
+            for v in ("f32", "f64", "i32"):
+                getattr(L, "mi355_spmv_multi_genl_%s_%s" % (o, v)).argtypes = [
+                    C.c_int, C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                    C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+                getattr(L, "mi355_spmv_multi_pattern_%s_%s" % (o, v)).argtypes = [
+                    C.c_int, C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int64, C.c_int32, C.c_void_p]
         _lib = L
     return _lib
@@ -582,45 +596,85 @@ def _require_matrix(t, name, rows, dtype):
     return ld
 
 
-class MultiPlan:
-    """mi355_spmv_multi_*: Y = alpha * A X + beta * Y for up to k_max vectors in one pass over A.  X (n_cols x k) and
-    Y (n_rows x k) are 2-D row-major device tensors; views with a larger stride(0) are taken as they are.  Holds
-    references to Ap and Aj so they outlive the object."""
+def _semiring_id(semiring):
+    return SEMIRINGS[semiring] if isinstance(semiring, str) else int(semiring)
 
-    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max):
+
+class MultiPlan:
+    """mi355_spmv_multi_*: Y = A X for up to k_max vectors in one pass over A — Y = alpha * A X + beta * Y under (+, *),
+    Y[r, j] = reduce over the row of combine(Ax, X[Aj, j]) under another semiring (set_semiring, or semiring=).  X
+    (n_cols x k) and Y (n_rows x k) are 2-D row-major device tensors; views with a larger stride(0) are taken as they
+    are.  val_dtype (the type of X, Y and all arithmetic) is float32, float64 or int32; mat_dtype="pattern" makes a
+    matrix without values (every entry one): execute then takes Ax=None.  int32 needs one of mat_dtype=torch.int32,
+    mat_dtype="pattern" or a semiring other than "plus_times" spelled out: MultiPlan(..., torch.int32, k_max) alone is
+    refused, as it was before int32 existed here.  Holds references to Ap and Aj so they outlive the object."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, mat_dtype=None, semiring="plus_times"):
         _require_device(Ap, Aj)
         if Aj.dtype != torch.int32:
             raise TypeError("Aj must be int32")
-        if val_dtype not in (torch.float32, torch.float64):
-            raise TypeError("val_dtype must be float32 or float64")
+        pattern = isinstance(mat_dtype, str) and mat_dtype == "pattern"
+        if mat_dtype is not None and not pattern and mat_dtype != val_dtype:
+            raise TypeError('mat_dtype must be val_dtype or "pattern" (mixed precision is not built on the multi path)')
+        sr = _semiring_id(semiring)
+        typed = pattern or sr != 0 or val_dtype == torch.int32 and mat_dtype is not None
+        if val_dtype not in (torch.float32, torch.float64) and not (typed and val_dtype == torch.int32):
+            raise TypeError("val_dtype must be float32 or float64"
+                            " (or int32 under a semiring, a pattern matrix or mat_dtype=torch.int32)")
         self.n_rows, self.n_cols, self.nnz, self.k_max = n_rows, n_cols, nnz, k_max
-        self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
+        self.Ap, self.Aj, self.val_dtype, self.pattern = Ap, Aj, val_dtype, pattern
         self._h = C.c_void_p()
         with torch.cuda.device(Ap.device):
-            st = lib().mi355_spmv_multi_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows,
-                                               n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), k_max)
-        _check(st, "mi355_spmv_multi_create")
+            if typed:
+                what = "mi355_spmv_multi_create_typed"
+                st = lib().mi355_spmv_multi_create_typed(
+                    C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_PATTERN if pattern else VAL_TYPES[val_dtype][0],
+                    VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), k_max)
+            else:       # plain fp32 / fp64 (+, *) objects
+                what = "mi355_spmv_multi_create"
+                st = lib().mi355_spmv_multi_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows,
+                                                   n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), k_max)
+        _check(st, what)
+        if sr != 0:
+            self.set_semiring(sr)
 
     def execute(self, Ax, X, Y, stream=None):
-        """Asynchronous on `stream` (default: torch's current stream).  k = X.size(1) = Y.size(1)."""
-        _require_device(Ax)
-        if Ax.dtype != self.val_dtype:
-            raise TypeError("value type differs from the plan's")
-        if Ax.numel() < self.nnz:
-            raise ValueError("operand shorter than the plan's sizes")
+        """Asynchronous on `stream` (default: torch's current stream).  k = X.size(1) = Y.size(1).  Ax is None for a
+        pattern plan (one that is given is ignored)."""
+        if getattr(self, "pattern", False):
+            Ax = None       # ignored: never checked, never passed on
+        elif Ax is None:
+            raise TypeError("Ax is None: only a pattern plan has no values")
+        else:
+            _require_device(Ax)
+            if Ax.dtype != self.val_dtype:
+                raise TypeError("value type differs from the plan's")
+            if Ax.numel() < self.nnz:
+                raise ValueError("operand shorter than the plan's sizes")
         ldx = _require_matrix(X, "X", self.n_cols, self.val_dtype)
         ldy = _require_matrix(Y, "Y", self.n_rows, self.val_dtype)
         if X.size(1) != Y.size(1):
             raise ValueError("X and Y hold different numbers of vectors")
-        st = lib().mi355_spmv_multi_execute(self._h, C.c_void_p(Ax.data_ptr()), C.c_void_p(X.data_ptr()), ldx,
-                                            C.c_void_p(Y.data_ptr()), ldy, X.size(1), _stream_ptr(stream))
+        st = lib().mi355_spmv_multi_execute(self._h, C.c_void_p(Ax.data_ptr()) if Ax is not None else None,
+                                            C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, X.size(1),
+                                            _stream_ptr(stream))
         _check(st, "mi355_spmv_multi_execute")
         return Y
 
     def set_alpha_beta(self, alpha, beta):
-        """Y = alpha * A X + beta * Y for the following executes (default 1, 0)."""
+        """Y = alpha * A X + beta * Y for the following executes (default 1, 0); (+, *) on float types only."""
         _check(lib().mi355_spmv_multi_set_alpha_beta(self._h, C.c_double(alpha), C.c_double(beta)),
                "mi355_spmv_multi_set_alpha_beta")
+
+    def set_semiring(self, semiring):
+        """The semiring of the following executes: a name of SEMIRINGS or its number."""
+        _check(lib().mi355_spmv_multi_set_semiring(self._h, C.c_int(_semiring_id(semiring))), "mi355_spmv_multi_set_semiring")
+
+    def types(self):
+        """{"mat_type", "vec_type", "semiring"} as the library holds them (MI355_VAL_*, MI355_SEMIRING_*)."""
+        m, v, s = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().mi355_spmv_multi_get_types(self._h, C.byref(m), C.byref(v), C.byref(s)), "mi355_spmv_multi_get_types")
+        return {"mat_type": m.value, "vec_type": v.value, "semiring": s.value}
 
     def info(self):
         mi = MultiInfo()
@@ -641,14 +695,17 @@ class MultiPlan:
             pass
 
 
-def spmm(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None):
-    """One-shot Y = A X for the k = X.size(1) vectors of a row-major X (mi355_spmv_multi_<off>_<val>): create, execute,
-    synchronise the stream, destroy."""
+def spmm(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None, semiring="plus_times"):
+    """One-shot Y = A X for the k = X.size(1) vectors of a row-major X: create, execute, synchronise the stream,
+    destroy.  (+, *) on float values: mi355_spmv_multi_<off>_<val>; another semiring, or int32 values:
+    mi355_spmv_multi_genl_<off>_<val>."""
     _require_device(Ap, Aj, Ax)
     if Aj.dtype != torch.int32:
         raise TypeError("Aj must be int32")
-    if Ax.dtype not in (torch.float32, torch.float64):
-        raise TypeError("Ax must be float32 or float64")
+    sr = _semiring_id(semiring)
+    genl = sr != 0 or Ax.dtype == torch.int32
+    if Ax.dtype not in ((torch.float32, torch.float64, torch.int32) if genl else (torch.float32, torch.float64)):
+        raise TypeError("Ax must be float32 or float64" + (" or int32" if genl else ""))
     if Ax.numel() < nnz:
         raise ValueError("operand shorter than the matrix")
     ldx = _require_matrix(X, "X", n_cols, Ax.dtype)
@@ -656,11 +713,37 @@ def spmm(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None):
     if X.size(1) != Y.size(1):
         raise ValueError("X and Y hold different numbers of vectors")
     o, v = OFF_TYPES[Ap.dtype][1], VAL_TYPES[Ax.dtype][1]
-    with torch.cuda.device(Ap.device):
-        st = getattr(lib(), "mi355_spmv_multi_%s_%s" % (o, v))(
-            n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), C.c_void_p(Ax.data_ptr()),
+    name = "mi355_spmv_multi_%s%s_%s" % ("genl_" if genl else "", o, v)
+    args = (n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), C.c_void_p(Ax.data_ptr()),
             C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, X.size(1), _stream_ptr(stream))
-    _check(st, "mi355_spmv_multi_%s_%s" % (o, v))
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(*(((sr,) if genl else ()) + args))
+    _check(st, name)
+    return Y
+
+
+def spmm_pattern(semiring, n_rows, n_cols, nnz, Ap, Aj, X, Y, stream=None):
+    """One-shot multi-vector SpMV with a PATTERN matrix — a structure and no values, every entry one
+    (mi355_spmv_multi_pattern_<off>_<val>): the arguments of spmm without Ax, the semiring first as in spmv_pattern."""
+    sr = _semiring_id(semiring)
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if not getattr(X, "is_cuda", False):
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if X.dtype not in VAL_TYPES:
+        raise TypeError("X must be float32, float64 or int32")
+    ldx = _require_matrix(X, "X", n_cols, X.dtype)
+    ldy = _require_matrix(Y, "Y", n_rows, X.dtype)
+    if X.size(1) != Y.size(1):
+        raise ValueError("X and Y hold different numbers of vectors")
+    o, v = OFF_TYPES[Ap.dtype][1], VAL_TYPES[X.dtype][1]
+    name = "mi355_spmv_multi_pattern_%s_%s" % (o, v)
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(sr, n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()),
+                                  C.c_void_p(Aj.data_ptr()), C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy,
+                                  X.size(1), _stream_ptr(stream))
+    _check(st, name)
     return Y
 
 

@@ -1,0 +1,4 @@
+// multi_i32.hip — the int32 instantiations of multi-vector SpMV: launch_multi over both offset widths, the five semirings,
+// valued and pattern matrices (multi_kernels.hpp; see the head of multi.hip).
+#define MI355_MULTI_TU int32_t
+#include "multi.hip"

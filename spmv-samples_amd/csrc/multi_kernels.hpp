@@ -1,0 +1,395 @@
+// multi_kernels.hpp — the device code and the launch of multi-vector SpMV (mi355_spmv_multi_*):
+// Y[r, j] = reduce over the row of combine(Ax[n], X[Aj[n], j]) for k vectors in one pass over A, over a semiring SR
+// (semiring.hpp), a value type in {float, double, int32_t} and a PATTERN flag (no stored values: every entry is one).
+// A header: multi.hip holds the entry points; the multi_*.hip units instantiate launch_multi per value type (under
+// MI355_MULTI_SPLIT_UNITS multi.hip only declares those instantiations; without it a unit that includes this header
+// instantiates what it uses, which is how the host simulation compiles multi.hip alone).
+//
+// X is row-major (n_cols x k, leading dimension ldx): the gather of one column index pulls a whole row of X, so the
+// 64/128-byte line a single-vector gather takes 4 bytes out of is used in full, and Aj / Ax cross HBM once, not k times.
+//
+//   multi_slice_kernel   one WAVE per slice of kMultiSlice merge items (row ends + nonzeros, so that empty rows cost
+//                        what they hold and a hub row is spread over as many waves as it has slices).  The wave finds
+//                        its two merge-path diagonals, keeps its rows' offsets in LDS, and walks its nonzeros 64 at a
+//                        time: Aj / Ax are loaded coalesced, one per lane, and handed to the (slot x column group)
+//                        lanes by shuffles.  A lane gathers 16 bytes of a row of X.  Partials stay in registers: steps
+//                        that lie inside one row accumulate per slot; a step that holds a row's end is reduced across
+//                        the slots by a segmented scan (shuffles), and the slot that holds the end stores the row of Y.
+//                        What is left of a row that runs on into the next slice goes to the slice's carry.
+//   multi_fixup_kernel   reduces the carries of a row into Y in slice order (no atomics: two executes, same bits).
+//
+// Identity rule: wherever nothing is there — a slot past the slice's last nonzero, a masked column, the reset of the
+// open partial, an empty row — the value is SR::identity(), never a combine() of zeros: under (min, +) a zero is a
+// path of length 0, and INT32_MAX + x overflows.  An identity only ever meets reduce().
+// What Y holds after the slice passes: every row r is written by exactly one slice — the one that holds the row's
+// last nonzero (for an empty row: its row-end item) — with the reduction of the row's nonzeros that lie in that slice,
+// the identity for an empty row.  Earlier slices of the row leave carries, and the fix-up sets
+// Y[r, j] = reduce(Y[r, j], carries in slice order).  (+, *) on floating point keeps alpha / beta: the slice writes
+// alpha * sum + beta * Y, the fix-up adds alpha * sum.  Under the other semirings, and for int32, Y is never read by
+// the slice kernel and alpha / beta do not exist.
+#pragma once
+
+#include <algorithm>
+#include <type_traits>
+
+#include "common.hpp"
+#include "semiring.hpp"
+
+namespace mi355 {
+
+constexpr int kMultiWaves = kBlock / kWave;     // slices per workgroup
+#ifndef MI355_MULTI_GEOMETRY
+#error "multi_kernels.hpp is included through multi.hip, which holds kMultiSlice and kMultiGroupsMax"
+#endif
+
+template <typename val_t>
+struct MultiArgs {
+    int32_t n_rows;
+    int64_t nnz, n_slices;
+    const int32_t* Aj;
+    const val_t* Ax;        // null for a PATTERN kernel, which never forms an address from it
+    const val_t* X;
+    val_t* Y;
+    int64_t ldx, ldy;
+    int32_t col_begin;      // first column of this pass's tile
+    int32_t cols;           // columns of it that exist (<= tile width): the others are masked on load and store
+    int32_t x_vec, y_vec;   // 1 = rows of X / Y are 16-byte aligned: one 16-byte access per lane
+    val_t alpha, beta;      // (+, *) on floating point only
+    int32_t* carry_row;     // [n_slices]: the row a slice leaves unfinished, or -1
+    val_t* carry_val;       // [n_slices][carry_ld]
+    int64_t carry_ld;
+};
+
+struct alignas(16) I32x4 { int32_t x, y, z, w; };   // four int32 columns per lane, as float4 for fp32
+template <typename val_t> struct Pack16;
+template <> struct Pack16<float> { using type = float4; };
+template <> struct Pack16<double> { using type = double2; };
+template <> struct Pack16<int32_t> { using type = I32x4; };
+
+// alpha / beta exist for (+, *) on floating point; everything else stores what it reduced
+template <int SRI, typename val_t>
+constexpr bool kMultiScaled = SRI == MI355_SEMIRING_PLUS_TIMES && std::is_floating_point<val_t>::value;
+
+// the lane's V columns of a row: one 16-byte access when the row is aligned and all V exist, else the nv that do
+template <typename val_t, int V>
+__device__ __forceinline__ void load_cols(val_t (&v)[V], const val_t* p, int nv, bool vec) {
+    if (vec && nv == V) {
+        const auto t = *reinterpret_cast<const typename Pack16<val_t>::type*>(p);
+        v[0] = t.x; v[1] = t.y;
+        if constexpr (V == 4) { v[2] = t.z; v[3] = t.w; }
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = j < nv ? p[j] : val_t(0);
+    }
+}
+
+template <typename val_t, int V>
+__device__ __forceinline__ void store_cols(const val_t (&v)[V], val_t* p, int nv, bool vec) {
+    if (vec && nv == V) {
+        typename Pack16<val_t>::type t;
+        t.x = v[0]; t.y = v[1];
+        if constexpr (V == 4) { t.z = v[2]; t.w = v[3]; }
+        *reinterpret_cast<typename Pack16<val_t>::type*>(p) = t;
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+            if (j < nv) p[j] = v[j];
+    }
+}
+
+// (+, *) on floating point: Y[r, tile] = alpha * sum + beta * Y[r, tile], Y read only when beta != 0.
+// Otherwise Y[r, tile] = sum, and Y is not read.
+template <int SRI, typename val_t, int V>
+__device__ __forceinline__ void store_row(const MultiArgs<val_t>& a, int64_t r, int c, const val_t (&sum)[V]) {
+    const int nv = min(max(a.cols - c * V, 0), V);
+    if (nv == 0) return;
+    val_t* yp = a.Y + r * a.ldy + a.col_begin + c * V;
+    if constexpr (kMultiScaled<SRI, val_t>) {
+        val_t out[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) out[j] = a.alpha * sum[j];
+        if (a.beta != val_t(0)) {
+            val_t old[V];
+            load_cols<val_t, V>(old, yp, nv, a.y_vec != 0);
+#pragma unroll
+            for (int j = 0; j < V; ++j) out[j] += a.beta * old[j];
+        }
+        store_cols<val_t, V>(out, yp, nv, a.y_vec != 0);
+    } else {
+        store_cols<val_t, V>(sum, yp, nv, a.y_vec != 0);
+    }
+}
+
+// the reduction over all slots of a per-slot partial, in every lane of the column group (xor butterfly: the same bits
+// everywhere for a commutative reduce, which all five are)
+template <typename SR, typename val_t, int V, int C>
+__device__ __forceinline__ void reduce_slots(val_t (&v)[V]) {
+#pragma unroll
+    for (int d = C; d < kWave; d <<= 1)
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = SR::reduce(v[j], __shfl_xor(v[j], d));
+}
+
+// C = lanes per nonzero slot (16-byte column groups of the tile); the wave holds S = 64 / C slots
+template <typename off_t, typename val_t, int C, int SRI, bool PATTERN>
+__global__ __launch_bounds__(kBlock) void multi_slice_kernel(const MultiArgs<val_t> a, const off_t* __restrict__ Ap) {
+    using SR = Semiring<SRI, val_t>;
+    constexpr int V = 16 / int(sizeof(val_t));
+    constexpr int S = kWave / C;
+    // row offsets of the slice relative to its first nonzero, clamped to [0, nn + 1]: entry i belongs to row r0 + i
+    __shared__ int32_t rel_all[kMultiWaves][kMultiSlice + 2];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int c = lane % C, s = lane / C;
+    int32_t* rel = rel_all[threadIdx.x / kWave];
+    const int64_t w = int64_t(blockIdx.x) * kMultiWaves + threadIdx.x / kWave;
+    const bool active = w < a.n_slices;
+    int64_t r0 = 0, r1 = 0, n0 = 0;
+    int nr = -1, nn = 0;
+    if (active) {
+        // merge-path diagonals of the slice: lanes 0..31 search its start, lanes 32..63 its end.  Row end r comes before
+        // nonzero n iff Ap[r + 1] <= n; (r, n) = row ends and nonzeros in front of the diagonal.
+        const int64_t items = int64_t(a.n_rows) + a.nnz;
+        int64_t d = (lane < 32 ? w : w + 1) * kMultiSlice;
+        if (d > items) d = items;
+        int64_t lo = d > a.nnz ? d - a.nnz : 0, hi = d < a.n_rows ? d : a.n_rows;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (int64_t(Ap[mid + 1]) <= d - mid - 1) lo = mid + 1; else hi = mid;
+        }
+        const int64_t n = d - lo;
+        r0 = __shfl(lo, 0); r1 = __shfl(lo, 32);
+        n0 = __shfl(n, 0);
+        nn = int(__shfl(n, 32) - n0);
+        // rows r0 .. r_last have nonzeros or their end here (row r1, when there is one, does not end in this slice)
+        const int64_t r_last = r1 < a.n_rows ? r1 : int64_t(a.n_rows) - 1;
+        nr = int(r_last - r0) + 1;
+        for (int i = lane; i <= nr; i += kWave) {
+            const int64_t v = int64_t(Ap[r0 + i]) - n0;
+            rel[i] = v < 0 ? 0 : v > nn ? nn + 1 : int32_t(v);
+        }
+    }
+    __syncthreads();
+    if (!active) return;
+
+    val_t acc[V];           // per-slot partial of the open row (the row whose nonzeros are not all seen yet)
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[j] = SR::identity();
+    int open_i = -1;        // that row, relative to r0; -1 = none (acc is the identity)
+    int holder = -1;        // >= 0: acc is not the identity in this slot only; -2: spread over the slots
+    const int nv = min(max(a.cols - c * V, 0), V);
+
+    for (int base = 0; base < nn; base += kWave) {
+        // 64 nonzeros, one per lane, coalesced; each lane finds its nonzero's row in the slice's offsets
+        const int m = base + lane;
+        int32_t col = 0;
+        val_t ax = val_t(1);    // a PATTERN matrix's every entry; a valued one's is loaded below
+        int ie = nr * 2;    // row * 2 + (1 = this nonzero is the last of its row); nr = no nonzero
+        if (m < nn) {
+            col = a.Aj[n0 + m];
+            if constexpr (!PATTERN) ax = a.Ax[n0 + m];
+            int lo = 0, hi = nr - 1;
+            while (lo < hi) {           // the last i with rel[i] <= m (empty rows repeat an offset: the last is the owner)
+                const int mid = (lo + hi + 1) >> 1;
+                if (rel[mid] <= m) lo = mid; else hi = mid - 1;
+            }
+            ie = lo * 2 + (rel[lo + 1] == m + 1 ? 1 : 0);
+        }
+        const int left = nn - base;
+        const int steps = left >= kWave ? C : (left + S - 1) / S;
+        for (int t = 0; t < steps; ++t) {
+            // slot s takes nonzero t * S + s of the 64
+            int32_t col_s = col;
+            val_t ax_s = ax;
+            int ie_s = ie;
+            if constexpr (C > 1) {
+                const int src = t * S + s;
+                col_s = __shfl(col, src);
+                if constexpr (!PATTERN) ax_s = __shfl(ax, src);
+                ie_s = __shfl(ie, src);
+            }
+            const int i_s = ie_s >> 1;
+            val_t p[V];
+            if (i_s < nr) {
+                val_t xv[V];
+                load_cols<val_t, V>(xv, a.X + int64_t(col_s) * a.ldx + a.col_begin + c * V, nv, a.x_vec != 0);
+                if constexpr (SRI == MI355_SEMIRING_PLUS_TIMES) {
+                    // a masked column was loaded as 0 and (+, *)'s product with it is the identity already
+#pragma unroll
+                    for (int j = 0; j < V; ++j) p[j] = SR::combine(ax_s, xv[j]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) p[j] = j < nv ? SR::combine(ax_s, xv[j]) : SR::identity();
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; ++j) p[j] = SR::identity();
+            }
+            const int i_first = __shfl(ie_s, 0) >> 1;
+            const int ie_last = __shfl(ie_s, kWave - 1);
+            if (i_first == (ie_last >> 1) && !(ie_last & 1)) {
+                // every slot is inside one row, and the row goes on: partials stay per slot
+#pragma unroll
+                for (int j = 0; j < V; ++j) acc[j] = SR::reduce(acc[j], p[j]);
+                open_i = i_first;
+                holder = -2;
+                continue;
+            }
+            // a row ends in this step (or the slice does).  The open row's partial joins slot 0, whose nonzero is the
+            // next of that row; then a segmented inclusive scan over the slots reduces each row's run of products.
+            if (open_i >= 0) {
+                if (holder >= 0) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) acc[j] = __shfl(acc[j], holder * C + c);
+                } else {
+                    reduce_slots<SR, val_t, V, C>(acc);
+                }
+                if (s == 0) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) p[j] = SR::reduce(p[j], acc[j]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[j] = SR::identity();
+            const int i_prev = __shfl_up(i_s, C);
+            const bool head = s == 0 || i_prev != i_s;
+            const unsigned long long heads = __ballot(head && c == 0);
+            const int start = 63 - __clzll(heads & (~0ull >> (63 - lane)));   // lane c == 0 of the slot that starts this run
+#pragma unroll
+            for (int d = C; d < kWave; d <<= 1) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const val_t o = __shfl_up(p[j], d);
+                    if (lane - c - d >= start) p[j] = SR::reduce(p[j], o);
+                }
+            }
+            const bool tail = s == S - 1 || ((heads >> (lane - c + C)) & 1ull);
+            if (i_s < nr && tail && (ie_s & 1)) store_row<SRI, val_t, V>(a, r0 + i_s, c, p);
+            // the last nonzero of the step: if its row goes on, its run's reduction is the new open partial
+            const int lv = min(S - 1, left - t * S - 1);
+            const int ie_lv = __shfl(ie_s, lv * C);
+            if (!(ie_lv & 1)) {
+                open_i = ie_lv >> 1;
+                holder = lv;
+                if (s == lv) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) acc[j] = p[j];
+                }
+            } else {
+                open_i = -1;
+                holder = -1;
+            }
+        }
+    }
+
+    // the carry: what this slice holds of a row that ends in a later one
+    if (open_i >= 0) {
+        if (holder >= 0) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[j] = __shfl(acc[j], holder * C + c);
+        } else {
+            reduce_slots<SR, val_t, V, C>(acc);
+        }
+        if (s == 0) {
+            val_t* cv = a.carry_val + w * a.carry_ld + a.col_begin + c * V;    // (carry_ld covers whole tiles)
+#pragma unroll
+            for (int j = 0; j < V; ++j) cv[j] = acc[j];
+        }
+    }
+    if (lane == 0) a.carry_row[w] = open_i >= 0 ? int32_t(r0 + open_i) : -1;
+
+    // empty rows whose end lies in this slice: the identity ((+, *): Y = beta * Y); a row with nonzeros is stored where
+    // its last one is
+    val_t none[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) none[j] = SR::identity();
+    for (int64_t r = r0 + s; r < r1; r += S)
+        if (Ap[r] == Ap[r + 1]) store_row<SRI, val_t, V>(a, r, c, none);
+}
+
+// one thread per (slice, column): the first slice that carries a row reduces all its carries, in slice order, into Y
+template <typename val_t, int SRI>
+__global__ __launch_bounds__(kBlock) void multi_fixup_kernel(int64_t n_slices, int32_t k, const int32_t* __restrict__ carry_row,
+                                                             const val_t* __restrict__ carry_val, int64_t carry_ld,
+                                                             val_t* __restrict__ Y, int64_t ldy, val_t alpha) {
+    using SR = Semiring<SRI, val_t>;
+    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    const int64_t t = gid / k;
+    const int j = int(gid % k);
+    if (t >= n_slices) return;
+    const int32_t r = carry_row[t];
+    if (r < 0 || (t > 0 && carry_row[t - 1] == r)) return;
+    val_t sum = carry_val[t * carry_ld + j];
+    for (int64_t u = t + 1; u < n_slices && carry_row[u] == r; ++u) sum = SR::reduce(sum, carry_val[u * carry_ld + j]);
+    val_t& y = Y[int64_t(r) * ldy + j];
+    if constexpr (kMultiScaled<SRI, val_t>) y += alpha * sum;
+    else y = SR::reduce(y, sum);
+}
+
+// what an execute reads of the object (struct mi355_spmv_multi, multi.hip)
+struct MultiShape {
+    int32_t n_rows = 0;
+    int64_t nnz = 0;
+    const void* Ap = nullptr;
+    const int32_t* Aj = nullptr;
+    double alpha = 1.0, beta = 0.0;
+    int64_t n_slices = 0;
+    int64_t carry_ld = 0;           // k_max rounded up to whole widest tiles
+    int32_t* carry_row = nullptr;
+    void* carry_val = nullptr;
+};
+
+// the passes of one execute (tiles of the widest width, the last one as narrow as fits) and the fix-up
+template <typename off_t, typename val_t, int SRI, bool PATTERN>
+int launch_multi(const MultiShape& m, const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, hipStream_t s) {
+    if (m.n_slices == 0) return MI355_SPMV_OK;      // no rows: nothing to write
+    constexpr int V = 16 / int(sizeof(val_t));
+    constexpr int kWidest = V * kMultiGroupsMax;
+    MultiArgs<val_t> a;
+    a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
+    a.Aj = m.Aj; a.Ax = PATTERN ? nullptr : static_cast<const val_t*>(Ax);
+    a.X = static_cast<const val_t*>(X); a.Y = static_cast<val_t*>(Y);
+    a.ldx = ldx; a.ldy = ldy;
+    a.x_vec = (reinterpret_cast<uintptr_t>(X) % 16 == 0 && (size_t(ldx) * sizeof(val_t)) % 16 == 0) ? 1 : 0;
+    a.y_vec = (reinterpret_cast<uintptr_t>(Y) % 16 == 0 && (size_t(ldy) * sizeof(val_t)) % 16 == 0) ? 1 : 0;
+    a.alpha = val_t(m.alpha); a.beta = val_t(m.beta);
+    a.carry_row = m.carry_row; a.carry_val = static_cast<val_t*>(m.carry_val); a.carry_ld = m.carry_ld;
+    const off_t* Ap = static_cast<const off_t*>(m.Ap);
+    const dim3 grid(unsigned((m.n_slices + kMultiWaves - 1) / kMultiWaves)), block(kBlock);
+    for (int32_t cb = 0; cb < k; cb += kWidest) {
+        a.col_begin = cb;
+        a.cols = std::min<int32_t>(k - cb, kWidest);
+        const int groups = (a.cols + V - 1) / V;
+        if (groups <= 1) hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, 1, SRI, PATTERN>), grid, block, 0, s, a, Ap);
+        else if (groups <= 2) hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, 2, SRI, PATTERN>), grid, block, 0, s, a, Ap);
+        else if (groups <= 4) hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, 4, SRI, PATTERN>), grid, block, 0, s, a, Ap);
+        else hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, 8, SRI, PATTERN>), grid, block, 0, s, a, Ap);
+        MI355_HIP_TRY(hipGetLastError());
+    }
+    if (m.n_slices > 1) {
+        const int64_t threads = m.n_slices * k;
+        hipLaunchKernelGGL((multi_fixup_kernel<val_t, SRI>), dim3(unsigned((threads + kBlock - 1) / kBlock)), block, 0, s,
+                           m.n_slices, k, m.carry_row, static_cast<const val_t*>(m.carry_val), m.carry_ld, a.Y, ldy, a.alpha);
+        MI355_HIP_TRY(hipGetLastError());
+    }
+    return MI355_SPMV_OK;
+}
+
+// MI355_MULTI_EACH(X, val_t, SRI): X(off_t, val_t, SRI, PATTERN) for both offset widths, valued and pattern — the four
+// launch_multi (sixteen slice kernels) of one value type under one semiring
+#define MI355_MULTI_EACH(X, VAL, SRI) \
+    X(int32_t, VAL, SRI, false) X(int64_t, VAL, SRI, false) X(int32_t, VAL, SRI, true) X(int64_t, VAL, SRI, true)
+#define MI355_MULTI_EACH_SEMIRING(X, VAL)                                                                      \
+    MI355_MULTI_EACH(X, VAL, MI355_SEMIRING_PLUS_TIMES) MI355_MULTI_EACH(X, VAL, MI355_SEMIRING_MIN_PLUS)      \
+    MI355_MULTI_EACH(X, VAL, MI355_SEMIRING_MAX_TIMES) MI355_MULTI_EACH(X, VAL, MI355_SEMIRING_MAX_PLUS)       \
+    MI355_MULTI_EACH(X, VAL, MI355_SEMIRING_OR_AND)
+#define MI355_MULTI_DEFINE(OFF, VAL, SRI, PATTERN) \
+    template int launch_multi<OFF, VAL, SRI, PATTERN>(const MultiShape&, const void*, const void*, int64_t, void*, int64_t, int32_t, hipStream_t);
+#define MI355_MULTI_DECLARE(OFF, VAL, SRI, PATTERN) extern MI355_MULTI_DEFINE(OFF, VAL, SRI, PATTERN)
+
+#ifdef MI355_MULTI_SPLIT_UNITS      // the library's build: multi_f32.hip, multi_f64.hip and multi_i32.hip define them
+MI355_MULTI_EACH_SEMIRING(MI355_MULTI_DECLARE, float)
+MI355_MULTI_EACH_SEMIRING(MI355_MULTI_DECLARE, double)
+MI355_MULTI_EACH_SEMIRING(MI355_MULTI_DECLARE, int32_t)
+#endif
+
+}  // namespace mi355

@@ -1,0 +1,112 @@
+"""The multi-vector kernels over semirings, int32 values and pattern matrices executed on the host, lane by lane
+(tests/cpp/multi_semiring_sim.cpp over tests/cpp/simt): csrc/multi.hip with the headers it includes, unchanged, built
+with the address and undefined-behaviour sanitizers and run over the WHOLE table of tests/multi_semiring_cases.py
+through the real mi355_spmv_multi_create_typed / set_semiring / set_alpha_beta / execute / destroy.  Each Y is held to
+the serial oracle exactly as the device run of the same table is (tests/test_gpu_multi_semiring.py); the children must
+end with status 0 and must have written nothing to stderr (where the sanitizers — a signed overflow of an identity
+that met combine() among them — and the stand-in's out-of-step check report), and each runs under a time limit.
+Nothing is loaded into this process, and the children's environment is this process's own (the sanitizer runtimes are
+linked statically).
+
+Cost: the table's ~3 000 executes run as concurrent child processes (at most 8): about a minute on 8 cores, plus the
+compilation once (every instantiation of the kernels: about four minutes; multi_sim, which tests/test_multi_sim_cpu.py
+runs, is brought up to date beside it in the same make call, so the two programs compile side by side)."""
+import os
+import subprocess
+
+import pytest
+
+import multi_cases as mc
+import multi_semiring_cases as sc
+from conftest import ROOT
+
+CPP = os.path.join(ROOT, "tests", "cpp")
+TIME_LIMIT = 900        # seconds per child
+
+
+def build():
+    """The program, by the rule of tests/cpp/multi_semiring_sim.mk (the Makefile's SIM_SAN flags).  Skips only where the
+    host compiler cannot link with those flags at all; any other failure to build is a failure."""
+    probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
+    if probe.returncode != 0:
+        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
+    # multi_sim too: the Makefile's own rule does not know the headers that multi.hip has come to include, so a multi_sim
+    # built before an edit to them would be stale when tests/test_multi_sim_cpu.py (which runs after this file) asks for it
+    subprocess.run(["make", "-s", "-j2", "-C", CPP, "-f", "multi_semiring_sim.mk", "multi_semiring_sim", "multi_sim"], check=True)
+    return os.path.join(CPP, "multi_semiring_sim")
+
+
+def batches(cases, n):
+    """Whole plan groups dealt to n batches, heaviest first onto the lightest batch (weight: merge items x columns)."""
+    weight = lambda g: sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (c.k + 8) for c in g)
+    out = [[0, []] for _ in range(n)]
+    for g in sorted(sc.groups(cases), key=weight, reverse=True):
+        b = min(out, key=lambda b: b[0])
+        b[0] += weight(g)
+        b[1] += g
+    return [b[1] for b in out if b[1]]
+
+
+@pytest.fixture(scope="module")
+def run(tmp_path_factory):
+    """Every case of the table through the sanitized program: {case name: (status, Y)}, and the children's reports."""
+    exe = build()
+    tmp = tmp_path_factory.mktemp("multi_semiring_sim")
+    env = dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1")
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    children = []
+    for i, cases in enumerate(batches(sc.table(), max(1, min(8, cpus)))):
+        src, dst = str(tmp / ("batch%d.bin" % i)), str(tmp / ("y%d.bin" % i))
+        order = sc.write_batch(src, cases)
+        children.append((subprocess.Popen([exe, src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env),
+                         order, dst))
+    results, reports = {}, []
+    for child, order, dst in children:
+        try:
+            out, err = child.communicate(timeout=TIME_LIMIT)
+        except subprocess.TimeoutExpired:
+            child.kill()
+            out, err = child.communicate()
+            err += "\n(killed after %d s)" % TIME_LIMIT
+        reports.append((child.returncode, out + err))
+        if child.returncode == 0:
+            for c, res in zip(order, sc.read_results(dst, order)):
+                results[c.name] = res
+    return results, reports
+
+
+def test_the_children_end_clean_with_an_empty_sanitizer_log(run):
+    for status, text in run[1]:
+        assert status == 0 and text == "", "status %s\n%s" % (status, text[-4000:])
+
+
+def test_every_combination_occurs_and_every_case_has_a_name_of_its_own(run):
+    """The table that the program just ran (every case has a result) covers every combination."""
+    table = sc.table()
+    assert {c.name for c in table} == set(run[0])
+    assert len({c.name for c in table}) == len(table)
+    assert 2500 <= len(table) <= 3300
+    seen = {(c.semiring, c.val, c.pattern, sc.tile_lanes(c.val, c.k)) for c in table}
+    want = {(s, v, p, lanes) for s in sc.SEMIRINGS for v in sc.VALS for p in (False, True) for lanes in mc.LANES_PER_SLOT}
+    assert seen == want, sorted(want - seen)
+    # two passes, both offset widths, both kinds of data and every structure under every semiring
+    assert {(c.semiring, c.val) for c in table if c.k > sc.TILE[c.val]} == {(s, v) for s in sc.SEMIRINGS for v in sc.VALS}
+    assert {(c.semiring, c.off) for c in table} == {(s, o) for s in sc.SEMIRINGS for o in sc.OFFS}
+    assert {(c.semiring, c.val, c.integer) for c in table if c.val != "i32"} == {
+        (s, v, i) for s in sc.SEMIRINGS for v in ("f32", "f64") for i in (False, True)}
+    assert {(c.matrix.name, c.semiring) for c in table} >= {(m.name, s) for m in sc.structures() for s in sc.SEMIRINGS}
+    assert {(c.alpha, c.beta) for c in table if c.semiring == "plus_times" and c.val != "i32"} == set(mc.AB_REDUCED)
+    assert all((c.alpha, c.beta) == (1.0, 0.0) for c in table if c.semiring != "plus_times" or c.val == "i32")
+    assert all(c.integer for c in table if c.val == "i32")
+
+
+def test_every_case_is_held_to_the_oracle(run, oracle):
+    results = run[0]
+    for c in sc.table():
+        assert c.name in results, "%s: no result (its child did not end clean)" % c.name
+        status, y = results[c.name]
+        assert status == 0, c.name
+        sc.check(oracle, c, y)
