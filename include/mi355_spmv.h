@@ -44,6 +44,7 @@ extern "C" {
 #define MI355_SPMV_HAS_PATTERN 1 /* MI355_VAL_PATTERN, mi355_spmv_merge_pattern_*, mi355_spmv_plan_get_mat_type */
 #define MI355_SPMV_HAS_MULTI 1   /* mi355_spmv_multi_*: Y = A X for k vectors in one pass over A */
 #define MI355_SPMV_HAS_MULTI_SEMIRING 1 /* mi355_spmv_multi_create_typed / _set_semiring / _get_types / _genl_* / _pattern_* */
+#define MI355_SPMV_HAS_MULTI_HALF 1 /* mi355_spmv_multi_create_half / _half_*: X and Y in binary16 / bfloat16, fp32 arithmetic */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -536,8 +537,8 @@ int mi355_spmv_functor_destroy(mi355_spmv_functor* functor);
  * aligned, else element by element.
  * Types: mi355_spmv_multi_create makes {I32, I64} offsets x {F32, F64} values under the (+, *) semiring and returns
  * MI355_SPMV_ENOTSUP for MI355_VAL_I32 / MI355_VAL_PATTERN; semirings, int32 values and pattern matrices come from
- * mi355_spmv_multi_create_typed below.  Column-major X, mixed precision and the dist_* entry points are not built
- * (DESIGN.md 3.10).
+ * mi355_spmv_multi_create_typed below, 16-bit X and Y from mi355_spmv_multi_create_half below that.  Column-major X and
+ * the dist_* entry points are not built.
  * The work is cut by NONZEROS: a wave owns a slice of slice_len merge items (row ends + nonzeros), so empty rows and
  * hub rows cost what they hold; a row that crosses slices leaves carries in scratch (sized for k_max at create), and
  * a fix-up kernel adds them in slice order — no float atomics: two executes on the same inputs give the same bits.
@@ -595,8 +596,8 @@ int mi355_spmv_multi_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const 
  *                  other than PLUS_TIMES while alpha / beta != 1 / 0, or set_alpha_beta to anything but 1 / 0 under
  *                  such a semiring or on an I32 object, is MI355_SPMV_ENOTSUP; an unknown semiring is EINVAL.
  *   execute        of a PATTERN object ignores Ax (it may be NULL).
- * Out of scope: harness labels (the reference's operator has one x), dist_*, mixed precision, column-major X, and
- * caller-text functors (mi355_spmv_functor_*) on the multi path.                                                   */
+ * Out of scope: harness labels (the reference's operator has one x), dist_*, column-major X, and caller-text functors
+ * (mi355_spmv_functor_*) on the multi path.                                                                        */
 int mi355_spmv_multi_create_typed(mi355_spmv_multi** out, int off_type, int mat_type, int vec_type, int32_t n_rows,
                                   int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj, int32_t k_max);
 int mi355_spmv_multi_set_semiring(mi355_spmv_multi* multi, int semiring);
@@ -628,6 +629,39 @@ int mi355_spmv_multi_pattern_i64_f64(int semiring, int32_t n_rows, int32_t n_col
     const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
 int mi355_spmv_multi_pattern_i64_i32(int semiring, int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
     const int32_t* X, int64_t ldx, int32_t* Y, int64_t ldy, int32_t k, void* stream);
+
+/* ---- multi-vector SpMV with 16-bit vectors and fp32 arithmetic (MI355_SPMV_HAS_MULTI_HALF) -------------------------
+ * For callers who hold X in 16 bits (GNN features, low-precision block Krylov, batched propagation) and would
+ * otherwise widen X, run, and narrow Y: two passes over the vectors saved, and half the gather traffic.
+ *   X, Y      row-major as above, both in vec_type: MI355_VAL_F16 (binary16) or MI355_VAL_BF16 (bfloat16)
+ *   matrix    values in vec_type, or in MI355_VAL_F32
+ * Every stored 16-bit value is widened exactly to fp32; products and sums are fp32.  For a row's fp32 sum S,
+ * out = alpha * S, + beta * float(Yold) when beta != 0, and Y = out rounded to vec_type ONCE: nearest even, overflow
+ * to +-inf, NaN stays NaN — also for a row that crosses slices (its carries and its last piece stay fp32 in scratch and
+ * the fix-up is the row's only writer).  Only (+, *) is built.  Everything else is the contract above: columns j >= k
+ * are never read or written, beta == 0 never reads Y, an empty row gets beta * Y (rounded once), any ldx, ldy >= k
+ * (16-byte accesses when the pointer and ld * 2 are multiples of 16), no atomics, kernels only.
+ * Tiles are 8 / 16 / 32 / 64 columns; scratch is n_slices * (4 + 2 * carry_ld * 4) bytes, carry_ld = k_max rounded up
+ * to a multiple of 64.
+ *   create_half   vec_type outside {F16, BF16} or an unknown type: MI355_SPMV_EINVAL; a known mat_type other than
+ *                 vec_type or F32 (F16 under BF16, F64, I32, PATTERN): MI355_SPMV_ENOTSUP; the size and pointer checks
+ *                 of mi355_spmv_multi_create, *out cleared on failure.
+ *   The object is executed, scaled, reported and destroyed by mi355_spmv_multi_execute / _set_alpha_beta / _get_info
+ *   (val_type = vec_type, widest_tile = 64) / _get_types (the stored matrix type) / _destroy; _set_semiring to anything
+ *   but MI355_SEMIRING_PLUS_TIMES is MI355_SPMV_ENOTSUP.
+ * Out of scope: semirings and PATTERN in 16 bits, fp32 Y from 16-bit X, dist_*, column-major X.                    */
+int mi355_spmv_multi_create_half(mi355_spmv_multi** out, int off_type, int mat_type, int vec_type, int32_t n_rows,
+                                 int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj, int32_t k_max);
+/* One-shots with the matrix in the vectors' type (Ax, X, Y: binary16 / bfloat16 as stored): the arguments of
+ * mi355_spmv_multi_<off>_<val>.  Argument errors are refused before any device call.                              */
+int mi355_spmv_multi_half_i32_f16(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_half_i32_bf16(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_half_i64_f16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

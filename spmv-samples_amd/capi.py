@@ -52,6 +52,8 @@ EXPORTS = (
     + ["mi355_spmv_multi_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
     + ["mi355_spmv_multi_" + n for n in ("create_typed", "set_semiring", "get_types")]
     + ["mi355_spmv_multi_%s_%s_%s" % (g, o, v) for g in ("genl", "pattern") for o in ("i32", "i64") for v in ("f32", "f64", "i32")]
+    + ["mi355_spmv_multi_create_half"]
+    + ["mi355_spmv_multi_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
 )
 
 
@@ -192,6 +194,10 @@ def lib():
                 getattr(L, "mi355_spmv_multi_pattern_%s_%s" % (o, v)).argtypes = [
                     C.c_int, C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int64, C.c_int32, C.c_void_p]
+        L.mi355_spmv_multi_create_half.argtypes = L.mi355_spmv_multi_create_typed.argtypes
+        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
+            for v in ("f16", "bf16"):
+                getattr(L, "mi355_spmv_multi_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_multi_%s_f32" % o).argtypes
         _lib = L
     return _lib
 
@@ -607,25 +613,39 @@ class MultiPlan:
     are.  val_dtype (the type of X, Y and all arithmetic) is float32, float64 or int32; mat_dtype="pattern" makes a
     matrix without values (every entry one): execute then takes Ax=None.  int32 needs one of mat_dtype=torch.int32,
     mat_dtype="pattern" or a semiring other than "plus_times" spelled out: MultiPlan(..., torch.int32, k_max) alone is
-    refused, as it was before int32 existed here.  Holds references to Ap and Aj so they outlive the object."""
+    refused, as it was before int32 existed here.  val_dtype float16 / bfloat16 (mi355_spmv_multi_create_half): X and Y
+    in 16 bits, fp32 arithmetic, Y rounded once; mat_dtype is then None or val_dtype (Ax in the same 16 bits) or
+    torch.float32, and the semiring "plus_times".  Holds references to Ap and Aj so they outlive the object."""
 
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, mat_dtype=None, semiring="plus_times"):
         _require_device(Ap, Aj)
         if Aj.dtype != torch.int32:
             raise TypeError("Aj must be int32")
         pattern = isinstance(mat_dtype, str) and mat_dtype == "pattern"
-        if mat_dtype is not None and not pattern and mat_dtype != val_dtype:
+        half = val_dtype in MAT_TYPES
+        if half and mat_dtype not in (None, val_dtype, torch.float32):
+            raise TypeError("mat_dtype under 16-bit vectors must be val_dtype or torch.float32")
+        if not half and mat_dtype is not None and not pattern and mat_dtype != val_dtype:
             raise TypeError('mat_dtype must be val_dtype or "pattern" (mixed precision is not built on the multi path)')
         sr = _semiring_id(semiring)
+        if half and sr != 0:
+            raise TypeError('16-bit vectors are built under the "plus_times" semiring only')
         typed = pattern or sr != 0 or val_dtype == torch.int32 and mat_dtype is not None
-        if val_dtype not in (torch.float32, torch.float64) and not (typed and val_dtype == torch.int32):
+        if val_dtype not in (torch.float32, torch.float64) and not half and not (typed and val_dtype == torch.int32):
             raise TypeError("val_dtype must be float32 or float64"
                             " (or int32 under a semiring, a pattern matrix or mat_dtype=torch.int32)")
         self.n_rows, self.n_cols, self.nnz, self.k_max = n_rows, n_cols, nnz, k_max
         self.Ap, self.Aj, self.val_dtype, self.pattern = Ap, Aj, val_dtype, pattern
+        self.mat_dtype = val_dtype if mat_dtype is None or pattern else mat_dtype      # the type of Ax
         self._h = C.c_void_p()
         with torch.cuda.device(Ap.device):
-            if typed:
+            if half:
+                what = "mi355_spmv_multi_create_half"
+                mat = VAL_TYPES[torch.float32][0] if self.mat_dtype == torch.float32 else MAT_TYPES[val_dtype][0]
+                st = lib().mi355_spmv_multi_create_half(
+                    C.byref(self._h), OFF_TYPES[Ap.dtype][0], mat, MAT_TYPES[val_dtype][0], n_rows, n_cols, nnz,
+                    C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), k_max)
+            elif typed:
                 what = "mi355_spmv_multi_create_typed"
                 st = lib().mi355_spmv_multi_create_typed(
                     C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_PATTERN if pattern else VAL_TYPES[val_dtype][0],
@@ -647,7 +667,7 @@ class MultiPlan:
             raise TypeError("Ax is None: only a pattern plan has no values")
         else:
             _require_device(Ax)
-            if Ax.dtype != self.val_dtype:
+            if Ax.dtype != getattr(self, "mat_dtype", self.val_dtype):
                 raise TypeError("value type differs from the plan's")
             if Ax.numel() < self.nnz:
                 raise ValueError("operand shorter than the plan's sizes")
@@ -698,12 +718,27 @@ class MultiPlan:
 def spmm(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None, semiring="plus_times"):
     """One-shot Y = A X for the k = X.size(1) vectors of a row-major X: create, execute, synchronise the stream,
     destroy.  (+, *) on float values: mi355_spmv_multi_<off>_<val>; another semiring, or int32 values:
-    mi355_spmv_multi_genl_<off>_<val>."""
+    mi355_spmv_multi_genl_<off>_<val>; float16 / bfloat16 Ax, X and Y under (+, *): mi355_spmv_multi_half_<off>_<val>
+    (fp32 arithmetic, Y rounded once)."""
     _require_device(Ap, Aj, Ax)
     if Aj.dtype != torch.int32:
         raise TypeError("Aj must be int32")
     sr = _semiring_id(semiring)
     genl = sr != 0 or Ax.dtype == torch.int32
+    if sr == 0 and Ax.dtype in MAT_TYPES:
+        if Ax.numel() < nnz:
+            raise ValueError("operand shorter than the matrix")
+        ldx = _require_matrix(X, "X", n_cols, Ax.dtype)
+        ldy = _require_matrix(Y, "Y", n_rows, Ax.dtype)
+        if X.size(1) != Y.size(1):
+            raise ValueError("X and Y hold different numbers of vectors")
+        name = "mi355_spmv_multi_half_%s_%s" % (OFF_TYPES[Ap.dtype][1], MAT_TYPES[Ax.dtype][1])
+        with torch.cuda.device(Ap.device):
+            st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
+                                      C.c_void_p(Ax.data_ptr()), C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy,
+                                      X.size(1), _stream_ptr(stream))
+        _check(st, name)
+        return Y
     if Ax.dtype not in ((torch.float32, torch.float64, torch.int32) if genl else (torch.float32, torch.float64)):
         raise TypeError("Ax must be float32 or float64" + (" or int32" if genl else ""))
     if Ax.numel() < nnz:

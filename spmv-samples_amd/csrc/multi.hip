@@ -3,7 +3,8 @@
 // path with the VECTOR / LIGHT / MERGE kinds.  The kernels and launch_multi: multi_kernels.hpp; their instantiations
 // per value type: the multi_<type>.hip units, which include this file with MI355_MULTI_TU set to the value type (the
 // library's build, MI355_MULTI_SPLIT_UNITS; without it this unit instantiates what it launches and stands alone).
-// DESIGN.md §3.10, §3.10.1.
+// 16-bit vectors (mi355_spmv_multi_create_half): multi_half_kernels.hpp, instantiated by multi_h16.hip, which includes
+// this file with MI355_MULTI_HALF_TU set.  DESIGN.md §3.10, §3.10.1, §3.10.2.
 #include <algorithm>
 #include <new>
 
@@ -11,14 +12,19 @@
 
 namespace mi355 {
 constexpr int kMultiSlice = 1024;               // merge items per slice (= per wave)
-constexpr int kMultiGroupsMax = 8;              // most 16-byte column groups of a tile: 32 fp32 / int32, 16 fp64 columns
+constexpr int kMultiGroupsMax = 8;              // most 16-byte column groups of a tile: 32 fp32 / int32, 16 fp64, 64 16-bit columns
 }  // namespace mi355
 #define MI355_MULTI_GEOMETRY 1
 #include "multi_kernels.hpp"
+#include "multi_half_kernels.hpp"
 
-#ifdef MI355_MULTI_TU   // an instantiation unit: the launch_multi of one value type, and nothing of what follows
+#if defined(MI355_MULTI_TU)   // an instantiation unit: the launch_multi of one value type, and nothing of what follows
 namespace mi355 {
 MI355_MULTI_EACH_SEMIRING(MI355_MULTI_DEFINE, MI355_MULTI_TU)
+}  // namespace mi355
+#elif defined(MI355_MULTI_HALF_TU)   // ... or every launch_multi_half
+namespace mi355 {
+MI355_MULTI_HALF_EACH(MI355_MULTI_HALF_DEFINE)
 }  // namespace mi355
 #else
 
@@ -26,18 +32,18 @@ using namespace mi355;
 
 struct mi355_spmv_multi {   // the opaque handle of include/mi355_spmv.h
     int off_type = 0;
-    int val_type = 0;               // the type of X, Y and of all arithmetic: F32 / F64 / I32
-    int mat_type = 0;               // = val_type, or MI355_VAL_PATTERN (no stored values: Ax is ignored)
+    int val_type = 0;               // the type of X and Y: F32 / F64 / I32 (and of all arithmetic), or F16 / BF16 (fp32 arithmetic)
+    int mat_type = 0;               // = val_type, or MI355_VAL_PATTERN (no stored values: Ax is ignored); F32 under F16 / BF16
     int semiring = MI355_SEMIRING_PLUS_TIMES;
     int32_t n_cols = 0, k_max = 0;
     MultiShape shape;               // what an execute reads (multi_kernels.hpp)
-    void* scratch = nullptr;        // carry_row, then carry_val
+    void* scratch = nullptr;        // carry_row, then carry_val (16-bit vectors: carry_val, tail_val, then carry_row)
     size_t scratch_bytes = 0;
 };
 
 namespace {
 
-int widest_tile(int val_type) { return val_type == MI355_VAL_F64 ? 16 : 32; }
+int widest_tile(int val_type) { return val_type == MI355_VAL_F64 ? 16 : is_half_matrix(val_type) ? 64 : 32; }
 bool known_semiring(int semiring) { return semiring >= 0 && semiring < MI355_SEMIRING_COUNT; }
 
 // argument-only checks of an execute (also run by the one-shots before they create anything); a pattern object has no Ax
@@ -75,6 +81,21 @@ int check_typed_types(int mat_type, int vec_type) {
     return MI355_SPMV_OK;
 }
 
+// mi355_spmv_multi_create_half: vec_type in {F16, BF16}; mat_type = vec_type or F32
+int check_half_types(int mat_type, int vec_type) {
+    if (!is_half_matrix(vec_type)) {
+        set_error("multi_create_half: vec_type %d is not a 16-bit type of X and Y (F16 or BF16)", vec_type);
+        return MI355_SPMV_EINVAL;
+    }
+    if (mat_type < MI355_VAL_F32 || mat_type > MI355_VAL_BF16) { set_error("multi_create_half: unknown matrix type %d", mat_type); return MI355_SPMV_EINVAL; }
+    if (mat_type != vec_type && mat_type != MI355_VAL_F32) {
+        set_error("multi_create_half: matrix type %d under vector type %d is not built (mat_type is vec_type or MI355_VAL_F32)",
+                  mat_type, vec_type);
+        return MI355_SPMV_ENOTSUP;
+    }
+    return MI355_SPMV_OK;
+}
+
 int check_create_args(const char* who, int off_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
                       int32_t k_max) {
     if (n_rows < 0 || n_cols < 0 || nnz < 0) { set_error("%s: negative size", who); return MI355_SPMV_EINVAL; }
@@ -86,11 +107,16 @@ int check_create_args(const char* who, int off_type, int32_t n_rows, int32_t n_c
     return MI355_SPMV_OK;
 }
 
-// every argument-only check of a create: `typed` = through mi355_spmv_multi_create_typed
-int check_create(const char* who, bool typed, int off_type, int mat_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+enum CreateHow { kPlain = 0, kTyped = 1, kHalf = 2 };   // mi355_spmv_multi_create, _create_typed, _create_half
+
+// every argument-only check of a create
+int check_create(const char* who, CreateHow how, int off_type, int mat_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
                  const void* Ap, const int32_t* Aj, int32_t k_max) {
     if (off_type != MI355_OFF_I32 && off_type != MI355_OFF_I64) { set_error("%s: unknown offset type %d", who, off_type); return MI355_SPMV_EINVAL; }
-    if (const int st = typed ? check_typed_types(mat_type, vec_type) : check_plain_type(vec_type)) return st;
+    if (const int st = how == kHalf    ? check_half_types(mat_type, vec_type)
+                       : how == kTyped ? check_typed_types(mat_type, vec_type)
+                                       : check_plain_type(vec_type))
+        return st;
     return check_create_args(who, off_type, n_rows, n_cols, nnz, Ap, Aj, k_max);
 }
 
@@ -108,17 +134,25 @@ int make_object(const char* who, mi355_spmv_multi** out, int off_type, int mat_t
     const int widest = widest_tile(vec_type);
     sh.carry_ld = int64_t(k_max + widest - 1) / widest * widest;
     if (sh.n_slices > 0) {
+        const bool half = is_half_matrix(vec_type);     // fp32 carries and tails (carry_ld * 4 is a multiple of 256), then the rows
         const size_t val_bytes = vec_type == MI355_VAL_F64 ? 8 : 4;
-        const size_t rows_bytes = (size_t(sh.n_slices) * sizeof(int32_t) + 255) / 256 * 256;
-        m->scratch_bytes = rows_bytes + size_t(sh.n_slices) * size_t(sh.carry_ld) * val_bytes;
+        const size_t rows_bytes = half ? size_t(sh.n_slices) * sizeof(int32_t) : (size_t(sh.n_slices) * sizeof(int32_t) + 255) / 256 * 256;
+        const size_t vals_bytes = size_t(sh.n_slices) * size_t(sh.carry_ld) * val_bytes;
+        m->scratch_bytes = rows_bytes + (half ? 2 : 1) * vals_bytes;
         const hipError_t e = hipMalloc(&m->scratch, m->scratch_bytes);
         if (e != hipSuccess) {
             set_error("%s: hipMalloc(%zu) -> %s", who, m->scratch_bytes, hipGetErrorString(e));
             delete m;
             return e == hipErrorOutOfMemory ? MI355_SPMV_ENOMEM : MI355_SPMV_EHIP;
         }
-        sh.carry_row = static_cast<int32_t*>(m->scratch);
-        sh.carry_val = static_cast<char*>(m->scratch) + rows_bytes;
+        if (half) {
+            sh.carry_val = m->scratch;
+            sh.tail_val = static_cast<char*>(m->scratch) + vals_bytes;
+            sh.carry_row = reinterpret_cast<int32_t*>(static_cast<char*>(m->scratch) + 2 * vals_bytes);
+        } else {
+            sh.carry_row = static_cast<int32_t*>(m->scratch);
+            sh.carry_val = static_cast<char*>(m->scratch) + rows_bytes;
+        }
     }
     *out = m;
     return MI355_SPMV_OK;
@@ -144,9 +178,18 @@ int launch_typed(const mi355_spmv_multi& m, const void* Ax, const void* X, int64
     return MI355_SPMV_EINVAL;
 }
 
+// 16-bit vectors: (+, *) only, the matrix in the vectors' type or in fp32
+template <typename off_t, typename vec_t>
+int launch_half(const mi355_spmv_multi& m, const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, hipStream_t s) {
+    return m.mat_type == MI355_VAL_F32 ? launch_multi_half<off_t, vec_t, float>(m.shape, Ax, X, ldx, Y, ldy, k, s)
+                                       : launch_multi_half<off_t, vec_t, vec_t>(m.shape, Ax, X, ldx, Y, ldy, k, s);
+}
+
 template <typename off_t>
 int launch_offsets(const mi355_spmv_multi& m, const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, hipStream_t s) {
     switch (m.val_type) {
+        case MI355_VAL_F16: return launch_half<off_t, mh::F16>(m, Ax, X, ldx, Y, ldy, k, s);
+        case MI355_VAL_BF16: return launch_half<off_t, Bf16>(m, Ax, X, ldx, Y, ldy, k, s);
         case MI355_VAL_F32: return launch_typed<off_t, float>(m, Ax, X, ldx, Y, ldy, k, s);
         case MI355_VAL_F64: return launch_typed<off_t, double>(m, Ax, X, ldx, Y, ldy, k, s);
         default: return launch_typed<off_t, int32_t>(m, Ax, X, ldx, Y, ldy, k, s);
@@ -156,12 +199,12 @@ int launch_offsets(const mi355_spmv_multi& m, const void* Ax, const void* X, int
 int passes_for(int val_type, int32_t k) { return (k + widest_tile(val_type) - 1) / widest_tile(val_type); }
 
 // create (k_max = k), set the semiring, execute, synchronise, destroy; every argument check comes before any device call
-int multi_one_shot(const char* who, bool typed, int off_type, int mat_type, int vec_type, int semiring, int32_t n_rows, int32_t n_cols,
+int multi_one_shot(const char* who, CreateHow how, int off_type, int mat_type, int vec_type, int semiring, int32_t n_rows, int32_t n_cols,
                    int64_t nnz, const void* Ap, const int32_t* Aj, const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy,
                    int32_t k, void* stream) {
     set_error("%s", "");
     if (!known_semiring(semiring)) { set_error("%s: unknown semiring %d", who, semiring); return MI355_SPMV_EINVAL; }
-    int st = check_create(who, typed, off_type, mat_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, k < 1 ? 1 : k);
+    int st = check_create(who, how, off_type, mat_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, k < 1 ? 1 : k);
     if (st == MI355_SPMV_OK) st = check_execute_args(who, mat_type == MI355_VAL_PATTERN, n_rows, nnz, k, Ax, X, ldx, Y, ldy, k);
     if (st != MI355_SPMV_OK) return st;
     mi355_spmv_multi* m = nullptr;
@@ -183,7 +226,7 @@ int mi355_spmv_multi_create(mi355_spmv_multi** out, int off_type, int val_type, 
     set_error("%s", "");
     if (!out) { set_error("multi_create: null object pointer"); return MI355_SPMV_EINVAL; }
     *out = nullptr;
-    if (const int st = check_create("multi_create", false, off_type, val_type, val_type, n_rows, n_cols, nnz, Ap, Aj, k_max)) return st;
+    if (const int st = check_create("multi_create", kPlain, off_type, val_type, val_type, n_rows, n_cols, nnz, Ap, Aj, k_max)) return st;
     return make_object("multi_create", out, off_type, val_type, val_type, n_rows, n_cols, nnz, Ap, Aj, k_max);
 }
 
@@ -192,14 +235,27 @@ int mi355_spmv_multi_create_typed(mi355_spmv_multi** out, int off_type, int mat_
     set_error("%s", "");
     if (!out) { set_error("multi_create_typed: null object pointer"); return MI355_SPMV_EINVAL; }
     *out = nullptr;
-    if (const int st = check_create("multi_create_typed", true, off_type, mat_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, k_max)) return st;
+    if (const int st = check_create("multi_create_typed", kTyped, off_type, mat_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, k_max)) return st;
     return make_object("multi_create_typed", out, off_type, mat_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, k_max);
+}
+
+int mi355_spmv_multi_create_half(mi355_spmv_multi** out, int off_type, int mat_type, int vec_type, int32_t n_rows, int32_t n_cols,
+                                 int64_t nnz, const void* Ap, const int32_t* Aj, int32_t k_max) {
+    set_error("%s", "");
+    if (!out) { set_error("multi_create_half: null object pointer"); return MI355_SPMV_EINVAL; }
+    *out = nullptr;
+    if (const int st = check_create("multi_create_half", kHalf, off_type, mat_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, k_max)) return st;
+    return make_object("multi_create_half", out, off_type, mat_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, k_max);
 }
 
 int mi355_spmv_multi_set_semiring(mi355_spmv_multi* m, int semiring) {
     set_error("%s", "");
     if (!m) { set_error("multi_set_semiring: null object"); return MI355_SPMV_EINVAL; }
     if (!known_semiring(semiring)) { set_error("multi_set_semiring: unknown semiring %d", semiring); return MI355_SPMV_EINVAL; }
+    if (semiring != MI355_SEMIRING_PLUS_TIMES && is_half_matrix(m->val_type)) {
+        set_error("multi_set_semiring: 16-bit vectors are built under the (+, *) semiring only");
+        return MI355_SPMV_ENOTSUP;
+    }
     if (semiring != MI355_SEMIRING_PLUS_TIMES && (m->shape.alpha != 1.0 || m->shape.beta != 0.0)) {
         set_error("multi_set_semiring: alpha/beta are set; they are defined for (+, *) only");
         return MI355_SPMV_ENOTSUP;
@@ -256,7 +312,7 @@ int mi355_spmv_multi_get_info(const mi355_spmv_multi* m, mi355_spmv_multi_info* 
     info->n_slices = m->shape.n_slices;
     info->grid_blocks = (m->shape.n_slices + kMultiWaves - 1) / kMultiWaves;
     info->scratch_bytes = int64_t(m->scratch_bytes);
-    snprintf(info->main_kernel, sizeof(info->main_kernel), "multi_slice_kernel");
+    snprintf(info->main_kernel, sizeof(info->main_kernel), is_half_matrix(m->val_type) ? "multi_half_slice_kernel" : "multi_slice_kernel");
     return MI355_SPMV_OK;
 }
 
@@ -274,7 +330,7 @@ int mi355_spmv_multi_destroy(mi355_spmv_multi* m) {
 #define MI355_SPMV_DEFINE_MULTI(SUF, OFF, OFFENUM, VAL, VALENUM)                                                       \
     int mi355_spmv_multi_##SUF(int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap, const int32_t* Aj, const VAL* Ax, \
                                const VAL* X, int64_t ldx, VAL* Y, int64_t ldy, int32_t k, void* stream) {              \
-        return multi_one_shot("multi", false, OFFENUM, VALENUM, VALENUM, MI355_SEMIRING_PLUS_TIMES, n_rows, n_cols,    \
+        return multi_one_shot("multi", kPlain, OFFENUM, VALENUM, VALENUM, MI355_SEMIRING_PLUS_TIMES, n_rows, n_cols,    \
                               (int64_t)nnz, Ap, Aj, Ax, X, ldx, Y, ldy, k, stream);                                    \
     }
 MI355_SPMV_DEFINE_MULTI(i32_f32, int32_t, MI355_OFF_I32, float, MI355_VAL_F32)
@@ -286,13 +342,13 @@ MI355_SPMV_DEFINE_MULTI(i64_f64, int64_t, MI355_OFF_I64, double, MI355_VAL_F64)
 #define MI355_SPMV_DEFINE_MULTI_GENL(SUF, OFF, OFFENUM, VAL, VALENUM)                                                  \
     int mi355_spmv_multi_genl_##SUF(int semiring, int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap, const int32_t* Aj, \
                                     const VAL* Ax, const VAL* X, int64_t ldx, VAL* Y, int64_t ldy, int32_t k, void* stream) { \
-        return multi_one_shot("multi_genl", true, OFFENUM, VALENUM, VALENUM, semiring, n_rows, n_cols, (int64_t)nnz, Ap, Aj, \
+        return multi_one_shot("multi_genl", kTyped, OFFENUM, VALENUM, VALENUM, semiring, n_rows, n_cols, (int64_t)nnz, Ap, Aj, \
                               Ax, X, ldx, Y, ldy, k, stream);                                                          \
     }                                                                                                                  \
     int mi355_spmv_multi_pattern_##SUF(int semiring, int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap,           \
                                        const int32_t* Aj, const VAL* X, int64_t ldx, VAL* Y, int64_t ldy, int32_t k,   \
                                        void* stream) {                                                                 \
-        return multi_one_shot("multi_pattern", true, OFFENUM, MI355_VAL_PATTERN, VALENUM, semiring, n_rows, n_cols,    \
+        return multi_one_shot("multi_pattern", kTyped, OFFENUM, MI355_VAL_PATTERN, VALENUM, semiring, n_rows, n_cols,    \
                               (int64_t)nnz, Ap, Aj, nullptr, X, ldx, Y, ldy, k, stream);                               \
     }
 MI355_SPMV_DEFINE_MULTI_GENL(i32_f32, int32_t, MI355_OFF_I32, float, MI355_VAL_F32)
@@ -302,6 +358,18 @@ MI355_SPMV_DEFINE_MULTI_GENL(i64_f32, int64_t, MI355_OFF_I64, float, MI355_VAL_F
 MI355_SPMV_DEFINE_MULTI_GENL(i64_f64, int64_t, MI355_OFF_I64, double, MI355_VAL_F64)
 MI355_SPMV_DEFINE_MULTI_GENL(i64_i32, int64_t, MI355_OFF_I64, int32_t, MI355_VAL_I32)
 
+// 16-bit vectors with the matrix in their type, (+, *): the arguments of mi355_spmv_multi_<off>_<val>
+#define MI355_SPMV_DEFINE_MULTI_HALF(SUF, OFF, OFFENUM, VALENUM)                                                       \
+    int mi355_spmv_multi_half_##SUF(int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap, const int32_t* Aj, const void* Ax, \
+                                    const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream) {       \
+        return multi_one_shot("multi_half", kHalf, OFFENUM, VALENUM, VALENUM, MI355_SEMIRING_PLUS_TIMES, n_rows, n_cols, \
+                              (int64_t)nnz, Ap, Aj, Ax, X, ldx, Y, ldy, k, stream);                                    \
+    }
+MI355_SPMV_DEFINE_MULTI_HALF(i32_f16, int32_t, MI355_OFF_I32, MI355_VAL_F16)
+MI355_SPMV_DEFINE_MULTI_HALF(i32_bf16, int32_t, MI355_OFF_I32, MI355_VAL_BF16)
+MI355_SPMV_DEFINE_MULTI_HALF(i64_f16, int64_t, MI355_OFF_I64, MI355_VAL_F16)
+MI355_SPMV_DEFINE_MULTI_HALF(i64_bf16, int64_t, MI355_OFF_I64, MI355_VAL_BF16)
+
 }  // extern "C"
 
-#endif  // MI355_MULTI_TU
+#endif  // MI355_MULTI_TU, MI355_MULTI_HALF_TU

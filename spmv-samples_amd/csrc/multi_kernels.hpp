@@ -336,6 +336,7 @@ struct MultiShape {
     int64_t carry_ld = 0;           // k_max rounded up to whole widest tiles
     int32_t* carry_row = nullptr;
     void* carry_val = nullptr;
+    void* tail_val = nullptr;       // 16-bit vectors only (multi_half_kernels.hpp): [n_slices][carry_ld] fp32
 };
 
 // the passes of one execute (tiles of the widest width, the last one as narrow as fits) and the fix-up
