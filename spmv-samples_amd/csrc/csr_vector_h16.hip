@@ -15,6 +15,7 @@
 // as before.
 
 #include "common.hpp"
+#include "half_convert.hpp"
 #include "row_dot.hpp"
 #include "row_launch.hpp"
 #include "xwindow.hpp"
@@ -85,15 +86,7 @@ __global__ __launch_bounds__(kBlock) void csr_vector_kernel(
     if (live && lane == 0) y[row] = (beta != 0.0f) ? alpha * sum + beta * y[row] : alpha * sum;
 }
 
-// fp32 -> binary16 / bfloat16, round to nearest even (overflow to +-inf, NaN stays NaN, subnormals kept)
-__device__ __forceinline__ _Float16 narrow_to(float v, _Float16) { return _Float16(v); }   // (v_cvt_f16_f32)
-__device__ __forceinline__ Bf16 narrow_to(float v, Bf16) {
-    unsigned u = __float_as_uint(v);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) u |= 0x00400000u;          // NaN: keep it one (quiet) when the payload's low bits go
-    else u += 0x7FFFu + ((u >> 16) & 1u);                            // nearest, ties to even; carries into the exponent up to inf
-    return Bf16{uint16_t(u >> 16)};
-}
-
+// fp32 -> binary16 / bfloat16 (half_convert.hpp's narrow_to)
 template <typename dst_t>
 __global__ __launch_bounds__(kBlock) void narrow_values_kernel(int64_t n, const float* __restrict__ src, dst_t* __restrict__ dst) {
     for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock)

@@ -122,188 +122,37 @@ __device__ __forceinline__ void store_row(const MultiArgs<val_t>& a, int64_t r, 
 
 // the reduction over all slots of a per-slot partial, in every lane of the column group (xor butterfly: the same bits
 // everywhere for a commutative reduce, which all five are)
-template <typename SR, typename val_t, int V, int C>
-__device__ __forceinline__ void reduce_slots(val_t (&v)[V]) {
+template <typename SR, typename acc_t, int V, int C>
+__device__ __forceinline__ void reduce_slots(acc_t (&v)[V]) {
 #pragma unroll
     for (int d = C; d < kWave; d <<= 1)
 #pragma unroll
         for (int j = 0; j < V; ++j) v[j] = SR::reduce(v[j], __shfl_xor(v[j], d));
 }
 
-// C = lanes per nonzero slot (16-byte column groups of the tile); the wave holds S = 64 / C slots
+// the typed kernels' policy (multi_slice_walk.inc says what a policy holds): everything in val_t, the values as stored or none (PATTERN), a row stored where it ends
+template <typename val_t, int SRI, bool PATTERN>
+struct MultiTypedPolicy {
+    using acc_t = val_t;
+    using SR = Semiring<SRI, val_t>;
+    using Args = MultiArgs<val_t>;
+    static constexpr int V = 16 / int(sizeof(val_t));
+    static constexpr bool kValued = !PATTERN, kMaskCombine = SRI != MI355_SEMIRING_PLUS_TIMES, kTails = false;
+    __device__ static __forceinline__ val_t ax(val_t v) { return v; }
+    __device__ static __forceinline__ void load_cols(val_t (&v)[V], const val_t* p, int nv, bool vec) {
+        mi355::load_cols<val_t, V>(v, p, nv, vec);
+    }
+    static constexpr bool kFields = false;
+    static constexpr val_t kAxFill = val_t(1);
+    __device__ static __forceinline__ void store_row(const Args& a, int64_t r, int c, const val_t (&sum)[V]) {
+        mi355::store_row<SRI, val_t, V>(a, r, c, sum);
+    }
+};
+
 template <typename off_t, typename val_t, int C, int SRI, bool PATTERN>
 __global__ __launch_bounds__(kBlock) void multi_slice_kernel(const MultiArgs<val_t> a, const off_t* __restrict__ Ap) {
-    using SR = Semiring<SRI, val_t>;
-    constexpr int V = 16 / int(sizeof(val_t));
-    constexpr int S = kWave / C;
-    // row offsets of the slice relative to its first nonzero, clamped to [0, nn + 1]: entry i belongs to row r0 + i
-    __shared__ int32_t rel_all[kMultiWaves][kMultiSlice + 2];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int c = lane % C, s = lane / C;
-    int32_t* rel = rel_all[threadIdx.x / kWave];
-    const int64_t w = int64_t(blockIdx.x) * kMultiWaves + threadIdx.x / kWave;
-    const bool active = w < a.n_slices;
-    int64_t r0 = 0, r1 = 0, n0 = 0;
-    int nr = -1, nn = 0;
-    if (active) {
-        // merge-path diagonals of the slice: lanes 0..31 search its start, lanes 32..63 its end.  Row end r comes before
-        // nonzero n iff Ap[r + 1] <= n; (r, n) = row ends and nonzeros in front of the diagonal.
-        const int64_t items = int64_t(a.n_rows) + a.nnz;
-        int64_t d = (lane < 32 ? w : w + 1) * kMultiSlice;
-        if (d > items) d = items;
-        int64_t lo = d > a.nnz ? d - a.nnz : 0, hi = d < a.n_rows ? d : a.n_rows;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (int64_t(Ap[mid + 1]) <= d - mid - 1) lo = mid + 1; else hi = mid;
-        }
-        const int64_t n = d - lo;
-        r0 = __shfl(lo, 0); r1 = __shfl(lo, 32);
-        n0 = __shfl(n, 0);
-        nn = int(__shfl(n, 32) - n0);
-        // rows r0 .. r_last have nonzeros or their end here (row r1, when there is one, does not end in this slice)
-        const int64_t r_last = r1 < a.n_rows ? r1 : int64_t(a.n_rows) - 1;
-        nr = int(r_last - r0) + 1;
-        for (int i = lane; i <= nr; i += kWave) {
-            const int64_t v = int64_t(Ap[r0 + i]) - n0;
-            rel[i] = v < 0 ? 0 : v > nn ? nn + 1 : int32_t(v);
-        }
-    }
-    __syncthreads();
-    if (!active) return;
-
-    val_t acc[V];           // per-slot partial of the open row (the row whose nonzeros are not all seen yet)
-#pragma unroll
-    for (int j = 0; j < V; ++j) acc[j] = SR::identity();
-    int open_i = -1;        // that row, relative to r0; -1 = none (acc is the identity)
-    int holder = -1;        // >= 0: acc is not the identity in this slot only; -2: spread over the slots
-    const int nv = min(max(a.cols - c * V, 0), V);
-
-    for (int base = 0; base < nn; base += kWave) {
-        // 64 nonzeros, one per lane, coalesced; each lane finds its nonzero's row in the slice's offsets
-        const int m = base + lane;
-        int32_t col = 0;
-        val_t ax = val_t(1);    // a PATTERN matrix's every entry; a valued one's is loaded below
-        int ie = nr * 2;    // row * 2 + (1 = this nonzero is the last of its row); nr = no nonzero
-        if (m < nn) {
-            col = a.Aj[n0 + m];
-            if constexpr (!PATTERN) ax = a.Ax[n0 + m];
-            int lo = 0, hi = nr - 1;
-            while (lo < hi) {           // the last i with rel[i] <= m (empty rows repeat an offset: the last is the owner)
-                const int mid = (lo + hi + 1) >> 1;
-                if (rel[mid] <= m) lo = mid; else hi = mid - 1;
-            }
-            ie = lo * 2 + (rel[lo + 1] == m + 1 ? 1 : 0);
-        }
-        const int left = nn - base;
-        const int steps = left >= kWave ? C : (left + S - 1) / S;
-        for (int t = 0; t < steps; ++t) {
-            // slot s takes nonzero t * S + s of the 64
-            int32_t col_s = col;
-            val_t ax_s = ax;
-            int ie_s = ie;
-            if constexpr (C > 1) {
-                const int src = t * S + s;
-                col_s = __shfl(col, src);
-                if constexpr (!PATTERN) ax_s = __shfl(ax, src);
-                ie_s = __shfl(ie, src);
-            }
-            const int i_s = ie_s >> 1;
-            val_t p[V];
-            if (i_s < nr) {
-                val_t xv[V];
-                load_cols<val_t, V>(xv, a.X + int64_t(col_s) * a.ldx + a.col_begin + c * V, nv, a.x_vec != 0);
-                if constexpr (SRI == MI355_SEMIRING_PLUS_TIMES) {
-                    // a masked column was loaded as 0 and (+, *)'s product with it is the identity already
-#pragma unroll
-                    for (int j = 0; j < V; ++j) p[j] = SR::combine(ax_s, xv[j]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < V; ++j) p[j] = j < nv ? SR::combine(ax_s, xv[j]) : SR::identity();
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < V; ++j) p[j] = SR::identity();
-            }
-            const int i_first = __shfl(ie_s, 0) >> 1;
-            const int ie_last = __shfl(ie_s, kWave - 1);
-            if (i_first == (ie_last >> 1) && !(ie_last & 1)) {
-                // every slot is inside one row, and the row goes on: partials stay per slot
-#pragma unroll
-                for (int j = 0; j < V; ++j) acc[j] = SR::reduce(acc[j], p[j]);
-                open_i = i_first;
-                holder = -2;
-                continue;
-            }
-            // a row ends in this step (or the slice does).  The open row's partial joins slot 0, whose nonzero is the
-            // next of that row; then a segmented inclusive scan over the slots reduces each row's run of products.
-            if (open_i >= 0) {
-                if (holder >= 0) {
-#pragma unroll
-                    for (int j = 0; j < V; ++j) acc[j] = __shfl(acc[j], holder * C + c);
-                } else {
-                    reduce_slots<SR, val_t, V, C>(acc);
-                }
-                if (s == 0) {
-#pragma unroll
-                    for (int j = 0; j < V; ++j) p[j] = SR::reduce(p[j], acc[j]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < V; ++j) acc[j] = SR::identity();
-            const int i_prev = __shfl_up(i_s, C);
-            const bool head = s == 0 || i_prev != i_s;
-            const unsigned long long heads = __ballot(head && c == 0);
-            const int start = 63 - __clzll(heads & (~0ull >> (63 - lane)));   // lane c == 0 of the slot that starts this run
-#pragma unroll
-            for (int d = C; d < kWave; d <<= 1) {
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const val_t o = __shfl_up(p[j], d);
-                    if (lane - c - d >= start) p[j] = SR::reduce(p[j], o);
-                }
-            }
-            const bool tail = s == S - 1 || ((heads >> (lane - c + C)) & 1ull);
-            if (i_s < nr && tail && (ie_s & 1)) store_row<SRI, val_t, V>(a, r0 + i_s, c, p);
-            // the last nonzero of the step: if its row goes on, its run's reduction is the new open partial
-            const int lv = min(S - 1, left - t * S - 1);
-            const int ie_lv = __shfl(ie_s, lv * C);
-            if (!(ie_lv & 1)) {
-                open_i = ie_lv >> 1;
-                holder = lv;
-                if (s == lv) {
-#pragma unroll
-                    for (int j = 0; j < V; ++j) acc[j] = p[j];
-                }
-            } else {
-                open_i = -1;
-                holder = -1;
-            }
-        }
-    }
-
-    // the carry: what this slice holds of a row that ends in a later one
-    if (open_i >= 0) {
-        if (holder >= 0) {
-#pragma unroll
-            for (int j = 0; j < V; ++j) acc[j] = __shfl(acc[j], holder * C + c);
-        } else {
-            reduce_slots<SR, val_t, V, C>(acc);
-        }
-        if (s == 0) {
-            val_t* cv = a.carry_val + w * a.carry_ld + a.col_begin + c * V;    // (carry_ld covers whole tiles)
-#pragma unroll
-            for (int j = 0; j < V; ++j) cv[j] = acc[j];
-        }
-    }
-    if (lane == 0) a.carry_row[w] = open_i >= 0 ? int32_t(r0 + open_i) : -1;
-
-    // empty rows whose end lies in this slice: the identity ((+, *): Y = beta * Y); a row with nonzeros is stored where
-    // its last one is
-    val_t none[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) none[j] = SR::identity();
-    for (int64_t r = r0 + s; r < r1; r += S)
-        if (Ap[r] == Ap[r + 1]) store_row<SRI, val_t, V>(a, r, c, none);
+    using P = MultiTypedPolicy<val_t, SRI, PATTERN>;
+#include "multi_slice_walk.inc"
 }
 
 // one thread per (slice, column): the first slice that carries a row reduces all its carries, in slice order, into Y
@@ -339,37 +188,54 @@ struct MultiShape {
     void* tail_val = nullptr;       // 16-bit vectors only (multi_half_kernels.hpp): [n_slices][carry_ld] fp32
 };
 
-// the passes of one execute (tiles of the widest width, the last one as narrow as fits) and the fix-up
-template <typename off_t, typename val_t, int SRI, bool PATTERN>
-int launch_multi(const MultiShape& m, const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, hipStream_t s) {
-    if (m.n_slices == 0) return MI355_SPMV_OK;      // no rows: nothing to write
-    constexpr int V = 16 / int(sizeof(val_t));
-    constexpr int kWidest = V * kMultiGroupsMax;
-    MultiArgs<val_t> a;
+// what both argument structs (MultiArgs, mh::MultiHalfArgs) hold alike, of the object and of one execute's operands
+template <typename Args, typename vec_t>
+void multi_fill_args(Args& a, const MultiShape& m, const void* X, int64_t ldx, void* Y, int64_t ldy) {
     a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
-    a.Aj = m.Aj; a.Ax = PATTERN ? nullptr : static_cast<const val_t*>(Ax);
-    a.X = static_cast<const val_t*>(X); a.Y = static_cast<val_t*>(Y);
+    a.Aj = m.Aj;
+    a.X = static_cast<const vec_t*>(X); a.Y = static_cast<vec_t*>(Y);
     a.ldx = ldx; a.ldy = ldy;
-    a.x_vec = (reinterpret_cast<uintptr_t>(X) % 16 == 0 && (size_t(ldx) * sizeof(val_t)) % 16 == 0) ? 1 : 0;
-    a.y_vec = (reinterpret_cast<uintptr_t>(Y) % 16 == 0 && (size_t(ldy) * sizeof(val_t)) % 16 == 0) ? 1 : 0;
-    a.alpha = val_t(m.alpha); a.beta = val_t(m.beta);
-    a.carry_row = m.carry_row; a.carry_val = static_cast<val_t*>(m.carry_val); a.carry_ld = m.carry_ld;
-    const off_t* Ap = static_cast<const off_t*>(m.Ap);
-    const dim3 grid(unsigned((m.n_slices + kMultiWaves - 1) / kMultiWaves)), block(kBlock);
+    a.x_vec = (reinterpret_cast<uintptr_t>(X) % 16 == 0 && (size_t(ldx) * sizeof(vec_t)) % 16 == 0) ? 1 : 0;
+    a.y_vec = (reinterpret_cast<uintptr_t>(Y) % 16 == 0 && (size_t(ldy) * sizeof(vec_t)) % 16 == 0) ? 1 : 0;
+    a.alpha = decltype(a.alpha)(m.alpha); a.beta = decltype(a.beta)(m.beta);
+    a.carry_row = m.carry_row; a.carry_val = static_cast<decltype(a.carry_val)>(m.carry_val); a.carry_ld = m.carry_ld;
+}
+
+// the passes of one execute: tiles of V * kMultiGroupsMax columns, the last one as narrow as fits.  slice(lanes) launches
+// the slice kernel of C = lanes::value lanes per slot on the tile that a.col_begin / a.cols describe.
+template <int V, typename Args, typename Slice>
+int multi_passes(Args& a, int32_t k, Slice slice) {
+    constexpr int kWidest = V * kMultiGroupsMax;
     for (int32_t cb = 0; cb < k; cb += kWidest) {
         a.col_begin = cb;
         a.cols = std::min<int32_t>(k - cb, kWidest);
         const int groups = (a.cols + V - 1) / V;
-        if (groups <= 1) hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, 1, SRI, PATTERN>), grid, block, 0, s, a, Ap);
-        else if (groups <= 2) hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, 2, SRI, PATTERN>), grid, block, 0, s, a, Ap);
-        else if (groups <= 4) hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, 4, SRI, PATTERN>), grid, block, 0, s, a, Ap);
-        else hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, 8, SRI, PATTERN>), grid, block, 0, s, a, Ap);
+        if (groups <= 1) slice(std::integral_constant<int, 1>());
+        else if (groups <= 2) slice(std::integral_constant<int, 2>());
+        else if (groups <= 4) slice(std::integral_constant<int, 4>());
+        else slice(std::integral_constant<int, 8>());
         MI355_HIP_TRY(hipGetLastError());
     }
+    return MI355_SPMV_OK;
+}
+
+// the slice passes and the fix-up
+template <typename off_t, typename val_t, int SRI, bool PATTERN>
+int launch_multi(const MultiShape& m, const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, hipStream_t s) {
+    if (m.n_slices == 0) return MI355_SPMV_OK;      // no rows: nothing to write
+    MultiArgs<val_t> a;
+    multi_fill_args<MultiArgs<val_t>, val_t>(a, m, X, ldx, Y, ldy);
+    a.Ax = PATTERN ? nullptr : static_cast<const val_t*>(Ax);
+    const off_t* Ap = static_cast<const off_t*>(m.Ap);
+    const dim3 grid(unsigned((m.n_slices + kMultiWaves - 1) / kMultiWaves)), block(kBlock);
+    if (const int st = multi_passes<16 / int(sizeof(val_t))>(a, k, [&](auto lanes) {
+            hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, decltype(lanes)::value, SRI, PATTERN>), grid, block, 0, s, a, Ap);
+        }))
+        return st;
     if (m.n_slices > 1) {
         const int64_t threads = m.n_slices * k;
         hipLaunchKernelGGL((multi_fixup_kernel<val_t, SRI>), dim3(unsigned((threads + kBlock - 1) / kBlock)), block, 0, s,
-                           m.n_slices, k, m.carry_row, static_cast<const val_t*>(m.carry_val), m.carry_ld, a.Y, ldy, a.alpha);
+                           m.n_slices, k, m.carry_row, a.carry_val, m.carry_ld, a.Y, ldy, a.alpha);
         MI355_HIP_TRY(hipGetLastError());
     }
     return MI355_SPMV_OK;

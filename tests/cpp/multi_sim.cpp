@@ -16,49 +16,17 @@
 // element outside is a report.  Padding columns of X hold NaN, of Y a canary; with y0_nan the k columns of Y hold NaN.
 // A result is: status, count = n_rows * ldy, then Y as count values (the missing tail of the last row as canary).
 #include <cmath>
-#include <cstdarg>
 #include <limits>
 #include <vector>
 
 #include "../../spmv-samples_amd/csrc/multi.hip"
 
-namespace mi355 {
-static char g_error[512];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-}  // namespace mi355
-extern "C" int mi355_spmv_stream_synchronize(void*) { return MI355_SPMV_OK; }
+#define SIM_NAME "multi_sim"
+#include "sim_io.hpp"
 
 namespace {
 
 constexpr double kCanary = -777.25;
-
-struct Buf {    // an allocation whose base is `off` elements past a 64-byte boundary
-    void* raw = nullptr;
-    char* p = nullptr;
-    void alloc(size_t elems, size_t elem_bytes, size_t off) {
-        release();
-        if (posix_memalign(&raw, 64, (elems + off) * elem_bytes + (elems + off == 0)) != 0) { perror("multi_sim: allocation"); exit(4); }
-        p = static_cast<char*>(raw) + off * elem_bytes;
-    }
-    void release() { free(raw); raw = nullptr; p = nullptr; }
-    ~Buf() { release(); }
-};
-
-FILE* g_in;
-FILE* g_out;
-
-void get(void* dst, size_t bytes) {
-    if (bytes && fread(dst, 1, bytes, g_in) != bytes) { fprintf(stderr, "multi_sim: batch file ends inside a record\n"); exit(4); }
-}
-int64_t word() { int64_t v; get(&v, 8); return v; }
-void put(const void* src, size_t bytes) {
-    if (bytes && fwrite(src, 1, bytes, g_out) != bytes) { perror("multi_sim: write"); exit(4); }
-}
 
 struct State {
     int off_type = 0, val_type = 0;

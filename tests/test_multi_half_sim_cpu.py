@@ -19,15 +19,12 @@ TIME_LIMIT = 900        # seconds per child
 
 
 def build():
-    """The program, by the rule of tests/cpp/multi_half_sim.mk (the Makefile's SIM_SAN flags).  Skips only where the
-    host compiler cannot link with those flags at all; any other failure to build is a failure."""
+    """The program, by the rule of tests/cpp/Makefile (its SIM_SAN flags).  Skips only where the host compiler cannot
+    link with those flags at all; any other failure to build is a failure."""
     probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
     if probe.returncode != 0:
         pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    # the two older programs too: their own rules do not know every header that multi.hip has come to include, so one
-    # built before an edit to them would be stale when its test file (which runs after this one) asks for it
-    subprocess.run(["make", "-s", "-j3", "-C", CPP, "-f", "multi_half_sim.mk", "multi_half_sim", "multi_semiring_sim", "multi_sim"],
-                   check=True)
+    subprocess.run(["make", "-s", "-C", CPP, "multi_half_sim"], check=True)
     return os.path.join(CPP, "multi_half_sim")
 
 

@@ -9,8 +9,7 @@ Nothing is loaded into this process, and the children's environment is this proc
 linked statically).
 
 Cost: the table's ~3 000 executes run as concurrent child processes (at most 8): about a minute on 8 cores, plus the
-compilation once (every instantiation of the kernels: about four minutes; multi_sim, which tests/test_multi_sim_cpu.py
-runs, is brought up to date beside it in the same make call, so the two programs compile side by side)."""
+compilation once (every instantiation of the kernels: about four minutes)."""
 import os
 import subprocess
 
@@ -25,14 +24,12 @@ TIME_LIMIT = 900        # seconds per child
 
 
 def build():
-    """The program, by the rule of tests/cpp/multi_semiring_sim.mk (the Makefile's SIM_SAN flags).  Skips only where the
-    host compiler cannot link with those flags at all; any other failure to build is a failure."""
+    """The program, by the rule of tests/cpp/Makefile (its SIM_SAN flags).  Skips only where the host compiler cannot
+    link with those flags at all; any other failure to build is a failure."""
     probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
     if probe.returncode != 0:
         pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    # multi_sim too: the Makefile's own rule does not know the headers that multi.hip has come to include, so a multi_sim
-    # built before an edit to them would be stale when tests/test_multi_sim_cpu.py (which runs after this file) asks for it
-    subprocess.run(["make", "-s", "-j2", "-C", CPP, "-f", "multi_semiring_sim.mk", "multi_semiring_sim", "multi_sim"], check=True)
+    subprocess.run(["make", "-s", "-C", CPP, "multi_semiring_sim"], check=True)
     return os.path.join(CPP, "multi_semiring_sim")
 
 
