@@ -1,0 +1,49 @@
+#!/usr/bin/env bash
+# device_asm_diff.sh — is the gfx950 device code of the row and merge kinds the same in two source trees?
+#
+#   scripts/device_asm_diff.sh emit <csrc dir> <out dir>     one <unit>.s per translation unit, with the Makefile's flags
+#   scripts/device_asm_diff.sh diff <out dir A> <out dir B>  compares them, one line per unit; exit 1 if any differs
+#
+# A refactor of xwindow.hpp / row_launch.hpp or of a file that includes them is checked this way instead of being
+# timed: `emit` on a checkout of the parent and on the working tree, then `diff`.  Comments, .file / .loc / .ident lines
+# and debug sections are dropped before the comparison, and the compilation unit's id (a hash of its path) is blanked.
+set -euo pipefail
+
+UNITS="csr_vector csr_vector_f64 csr_vector_h16 light_rows light_rows_f64 merge_path_f32 merge_path_f64 merge_path_i32 merge_path_pattern rows_plan"
+HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+HIPFLAGS=${HIPFLAGS:--O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function}
+JOBS=${JOBS:-4}
+
+strip_asm() {   # comments, file / line records, debug sections, blank lines; the unit id is a hash of the file's path
+    sed -e 's/[[:space:]]*;.*$//' -e 's/__hip_cuid_[0-9a-f]*/__hip_cuid/g' -e '/^[[:space:]]*\.\(file\|loc\|ident\)[[:space:]]/d' "$1" |
+        awk '/^[[:space:]]*\.section[[:space:]]+\.debug/ { skip = 1; next }
+             /^[[:space:]]*\.(section|text|data|rodata|amdgpu_metadata)/ { skip = 0 }
+             !skip && NF'
+}
+
+case "${1:-}" in
+emit)
+    src=$(cd "$2" && pwd)
+    mkdir -p "$3"
+    out=$(cd "$3" && pwd)
+    cd "$src"
+    # shellcheck disable=SC2086
+    printf '%s\n' $UNITS | xargs -P "$JOBS" -I{} $HIPCC $HIPFLAGS --cuda-device-only -S {}.hip -o "$out/{}.s"
+    ;;
+diff)
+    status=0
+    for u in $UNITS; do
+        if cmp -s <(strip_asm "$2/$u.s") <(strip_asm "$3/$u.s"); then
+            echo "$u: identical ($(strip_asm "$2/$u.s" | wc -l) lines)"
+        else
+            echo "$u: DIFFERS ($(diff <(strip_asm "$2/$u.s") <(strip_asm "$3/$u.s") | grep -c '^[<>]' || true) diff lines)"
+            status=1
+        fi
+    done
+    exit $status
+    ;;
+*)
+    sed -n '2,9p' "$0"
+    exit 2
+    ;;
+esac

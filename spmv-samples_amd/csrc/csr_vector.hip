@@ -13,6 +13,9 @@
 // The 4-byte-per-lane kernel csr_vector_kernel is the form of the reference
 // (one row per vector, grid = ceil(rows / vectors per block), cusp_warp_reduce.cuh:70-87);
 // it runs small matrices of either kind (rows_plan.hip, shape_rows) and operands that are not 16-byte aligned.
+// Here a kernel is how a workgroup gets its rows; from there to the chunk body (xwindow.hpp) the text is shared with LIGHT
+// and the 16-bit kernels and included: row_chunk_window.inc, row_chunk_sweep.inc.  The plain kernel's body is
+// row_dot.hpp's plain_rows, its launch row_launch.hpp's launch_plain_rows.
 
 #include <cstdlib>
 
@@ -53,38 +56,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock || R == 2 ? 4 : 3)) voi
     int64_t rb, re;
     cmap.range(chunk, n_rows, rb, re);
     if (rb >= re) return;   // (balanced plans: a hub row heavier than a chunk leaves empty chunks behind it)
-    bool fits;
-    const int64_t base = stage_chunk_bounds<val_t>(scr, rb, re, Ap, cmap.rel_limit, fits);
-    if (!fits) {            // (uniform) more nonzeros than 32-bit chunk-relative offsets reach
-        chunk_rows_wide<BLOCK, val_t>(rb, re, Ap, Aj, Ax, x, y, alpha, beta, cmap.giant_len);
-        return;
-    }
-    __syncthreads();
-    const int32_t* const Aj_c = Aj + base;       // the chunk's view: element 0 = its first 16-byte group
-    const val_t* const Ax_c = Ax + base;
-    const int64_t left = nnz - base;
-    const int32_t nnz_c = int32_t(left < kRel32Limit + 32768 ? left : kRel32Limit + 32768);
-    // the window is staged inside chunk_rows, behind the first group's stream loads
-    if constexpr (NSEG > 1) {
-        auto stage = [&] { return stage_x_segments<val_t>(rb, re, n_cols, x, scr.s_x, window_cap, segs); };
-        chunk_rows_any<BLOCK, T, R, true, ADAPT, val_t>(rb, re, nnz_c, Aj_c, Ax_c, x, y, stage, scr);
-    } else {
-        auto first_last = [&](int64_t r, int& first, int& last) {
-            const int32_t s = scr.s_b[r - rb], e = scr.s_b[r - rb + 1];
-            if (e <= s) return false;
-            first = Aj_c[s];
-            last = Aj_c[e - 1];
-            return true;
-        };
-        auto stage = [&] {
-            return stage_x_window<val_t>(rb, re, n_cols, first_last, x, scr.s_x, window_cap, s_red, hint);
-        };
-        if constexpr (PACKED)   // (hint.use holds: the window staged is the one the index was encoded against)
-            chunk_rows_any<BLOCK, T, R, true, false, val_t, decltype(stage)&, false, true>(rb, re, nnz_c, Aj_c, Ax_c, x, y, stage,
-                                                                                          scr, Aj16 + base);
-        else
-            chunk_rows_any<BLOCK, T, R, NSEG == 1, ADAPT, val_t>(rb, re, nnz_c, Aj_c, Ax_c, x, y, stage, scr);
-    }
+    using mat_t = val_t;
+    constexpr bool kBarrierAfterWide = false;
+#include "row_chunk_window.inc"
 }
 
 // The band is wider than any window of x: one 1 024-thread workgroup per CU, a chunk = one group of rows held in
@@ -102,39 +76,14 @@ __global__ __launch_bounds__(kHugeBlock, 4) void csr_vector_sweep_kernel(
     int64_t rb, re;
     cmap.range(chunk, n_rows, rb, re);
     if (rb >= re) return;
-    bool fits;
-    const int64_t base = stage_chunk_bounds<val_t>(scr, rb, re, Ap, cmap.rel_limit, fits);
-    if (!fits) {
-        chunk_rows_wide<kHugeBlock, val_t>(rb, re, Ap, Aj, Ax, x, y, alpha, beta, 0);
-        return;
-    }
-    __syncthreads();
-    const int64_t left = nnz - base;
-    const int32_t nnz_c = int32_t(left < kRel32Limit + 32768 ? left : kRel32Limit + 32768);
-    // (a persistent workgroup per CU walking its share of the chunks measured WORSE, 194 vs 187 us at two passes,
-    // 438 vs 358 at seven: the hardware dispatcher's refill costs less than the registers the loop does)
-    chunk_rows_sweep<kHugeBlock, T, R, val_t>(rb, re, nnz_c, Aj + base, Ax + base, x, y, n_cols, window_cap, hint, scr);
+#include "row_chunk_sweep.inc"
 }
 
 template <int T, typename off_t, typename val_t>
 __global__ __launch_bounds__(kBlock) void csr_vector_kernel(
     int32_t n_rows, off_t nnz, const off_t* __restrict__ Ap, const int32_t* __restrict__ Aj,
     const val_t* __restrict__ Ax, const val_t* __restrict__ x, val_t* __restrict__ y, val_t alpha, val_t beta) {
-    constexpr int ROWS_PER_BLOCK = kBlock / T;
-    const unsigned blk = xcd_contiguous_id(blockIdx.x, gridDim.x);
-    const int lane = threadIdx.x & (T - 1);
-    const int64_t row = int64_t(blk) * ROWS_PER_BLOCK + (threadIdx.x / T);
-    const bool live = row < n_rows;
-    // a vector past the last row runs as an empty row so that every lane of the
-    // wave reaches the shuffles below
-    off_t start = 0, end = 0;
-    if (live) {
-        start = Ap[row];
-        end = Ap[row + 1];
-    }
-    val_t sum = row_partial<T, off_t, val_t>(start, end, lane, Aj, Ax, x);
-    sum = vector_reduce<T, val_t>(sum);
-    if (live && lane == 0) y[row] = (beta != val_t(0)) ? alpha * sum + beta * y[row] : alpha * sum;
+    plain_rows<T, off_t, val_t>(n_rows, Ap, Aj, Ax, x, y, alpha, beta);
 }
 
 // VECTOR's kernels for the launch path it shares with LIGHT (row_launch.hpp): a workgroup takes the chunk of its index
@@ -156,14 +105,8 @@ struct VectorRows {
 // the plain kernel over the plan's rows, its grid from the row count (both kinds' small matrices: rows_plan.hip, shape_rows)
 template <typename off_t, typename val_t>
 int launch_vector_plain(const Plan& p, const off_t* Ap, const val_t* Ax, const val_t* x, val_t* y, hipStream_t s) {
-    return with_lanes(p, VectorRows::name, [&](auto lanes) -> int {
-        constexpr int T = decltype(lanes)::value, rows_per_block = kBlock / T;
-        const dim3 grid((unsigned)((int64_t(p.n_rows) + rows_per_block - 1) / rows_per_block)), block(kBlock);
-        hipLaunchKernelGGL((csr_vector_kernel<T, off_t, val_t>), grid, block, 0, s, p.n_rows, (off_t)p.nnz, Ap, p.Aj, Ax, x, y,
-                           (val_t)p.alpha, (val_t)p.beta);
-        MI355_HIP_TRY(hipGetLastError());
-        return MI355_SPMV_OK;
-    });
+    return launch_plain_rows(p, VectorRows::name, Ap, Ax, x, y, s,
+                             [](auto lanes) { return csr_vector_kernel<decltype(lanes)::value, off_t, val_t>; });
 }
 
 // One translation unit per value type (csr_vector_f64.hip includes this file with MI355_TU_F64): the two

@@ -12,7 +12,8 @@
 // 4-byte-per-lane kernel below, which is right for any CSR.  The kernels are csr_vector.hip's two, for a stored type of
 // their own, in a namespace of their own: a template argument is part of a kernel's name, so a mat_t on the fp32 / fp64
 // kernels themselves would rename every one of them; as it is their translation units compile to the same device code
-// as before.
+// as before.  Only the kernels' heads are written here: the window kernel's text from its rows to the chunk body is
+// row_chunk_window.inc, the plain kernel's body is row_dot.hpp's plain_rows, both over mat_t.
 
 #include "common.hpp"
 #include "half_convert.hpp"
@@ -43,27 +44,10 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock || R == 2 ? 4 : 3)) voi
     int64_t rb, re;
     cmap.range(chunk, n_rows, rb, re);
     if (rb >= re) return;
-    bool fits;
-    const int64_t base = stage_chunk_bounds<float>(scr, rb, re, Ap, cmap.rel_limit, fits);
-    if (!fits) {            // (uniform) more nonzeros than 32-bit chunk-relative offsets reach
-        chunk_rows_wide<BLOCK, float>(rb, re, Ap, Aj, Ax, x, y, alpha, beta, cmap.giant_len);
-        return;
-    }
-    __syncthreads();
-    const int32_t* const Aj_c = Aj + base;       // the chunk's view: element 0 = its first group (base is a multiple of 4)
-    const mat_t* const Ax_c = Ax + base;
-    const int64_t left = nnz - base;
-    const int32_t nnz_c = int32_t(left < kRel32Limit + 32768 ? left : kRel32Limit + 32768);
-    auto first_last = [&](int64_t r, int& first, int& last) {
-        const int32_t s = scr.s_b[r - rb], e = scr.s_b[r - rb + 1];
-        if (e <= s) return false;
-        first = Aj_c[s];
-        last = Aj_c[e - 1];
-        return true;
-    };
-    auto stage = [&] { return stage_x_window<float>(rb, re, n_cols, first_last, x, scr.s_x, window_cap, s_red, hint); };
-    chunk_rows_any<BLOCK, T, R, NSEG == 1, false, float, decltype(stage)&, false, PACKED>(rb, re, nnz_c, Aj_c, Ax_c, x, y, stage, scr,
-                                                                                          PACKED ? Aj16 + base : nullptr);
+    using val_t = float;
+    constexpr bool ADAPT = false, kBarrierAfterWide = false;
+    const SegmentPlan segs{};   // (named by the shared text where NSEG > 1, which no kernel here is)
+#include "row_chunk_window.inc"
 }
 
 // ... and its csr_vector_kernel: one row per T-lane vector, 4-byte (here 2-byte) loads per lane, any CSR
@@ -71,19 +55,7 @@ template <int T, typename off_t, typename mat_t>
 __global__ __launch_bounds__(kBlock) void csr_vector_kernel(
     int32_t n_rows, off_t nnz, const off_t* __restrict__ Ap, const int32_t* __restrict__ Aj,
     const mat_t* __restrict__ Ax, const float* __restrict__ x, float* __restrict__ y, float alpha, float beta) {
-    constexpr int ROWS_PER_BLOCK = kBlock / T;
-    const unsigned blk = xcd_contiguous_id(blockIdx.x, gridDim.x);
-    const int lane = threadIdx.x & (T - 1);
-    const int64_t row = int64_t(blk) * ROWS_PER_BLOCK + (threadIdx.x / T);
-    const bool live = row < n_rows;
-    off_t start = 0, end = 0;   // (a vector past the last row runs as an empty row: every lane reaches the shuffles)
-    if (live) {
-        start = Ap[row];
-        end = Ap[row + 1];
-    }
-    float sum = row_partial<T, off_t, float>(start, end, lane, Aj, Ax, x);
-    sum = vector_reduce<T, float>(sum);
-    if (live && lane == 0) y[row] = (beta != 0.0f) ? alpha * sum + beta * y[row] : alpha * sum;
+    plain_rows<T, off_t, float>(n_rows, Ap, Aj, Ax, x, y, alpha, beta);
 }
 
 // fp32 -> binary16 / bfloat16 (half_convert.hpp's narrow_to)
@@ -97,18 +69,6 @@ struct Rows {   // (what launch_chunked asks of a kind)
     static constexpr const char* name = "csr_vector (16-bit matrix)";
     static constexpr bool kCounters = false;
 };
-
-template <typename off_t, typename mat_t>
-static int launch_plain(const Plan& p, const off_t* Ap, const mat_t* Ax, const float* x, float* y, hipStream_t s) {
-    return with_lanes(p, Rows::name, [&](auto lanes) -> int {
-        constexpr int T = decltype(lanes)::value, rows_per_block = kBlock / T;
-        const dim3 grid((unsigned)((int64_t(p.n_rows) + rows_per_block - 1) / rows_per_block)), block(kBlock);
-        hipLaunchKernelGGL((csr_vector_kernel<T, off_t, mat_t>), grid, block, 0, s, p.n_rows, (off_t)p.nnz, Ap, p.Aj, Ax, x, y,
-                           (float)p.alpha, (float)p.beta);
-        MI355_HIP_TRY(hipGetLastError());
-        return MI355_SPMV_OK;
-    });
-}
 
 // row_launch.hpp's launch_rows_window for the shapes built here
 template <int BLOCK, typename mat_t>
@@ -139,7 +99,8 @@ int launch_vector_half(const Plan& p, const off_t* Ap, const mat_t* Ax, const fl
     const bool aligned = ((reinterpret_cast<uintptr_t>(p.Aj) | reinterpret_cast<uintptr_t>(x)) & 15u) == 0 &&
                          (reinterpret_cast<uintptr_t>(Ax) & 7u) == 0;
     if (!half_matrix_chunked(p) || !aligned || p.nnz < 4 || (p.knob.plain != 0 && !p.is_block))
-        return h16::launch_plain<off_t, mat_t>(p, Ap, Ax, x, y, s);
+        return launch_plain_rows(p, h16::Rows::name, Ap, Ax, x, y, s,
+                                 [](auto lanes) { return h16::csr_vector_kernel<decltype(lanes)::value, off_t, mat_t>; });
     const RowOperands<float, mat_t> o{p, ApView{Ap, sizeof(off_t) == 8 ? 1 : 0}, Ax, x, y, s,
                                       chunk_lds_bytes(p.window_elems, p.rows_cap, sizeof(float))};
     return p.block_threads == kHugeBlock   ? h16::launch_window<kHugeBlock, mat_t>(o)

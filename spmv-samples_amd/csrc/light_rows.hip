@@ -30,6 +30,10 @@
 //  * x is read with plain loads / the LDS window (no texture path on CDNA; the
 //    reference's texture fetch, LightSpMV.cuh:59-88, has no counterpart).
 //
+// A chunk's way from its rows to the chunk body is the text VECTOR's kernels include (row_chunk_window.inc,
+// row_chunk_sweep.inc), here behind opaque copies of the operand pointers; the single dequeue of equal-row chunks is
+// light_dequeue_once, for the window and the sweep kernel.
+//
 // Exit condition: a workgroup drains its own shard, asks once which other shards still
 // hold rows, visits those and leaves; a visit ends on the first dequeue at or past the
 // shard's end, which every workgroup reaches whatever the interleaving, so the grid
@@ -86,6 +90,32 @@ __device__ __forceinline__ void light_leave(unsigned long long* __restrict__ cou
     }
 }
 
+// Equal-row chunks, one dequeue per workgroup (light_rows_window_kernel without ADAPT, light_rows_sweep_kernel): the
+// workgroup's chunk, or -1.  static_mode: the chunk of its index, the counters are not touched.  Otherwise it starts on
+// the shard of its XCD (neighbouring chunks share windows of x in that L2) and tries the other shards if that one is dry;
+// there are exactly as many workgroups as chunks, so everybody finds one.  All threads call; s_got is the kernel's LDS word.
+__device__ __forceinline__ int64_t light_dequeue_once(const ChunkMap& cmap, unsigned long long* __restrict__ counters,
+                                                      unsigned long long& s_got, bool static_mode) {
+    const int home = blockIdx.x % kXcds;
+    int64_t chunk = -1;
+    if (static_mode) {
+        chunk = xcd_contiguous_id(blockIdx.x, gridDim.x);
+        if (chunk >= cmap.n_chunks) chunk = -1;
+    } else {
+        for (int visit = 0; visit < kXcds && chunk < 0; ++visit) {   // (uniform over the workgroup)
+            const int shard = (home + visit) % kXcds;
+            const int64_t shard_begin = cmap.n_chunks * shard / kXcds;          // in chunks
+            const int64_t shard_end = cmap.n_chunks * (shard + 1) / kXcds;
+            if (threadIdx.x == 0) s_got = atomicAdd(&counters[shard * kCounterStride], 1ull);
+            __syncthreads();
+            const int64_t c = shard_begin + int64_t(wave_broadcast_u64(s_got));
+            if (c < shard_end) chunk = c;
+            __syncthreads();          // s_got read by all before the next shard's dequeue overwrites it
+        }
+    }
+    return chunk;
+}
+
 // (512 threads: two workgroups per CU need 4 waves per SIMD, i.e. <= 128 VGPRs; 256 threads: three workgroups
 // per CU need 3 waves per SIMD, <= 168 VGPRs.)  Like the CSR-vector kernel this one does not depend on the
 // width of the row offsets: a chunk is walked with 32-bit offsets relative to its first nonzero.
@@ -105,7 +135,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock || R == 2 ? 4 : 3)) voi
     scr.long_steps = cmap.long_steps;
     scr.giant_len = cmap.giant_len;
     // the body of one chunk (all threads; ends with the results swept to y)
-    auto run_chunk = [&](int64_t chunk_begin, int64_t chunk_end) {
+    auto run_chunk = [&](int64_t rb, int64_t re) {
         // Opaque copies of the operand pointers, once per chunk: without them every per-thread address the chunk
         // body derives from a kernel argument is a loop invariant of the persistent loop, gets computed once up
         // front, lives in VGPRs across the whole body and is spilled (the same body in the one-chunk-per-workgroup
@@ -117,67 +147,22 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock || R == 2 ? 4 : 3)) voi
         const val_t* Ax = Ax_arg + zero;
         const val_t* x = x_arg + zero;
         val_t* y = y_arg + zero;
-        bool fits;
-        const int64_t base = stage_chunk_bounds<val_t>(scr, chunk_begin, chunk_end, Ap, cmap.rel_limit, fits);
-        if (!fits) {          // (uniform) more nonzeros than 32-bit chunk-relative offsets reach
-            chunk_rows_wide<BLOCK, val_t>(chunk_begin, chunk_end, Ap, Aj, Ax, x, y, alpha, beta, cmap.giant_len);
-            __syncthreads();
-            return;
-        }
-        __syncthreads();      // (also orders the read of s_got before the next dequeue writes it)
-        const int32_t* const Aj_c = Aj + base;
-        const val_t* const Ax_c = Ax + base;
-        const int64_t left = nnz - base;
-        const int32_t nnz_c = int32_t(left < kRel32Limit + 32768 ? left : kRel32Limit + 32768);
-        // the window is staged inside chunk_rows, behind the first group's stream loads
-        if constexpr (NSEG > 1) {
-            auto stage = [&] {
-                return stage_x_segments<val_t>(chunk_begin, chunk_end, n_cols, x, scr.s_x, window_cap, segs);
-            };
-            chunk_rows_any<BLOCK, T, R, true, ADAPT, val_t>(chunk_begin, chunk_end, nnz_c, Aj_c, Ax_c, x, y, stage, scr);
-        } else {
-            auto first_last = [&](int64_t r, int& first, int& last) {
-                const int32_t s = scr.s_b[r - chunk_begin], e = scr.s_b[r - chunk_begin + 1];
-                if (e <= s) return false;
-                first = Aj_c[s];
-                last = Aj_c[e - 1];
-                return true;
-            };
-            auto stage = [&] {
-                return stage_x_window<val_t>(chunk_begin, chunk_end, n_cols, first_last, x, scr.s_x, window_cap, s_red, hint);
-            };
-            chunk_rows_any<BLOCK, T, R, NSEG == 1, ADAPT, val_t>(chunk_begin, chunk_end, nnz_c, Aj_c, Ax_c, x, y, stage, scr);
-        }
+        using mat_t = val_t;
+        constexpr bool PACKED = false, kBarrierAfterWide = true;
+        const uint16_t* const Aj16 = nullptr;   // (VECTOR only: LIGHT plans hold no packed index)
+#include "row_chunk_window.inc"
     };
     // static_mode — few chunks per workgroup slot (small matrices): there is nothing to balance, every workgroup
     // takes the chunk of its index and the counters are not touched (the dequeue costs two dependent atomics
     // and a shard poll per workgroup: 32 vs 14 us on 2^17 rows).
     const bool static_mode = cmap.n_chunks <= int64_t(gridDim.x) && !cmap.dequeue_once;
-    const int home = blockIdx.x % kXcds;
     if constexpr (!ADAPT) {
         // Equal-row chunks (uniform matrices): ONE dequeue per workgroup, as many workgroups as chunks.  The
         // rows are still handed out by the global counters in arrival order — LightSpMV's scheme — but the loop
         // that keeps a persistent workgroup alive is the hardware dispatcher's: the body then compiles like the
         // CSR-vector kernel's (no loop-carried state: 127 instead of 168+ VGPRs, so the 512-thread plan fits
-        // two workgroups per CU), and chunks of equal cost need no stealing.  A workgroup starts on the shard of
-        // its XCD (neighbouring chunks share windows of x in that L2) and tries the other shards if it is dry;
-        // there are exactly as many workgroups as chunks, so everybody finds one.
-        int64_t chunk = -1;
-        if (static_mode) {
-            chunk = xcd_contiguous_id(blockIdx.x, gridDim.x);
-            if (chunk >= cmap.n_chunks) chunk = -1;
-        } else {
-            for (int visit = 0; visit < kXcds && chunk < 0; ++visit) {   // (uniform over the workgroup)
-                const int shard = (home + visit) % kXcds;
-                const int64_t shard_begin = cmap.n_chunks * shard / kXcds;          // in chunks
-                const int64_t shard_end = cmap.n_chunks * (shard + 1) / kXcds;
-                if (threadIdx.x == 0) s_got = atomicAdd(&counters[shard * kCounterStride], 1ull);
-                __syncthreads();
-                const int64_t c = shard_begin + int64_t(wave_broadcast_u64(s_got));
-                if (c < shard_end) chunk = c;
-                __syncthreads();          // s_got read by all before the next shard's dequeue overwrites it
-            }
-        }
+        // two workgroups per CU), and chunks of equal cost need no stealing.
+        const int64_t chunk = light_dequeue_once(cmap, counters, s_got, static_mode);
         if (chunk >= 0) {
             int64_t chunk_begin, chunk_end;
             cmap.range(chunk, n_rows, chunk_begin, chunk_end);
@@ -191,7 +176,9 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock || R == 2 ? 4 : 3)) voi
     // 100 long ones), and stealing across the XCDs' shards is what balances them (R-MAT-24: 2.6 ms against
     // 3.7 ms for one workgroup per chunk in index order).
     // ONE loop with ONE call of the chunk body (two call sites made the compiler keep the body as a real
-    // function for the biggest instantiations: captures through scratch memory, a call per chunk).
+    // function for the biggest instantiations: captures through scratch memory, a call per chunk).  Its dequeue is its
+    // own text, not light_dequeue_once: it goes on from the shard it stopped at and asks once which others are busy.
+    const int home = blockIdx.x % kXcds;
     unsigned busy = 1u << home;
     int visit = 0;
     bool took_static = false;
@@ -299,36 +286,11 @@ __global__ __launch_bounds__(kHugeBlock, 4) void light_rows_sweep_kernel(
     scr.alpha = alpha;
     scr.beta = beta;
     const bool static_mode = cmap.n_chunks <= int64_t(gridDim.x) && !cmap.dequeue_once;
-    const int home = blockIdx.x % kXcds;
-    int64_t chunk = -1;
-    if (static_mode) {
-        chunk = xcd_contiguous_id(blockIdx.x, gridDim.x);
-        if (chunk >= cmap.n_chunks) chunk = -1;
-    } else {
-        for (int visit = 0; visit < kXcds && chunk < 0; ++visit) {   // (uniform over the workgroup)
-            const int shard = (home + visit) % kXcds;
-            const int64_t shard_begin = cmap.n_chunks * shard / kXcds;
-            const int64_t shard_end = cmap.n_chunks * (shard + 1) / kXcds;
-            if (threadIdx.x == 0) s_got = atomicAdd(&counters[shard * kCounterStride], 1ull);
-            __syncthreads();
-            const int64_t c = shard_begin + int64_t(wave_broadcast_u64(s_got));
-            if (c < shard_end) chunk = c;
-            __syncthreads();
-        }
-    }
+    const int64_t chunk = light_dequeue_once(cmap, counters, s_got, static_mode);
     int64_t rb = 0, re = 0;
     if (chunk >= 0) cmap.range(chunk, n_rows, rb, re);
     if (rb < re) {
-        bool fits;
-        const int64_t base = stage_chunk_bounds<val_t>(scr, rb, re, Ap, cmap.rel_limit, fits);
-        if (!fits) {
-            chunk_rows_wide<kHugeBlock, val_t>(rb, re, Ap, Aj, Ax, x, y, alpha, beta, 0);
-        } else {
-            __syncthreads();
-            const int64_t left = nnz - base;
-            const int32_t nnz_c = int32_t(left < kRel32Limit + 32768 ? left : kRel32Limit + 32768);
-            chunk_rows_sweep<kHugeBlock, T, R, val_t>(rb, re, nnz_c, Aj + base, Ax + base, x, y, n_cols, window_cap, hint, scr);
-        }
+#include "row_chunk_sweep.inc"
     }
     if (!static_mode) light_leave(counters);
 }

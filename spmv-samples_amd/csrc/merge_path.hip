@@ -516,6 +516,8 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= kWideBlock ? 4 : 3)) void merge_ro
         const int64_t row_lo = uniform_i64(s_diag[0]), y_first = uniform_i64(s_diag[1]), y_last = uniform_i64(s_diag[3]);
         const int64_t base = y_first & ~int64_t(3);
         const int64_t left = nnz - base;
+        // (not xwindow.hpp's chunk_nnz_reach, which caps 32 768 higher: a run spans kMergeSuperItems nonzeros at most, far
+        // below either cap, so both are right; this one stays as the kernels on record were compiled)
         const int32_t nnz_c = int32_t(left < kRel32Limit ? left : kRel32Limit);
         // opaque copies of the operand pointers, once per piece (see light_rows.hip: keeps per-thread addresses from
         // being hoisted out of this loop and spilled)

@@ -92,4 +92,28 @@ __device__ __forceinline__ val_t vector_reduce(val_t v) {
     return v;
 }
 
+// The body of the plain kernels (csr_vector_kernel of csr_vector.hip, and of csr_vector_h16.hip for a 16-bit mat_t): the
+// form of the reference, one row per T-lane vector of a kBlock-thread workgroup, grid = ceil(rows / vectors per
+// workgroup), right for any CSR.
+template <int T, typename off_t, typename val_t, typename mat_t>
+__device__ __forceinline__ void plain_rows(int32_t n_rows, const off_t* __restrict__ Ap, const int32_t* __restrict__ Aj,
+                                           const mat_t* __restrict__ Ax, const val_t* __restrict__ x,
+                                           val_t* __restrict__ y, val_t alpha, val_t beta) {
+    constexpr int ROWS_PER_BLOCK = kBlock / T;
+    const unsigned blk = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const int lane = threadIdx.x & (T - 1);
+    const int64_t row = int64_t(blk) * ROWS_PER_BLOCK + (threadIdx.x / T);
+    const bool live = row < n_rows;
+    // a vector past the last row runs as an empty row so that every lane of the
+    // wave reaches the shuffles below
+    off_t start = 0, end = 0;
+    if (live) {
+        start = Ap[row];
+        end = Ap[row + 1];
+    }
+    val_t sum = row_partial<T, off_t, val_t>(start, end, lane, Aj, Ax, x);
+    sum = vector_reduce<T, val_t>(sum);
+    if (live && lane == 0) y[row] = (beta != val_t(0)) ? alpha * sum + beta * y[row] : alpha * sum;
+}
+
 }  // namespace mi355

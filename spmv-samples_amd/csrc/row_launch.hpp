@@ -29,6 +29,21 @@ static int with_lanes(const Plan& p, const char* kind, F&& f) {
     return MI355_SPMV_EINVAL;
 }
 
+// A plain kernel (row_dot.hpp, plain_rows) over the plan's rows, its grid from the row count; kernel_of(lanes) names the
+// kernel for the plan's lanes per row.
+template <typename off_t, typename val_t, typename mat_t, typename KernelOf>
+static int launch_plain_rows(const Plan& p, const char* kind, const off_t* Ap, const mat_t* Ax, const val_t* x, val_t* y,
+                             hipStream_t s, KernelOf kernel_of) {
+    return with_lanes(p, kind, [&](auto lanes) -> int {
+        constexpr int rows_per_block = kBlock / decltype(lanes)::value;
+        const dim3 grid((unsigned)((int64_t(p.n_rows) + rows_per_block - 1) / rows_per_block)), block(kBlock);
+        hipLaunchKernelGGL(kernel_of(lanes), grid, block, 0, s, p.n_rows, (off_t)p.nnz, Ap, p.Aj, Ax, x, y, (val_t)p.alpha,
+                           (val_t)p.beta);
+        MI355_HIP_TRY(hipGetLastError());
+        return MI355_SPMV_OK;
+    });
+}
+
 // what every launch of a chunked kernel of a plan passes
 template <typename val_t, typename mat_t = val_t>   // (mat_t: the type Ax is stored in, xwindow.hpp chunk_rows)
 struct RowOperands {

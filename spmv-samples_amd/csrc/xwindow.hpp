@@ -20,6 +20,10 @@
 //   * if the sampled span exceeds the LDS capacity the window is centred on it.
 // The reference has no counterpart (it reads x through the texture path or plain
 // loads: LightSpMV.cuh:59-88, cusp_warp_reduce.cuh:41-48).
+//
+// The chunk bodies here (chunk_rows, chunk_rows_any, chunk_rows_sweep, chunk_rows_wide) start behind a prologue —
+// stage_chunk_bounds, the exit to chunk_rows_wide, a barrier, the chunk's views of Aj / Ax — that the row kinds'
+// kernels include from row_chunk_window.inc / row_chunk_sweep.inc; merge_path.hip's merge_rows_kernel has its own.
 #pragma once
 
 #include <climits>
@@ -280,6 +284,14 @@ constexpr int kHugeRow = 1024;        // a long row beyond this many nonzeros is
 // pairs in the loop, and ONE kernel body for both offset widths.  A chunk whose nonzeros span more than this
 // (rows of ~10^9 nonzeros that the giant-row pass did not take) goes through chunk_rows_wide instead.
 constexpr int64_t kRel32Limit = int64_t(INT32_MAX) - 65536;
+
+// The `nnz` a chunk body is given: the elements of Aj / Ax from the chunk's base to the arrays' end (`left`), which is
+// what keeps load_group from reading past them, held to 32 bits.  A chunk on the 32-bit path spans at most kRel32Limit
+// from its base (stage_chunk_bounds), so any cap from there up to INT32_MAX - 4 (`j + 4` must not overflow) is right;
+// this one sits 32 768 above the limit.  (merge_rows_kernel caps at kRel32Limit itself: merge_path.hip says why.)
+__host__ __device__ constexpr int32_t chunk_nnz_reach(int64_t left) {
+    return int32_t(left < kRel32Limit + 32768 ? left : kRel32Limit + 32768);
+}
 
 // A 64-bit value that is the same in every lane, moved to scalar registers.
 __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
