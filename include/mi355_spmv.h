@@ -45,6 +45,7 @@ extern "C" {
 #define MI355_SPMV_HAS_MULTI 1   /* mi355_spmv_multi_*: Y = A X for k vectors in one pass over A */
 #define MI355_SPMV_HAS_MULTI_SEMIRING 1 /* mi355_spmv_multi_create_typed / _set_semiring / _get_types / _genl_* / _pattern_* */
 #define MI355_SPMV_HAS_MULTI_HALF 1 /* mi355_spmv_multi_create_half / _half_*: X and Y in binary16 / bfloat16, fp32 arithmetic */
+#define MI355_SPMV_HAS_SDDMM 1 /* mi355_spmv_sddmm_*: dot(U[r], V[c]) at every stored entry (r, c) of A in one pass over A */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -662,6 +663,53 @@ int mi355_spmv_multi_half_i64_f16(int32_t n_rows, int32_t n_cols, int64_t nnz, c
     const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream);
 int mi355_spmv_multi_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
     const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream);
+
+/* ---- SDDMM: the dot of a row of U and a row of V at every stored entry of A (MI355_SPMV_HAS_SDDMM) ------------------
+ * For callers who train or attend over a graph: the gradient of multi-vector SpMV with respect to Ax
+ * (dAx = SDDMM of dY and X), the edge score of graph attention, the edge residual of a factorisation on a sparse sample.
+ *   out[n] = alpha * s[n] * sum_{j < k} U[r(n) * ldu + j] * V[Aj[n] * ldv + j]  +  beta * out[n]    for n < nnz
+ * r(n) is the row that owns entry n; s[n] = Ax[n], or 1 when Ax is NULL (a pattern matrix: no address is formed from Ax).
+ *   U     n_rows x k, ROW-major, ldu >= k        V     n_cols x k, ROW-major, ldv >= k
+ *   out   nnz values of the value type, in CSR order; it must not overlap Ax, U or V
+ * Elements j >= k of a row of U or V are never read; with beta = 0 (the default; alpha = 1) out is never read.  Rows of
+ * U / V are read 16 bytes per lane when the pointer and ld * sizeof(value) are 16-byte aligned, else element by element;
+ * both add in the same order: an element of out depends on its row of U, its row of V, s, alpha, beta, its old value and
+ * k only, never on where the entry lies in A nor on alignment, and two executes on the same inputs give the same bits.
+ * Types: {I32, I64} offsets x {F32, F64} values.  MI355_VAL_I32: MI355_SPMV_ENOTSUP; PATTERN / F16 / BF16 / unknown as
+ * val_type: MI355_SPMV_EINVAL (a pattern MATRIX is Ax = NULL at execute).  16-bit U / V, semirings, column-major
+ * operands and the dist_* entry points are not built.
+ * The work is cut as the multi-vector kind's: a wave owns a slice of slice_len merge items (row ends + nonzeros).  Each
+ * element of out has one writer: no carries, no scratch, no atomics, ONE kernel per execute for any k >= 1.
+ * Life cycle: create retains Ap / Aj (not copied; it does not read them), allocates nothing on the device and makes no
+ * device call; execute is asynchronous on `stream`, allocates nothing, never synchronises, launches one kernel
+ * (graph-capturable; none when nnz or n_rows is 0); one stream at a time per object.  Every argument error (a null
+ * pointer with nonzero sizes, k < 1, ldu or ldv < k, a negative size, nnz beyond 32-bit offsets, an unknown off_type) is
+ * MI355_SPMV_EINVAL before any device call, and the text of the last error names the argument.                    */
+typedef struct mi355_spmv_sddmm mi355_spmv_sddmm;
+typedef struct mi355_spmv_sddmm_info {
+    int32_t off_type, val_type;
+    int32_t slice_len;       /* merge items (row ends + nonzeros) per slice = per wave                    */
+    int32_t block_threads;
+    int64_t n_slices;
+    int64_t grid_blocks;     /* workgroups of the one kernel                                              */
+    char main_kernel[64];
+} mi355_spmv_sddmm_info;
+int mi355_spmv_sddmm_create(mi355_spmv_sddmm** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols,
+                            int64_t nnz, const void* Ap, const int32_t* Aj);
+int mi355_spmv_sddmm_set_alpha_beta(mi355_spmv_sddmm* sddmm, double alpha, double beta);
+int mi355_spmv_sddmm_execute(mi355_spmv_sddmm* sddmm, const void* Ax, const void* U, int64_t ldu,
+                             const void* V, int64_t ldv, void* out, int32_t k, void* stream);
+int mi355_spmv_sddmm_get_info(const mi355_spmv_sddmm* sddmm, mi355_spmv_sddmm_info* info);
+int mi355_spmv_sddmm_destroy(mi355_spmv_sddmm* sddmm);
+/* One-shots: create, execute, destroy.  They do not synchronise the stream.                                      */
+int mi355_spmv_sddmm_i32_f32(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, const float* Ax,
+    const float* U, int64_t ldu, const float* V, int64_t ldv, float* out, int32_t k, void* stream);
+int mi355_spmv_sddmm_i32_f64(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, const double* Ax,
+    const double* U, int64_t ldu, const double* V, int64_t ldv, double* out, int32_t k, void* stream);
+int mi355_spmv_sddmm_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, const float* Ax,
+    const float* U, int64_t ldu, const float* V, int64_t ldv, float* out, int32_t k, void* stream);
+int mi355_spmv_sddmm_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, const double* Ax,
+    const double* U, int64_t ldu, const double* V, int64_t ldv, double* out, int32_t k, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

@@ -54,6 +54,8 @@ EXPORTS = (
     + ["mi355_spmv_multi_%s_%s_%s" % (g, o, v) for g in ("genl", "pattern") for o in ("i32", "i64") for v in ("f32", "f64", "i32")]
     + ["mi355_spmv_multi_create_half"]
     + ["mi355_spmv_multi_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
+    + ["mi355_spmv_sddmm_" + n for n in ("create", "set_alpha_beta", "execute", "get_info", "destroy")]
+    + ["mi355_spmv_sddmm_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
 )
 
 
@@ -99,6 +101,11 @@ class MultiInfo(C.Structure):
                 ("block_threads", C.c_int32), ("widest_tile", C.c_int32), ("passes", C.c_int32), ("n_kernels", C.c_int32),
                 ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("scratch_bytes", C.c_int64),
                 ("main_kernel", C.c_char * 64)]
+
+
+class SddmmInfo(C.Structure):
+    _fields_ = [("off_type", C.c_int32), ("val_type", C.c_int32), ("slice_len", C.c_int32), ("block_threads", C.c_int32),
+                ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("main_kernel", C.c_char * 64)]
 
 
 EXCHANGES = {"auto": 0, "bcast": 1, "sendrecv": 2, "allgather": 3}
@@ -198,6 +205,18 @@ def lib():
         for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
             for v in ("f16", "bf16"):
                 getattr(L, "mi355_spmv_multi_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_multi_%s_f32" % o).argtypes
+        L.mi355_spmv_sddmm_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64,
+                                              C.c_void_p, C.c_void_p]
+        L.mi355_spmv_sddmm_set_alpha_beta.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        L.mi355_spmv_sddmm_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.c_int32, C.c_void_p]
+        L.mi355_spmv_sddmm_get_info.argtypes = [C.c_void_p, C.POINTER(SddmmInfo)]
+        L.mi355_spmv_sddmm_destroy.argtypes = [C.c_void_p]
+        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
+            for v in ("f32", "f64"):
+                getattr(L, "mi355_spmv_sddmm_%s_%s" % (o, v)).argtypes = [
+                    C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                    C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -780,6 +799,106 @@ def spmm_pattern(semiring, n_rows, n_cols, nnz, Ap, Aj, X, Y, stream=None):
                                   X.size(1), _stream_ptr(stream))
     _check(st, name)
     return Y
+
+
+def _sddmm_operands(n_rows, n_cols, nnz, val_dtype, Ax, U, V, out, k):
+    """The checks of an SDDMM execute, in MultiPlan's words: (Ax or None, ldu, ldv, out, k)."""
+    if Ax is not None:
+        _require_device(Ax)
+        if Ax.dtype != val_dtype:
+            raise TypeError("value type differs from the plan's")
+        if Ax.numel() < nnz:
+            raise ValueError("operand shorter than the plan's sizes")
+    ldu = _require_matrix(U, "U", n_rows, val_dtype)
+    ldv = _require_matrix(V, "V", n_cols, val_dtype)
+    if k is None:
+        k = U.size(1)
+    if k < 1 or k > U.size(1) or k > V.size(1):
+        raise ValueError("k outside 1 .. the columns U and V hold")
+    if out is None:
+        out = torch.empty(nnz, dtype=val_dtype, device=U.device)
+    else:
+        _require_device(out)
+        if out.dtype != val_dtype:
+            raise TypeError("value type differs from the plan's")
+        if out.dim() != 1 or out.numel() < nnz:
+            raise ValueError("operand shorter than the plan's sizes")
+    return Ax, ldu, ldv, out, k
+
+
+class SddmmPlan:
+    """mi355_spmv_sddmm_*: out[n] = alpha * s[n] * dot(U[r(n), :k], V[Aj[n], :k]) + beta * out[n] for every stored entry n
+    of A, in one pass over A and one kernel for any k; s = Ax, or 1 with Ax=None (a pattern matrix).  U (n_rows x k) and
+    V (n_cols x k) are 2-D row-major device tensors; views with a larger stride(0) are taken as they are.  out holds nnz
+    values in CSR order.  val_dtype is float32 or float64.  The gradient of spmm with respect to Ax is
+    SddmmPlan.execute(None, dY, X).  Holds references to Ap and Aj so they outlive the object; creating one touches no
+    device memory."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype):
+        _require_device(Ap, Aj)
+        if Aj.dtype != torch.int32:
+            raise TypeError("Aj must be int32")
+        if val_dtype not in (torch.float32, torch.float64):
+            raise TypeError("val_dtype must be float32 or float64")
+        self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
+        self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
+        self._h = C.c_void_p()
+        _check(lib().mi355_spmv_sddmm_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz,
+                                             C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr())), "mi355_spmv_sddmm_create")
+
+    def execute(self, Ax, U, V, out=None, k=None, stream=None):
+        """Asynchronous on `stream` (default: torch's current stream); returns out (made when None: then beta must be 0).
+        k defaults to U.size(1); ldu / ldv are the operands' stride(0)."""
+        Ax, ldu, ldv, out, k = _sddmm_operands(self.n_rows, self.n_cols, self.nnz, self.val_dtype, Ax, U, V, out, k)
+        with torch.cuda.device(self.Ap.device):
+            st = lib().mi355_spmv_sddmm_execute(self._h, C.c_void_p(Ax.data_ptr()) if Ax is not None else None,
+                                                C.c_void_p(U.data_ptr()), ldu, C.c_void_p(V.data_ptr()), ldv,
+                                                C.c_void_p(out.data_ptr()), k, _stream_ptr(stream))
+        _check(st, "mi355_spmv_sddmm_execute")
+        return out
+
+    def set_alpha_beta(self, alpha, beta):
+        """out = alpha * s * dot + beta * out for the following executes (default 1, 0)."""
+        _check(lib().mi355_spmv_sddmm_set_alpha_beta(self._h, C.c_double(alpha), C.c_double(beta)),
+               "mi355_spmv_sddmm_set_alpha_beta")
+
+    def info(self):
+        si = SddmmInfo()
+        _check(lib().mi355_spmv_sddmm_get_info(self._h, C.byref(si)), "mi355_spmv_sddmm_get_info")
+        d = {n: getattr(si, n) for n, _ in si._fields_}
+        d["main_kernel"] = d["main_kernel"].decode()
+        return d
+
+    def destroy(self):
+        if self._h:
+            lib().mi355_spmv_sddmm_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def sddmm(n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out=None, stream=None):
+    """One-shot SDDMM (mi355_spmv_sddmm_<off>_<val>): out[n] = s[n] * dot(U[r(n)], V[Aj[n]]) for the k = U.size(1) columns
+    of row-major U and V; Ax=None is a pattern matrix.  Asynchronous on `stream`: it does not synchronise."""
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if not getattr(U, "is_cuda", False):
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if U.dtype not in (torch.float32, torch.float64):
+        raise TypeError("U must be float32 or float64")
+    Ax, ldu, ldv, out, k = _sddmm_operands(n_rows, n_cols, nnz, U.dtype, Ax, U, V, out, None)
+    name = "mi355_spmv_sddmm_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[U.dtype][1])
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
+                                  C.c_void_p(Ax.data_ptr()) if Ax is not None else None, C.c_void_p(U.data_ptr()), ldu,
+                                  C.c_void_p(V.data_ptr()), ldv, C.c_void_p(out.data_ptr()), k, _stream_ptr(stream))
+    _check(st, name)
+    return out
 
 
 C_TYPE_NAMES = {torch.float32: "float", torch.float64: "double", torch.int32: "int", torch.int64: "long long"}

@@ -1,0 +1,348 @@
+// sddmm.hip — sampled dense-dense matrix product on the structure of A (mi355_spmv_sddmm_*):
+//   out[n] = alpha * s[n] * sum_{j < k} U[r(n), j] * V[Aj[n], j] + beta * out[n]        for every stored entry n of A
+// r(n) = the row that owns entry n, s[n] = Ax[n] (1 for a pattern: Ax == NULL).  The gradient of multi-vector SpMV with
+// respect to Ax, the edge score of graph attention, the residual of a factorisation on a sparse sample.  An object of
+// its own beside mi355_spmv_multi: the kernel, its launch and the extern "C" entry points, all in this unit.
+//
+//   sddmm_slice_kernel   one WAVE per slice of kSddmmSlice merge items (row ends + nonzeros: a run of empty rows cannot
+//                        make the row range of a slice unbounded, a hub row is spread over as many waves as it has
+//                        slices) — the cut of multi_slice_walk.inc, restated here.  The wave finds its two merge-path
+//                        diagonals, keeps its rows' offsets in LDS relative to its first nonzero, and walks its
+//                        nonzeros 64 at a time: Aj (and Ax) are loaded coalesced, one per lane, and each lane finds its
+//                        nonzero's row by a binary search in LDS.  Lanes are (nonzero slot x 16-byte column group):
+//                        a slot of C lanes takes one nonzero, lane c gathers its 16 bytes of V[col] and of U[row] and
+//                        multiplies them into ONE scalar partial; for k wider than the tile of C groups the lane goes
+//                        on to the next tile and keeps adding into the same register (A and out cross HBM once whatever
+//                        k is).  An xor-shuffle tree over the C lanes of the slot gives the dot.
+//   the store            the reduction runs across the column lanes of one slot, not across the slots of a row: no
+//                        carries, no fix-up, no scratch, no atomics, one writer per element.  The C steps of a group of
+//                        64 nonzeros hand their dots back to the lane that loaded the nonzero (one shuffle per step);
+//                        that lane still holds Ax[n], so out[n0 + m] is scaled and stored once, 64 contiguous values.
+//
+// Order of addition: a lane adds its columns in ascending order, tile after tile, into one partial that starts at +0
+// (a masked column is loaded as 0 and adds +0), and the tree adds lanes at distance 1, 2, 4, ...: an element of out is
+// a function of (U[r, :k], V[c, :k], s, alpha, beta, out_old, k) only — not of where in a slice, step or slot its
+// nonzero falls, and not of the alignment of U and V (the 16-byte and the element-by-element load fill the same
+// registers; the arithmetic is one piece of code behind both).
+#include <new>
+
+#include "common.hpp"
+
+namespace mi355 {
+
+constexpr int kSddmmSlice = 1024;                  // merge items per slice (= per wave): kMultiSlice's length
+constexpr int kSddmmGroupsMax = 8;                 // most 16-byte column groups of a tile: 32 fp32, 16 fp64 columns
+constexpr int kSddmmWaves = kBlock / kWave;        // slices per workgroup
+
+template <typename val_t>
+struct SddmmArgs {
+    int32_t n_rows;
+    int64_t nnz, n_slices;
+    const int32_t* Aj;
+    const val_t* Ax;        // null for a pattern kernel, which never forms an address from it
+    const val_t* U;
+    const val_t* V;
+    val_t* out;
+    int64_t ldu, ldv;
+    int32_t k;
+    int32_t u_vec, v_vec;   // 1 = rows of U / V are 16-byte aligned: one 16-byte load per lane and tile
+    val_t alpha, beta;
+};
+
+template <typename val_t> struct SddmmPack16;
+template <> struct SddmmPack16<float> { using type = float4; };
+template <> struct SddmmPack16<double> { using type = double2; };
+
+// the lane's W columns of a row: one 16-byte load when the row is aligned and all W exist, else the nv that do; a
+// column that does not exist is 0 and is never read
+template <typename val_t, int W>
+__device__ __forceinline__ void sddmm_load_cols(val_t (&v)[W], const val_t* p, int nv, bool vec) {
+    if (vec && nv == W) {
+        const auto t = *reinterpret_cast<const typename SddmmPack16<val_t>::type*>(p);
+        v[0] = t.x; v[1] = t.y;
+        if constexpr (W == 4) { v[2] = t.z; v[3] = t.w; }
+    } else {
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[j] = j < nv ? p[j] : val_t(0);
+    }
+}
+
+// one rounding per column whatever the compiler would otherwise choose to contract: the promise above, spelled out
+__device__ __forceinline__ float sddmm_fma(float x, float y, float z) { return __builtin_fmaf(x, y, z); }
+__device__ __forceinline__ double sddmm_fma(double x, double y, double z) { return __builtin_fma(x, y, z); }
+
+// C = lanes per nonzero slot (16-byte column groups of a tile); the wave holds S = 64 / C slots
+template <typename off_t, typename val_t, int C, bool VALUED>
+__global__ __launch_bounds__(kBlock) void sddmm_slice_kernel(const SddmmArgs<val_t> a, const off_t* __restrict__ Ap) {
+    constexpr int W = 16 / int(sizeof(val_t));      // columns of a lane per tile
+    constexpr int S = kWave / C;
+    // row offsets of the slice relative to its first nonzero, clamped to [0, nn + 1]: entry i belongs to row r0 + i
+    __shared__ int32_t rel_all[kSddmmWaves][kSddmmSlice + 2];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int c = lane % C, s = lane / C;
+    int32_t* rel = rel_all[threadIdx.x / kWave];
+    const int64_t w = int64_t(blockIdx.x) * kSddmmWaves + threadIdx.x / kWave;
+    const bool active = w < a.n_slices;
+    int64_t r0 = 0, n0 = 0;
+    int nr = 0, nn = 0;
+    if (active) {
+        // merge-path diagonals of the slice: lanes 0..31 search its start, lanes 32..63 its end.  Row end r comes before
+        // nonzero n iff Ap[r + 1] <= n; (r, n) = row ends and nonzeros in front of the diagonal.
+        const int64_t items = int64_t(a.n_rows) + a.nnz;
+        int64_t d = (lane < 32 ? w : w + 1) * kSddmmSlice;
+        if (d > items) d = items;
+        int64_t lo = d > a.nnz ? d - a.nnz : 0, hi = d < a.n_rows ? d : a.n_rows;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (int64_t(Ap[mid + 1]) <= d - mid - 1) lo = mid + 1; else hi = mid;
+        }
+        const int64_t n = d - lo;
+        r0 = __shfl(lo, 0);
+        const int64_t r1 = __shfl(lo, 32);
+        n0 = __shfl(n, 0);
+        nn = int(__shfl(n, 32) - n0);
+        // rows r0 .. r_last have nonzeros or their end here (row r1, when there is one, does not end in this slice)
+        const int64_t r_last = r1 < a.n_rows ? r1 : int64_t(a.n_rows) - 1;
+        nr = int(r_last - r0) + 1;
+        for (int i = lane; i <= nr; i += kWave) {
+            const int64_t v = int64_t(Ap[r0 + i]) - n0;
+            rel[i] = v < 0 ? 0 : v > nn ? nn + 1 : int32_t(v);
+        }
+    }
+    __syncthreads();
+    if (!active) return;
+
+    for (int base = 0; base < nn; base += kWave) {
+        // 64 nonzeros, one per lane, coalesced; each lane finds its nonzero's row in the slice's offsets
+        const int m = base + lane;
+        int32_t col = 0;
+        int row_i = 0;
+        [[maybe_unused]] val_t ax = val_t(1);
+        if (m < nn) {
+            col = a.Aj[n0 + m];
+            if constexpr (VALUED) ax = a.Ax[n0 + m];
+            int lo = 0, hi = nr - 1;
+            while (lo < hi) {           // the last i with rel[i] <= m (empty rows repeat an offset: the last is the owner)
+                const int mid = (lo + hi + 1) >> 1;
+                if (rel[mid] <= m) lo = mid; else hi = mid - 1;
+            }
+            row_i = lo;
+        }
+        const int left = nn - base;
+        const int steps = left >= kWave ? C : (left + S - 1) / S;
+        val_t dot = val_t(0);           // of this lane's own nonzero m, handed back by the step that took it
+        for (int t = 0; t < steps; ++t) {
+            // slot s takes nonzero t * S + s of the 64
+            const int src = t * S + s;
+            int32_t col_s = col;
+            int row_s = row_i;
+            if constexpr (C > 1) {
+                col_s = __shfl(col, src);
+                row_s = __shfl(row_i, src);
+            }
+            val_t part = val_t(0);
+            if (src < left) {
+                const val_t* up = a.U + (r0 + row_s) * a.ldu + c * W;
+                const val_t* vp = a.V + int64_t(col_s) * a.ldv + c * W;
+                for (int32_t cb = 0; cb < a.k; cb += C * W) {       // the tiles of k: the same register all along
+                    const int nv = min(max(a.k - cb - c * W, 0), W);
+                    if (nv > 0) {
+                        val_t u[W], v[W];
+                        sddmm_load_cols<val_t, W>(u, up + cb, nv, a.u_vec != 0);
+                        sddmm_load_cols<val_t, W>(v, vp + cb, nv, a.v_vec != 0);
+#pragma unroll
+                        for (int j = 0; j < W; ++j) part = sddmm_fma(u[j], v[j], part);
+                    }
+                }
+            }
+            // the dot of the slot's nonzero, in every lane of the slot: a fixed tree over its C lanes
+#pragma unroll
+            for (int d = 1; d < C; d <<= 1) part += __shfl_xor(part, d);
+            // back to the lane that loaded the nonzero: lane l holds nonzero l = t' * S + s', taken at step t' by slot s'
+            val_t mine = part;
+            if constexpr (C > 1) mine = __shfl(part, (lane % S) * C);
+            if (lane / S == t) dot = mine;
+        }
+        if (m < nn) {
+            val_t o;
+            if constexpr (VALUED) o = a.alpha * (ax * dot); else o = a.alpha * dot;
+            if (a.beta != val_t(0)) o += a.beta * a.out[n0 + m];
+            a.out[n0 + m] = o;
+        }
+    }
+}
+
+}  // namespace mi355
+
+using namespace mi355;
+
+struct mi355_spmv_sddmm {   // the opaque handle of include/mi355_spmv.h: host memory only, nothing on the device
+    int off_type = 0, val_type = 0;
+    int32_t n_rows = 0, n_cols = 0;
+    int64_t nnz = 0;
+    const void* Ap = nullptr;
+    const int32_t* Aj = nullptr;
+    double alpha = 1.0, beta = 0.0;
+    int64_t n_slices = 0;
+};
+
+namespace {
+
+// argument-only checks of a create (also run by the one-shots before they make anything)
+int sddmm_check_create(const char* who, int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
+                       const int32_t* Aj) {
+    if (off_type != MI355_OFF_I32 && off_type != MI355_OFF_I64) { set_error("%s: unknown off_type %d", who, off_type); return MI355_SPMV_EINVAL; }
+    if (val_type == MI355_VAL_I32) {
+        set_error("%s: val_type MI355_VAL_I32 is not built (fp32 / fp64 values)", who);
+        return MI355_SPMV_ENOTSUP;
+    }
+    if (val_type != MI355_VAL_F32 && val_type != MI355_VAL_F64) {
+        set_error("%s: val_type %d is not a type of U, V and out (F32 or F64; a pattern matrix is Ax = NULL at execute)", who, val_type);
+        return MI355_SPMV_EINVAL;
+    }
+    if (n_rows < 0) { set_error("%s: negative n_rows", who); return MI355_SPMV_EINVAL; }
+    if (n_cols < 0) { set_error("%s: negative n_cols", who); return MI355_SPMV_EINVAL; }
+    if (nnz < 0) { set_error("%s: negative nnz", who); return MI355_SPMV_EINVAL; }
+    if (off_type == MI355_OFF_I32 && nnz > INT32_MAX) { set_error("%s: nnz does not fit 32-bit offsets", who); return MI355_SPMV_EINVAL; }
+    if (n_rows > 0 && !Ap) { set_error("%s: null Ap", who); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && !Aj) { set_error("%s: null Aj", who); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && (n_cols == 0 || n_rows == 0)) { set_error("%s: nnz > 0 but n_rows or n_cols is 0", who); return MI355_SPMV_EINVAL; }
+    return MI355_SPMV_OK;
+}
+
+// argument-only checks of an execute
+int sddmm_check_execute(const char* who, int64_t nnz, const void* U, int64_t ldu, const void* V, int64_t ldv, const void* out, int32_t k) {
+    if (k < 1) { set_error("%s: k = %d below 1", who, k); return MI355_SPMV_EINVAL; }
+    if (ldu < k) { set_error("%s: ldu = %lld below k = %d", who, (long long)ldu, k); return MI355_SPMV_EINVAL; }
+    if (ldv < k) { set_error("%s: ldv = %lld below k = %d", who, (long long)ldv, k); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && !U) { set_error("%s: null U", who); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && !V) { set_error("%s: null V", who); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && !out) { set_error("%s: null out", who); return MI355_SPMV_EINVAL; }
+    return MI355_SPMV_OK;
+}
+
+void sddmm_fill(mi355_spmv_sddmm& m, int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
+                const int32_t* Aj) {
+    m.off_type = off_type; m.val_type = val_type;
+    m.n_rows = n_rows; m.n_cols = n_cols; m.nnz = nnz;
+    m.Ap = Ap; m.Aj = Aj;
+    m.n_slices = (int64_t(n_rows) + nnz + kSddmmSlice - 1) / kSddmmSlice;
+}
+
+// the one launch of an execute: C from k alone, valued / pattern from Ax
+template <typename off_t, typename val_t, bool VALUED>
+int sddmm_launch(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out,
+                 int32_t k, hipStream_t s) {
+    SddmmArgs<val_t> a;
+    a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
+    a.Aj = m.Aj;
+    a.Ax = VALUED ? static_cast<const val_t*>(Ax) : nullptr;
+    a.U = static_cast<const val_t*>(U); a.V = static_cast<const val_t*>(V);
+    a.out = static_cast<val_t*>(out);
+    a.ldu = ldu; a.ldv = ldv; a.k = k;
+    a.u_vec = (reinterpret_cast<uintptr_t>(U) % 16 == 0 && (size_t(ldu) * sizeof(val_t)) % 16 == 0) ? 1 : 0;
+    a.v_vec = (reinterpret_cast<uintptr_t>(V) % 16 == 0 && (size_t(ldv) * sizeof(val_t)) % 16 == 0) ? 1 : 0;
+    a.alpha = val_t(m.alpha); a.beta = val_t(m.beta);
+    const off_t* Ap = static_cast<const off_t*>(m.Ap);
+    const dim3 grid(unsigned((m.n_slices + kSddmmWaves - 1) / kSddmmWaves)), block(kBlock);
+    constexpr int W = 16 / int(sizeof(val_t));
+    const int groups = (k + W - 1) / W;
+    if (groups <= 1) hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, 1, VALUED>), grid, block, 0, s, a, Ap);
+    else if (groups <= 2) hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, 2, VALUED>), grid, block, 0, s, a, Ap);
+    else if (groups <= 4) hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, 4, VALUED>), grid, block, 0, s, a, Ap);
+    else hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, kSddmmGroupsMax, VALUED>), grid, block, 0, s, a, Ap);
+    MI355_HIP_TRY(hipGetLastError());
+    return MI355_SPMV_OK;
+}
+
+template <typename off_t, typename val_t>
+int sddmm_launch_values(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out,
+                        int32_t k, hipStream_t s) {
+    return Ax ? sddmm_launch<off_t, val_t, true>(m, Ax, U, ldu, V, ldv, out, k, s)
+              : sddmm_launch<off_t, val_t, false>(m, Ax, U, ldu, V, ldv, out, k, s);
+}
+
+int sddmm_run(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out, int32_t k,
+              void* stream) {
+    if (m.nnz == 0 || m.n_rows == 0) return MI355_SPMV_OK;      // no stored entry: nothing to write, nothing launched
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (m.off_type == MI355_OFF_I32)
+        return m.val_type == MI355_VAL_F64 ? sddmm_launch_values<int32_t, double>(m, Ax, U, ldu, V, ldv, out, k, s)
+                                           : sddmm_launch_values<int32_t, float>(m, Ax, U, ldu, V, ldv, out, k, s);
+    return m.val_type == MI355_VAL_F64 ? sddmm_launch_values<int64_t, double>(m, Ax, U, ldu, V, ldv, out, k, s)
+                                       : sddmm_launch_values<int64_t, float>(m, Ax, U, ldu, V, ldv, out, k, s);
+}
+
+// the one-shots: the object lives on the caller's stack for the one launch (which copies what it reads of it into the
+// kernel's arguments); every argument check comes before any device call, and nothing synchronises
+int sddmm_one_shot(int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
+                   const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out, int32_t k, void* stream) {
+    set_error("%s", "");
+    if (const int st = sddmm_check_create("sddmm", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj)) return st;
+    if (const int st = sddmm_check_execute("sddmm", nnz, U, ldu, V, ldv, out, k)) return st;
+    mi355_spmv_sddmm m;
+    sddmm_fill(m, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj);
+    return sddmm_run(m, Ax, U, ldu, V, ldv, out, k, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355_spmv_sddmm_create(mi355_spmv_sddmm** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+                            const void* Ap, const int32_t* Aj) {
+    set_error("%s", "");
+    if (!out) { set_error("sddmm_create: null object pointer (out)"); return MI355_SPMV_EINVAL; }
+    *out = nullptr;
+    if (const int st = sddmm_check_create("sddmm_create", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj)) return st;
+    mi355_spmv_sddmm* m = new (std::nothrow) mi355_spmv_sddmm();
+    if (!m) { set_error("sddmm_create: host allocation failed"); return MI355_SPMV_ENOMEM; }
+    sddmm_fill(*m, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj);
+    *out = m;
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_sddmm_set_alpha_beta(mi355_spmv_sddmm* m, double alpha, double beta) {
+    set_error("%s", "");
+    if (!m) { set_error("sddmm_set_alpha_beta: null object"); return MI355_SPMV_EINVAL; }
+    m->alpha = alpha;
+    m->beta = beta;
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_sddmm_execute(mi355_spmv_sddmm* m, const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out,
+                             int32_t k, void* stream) {
+    set_error("%s", "");
+    if (!m) { set_error("sddmm_execute: null object"); return MI355_SPMV_EINVAL; }
+    if (const int st = sddmm_check_execute("sddmm_execute", m->nnz, U, ldu, V, ldv, out, k)) return st;
+    return sddmm_run(*m, Ax, U, ldu, V, ldv, out, k, stream);
+}
+
+int mi355_spmv_sddmm_get_info(const mi355_spmv_sddmm* m, mi355_spmv_sddmm_info* info) {
+    if (!m || !info) { set_error("sddmm_get_info: null argument"); return MI355_SPMV_EINVAL; }
+    memset(info, 0, sizeof(*info));
+    info->off_type = m->off_type; info->val_type = m->val_type;
+    info->slice_len = kSddmmSlice;
+    info->block_threads = kBlock;
+    info->n_slices = m->n_slices;
+    info->grid_blocks = (m->n_slices + kSddmmWaves - 1) / kSddmmWaves;
+    snprintf(info->main_kernel, sizeof(info->main_kernel), "sddmm_slice_kernel");
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_sddmm_destroy(mi355_spmv_sddmm* m) {
+    delete m;
+    return MI355_SPMV_OK;
+}
+
+#define MI355_SPMV_DEFINE_SDDMM(SUF, OFF, OFFENUM, VAL, VALENUM)                                                       \
+    int mi355_spmv_sddmm_##SUF(int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap, const int32_t* Aj, const VAL* Ax, \
+                               const VAL* U, int64_t ldu, const VAL* V, int64_t ldv, VAL* out, int32_t k, void* stream) { \
+        return sddmm_one_shot(OFFENUM, VALENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, Ax, U, ldu, V, ldv, out, k, stream); \
+    }
+MI355_SPMV_DEFINE_SDDMM(i32_f32, int32_t, MI355_OFF_I32, float, MI355_VAL_F32)
+MI355_SPMV_DEFINE_SDDMM(i32_f64, int32_t, MI355_OFF_I32, double, MI355_VAL_F64)
+MI355_SPMV_DEFINE_SDDMM(i64_f32, int64_t, MI355_OFF_I64, float, MI355_VAL_F32)
+MI355_SPMV_DEFINE_SDDMM(i64_f64, int64_t, MI355_OFF_I64, double, MI355_VAL_F64)
+
+}  // extern "C"
