@@ -58,6 +58,20 @@ constexpr int kCus = 256;            // compute units per MI355X
 
 void set_error(const char* fmt, ...);
 
+// the structure checks of every object made of a caller's CSR arrays (multi.hip, sddmm.hip), argument-only and in this
+// order; `who` names the entry point in the text
+inline int check_csr_structure(const char* who, int off_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
+                               const int32_t* Aj) {
+    if (n_rows < 0) { set_error("%s: negative n_rows", who); return MI355_SPMV_EINVAL; }
+    if (n_cols < 0) { set_error("%s: negative n_cols", who); return MI355_SPMV_EINVAL; }
+    if (nnz < 0) { set_error("%s: negative nnz", who); return MI355_SPMV_EINVAL; }
+    if (off_type == MI355_OFF_I32 && nnz > INT32_MAX) { set_error("%s: nnz does not fit 32-bit offsets", who); return MI355_SPMV_EINVAL; }
+    if (n_rows > 0 && !Ap) { set_error("%s: null Ap", who); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && !Aj) { set_error("%s: null Aj", who); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && (n_cols == 0 || n_rows == 0)) { set_error("%s: nnz > 0 but n_rows or n_cols is 0", who); return MI355_SPMV_EINVAL; }
+    return MI355_SPMV_OK;
+}
+
 // mat_t of a PATTERN matrix (MI355_VAL_PATTERN: every stored entry is one, in the type of x and y): a tag that takes
 // no storage.  The merge kind's tile kernel and launch_merge are instantiated with it in the place of the stored
 // value type; the kernel then issues no Ax load at all and no address is ever formed from the pointer.

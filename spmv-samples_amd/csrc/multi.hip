@@ -4,19 +4,21 @@
 // per value type: the multi_<type>.hip units, which include this file with MI355_MULTI_TU set to the value type (the
 // library's build, MI355_MULTI_SPLIT_UNITS; without it this unit instantiates what it launches and stands alone).
 // 16-bit vectors (mi355_spmv_multi_create_half): multi_half_kernels.hpp, instantiated by multi_h16.hip, which includes
-// this file with MI355_MULTI_HALF_TU set.  DESIGN.md §3.10, §3.10.1, §3.10.2.
+// this file with MI355_MULTI_HALF_TU set.  The slice geometry and the cut are the slice kinds' own, shared with SDDMM:
+// slice_cut.hpp, slice_cut.inc.  DESIGN.md §3.10, §3.10.1, §3.10.2.
 #include <algorithm>
 #include <new>
 
-#include "common.hpp"
-
-namespace mi355 {
-constexpr int kMultiSlice = 1024;               // merge items per slice (= per wave)
-constexpr int kMultiGroupsMax = 8;              // most 16-byte column groups of a tile: 32 fp32 / int32, 16 fp64, 64 16-bit columns
-}  // namespace mi355
-#define MI355_MULTI_GEOMETRY 1
 #include "multi_kernels.hpp"
 #include "multi_half_kernels.hpp"
+
+namespace mi355 {
+// The geometry that the host simulation's tables are written for: tests/test_multi_sim_cpu.py reads these two lines
+// and holds tests/multi_cases.py to them.  The kernels use slice_cut.hpp's constants; a change there stops here.
+constexpr int kMultiSlice = 1024;
+constexpr int kMultiGroupsMax = 8;
+static_assert(kMultiSlice == kSliceLen && kMultiGroupsMax == kSliceGroupsMax, "tests/multi_cases.py is tabled for this geometry");
+}  // namespace mi355
 
 #if defined(MI355_MULTI_TU)   // an instantiation unit: the launch_multi of one value type, and nothing of what follows
 namespace mi355 {
@@ -98,13 +100,12 @@ int check_half_types(int mat_type, int vec_type) {
 
 int check_create_args(const char* who, int off_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
                       int32_t k_max) {
-    if (n_rows < 0 || n_cols < 0 || nnz < 0) { set_error("%s: negative size", who); return MI355_SPMV_EINVAL; }
-    if (k_max < 1 || k_max > (1 << 20)) { set_error("%s: k_max = %d outside 1 .. 2^20", who, k_max); return MI355_SPMV_EINVAL; }
-    if (off_type == MI355_OFF_I32 && nnz > INT32_MAX) { set_error("%s: nnz does not fit 32-bit offsets", who); return MI355_SPMV_EINVAL; }
-    if (n_rows > 0 && !Ap) { set_error("%s: null Ap", who); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && !Aj) { set_error("%s: null Aj", who); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && (n_cols == 0 || n_rows == 0)) { set_error("%s: nonzeros but no rows or no columns", who); return MI355_SPMV_EINVAL; }
-    return MI355_SPMV_OK;
+    // k_max is reported behind a negative size and in front of every other structure check, as it always was
+    if (n_rows >= 0 && n_cols >= 0 && nnz >= 0 && (k_max < 1 || k_max > (1 << 20))) {
+        set_error("%s: k_max = %d outside 1 .. 2^20", who, k_max);
+        return MI355_SPMV_EINVAL;
+    }
+    return check_csr_structure(who, off_type, n_rows, n_cols, nnz, Ap, Aj);
 }
 
 enum CreateHow { kPlain = 0, kTyped = 1, kHalf = 2 };   // mi355_spmv_multi_create, _create_typed, _create_half
@@ -129,8 +130,7 @@ int make_object(const char* who, mi355_spmv_multi** out, int off_type, int mat_t
     m->n_cols = n_cols; m->k_max = k_max;
     MultiShape& sh = m->shape;
     sh.n_rows = n_rows; sh.nnz = nnz; sh.Ap = Ap; sh.Aj = Aj;
-    const int64_t items = int64_t(n_rows) + nnz;
-    sh.n_slices = (items + kMultiSlice - 1) / kMultiSlice;
+    sh.n_slices = slice_count(n_rows, nnz);
     const int widest = widest_tile(vec_type);
     sh.carry_ld = int64_t(k_max + widest - 1) / widest * widest;
     if (sh.n_slices > 0) {
@@ -304,13 +304,13 @@ int mi355_spmv_multi_get_info(const mi355_spmv_multi* m, mi355_spmv_multi_info* 
     if (!m || !info) { set_error("multi_get_info: null argument"); return MI355_SPMV_EINVAL; }
     memset(info, 0, sizeof(*info));
     info->off_type = m->off_type; info->val_type = m->val_type; info->k_max = m->k_max;
-    info->slice_len = kMultiSlice;
+    info->slice_len = kSliceLen;
     info->block_threads = kBlock;
     info->widest_tile = widest_tile(m->val_type);
     info->passes = passes_for(m->val_type, m->k_max);
     info->n_kernels = info->passes + (m->shape.n_slices > 1 ? 1 : 0);
     info->n_slices = m->shape.n_slices;
-    info->grid_blocks = (m->shape.n_slices + kMultiWaves - 1) / kMultiWaves;
+    info->grid_blocks = slice_grid(m->shape.n_slices);
     info->scratch_bytes = int64_t(m->scratch_bytes);
     snprintf(info->main_kernel, sizeof(info->main_kernel), is_half_matrix(m->val_type) ? "multi_half_slice_kernel" : "multi_slice_kernel");
     return MI355_SPMV_OK;

@@ -161,7 +161,7 @@ int launch_multi_half(const MultiShape& m, const void* Ax, const void* X, int64_
     a.Ax = static_cast<const mat_t*>(Ax);
     a.tail_val = static_cast<float*>(m.tail_val);
     const off_t* Ap = static_cast<const off_t*>(m.Ap);
-    const dim3 grid(unsigned((m.n_slices + kMultiWaves - 1) / kMultiWaves)), block(kBlock);
+    const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
     if (const int st = multi_passes<mh::kHalfV>(a, k, [&](auto lanes) {
             hipLaunchKernelGGL((mh::multi_half_slice_kernel<off_t, vec_t, mat_t, decltype(lanes)::value>), grid, block, 0, s, a, Ap);
         }))

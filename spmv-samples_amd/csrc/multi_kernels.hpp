@@ -8,7 +8,7 @@
 // X is row-major (n_cols x k, leading dimension ldx): the gather of one column index pulls a whole row of X, so the
 // 64/128-byte line a single-vector gather takes 4 bytes out of is used in full, and Aj / Ax cross HBM once, not k times.
 //
-//   multi_slice_kernel   one WAVE per slice of kMultiSlice merge items (row ends + nonzeros, so that empty rows cost
+//   multi_slice_kernel   one WAVE per slice of kSliceLen merge items (row ends + nonzeros, so that empty rows cost
 //                        what they hold and a hub row is spread over as many waves as it has slices).  The wave finds
 //                        its two merge-path diagonals, keeps its rows' offsets in LDS, and walks its nonzeros 64 at a
 //                        time: Aj / Ax are loaded coalesced, one per lane, and handed to the (slot x column group)
@@ -16,6 +16,8 @@
 //                        that lie inside one row accumulate per slot; a step that holds a row's end is reduced across
 //                        the slots by a segmented scan (shuffles), and the slot that holds the end stores the row of Y.
 //                        What is left of a row that runs on into the next slice goes to the slice's carry.
+//                        The cut (the diagonals, the offsets in LDS, a nonzero's row) and the 16-byte column access
+//                        are shared with SDDMM: slice_cut.hpp, slice_cut.inc, slice_cut_row.inc.
 //   multi_fixup_kernel   reduces the carries of a row into Y in slice order (no atomics: two executes, same bits).
 //
 // Identity rule: wherever nothing is there — a slot past the slice's last nonzero, a masked column, the reset of the
@@ -32,15 +34,10 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.hpp"
 #include "semiring.hpp"
+#include "slice_cut.hpp"
 
 namespace mi355 {
-
-constexpr int kMultiWaves = kBlock / kWave;     // slices per workgroup
-#ifndef MI355_MULTI_GEOMETRY
-#error "multi_kernels.hpp is included through multi.hip, which holds kMultiSlice and kMultiGroupsMax"
-#endif
 
 template <typename val_t>
 struct MultiArgs {
@@ -60,42 +57,9 @@ struct MultiArgs {
     int64_t carry_ld;
 };
 
-struct alignas(16) I32x4 { int32_t x, y, z, w; };   // four int32 columns per lane, as float4 for fp32
-template <typename val_t> struct Pack16;
-template <> struct Pack16<float> { using type = float4; };
-template <> struct Pack16<double> { using type = double2; };
-template <> struct Pack16<int32_t> { using type = I32x4; };
-
 // alpha / beta exist for (+, *) on floating point; everything else stores what it reduced
 template <int SRI, typename val_t>
 constexpr bool kMultiScaled = SRI == MI355_SEMIRING_PLUS_TIMES && std::is_floating_point<val_t>::value;
-
-// the lane's V columns of a row: one 16-byte access when the row is aligned and all V exist, else the nv that do
-template <typename val_t, int V>
-__device__ __forceinline__ void load_cols(val_t (&v)[V], const val_t* p, int nv, bool vec) {
-    if (vec && nv == V) {
-        const auto t = *reinterpret_cast<const typename Pack16<val_t>::type*>(p);
-        v[0] = t.x; v[1] = t.y;
-        if constexpr (V == 4) { v[2] = t.z; v[3] = t.w; }
-    } else {
-#pragma unroll
-        for (int j = 0; j < V; ++j) v[j] = j < nv ? p[j] : val_t(0);
-    }
-}
-
-template <typename val_t, int V>
-__device__ __forceinline__ void store_cols(const val_t (&v)[V], val_t* p, int nv, bool vec) {
-    if (vec && nv == V) {
-        typename Pack16<val_t>::type t;
-        t.x = v[0]; t.y = v[1];
-        if constexpr (V == 4) { t.z = v[2]; t.w = v[3]; }
-        *reinterpret_cast<typename Pack16<val_t>::type*>(p) = t;
-    } else {
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-            if (j < nv) p[j] = v[j];
-    }
-}
 
 // (+, *) on floating point: Y[r, tile] = alpha * sum + beta * Y[r, tile], Y read only when beta != 0.
 // Otherwise Y[r, tile] = sum, and Y is not read.
@@ -195,25 +159,21 @@ void multi_fill_args(Args& a, const MultiShape& m, const void* X, int64_t ldx, v
     a.Aj = m.Aj;
     a.X = static_cast<const vec_t*>(X); a.Y = static_cast<vec_t*>(Y);
     a.ldx = ldx; a.ldy = ldy;
-    a.x_vec = (reinterpret_cast<uintptr_t>(X) % 16 == 0 && (size_t(ldx) * sizeof(vec_t)) % 16 == 0) ? 1 : 0;
-    a.y_vec = (reinterpret_cast<uintptr_t>(Y) % 16 == 0 && (size_t(ldy) * sizeof(vec_t)) % 16 == 0) ? 1 : 0;
+    a.x_vec = rows_aligned16<vec_t>(X, ldx) ? 1 : 0;
+    a.y_vec = rows_aligned16<vec_t>(Y, ldy) ? 1 : 0;
     a.alpha = decltype(a.alpha)(m.alpha); a.beta = decltype(a.beta)(m.beta);
     a.carry_row = m.carry_row; a.carry_val = static_cast<decltype(a.carry_val)>(m.carry_val); a.carry_ld = m.carry_ld;
 }
 
-// the passes of one execute: tiles of V * kMultiGroupsMax columns, the last one as narrow as fits.  slice(lanes) launches
+// the passes of one execute: tiles of V * kSliceGroupsMax columns, the last one as narrow as fits.  slice(lanes) launches
 // the slice kernel of C = lanes::value lanes per slot on the tile that a.col_begin / a.cols describe.
 template <int V, typename Args, typename Slice>
 int multi_passes(Args& a, int32_t k, Slice slice) {
-    constexpr int kWidest = V * kMultiGroupsMax;
+    constexpr int kWidest = V * kSliceGroupsMax;
     for (int32_t cb = 0; cb < k; cb += kWidest) {
         a.col_begin = cb;
         a.cols = std::min<int32_t>(k - cb, kWidest);
-        const int groups = (a.cols + V - 1) / V;
-        if (groups <= 1) slice(std::integral_constant<int, 1>());
-        else if (groups <= 2) slice(std::integral_constant<int, 2>());
-        else if (groups <= 4) slice(std::integral_constant<int, 4>());
-        else slice(std::integral_constant<int, 8>());
+        with_slot_lanes((a.cols + V - 1) / V, slice);
         MI355_HIP_TRY(hipGetLastError());
     }
     return MI355_SPMV_OK;
@@ -227,7 +187,7 @@ int launch_multi(const MultiShape& m, const void* Ax, const void* X, int64_t ldx
     multi_fill_args<MultiArgs<val_t>, val_t>(a, m, X, ldx, Y, ldy);
     a.Ax = PATTERN ? nullptr : static_cast<const val_t*>(Ax);
     const off_t* Ap = static_cast<const off_t*>(m.Ap);
-    const dim3 grid(unsigned((m.n_slices + kMultiWaves - 1) / kMultiWaves)), block(kBlock);
+    const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
     if (const int st = multi_passes<16 / int(sizeof(val_t))>(a, k, [&](auto lanes) {
             hipLaunchKernelGGL((multi_slice_kernel<off_t, val_t, decltype(lanes)::value, SRI, PATTERN>), grid, block, 0, s, a, Ap);
         }))

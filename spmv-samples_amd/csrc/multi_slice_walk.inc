@@ -4,6 +4,8 @@
 // and the typed kernels then no longer compile to the registers and occupancy on record (profiles/); included text is
 // compiled as part of the kernel, as it always was.
 //
+// The walk begins with the cut that SDDMM shares (slice_cut.inc, included below; slice_cut.hpp holds the geometry).
+//
 // In scope where it is included: the kernel's arguments a (the policy's Args) and Ap (const off_t* __restrict__), the
 // kernel's template argument C = lanes per nonzero slot (16-byte column groups of the tile; the wave holds S = 64 / C
 // slots), and a policy type P that says what differs between the value-type families:
@@ -27,42 +29,9 @@
     using acc_t = typename P::acc_t;
     constexpr int V = P::V;
     constexpr int S = kWave / C;
-    // row offsets of the slice relative to its first nonzero, clamped to [0, nn + 1]: entry i belongs to row r0 + i
-    __shared__ int32_t rel_all[kMultiWaves][kMultiSlice + 2];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int c = lane % C, s = lane / C;
-    int32_t* rel = rel_all[threadIdx.x / kWave];
-    const int64_t w = int64_t(blockIdx.x) * kMultiWaves + threadIdx.x / kWave;
-    const bool active = w < a.n_slices;
-    int64_t r0 = 0, r1 = 0, n0 = 0;
-    int nr = -1, nn = 0;
-    bool carried_in = false;    // (kTails) row r0 began in an earlier slice
-    if (active) {
-        // merge-path diagonals of the slice: lanes 0..31 search its start, lanes 32..63 its end.  Row end r comes before
-        // nonzero n iff Ap[r + 1] <= n; (r, n) = row ends and nonzeros in front of the diagonal.
-        const int64_t items = int64_t(a.n_rows) + a.nnz;
-        int64_t d = (lane < 32 ? w : w + 1) * kMultiSlice;
-        if (d > items) d = items;
-        int64_t lo = d > a.nnz ? d - a.nnz : 0, hi = d < a.n_rows ? d : a.n_rows;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (int64_t(Ap[mid + 1]) <= d - mid - 1) lo = mid + 1; else hi = mid;
-        }
-        const int64_t n = d - lo;
-        r0 = __shfl(lo, 0); r1 = __shfl(lo, 32);
-        n0 = __shfl(n, 0);
-        nn = int(__shfl(n, 32) - n0);
-        // rows r0 .. r_last have nonzeros or their end here (row r1, when there is one, does not end in this slice)
-        const int64_t r_last = r1 < a.n_rows ? r1 : int64_t(a.n_rows) - 1;
-        nr = int(r_last - r0) + 1;
-        for (int i = lane; i <= nr; i += kWave) {
-            const int64_t v = int64_t(Ap[r0 + i]) - n0;
-            rel[i] = v < 0 ? 0 : v > nn ? nn + 1 : int32_t(v);
-        }
-        if constexpr (P::kTails) carried_in = int64_t(Ap[r0]) < n0;
-    }
-    __syncthreads();
-    if (!active) return;
+    constexpr bool kCutCarriedIn = P::kTails, kCutKeepsR1 = true;   // what slice_cut.inc asks its includer
+    constexpr int kCutNrInit = -1;
+#include "slice_cut.inc"        // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
 
     acc_t acc[V];           // per-slot partial of the open row (the row whose nonzeros are not all seen yet)
 #pragma unroll
@@ -80,15 +49,11 @@
         if (m < nn) {
             col = a.Aj[n0 + m];
             if constexpr (P::kValued) ax = P::ax(a.Ax[n0 + m]);
-            int lo = 0, hi = nr - 1;
-            while (lo < hi) {           // the last i with rel[i] <= m (empty rows repeat an offset: the last is the owner)
-                const int mid = (lo + hi + 1) >> 1;
-                if (rel[mid] <= m) lo = mid; else hi = mid - 1;
-            }
+#include "slice_cut_row.inc"     // leaves lo: the nonzero's row, relative to r0
             ie = lo * 2 + (rel[lo + 1] == m + 1 ? 1 : 0);
         }
         const int left = nn - base;
-        const int steps = left >= kWave ? C : (left + S - 1) / S;
+        const int steps = slice_group_steps<C>(left);
         for (int t = 0; t < steps; ++t) {
             // slot s takes nonzero t * S + s of the 64
             int32_t col_s = col;

@@ -4,11 +4,10 @@
 // respect to Ax, the edge score of graph attention, the residual of a factorisation on a sparse sample.  An object of
 // its own beside mi355_spmv_multi: the kernel, its launch and the extern "C" entry points, all in this unit.
 //
-//   sddmm_slice_kernel   one WAVE per slice of kSddmmSlice merge items (row ends + nonzeros: a run of empty rows cannot
-//                        make the row range of a slice unbounded, a hub row is spread over as many waves as it has
-//                        slices) — the cut of multi_slice_walk.inc, restated here.  The wave finds its two merge-path
-//                        diagonals, keeps its rows' offsets in LDS relative to its first nonzero, and walks its
-//                        nonzeros 64 at a time: Aj (and Ax) are loaded coalesced, one per lane, and each lane finds its
+//   sddmm_slice_kernel   one WAVE per slice of kSliceLen merge items (row ends + nonzeros): the cut of the multi-vector
+//                        kind, shared with it (slice_cut.hpp, slice_cut.inc, slice_cut_row.inc).  The wave finds its two
+//                        merge-path diagonals, keeps its rows' offsets in LDS relative to its first nonzero, and walks
+//                        its nonzeros 64 at a time: Aj (and Ax) are loaded coalesced, one per lane, and each lane finds its
 //                        nonzero's row by a binary search in LDS.  Lanes are (nonzero slot x 16-byte column group):
 //                        a slot of C lanes takes one nonzero, lane c gathers its 16 bytes of V[col] and of U[row] and
 //                        multiplies them into ONE scalar partial; for k wider than the tile of C groups the lane goes
@@ -26,13 +25,15 @@
 // registers; the arithmetic is one piece of code behind both).
 #include <new>
 
-#include "common.hpp"
+#include "slice_cut.hpp"
 
 namespace mi355 {
 
-constexpr int kSddmmSlice = 1024;                  // merge items per slice (= per wave): kMultiSlice's length
-constexpr int kSddmmGroupsMax = 8;                 // most 16-byte column groups of a tile: 32 fp32, 16 fp64 columns
-constexpr int kSddmmWaves = kBlock / kWave;        // slices per workgroup
+// The geometry that the host simulation's tables are written for: tests/test_sddmm_sim_cpu.py reads these two lines
+// and holds tests/sddmm_cases.py to them.  The kernel uses slice_cut.hpp's constants; a change there stops here.
+constexpr int kSddmmSlice = 1024;
+constexpr int kSddmmGroupsMax = 8;
+static_assert(kSddmmSlice == kSliceLen && kSddmmGroupsMax == kSliceGroupsMax, "tests/sddmm_cases.py is tabled for this geometry");
 
 template <typename val_t>
 struct SddmmArgs {
@@ -49,24 +50,6 @@ struct SddmmArgs {
     val_t alpha, beta;
 };
 
-template <typename val_t> struct SddmmPack16;
-template <> struct SddmmPack16<float> { using type = float4; };
-template <> struct SddmmPack16<double> { using type = double2; };
-
-// the lane's W columns of a row: one 16-byte load when the row is aligned and all W exist, else the nv that do; a
-// column that does not exist is 0 and is never read
-template <typename val_t, int W>
-__device__ __forceinline__ void sddmm_load_cols(val_t (&v)[W], const val_t* p, int nv, bool vec) {
-    if (vec && nv == W) {
-        const auto t = *reinterpret_cast<const typename SddmmPack16<val_t>::type*>(p);
-        v[0] = t.x; v[1] = t.y;
-        if constexpr (W == 4) { v[2] = t.z; v[3] = t.w; }
-    } else {
-#pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = j < nv ? p[j] : val_t(0);
-    }
-}
-
 // one rounding per column whatever the compiler would otherwise choose to contract: the promise above, spelled out
 __device__ __forceinline__ float sddmm_fma(float x, float y, float z) { return __builtin_fmaf(x, y, z); }
 __device__ __forceinline__ double sddmm_fma(double x, double y, double z) { return __builtin_fma(x, y, z); }
@@ -76,41 +59,9 @@ template <typename off_t, typename val_t, int C, bool VALUED>
 __global__ __launch_bounds__(kBlock) void sddmm_slice_kernel(const SddmmArgs<val_t> a, const off_t* __restrict__ Ap) {
     constexpr int W = 16 / int(sizeof(val_t));      // columns of a lane per tile
     constexpr int S = kWave / C;
-    // row offsets of the slice relative to its first nonzero, clamped to [0, nn + 1]: entry i belongs to row r0 + i
-    __shared__ int32_t rel_all[kSddmmWaves][kSddmmSlice + 2];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int c = lane % C, s = lane / C;
-    int32_t* rel = rel_all[threadIdx.x / kWave];
-    const int64_t w = int64_t(blockIdx.x) * kSddmmWaves + threadIdx.x / kWave;
-    const bool active = w < a.n_slices;
-    int64_t r0 = 0, n0 = 0;
-    int nr = 0, nn = 0;
-    if (active) {
-        // merge-path diagonals of the slice: lanes 0..31 search its start, lanes 32..63 its end.  Row end r comes before
-        // nonzero n iff Ap[r + 1] <= n; (r, n) = row ends and nonzeros in front of the diagonal.
-        const int64_t items = int64_t(a.n_rows) + a.nnz;
-        int64_t d = (lane < 32 ? w : w + 1) * kSddmmSlice;
-        if (d > items) d = items;
-        int64_t lo = d > a.nnz ? d - a.nnz : 0, hi = d < a.n_rows ? d : a.n_rows;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (int64_t(Ap[mid + 1]) <= d - mid - 1) lo = mid + 1; else hi = mid;
-        }
-        const int64_t n = d - lo;
-        r0 = __shfl(lo, 0);
-        const int64_t r1 = __shfl(lo, 32);
-        n0 = __shfl(n, 0);
-        nn = int(__shfl(n, 32) - n0);
-        // rows r0 .. r_last have nonzeros or their end here (row r1, when there is one, does not end in this slice)
-        const int64_t r_last = r1 < a.n_rows ? r1 : int64_t(a.n_rows) - 1;
-        nr = int(r_last - r0) + 1;
-        for (int i = lane; i <= nr; i += kWave) {
-            const int64_t v = int64_t(Ap[r0 + i]) - n0;
-            rel[i] = v < 0 ? 0 : v > nn ? nn + 1 : int32_t(v);
-        }
-    }
-    __syncthreads();
-    if (!active) return;
+    constexpr bool kCutCarriedIn = false, kCutKeepsR1 = false;      // what slice_cut.inc asks its includer
+    constexpr int kCutNrInit = 0;
+#include "slice_cut.inc"        // leaves lane, c, s, w, r0, n0, nn, nr, rel
 
     for (int base = 0; base < nn; base += kWave) {
         // 64 nonzeros, one per lane, coalesced; each lane finds its nonzero's row in the slice's offsets
@@ -121,15 +72,11 @@ __global__ __launch_bounds__(kBlock) void sddmm_slice_kernel(const SddmmArgs<val
         if (m < nn) {
             col = a.Aj[n0 + m];
             if constexpr (VALUED) ax = a.Ax[n0 + m];
-            int lo = 0, hi = nr - 1;
-            while (lo < hi) {           // the last i with rel[i] <= m (empty rows repeat an offset: the last is the owner)
-                const int mid = (lo + hi + 1) >> 1;
-                if (rel[mid] <= m) lo = mid; else hi = mid - 1;
-            }
+#include "slice_cut_row.inc"     // leaves lo: the nonzero's row, relative to r0
             row_i = lo;
         }
         const int left = nn - base;
-        const int steps = left >= kWave ? C : (left + S - 1) / S;
+        const int steps = slice_group_steps<C>(left);
         val_t dot = val_t(0);           // of this lane's own nonzero m, handed back by the step that took it
         for (int t = 0; t < steps; ++t) {
             // slot s takes nonzero t * S + s of the 64
@@ -148,8 +95,8 @@ __global__ __launch_bounds__(kBlock) void sddmm_slice_kernel(const SddmmArgs<val
                     const int nv = min(max(a.k - cb - c * W, 0), W);
                     if (nv > 0) {
                         val_t u[W], v[W];
-                        sddmm_load_cols<val_t, W>(u, up + cb, nv, a.u_vec != 0);
-                        sddmm_load_cols<val_t, W>(v, vp + cb, nv, a.v_vec != 0);
+                        load_cols<val_t, W>(u, up + cb, nv, a.u_vec != 0);
+                        load_cols<val_t, W>(v, vp + cb, nv, a.v_vec != 0);
 #pragma unroll
                         for (int j = 0; j < W; ++j) part = sddmm_fma(u[j], v[j], part);
                     }
@@ -200,14 +147,7 @@ int sddmm_check_create(const char* who, int off_type, int val_type, int32_t n_ro
         set_error("%s: val_type %d is not a type of U, V and out (F32 or F64; a pattern matrix is Ax = NULL at execute)", who, val_type);
         return MI355_SPMV_EINVAL;
     }
-    if (n_rows < 0) { set_error("%s: negative n_rows", who); return MI355_SPMV_EINVAL; }
-    if (n_cols < 0) { set_error("%s: negative n_cols", who); return MI355_SPMV_EINVAL; }
-    if (nnz < 0) { set_error("%s: negative nnz", who); return MI355_SPMV_EINVAL; }
-    if (off_type == MI355_OFF_I32 && nnz > INT32_MAX) { set_error("%s: nnz does not fit 32-bit offsets", who); return MI355_SPMV_EINVAL; }
-    if (n_rows > 0 && !Ap) { set_error("%s: null Ap", who); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && !Aj) { set_error("%s: null Aj", who); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && (n_cols == 0 || n_rows == 0)) { set_error("%s: nnz > 0 but n_rows or n_cols is 0", who); return MI355_SPMV_EINVAL; }
-    return MI355_SPMV_OK;
+    return check_csr_structure(who, off_type, n_rows, n_cols, nnz, Ap, Aj);
 }
 
 // argument-only checks of an execute
@@ -226,7 +166,7 @@ void sddmm_fill(mi355_spmv_sddmm& m, int off_type, int val_type, int32_t n_rows,
     m.off_type = off_type; m.val_type = val_type;
     m.n_rows = n_rows; m.n_cols = n_cols; m.nnz = nnz;
     m.Ap = Ap; m.Aj = Aj;
-    m.n_slices = (int64_t(n_rows) + nnz + kSddmmSlice - 1) / kSddmmSlice;
+    m.n_slices = slice_count(n_rows, nnz);
 }
 
 // the one launch of an execute: C from k alone, valued / pattern from Ax
@@ -240,17 +180,15 @@ int sddmm_launch(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64
     a.U = static_cast<const val_t*>(U); a.V = static_cast<const val_t*>(V);
     a.out = static_cast<val_t*>(out);
     a.ldu = ldu; a.ldv = ldv; a.k = k;
-    a.u_vec = (reinterpret_cast<uintptr_t>(U) % 16 == 0 && (size_t(ldu) * sizeof(val_t)) % 16 == 0) ? 1 : 0;
-    a.v_vec = (reinterpret_cast<uintptr_t>(V) % 16 == 0 && (size_t(ldv) * sizeof(val_t)) % 16 == 0) ? 1 : 0;
+    a.u_vec = rows_aligned16<val_t>(U, ldu) ? 1 : 0;
+    a.v_vec = rows_aligned16<val_t>(V, ldv) ? 1 : 0;
     a.alpha = val_t(m.alpha); a.beta = val_t(m.beta);
     const off_t* Ap = static_cast<const off_t*>(m.Ap);
-    const dim3 grid(unsigned((m.n_slices + kSddmmWaves - 1) / kSddmmWaves)), block(kBlock);
+    const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
     constexpr int W = 16 / int(sizeof(val_t));
-    const int groups = (k + W - 1) / W;
-    if (groups <= 1) hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, 1, VALUED>), grid, block, 0, s, a, Ap);
-    else if (groups <= 2) hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, 2, VALUED>), grid, block, 0, s, a, Ap);
-    else if (groups <= 4) hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, 4, VALUED>), grid, block, 0, s, a, Ap);
-    else hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, kSddmmGroupsMax, VALUED>), grid, block, 0, s, a, Ap);
+    with_slot_lanes((k + W - 1) / W, [&](auto lanes) {
+        hipLaunchKernelGGL((sddmm_slice_kernel<off_t, val_t, decltype(lanes)::value, VALUED>), grid, block, 0, s, a, Ap);
+    });
     MI355_HIP_TRY(hipGetLastError());
     return MI355_SPMV_OK;
 }
@@ -322,10 +260,10 @@ int mi355_spmv_sddmm_get_info(const mi355_spmv_sddmm* m, mi355_spmv_sddmm_info* 
     if (!m || !info) { set_error("sddmm_get_info: null argument"); return MI355_SPMV_EINVAL; }
     memset(info, 0, sizeof(*info));
     info->off_type = m->off_type; info->val_type = m->val_type;
-    info->slice_len = kSddmmSlice;
+    info->slice_len = kSliceLen;
     info->block_threads = kBlock;
     info->n_slices = m->n_slices;
-    info->grid_blocks = (m->n_slices + kSddmmWaves - 1) / kSddmmWaves;
+    info->grid_blocks = slice_grid(m->n_slices);
     snprintf(info->main_kernel, sizeof(info->main_kernel), "sddmm_slice_kernel");
     return MI355_SPMV_OK;
 }

@@ -7,7 +7,8 @@ CSRC     := ../../spmv-samples_amd/csrc
 # the sanitizer runtimes are linked statically: the program then loads the same way whatever the environment preloads
 SIM_SAN  ?= -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan
 
-sddmm_sim: sddmm_sim.cpp simt/hip/hip_runtime.h sim_io.hpp $(CSRC)/sddmm.hip $(CSRC)/common.hpp ../../include/mi355_spmv.h
+sddmm_sim: sddmm_sim.cpp simt/hip/hip_runtime.h sim_io.hpp $(CSRC)/sddmm.hip $(CSRC)/slice_cut.hpp \
+           $(CSRC)/slice_cut.inc $(CSRC)/slice_cut_row.inc $(CSRC)/common.hpp ../../include/mi355_spmv.h
 	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer $(SIM_SAN) -Isimt -o $@ $<
 
 clean:

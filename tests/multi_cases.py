@@ -17,10 +17,11 @@ import struct
 import numpy as np
 
 # The kernel's geometry.  Both test files assert it: the host file against the constants of csrc/multi.hip and
-# csrc/common.hpp (kMultiSlice, kWave, kMultiGroupsMax), the device file against info() (assert_geometry).
+# csrc/common.hpp (kMultiSlice, kWave, kMultiGroupsMax; multi.hip asserts them equal to slice_cut.hpp's kSliceLen and
+# kSliceGroupsMax, which the kernels use), the device file against info() (assert_geometry).
 SLICE_LEN = 1024                    # merge items per slice = info()["slice_len"]
 STEP = 64                           # nonzeros per step = the wave width
-LANES_PER_SLOT = (1, 2, 4, 8)       # up to kMultiGroupsMax 16-byte column groups: widest_tile = 8 * VEC
+LANES_PER_SLOT = (1, 2, 4, 8)       # up to kSliceGroupsMax 16-byte column groups: widest_tile = 8 * VEC
 SLOTS = tuple(STEP // c for c in LANES_PER_SLOT)
 CANARY = -777.25
 KF = 72                             # columns of the full X / Y0 of a matrix: a case takes columns c0 .. c0 + k

@@ -209,6 +209,23 @@ def test_nothing_stored_launches_nothing(sp):
         plan.destroy()
 
 
+@pytest.mark.parametrize("n_rows,nnz", [(0, 0), (1, 0), (23, 1000), (1, 1023), (1025, 0), (96, 4000), (4096, 1)])
+def test_the_multi_object_and_the_sddmm_object_cut_alike(sp, n_rows, nnz):
+    """No rows, one item, and n_rows + nnz = 1 023, 1 024, 1 025, 4 096, 4 097: both objects report one slice length, one
+    slice count and one grid (a create reads nothing of Ap / Aj; the multi object's needs the device for its carries)."""
+    lib = sp.capi.lib()
+    dummy = C.c_void_p(256)
+    hm, hs = C.c_void_p(), C.c_void_p()
+    assert lib.mi355_spmv_multi_create(C.byref(hm), 1, 0, n_rows, 7, nnz, dummy, dummy, 4) == 0
+    assert lib.mi355_spmv_sddmm_create(C.byref(hs), 1, 0, n_rows, 7, nnz, dummy, dummy) == 0
+    mi, si = sp.capi.MultiInfo(), sp.capi.SddmmInfo()
+    assert lib.mi355_spmv_multi_get_info(hm, C.byref(mi)) == 0 and lib.mi355_spmv_sddmm_get_info(hs, C.byref(si)) == 0
+    assert lib.mi355_spmv_multi_destroy(hm) == 0 and lib.mi355_spmv_sddmm_destroy(hs) == 0
+    assert (mi.slice_len, mi.n_slices, mi.grid_blocks) == (si.slice_len, si.n_slices, si.grid_blocks)
+    assert si.slice_len == sc.SLICE_LEN and si.n_slices == -(-(n_rows + nnz) // sc.SLICE_LEN)
+    assert si.grid_blocks == -(-si.n_slices // (si.block_threads // sc.STEP))
+
+
 @pytest.mark.parametrize("val", ["f32", "f64"])
 def test_sddmm_is_the_adjoint_of_spmm_in_ax(sp, val):
     """For integer dY, X, Ax: sum(out * Ax) == sum(dY * spmm(A, X)) exactly, out = SDDMM(dY, X) on the pattern — the
