@@ -46,6 +46,7 @@ extern "C" {
 #define MI355_SPMV_HAS_MULTI_SEMIRING 1 /* mi355_spmv_multi_create_typed / _set_semiring / _get_types / _genl_* / _pattern_* */
 #define MI355_SPMV_HAS_MULTI_HALF 1 /* mi355_spmv_multi_create_half / _half_*: X and Y in binary16 / bfloat16, fp32 arithmetic */
 #define MI355_SPMV_HAS_SDDMM 1 /* mi355_spmv_sddmm_*: dot(U[r], V[c]) at every stored entry (r, c) of A in one pass over A */
+#define MI355_SPMV_HAS_SDDMM_HALF 1 /* mi355_spmv_sddmm_create_half / _get_types / _half_*: U and V in binary16 / bfloat16, fp32 Ax and out */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -676,8 +677,9 @@ int mi355_spmv_multi_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, 
  * both add in the same order: an element of out depends on its row of U, its row of V, s, alpha, beta, its old value and
  * k only, never on where the entry lies in A nor on alignment, and two executes on the same inputs give the same bits.
  * Types: {I32, I64} offsets x {F32, F64} values.  MI355_VAL_I32: MI355_SPMV_ENOTSUP; PATTERN / F16 / BF16 / unknown as
- * val_type: MI355_SPMV_EINVAL (a pattern MATRIX is Ax = NULL at execute).  16-bit U / V, semirings, column-major
- * operands and the dist_* entry points are not built.
+ * val_type: MI355_SPMV_EINVAL (a pattern MATRIX is Ax = NULL at execute).  16-bit U / V under fp32 values are an object
+ * of their own (mi355_spmv_sddmm_create_half, below).  Semirings, column-major operands and the dist_* entry points are
+ * not built.
  * The work is cut as the multi-vector kind's: a wave owns a slice of slice_len merge items (row ends + nonzeros).  Each
  * element of out has one writer: no carries, no scratch, no atomics, ONE kernel per execute for any k >= 1.
  * Life cycle: create retains Ap / Aj (not copied; it does not read them), allocates nothing on the device and makes no
@@ -710,6 +712,40 @@ int mi355_spmv_sddmm_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const 
     const float* U, int64_t ldu, const float* V, int64_t ldv, float* out, int32_t k, void* stream);
 int mi355_spmv_sddmm_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, const double* Ax,
     const double* U, int64_t ldu, const double* V, int64_t ldv, double* out, int32_t k, void* stream);
+
+/* ---- SDDMM with 16-bit U and V and fp32 values and arithmetic (MI355_SPMV_HAS_SDDMM_HALF) ---------------------------
+ * For callers who keep features in 16 bits (mi355_spmv_multi_create_half) and want dAx or edge scores without widening
+ * dY and X first: no widening pass over the n x k operands, and half the bytes gathered per column.
+ *   out[n] = alpha * s[n] * sum_{j < k} float(U[r(n) * ldu + j]) * float(V[Aj[n] * ldv + j])  +  beta * out[n]
+ *   U, V      row-major as above, both in ONE vec_type: MI355_VAL_F16 (binary16) or MI355_VAL_BF16 (bfloat16)
+ *   Ax, out   fp32 (Ax NULL: a pattern matrix, s = 1)
+ * Every stored 16-bit value is widened exactly to fp32; products and sums are fp32; nothing is rounded to 16 bits.
+ * Everything else is the contract above: columns j >= k are never read, beta == 0 never reads out, any ldu, ldv >= k
+ * (16-byte loads when the pointer and ld * 2 are multiples of 16, else element by element; both add in the same order),
+ * one writer per element, no carries, no scratch, no atomics, ONE kernel per execute for any k >= 1 (none when nnz or
+ * n_rows is 0), graph-capturable.  A lane's 16 bytes are 8 columns: tiles of 8 / 16 / 32 / 64 columns, so the order of
+ * addition differs from the fp32 object's (4 columns per lane) and the two agree within rounding, not bit for bit
+ * (bit for bit where every partial sum is exact, as on small integers).
+ *   create_half   vec_type outside {F16, BF16}: MI355_SPMV_EINVAL (the text names vec_type); every other check is
+ *                 mi355_spmv_sddmm_create's; *out cleared on failure; no device call.
+ *   The object is executed, scaled, reported and destroyed by mi355_spmv_sddmm_execute / _set_alpha_beta / _get_info
+ *   (val_type = MI355_VAL_F32, main_kernel = "sddmm_half_slice_kernel") / _destroy.
+ *   get_types     (F32, F16 | BF16) for this object, (val_type, val_type) for one of mi355_spmv_sddmm_create; either
+ *                 pointer may be NULL.
+ * Out of scope: 16-bit out / Ax, fp32 U with 16-bit V or the reverse, semirings, column-major operands, dist_*, harness
+ * labels, an autograd.Function.                                                                                    */
+int mi355_spmv_sddmm_create_half(mi355_spmv_sddmm** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols,
+                                 int64_t nnz, const void* Ap, const int32_t* Aj);
+int mi355_spmv_sddmm_get_types(const mi355_spmv_sddmm* sddmm, int* val_type, int* vec_type);
+/* One-shots (U, V: binary16 / bfloat16 as stored): create_half, execute, destroy.  They do not synchronise the stream. */
+int mi355_spmv_sddmm_half_i32_f16(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, const float* Ax,
+    const void* U, int64_t ldu, const void* V, int64_t ldv, float* out, int32_t k, void* stream);
+int mi355_spmv_sddmm_half_i32_bf16(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, const float* Ax,
+    const void* U, int64_t ldu, const void* V, int64_t ldv, float* out, int32_t k, void* stream);
+int mi355_spmv_sddmm_half_i64_f16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, const float* Ax,
+    const void* U, int64_t ldu, const void* V, int64_t ldv, float* out, int32_t k, void* stream);
+int mi355_spmv_sddmm_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, const float* Ax,
+    const void* U, int64_t ldu, const void* V, int64_t ldv, float* out, int32_t k, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

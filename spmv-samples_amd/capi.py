@@ -56,6 +56,8 @@ EXPORTS = (
     + ["mi355_spmv_multi_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
     + ["mi355_spmv_sddmm_" + n for n in ("create", "set_alpha_beta", "execute", "get_info", "destroy")]
     + ["mi355_spmv_sddmm_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
+    + ["mi355_spmv_sddmm_create_half", "mi355_spmv_sddmm_get_types"]
+    + ["mi355_spmv_sddmm_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
 )
 
 
@@ -217,6 +219,11 @@ def lib():
                 getattr(L, "mi355_spmv_sddmm_%s_%s" % (o, v)).argtypes = [
                     C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+        L.mi355_spmv_sddmm_create_half.argtypes = L.mi355_spmv_sddmm_create.argtypes
+        L.mi355_spmv_sddmm_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        for o in ("i32", "i64"):
+            for v in ("f16", "bf16"):
+                getattr(L, "mi355_spmv_sddmm_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_sddmm_%s_f32" % o).argtypes
         _lib = L
     return _lib
 
@@ -801,16 +808,18 @@ def spmm_pattern(semiring, n_rows, n_cols, nnz, Ap, Aj, X, Y, stream=None):
     return Y
 
 
-def _sddmm_operands(n_rows, n_cols, nnz, val_dtype, Ax, U, V, out, k):
-    """The checks of an SDDMM execute, in MultiPlan's words: (Ax or None, ldu, ldv, out, k)."""
+def _sddmm_operands(n_rows, n_cols, nnz, val_dtype, Ax, U, V, out, k, vec_dtype=None):
+    """The checks of an SDDMM execute, in MultiPlan's words: (Ax or None, ldu, ldv, out, k).  vec_dtype: the type of U and V
+    where it is not val_dtype (a 16-bit plan)."""
+    vec_dtype = val_dtype if vec_dtype is None else vec_dtype
     if Ax is not None:
         _require_device(Ax)
         if Ax.dtype != val_dtype:
             raise TypeError("value type differs from the plan's")
         if Ax.numel() < nnz:
             raise ValueError("operand shorter than the plan's sizes")
-    ldu = _require_matrix(U, "U", n_rows, val_dtype)
-    ldv = _require_matrix(V, "V", n_cols, val_dtype)
+    ldu = _require_matrix(U, "U", n_rows, vec_dtype)
+    ldv = _require_matrix(V, "V", n_cols, vec_dtype)
     if k is None:
         k = U.size(1)
     if k < 1 or k > U.size(1) or k > V.size(1):
@@ -832,24 +841,39 @@ class SddmmPlan:
     V (n_cols x k) are 2-D row-major device tensors; views with a larger stride(0) are taken as they are.  out holds nnz
     values in CSR order.  val_dtype is float32 or float64.  The gradient of spmm with respect to Ax is
     SddmmPlan.execute(None, dY, X).  Holds references to Ap and Aj so they outlive the object; creating one touches no
-    device memory."""
+    device memory.
 
-    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype):
+    vec_dtype=torch.float16 / torch.bfloat16 (mi355_spmv_sddmm_create_half; val_dtype must be float32): U and V are held
+    in that type, Ax and out stay float32, every stored value is widened exactly and products and sums are float32.
+    plan.vec_dtype is the type of U and V (val_dtype without the argument)."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, vec_dtype=None):
         _require_device(Ap, Aj)
         if Aj.dtype != torch.int32:
             raise TypeError("Aj must be int32")
         if val_dtype not in (torch.float32, torch.float64):
             raise TypeError("val_dtype must be float32 or float64")
+        if vec_dtype is not None:
+            if vec_dtype not in MAT_TYPES:
+                raise TypeError("vec_dtype must be float16 or bfloat16 (or None: U and V in val_dtype)")
+            if val_dtype != torch.float32:
+                raise TypeError("vec_dtype needs val_dtype float32 (16-bit U and V under float32 Ax and out)")
         self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
         self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
+        self.vec_dtype = val_dtype if vec_dtype is None else vec_dtype
         self._h = C.c_void_p()
-        _check(lib().mi355_spmv_sddmm_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz,
-                                             C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr())), "mi355_spmv_sddmm_create")
+        args = (n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()))
+        if vec_dtype is None:
+            _check(lib().mi355_spmv_sddmm_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], *args),
+                   "mi355_spmv_sddmm_create")
+        else:
+            _check(lib().mi355_spmv_sddmm_create_half(C.byref(self._h), OFF_TYPES[Ap.dtype][0], MAT_TYPES[vec_dtype][0], *args),
+                   "mi355_spmv_sddmm_create_half")
 
     def execute(self, Ax, U, V, out=None, k=None, stream=None):
         """Asynchronous on `stream` (default: torch's current stream); returns out (made when None: then beta must be 0).
         k defaults to U.size(1); ldu / ldv are the operands' stride(0)."""
-        Ax, ldu, ldv, out, k = _sddmm_operands(self.n_rows, self.n_cols, self.nnz, self.val_dtype, Ax, U, V, out, k)
+        Ax, ldu, ldv, out, k = _sddmm_operands(self.n_rows, self.n_cols, self.nnz, self.val_dtype, Ax, U, V, out, k, self.vec_dtype)
         with torch.cuda.device(self.Ap.device):
             st = lib().mi355_spmv_sddmm_execute(self._h, C.c_void_p(Ax.data_ptr()) if Ax is not None else None,
                                                 C.c_void_p(U.data_ptr()), ldu, C.c_void_p(V.data_ptr()), ldv,
@@ -893,6 +917,26 @@ def sddmm(n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out=None, stream=None):
         raise TypeError("U must be float32 or float64")
     Ax, ldu, ldv, out, k = _sddmm_operands(n_rows, n_cols, nnz, U.dtype, Ax, U, V, out, None)
     name = "mi355_spmv_sddmm_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[U.dtype][1])
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
+                                  C.c_void_p(Ax.data_ptr()) if Ax is not None else None, C.c_void_p(U.data_ptr()), ldu,
+                                  C.c_void_p(V.data_ptr()), ldv, C.c_void_p(out.data_ptr()), k, _stream_ptr(stream))
+    _check(st, name)
+    return out
+
+
+def sddmm_half(n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out=None, stream=None):
+    """One-shot SDDMM on 16-bit U and V (mi355_spmv_sddmm_half_<off>_<f16|bf16>): sddmm's arguments with U and V in one of
+    float16 / bfloat16, Ax (or None) and out in float32.  Asynchronous on `stream`: it does not synchronise."""
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if not getattr(U, "is_cuda", False):
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if U.dtype not in MAT_TYPES:
+        raise TypeError("U must be float16 or bfloat16")
+    Ax, ldu, ldv, out, k = _sddmm_operands(n_rows, n_cols, nnz, torch.float32, Ax, U, V, out, None, U.dtype)
+    name = "mi355_spmv_sddmm_half_%s_%s" % (OFF_TYPES[Ap.dtype][1], MAT_TYPES[U.dtype][1])
     with torch.cuda.device(Ap.device):
         st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
                                   C.c_void_p(Ax.data_ptr()) if Ax is not None else None, C.c_void_p(U.data_ptr()), ldu,

@@ -16,18 +16,17 @@
 //     tail, reads Yold only when beta != 0 and stores the rounded row.  It is the row's only writer.
 //   - every execute rewrites carry_row of every slice, and the carry / tail of every slice that has one, for the k
 //     columns of the execute: the fix-up reads nothing that an earlier (wider) execute left.
-// The conversions: half_convert.hpp.
+// The conversions: half_convert.hpp; the widening load of a lane's eight columns (mh::load_cols, U32x4, kHalfV):
+// half_cols.hpp, shared with SDDMM's 16-bit kernel.
 #pragma once
 
-#include "half_convert.hpp"
+#include "half_cols.hpp"
 #include "multi_kernels.hpp"
 
 namespace mi355 {
 namespace mh {
 
 using mi355::F16;           // (binary16 as multi.hip names it)
-
-constexpr int kHalfV = 8;   // columns of a lane: 16 bytes of a row of X / Y
 
 template <typename vec_t, typename mat_t>
 struct MultiHalfArgs {
@@ -47,25 +46,6 @@ struct MultiHalfArgs {
     float* tail_val;        // [n_slices][carry_ld]: the partial of the slice's first row, when that row began earlier and ends here
     int64_t carry_ld;
 };
-
-struct __attribute__((aligned(16), may_alias)) U32x4 { uint32_t x, y, z, w; };   // eight 16-bit columns per lane
-
-// the lane's 8 columns of a row, widened: one 16-byte access when the row is aligned and all 8 exist, else the nv that do
-template <typename vec_t>
-__device__ __forceinline__ void load_cols(float (&v)[kHalfV], const vec_t* p, int nv, bool vec) {
-    if (vec && nv == kHalfV) {
-        const U32x4 t = *reinterpret_cast<const U32x4*>(p);
-        const uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            v[2 * q] = widen(from_bits(uint16_t(w[q] & 0xFFFFu), vec_t()));
-            v[2 * q + 1] = widen(from_bits(uint16_t(w[q] >> 16), vec_t()));
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kHalfV; ++j) v[j] = j < nv ? widen(p[j]) : 0.0f;
-    }
-}
 
 template <typename vec_t>
 __device__ __forceinline__ void store_cols(const float (&v)[kHalfV], vec_t* p, int nv, bool vec) {

@@ -23,8 +23,12 @@
 // a function of (U[r, :k], V[c, :k], s, alpha, beta, out_old, k) only — not of where in a slice, step or slot its
 // nonzero falls, and not of the alignment of U and V (the 16-byte and the element-by-element load fill the same
 // registers; the arithmetic is one piece of code behind both).
+//
+// U and V in 16 bits under fp32 Ax, out and arithmetic (mi355_spmv_sddmm_create_half): sddmm_half_slice_kernel and its
+// launch, sddmm_half_kernel.hpp; the object and the entry points are this unit's.
 #include <new>
 
+#include "sddmm_half_kernel.hpp"
 #include "slice_cut.hpp"
 
 namespace mi355 {
@@ -125,6 +129,7 @@ using namespace mi355;
 
 struct mi355_spmv_sddmm {   // the opaque handle of include/mi355_spmv.h: host memory only, nothing on the device
     int off_type = 0, val_type = 0;
+    int vec_type = 0;       // the type of U and V: val_type, or F16 / BF16 under F32 values (create_half)
     int32_t n_rows = 0, n_cols = 0;
     int64_t nnz = 0;
     const void* Ap = nullptr;
@@ -161,9 +166,19 @@ int sddmm_check_execute(const char* who, int64_t nnz, const void* U, int64_t ldu
     return MI355_SPMV_OK;
 }
 
-void sddmm_fill(mi355_spmv_sddmm& m, int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
-                const int32_t* Aj) {
-    m.off_type = off_type; m.val_type = val_type;
+// the checks of create_half (and of the 16-bit one-shots): vec_type first, then what a create of fp32 values checks
+int sddmm_check_create_half(const char* who, int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
+                            const int32_t* Aj) {
+    if (vec_type != MI355_VAL_F16 && vec_type != MI355_VAL_BF16) {
+        set_error("%s: vec_type %d is not a 16-bit type of U and V (MI355_VAL_F16 or MI355_VAL_BF16)", who, vec_type);
+        return MI355_SPMV_EINVAL;
+    }
+    return sddmm_check_create(who, off_type, MI355_VAL_F32, n_rows, n_cols, nnz, Ap, Aj);
+}
+
+void sddmm_fill(mi355_spmv_sddmm& m, int off_type, int val_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+                const void* Ap, const int32_t* Aj) {
+    m.off_type = off_type; m.val_type = val_type; m.vec_type = vec_type;
     m.n_rows = n_rows; m.n_cols = n_cols; m.nnz = nnz;
     m.Ap = Ap; m.Aj = Aj;
     m.n_slices = slice_count(n_rows, nnz);
@@ -204,6 +219,15 @@ int sddmm_run(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64_t 
               void* stream) {
     if (m.nnz == 0 || m.n_rows == 0) return MI355_SPMV_OK;      // no stored entry: nothing to write, nothing launched
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (m.vec_type != m.val_type) {     // 16-bit U and V under fp32 values
+        const bool i32 = m.off_type == MI355_OFF_I32;
+        auto run = [&](auto off, auto vec) {
+            return sddmm_half_launch<decltype(off), decltype(vec)>(m.n_rows, m.nnz, m.n_slices, m.Ap, m.Aj, m.alpha, m.beta, Ax, U, ldu, V,
+                                                                   ldv, out, k, s);
+        };
+        if (m.vec_type == MI355_VAL_F16) return i32 ? run(int32_t(), F16()) : run(int64_t(), F16());
+        return i32 ? run(int32_t(), Bf16()) : run(int64_t(), Bf16());
+    }
     if (m.off_type == MI355_OFF_I32)
         return m.val_type == MI355_VAL_F64 ? sddmm_launch_values<int32_t, double>(m, Ax, U, ldu, V, ldv, out, k, s)
                                            : sddmm_launch_values<int32_t, float>(m, Ax, U, ldu, V, ldv, out, k, s);
@@ -219,7 +243,17 @@ int sddmm_one_shot(int off_type, int val_type, int32_t n_rows, int32_t n_cols, i
     if (const int st = sddmm_check_create("sddmm", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj)) return st;
     if (const int st = sddmm_check_execute("sddmm", nnz, U, ldu, V, ldv, out, k)) return st;
     mi355_spmv_sddmm m;
-    sddmm_fill(m, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj);
+    sddmm_fill(m, off_type, val_type, val_type, n_rows, n_cols, nnz, Ap, Aj);
+    return sddmm_run(m, Ax, U, ldu, V, ldv, out, k, stream);
+}
+
+int sddmm_half_one_shot(int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
+                        const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out, int32_t k, void* stream) {
+    set_error("%s", "");
+    if (const int st = sddmm_check_create_half("sddmm_half", off_type, vec_type, n_rows, n_cols, nnz, Ap, Aj)) return st;
+    if (const int st = sddmm_check_execute("sddmm_half", nnz, U, ldu, V, ldv, out, k)) return st;
+    mi355_spmv_sddmm m;
+    sddmm_fill(m, off_type, MI355_VAL_F32, vec_type, n_rows, n_cols, nnz, Ap, Aj);
     return sddmm_run(m, Ax, U, ldu, V, ldv, out, k, stream);
 }
 
@@ -235,8 +269,28 @@ int mi355_spmv_sddmm_create(mi355_spmv_sddmm** out, int off_type, int val_type, 
     if (const int st = sddmm_check_create("sddmm_create", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj)) return st;
     mi355_spmv_sddmm* m = new (std::nothrow) mi355_spmv_sddmm();
     if (!m) { set_error("sddmm_create: host allocation failed"); return MI355_SPMV_ENOMEM; }
-    sddmm_fill(*m, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj);
+    sddmm_fill(*m, off_type, val_type, val_type, n_rows, n_cols, nnz, Ap, Aj);
     *out = m;
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_sddmm_create_half(mi355_spmv_sddmm** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+                                 const void* Ap, const int32_t* Aj) {
+    set_error("%s", "");
+    if (!out) { set_error("sddmm_create_half: null object pointer (out)"); return MI355_SPMV_EINVAL; }
+    *out = nullptr;
+    if (const int st = sddmm_check_create_half("sddmm_create_half", off_type, vec_type, n_rows, n_cols, nnz, Ap, Aj)) return st;
+    mi355_spmv_sddmm* m = new (std::nothrow) mi355_spmv_sddmm();
+    if (!m) { set_error("sddmm_create_half: host allocation failed"); return MI355_SPMV_ENOMEM; }
+    sddmm_fill(*m, off_type, MI355_VAL_F32, vec_type, n_rows, n_cols, nnz, Ap, Aj);
+    *out = m;
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_sddmm_get_types(const mi355_spmv_sddmm* m, int* val_type, int* vec_type) {
+    if (!m) { set_error("sddmm_get_types: null object"); return MI355_SPMV_EINVAL; }
+    if (val_type) *val_type = m->val_type;
+    if (vec_type) *vec_type = m->vec_type;
     return MI355_SPMV_OK;
 }
 
@@ -264,7 +318,7 @@ int mi355_spmv_sddmm_get_info(const mi355_spmv_sddmm* m, mi355_spmv_sddmm_info* 
     info->block_threads = kBlock;
     info->n_slices = m->n_slices;
     info->grid_blocks = slice_grid(m->n_slices);
-    snprintf(info->main_kernel, sizeof(info->main_kernel), "sddmm_slice_kernel");
+    snprintf(info->main_kernel, sizeof(info->main_kernel), m->vec_type != m->val_type ? "sddmm_half_slice_kernel" : "sddmm_slice_kernel");
     return MI355_SPMV_OK;
 }
 
@@ -282,5 +336,15 @@ MI355_SPMV_DEFINE_SDDMM(i32_f32, int32_t, MI355_OFF_I32, float, MI355_VAL_F32)
 MI355_SPMV_DEFINE_SDDMM(i32_f64, int32_t, MI355_OFF_I32, double, MI355_VAL_F64)
 MI355_SPMV_DEFINE_SDDMM(i64_f32, int64_t, MI355_OFF_I64, float, MI355_VAL_F32)
 MI355_SPMV_DEFINE_SDDMM(i64_f64, int64_t, MI355_OFF_I64, double, MI355_VAL_F64)
+
+#define MI355_SPMV_DEFINE_SDDMM_HALF(SUF, OFF, OFFENUM, VECENUM)                                                              \
+    int mi355_spmv_sddmm_half_##SUF(int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap, const int32_t* Aj, const float* Ax, \
+                                    const void* U, int64_t ldu, const void* V, int64_t ldv, float* out, int32_t k, void* stream) { \
+        return sddmm_half_one_shot(OFFENUM, VECENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, Ax, U, ldu, V, ldv, out, k, stream); \
+    }
+MI355_SPMV_DEFINE_SDDMM_HALF(i32_f16, int32_t, MI355_OFF_I32, MI355_VAL_F16)
+MI355_SPMV_DEFINE_SDDMM_HALF(i32_bf16, int32_t, MI355_OFF_I32, MI355_VAL_BF16)
+MI355_SPMV_DEFINE_SDDMM_HALF(i64_f16, int64_t, MI355_OFF_I64, MI355_VAL_F16)
+MI355_SPMV_DEFINE_SDDMM_HALF(i64_bf16, int64_t, MI355_OFF_I64, MI355_VAL_BF16)
 
 }  // extern "C"
