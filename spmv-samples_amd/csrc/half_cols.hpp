@@ -1,7 +1,7 @@
 // half_cols.hpp — a lane's 16 bytes of a row held in 16 bits: EIGHT columns of binary16 / bfloat16, widened exactly into
 // eight fp32 registers (half_convert.hpp's widen).  What the two kinds that read 16-bit rows share: multi-vector SpMV with
 // 16-bit X and Y (multi_half_kernels.hpp, which adds the narrowing store) and SDDMM with 16-bit U and V
-// (sddmm_half_kernel.hpp).  The names stay in mh, the namespace they were written in: multi_half_slice_kernel compiles to
+// (sddmm_half_kernel.hpp, which hands load_cols to sddmm_slice_walk.inc by a using-declaration).  The names stay in mh, the namespace they were written in: multi_half_slice_kernel compiles to
 // the device code on record, and what a kernel calls does not enter its name.
 #pragma once
 

@@ -1,7 +1,7 @@
 // half_convert.hpp — the 16-bit storage types (binary16 as F16, bfloat16 as common.hpp's Bf16) and their conversions to and
 // from fp32: widen is exact; narrow_to rounds to nearest even (overflow to +-inf, NaN stays NaN, subnormals kept).
 // What csr_vector_h16.hip (narrowing a matrix's values), multi_half_kernels.hpp (16-bit X and Y) and sddmm_half_kernel.hpp
-// (16-bit U and V) convert with; the widening load of a lane's eight columns built on them: half_cols.hpp.
+// (16-bit U and V, through sddmm_slice_walk.inc's load_cols) convert with; the widening load of a lane's eight columns built on them: half_cols.hpp.
 // Plain C++ (casts and integer bit operations); where the compiler has no _Float16 (the host compiler of the
 // lane-by-lane simulation) binary16 is held as uint16_t and converted in software.
 #pragma once

@@ -7,7 +7,8 @@
 //   sddmm_slice_kernel   one WAVE per slice of kSliceLen merge items (row ends + nonzeros): the cut of the multi-vector
 //                        kind, shared with it (slice_cut.hpp, slice_cut.inc, slice_cut_row.inc).  The wave finds its two
 //                        merge-path diagonals, keeps its rows' offsets in LDS relative to its first nonzero, and walks
-//                        its nonzeros 64 at a time: Aj (and Ax) are loaded coalesced, one per lane, and each lane finds its
+//                        its nonzeros 64 at a time (sddmm_slice_walk.inc: the walk is ONE text, this kernel's and
+//                        sddmm_half_slice_kernel's): Aj (and Ax) are loaded coalesced, one per lane, and each lane finds its
 //                        nonzero's row by a binary search in LDS.  Lanes are (nonzero slot x 16-byte column group):
 //                        a slot of C lanes takes one nonzero, lane c gathers its 16 bytes of V[col] and of U[row] and
 //                        multiplies them into ONE scalar partial; for k wider than the tile of C groups the lane goes
@@ -22,14 +23,25 @@
 // (a masked column is loaded as 0 and adds +0), and the tree adds lanes at distance 1, 2, 4, ...: an element of out is
 // a function of (U[r, :k], V[c, :k], s, alpha, beta, out_old, k) only — not of where in a slice, step or slot its
 // nonzero falls, and not of the alignment of U and V (the 16-byte and the element-by-element load fill the same
-// registers; the arithmetic is one piece of code behind both).
+// registers; the arithmetic is one piece of code behind both, and behind every type of U and V: sddmm_slice_walk.inc).
 //
 // U and V in 16 bits under fp32 Ax, out and arithmetic (mi355_spmv_sddmm_create_half): sddmm_half_slice_kernel and its
-// launch, sddmm_half_kernel.hpp; the object and the entry points are this unit's.
+// launch, sddmm_half_kernel.hpp, around the same walk; the object and the entry points are this unit's.
 #include <new>
+#include <type_traits>
 
-#include "sddmm_half_kernel.hpp"
 #include "slice_cut.hpp"
+
+struct mi355_spmv_sddmm {   // the opaque handle of include/mi355_spmv.h: host memory only, nothing on the device
+    int off_type = 0, val_type = 0;
+    int vec_type = 0;       // the type of U and V: val_type, or F16 / BF16 under F32 values (create_half)
+    int32_t n_rows = 0, n_cols = 0;
+    int64_t nnz = 0;
+    const void* Ap = nullptr;
+    const int32_t* Aj = nullptr;
+    double alpha = 1.0, beta = 0.0;
+    int64_t n_slices = 0;
+};
 
 namespace mi355 {
 
@@ -54,6 +66,23 @@ struct SddmmArgs {
     val_t alpha, beta;
 };
 
+// the arguments of an execute, Args = SddmmArgs<val_t> or SddmmHalfArgs<vec_t> (sddmm_half_kernel.hpp): the two structs
+// have the same fields, of their own types
+template <typename Args>
+Args sddmm_args(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out, int32_t k) {
+    Args a;
+    a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
+    a.Aj = m.Aj;
+    a.Ax = static_cast<decltype(a.Ax)>(Ax);
+    a.U = static_cast<decltype(a.U)>(U); a.V = static_cast<decltype(a.V)>(V);
+    a.out = static_cast<decltype(a.out)>(out);
+    a.ldu = ldu; a.ldv = ldv; a.k = k;
+    a.u_vec = rows_aligned16<std::remove_pointer_t<decltype(a.U)>>(U, ldu) ? 1 : 0;
+    a.v_vec = rows_aligned16<std::remove_pointer_t<decltype(a.V)>>(V, ldv) ? 1 : 0;
+    a.alpha = decltype(a.alpha)(m.alpha); a.beta = decltype(a.beta)(m.beta);
+    return a;
+}
+
 // one rounding per column whatever the compiler would otherwise choose to contract: the promise above, spelled out
 __device__ __forceinline__ float sddmm_fma(float x, float y, float z) { return __builtin_fmaf(x, y, z); }
 __device__ __forceinline__ double sddmm_fma(double x, double y, double z) { return __builtin_fma(x, y, z); }
@@ -61,82 +90,21 @@ __device__ __forceinline__ double sddmm_fma(double x, double y, double z) { retu
 // C = lanes per nonzero slot (16-byte column groups of a tile); the wave holds S = 64 / C slots
 template <typename off_t, typename val_t, int C, bool VALUED>
 __global__ __launch_bounds__(kBlock) void sddmm_slice_kernel(const SddmmArgs<val_t> a, const off_t* __restrict__ Ap) {
+    using acc_t = val_t;
     constexpr int W = 16 / int(sizeof(val_t));      // columns of a lane per tile
     constexpr int S = kWave / C;
     constexpr bool kCutCarriedIn = false, kCutKeepsR1 = false;      // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = 0;
-#include "slice_cut.inc"        // leaves lane, c, s, w, r0, n0, nn, nr, rel
-
-    for (int base = 0; base < nn; base += kWave) {
-        // 64 nonzeros, one per lane, coalesced; each lane finds its nonzero's row in the slice's offsets
-        const int m = base + lane;
-        int32_t col = 0;
-        int row_i = 0;
-        [[maybe_unused]] val_t ax = val_t(1);
-        if (m < nn) {
-            col = a.Aj[n0 + m];
-            if constexpr (VALUED) ax = a.Ax[n0 + m];
-#include "slice_cut_row.inc"     // leaves lo: the nonzero's row, relative to r0
-            row_i = lo;
-        }
-        const int left = nn - base;
-        const int steps = slice_group_steps<C>(left);
-        val_t dot = val_t(0);           // of this lane's own nonzero m, handed back by the step that took it
-        for (int t = 0; t < steps; ++t) {
-            // slot s takes nonzero t * S + s of the 64
-            const int src = t * S + s;
-            int32_t col_s = col;
-            int row_s = row_i;
-            if constexpr (C > 1) {
-                col_s = __shfl(col, src);
-                row_s = __shfl(row_i, src);
-            }
-            val_t part = val_t(0);
-            if (src < left) {
-                const val_t* up = a.U + (r0 + row_s) * a.ldu + c * W;
-                const val_t* vp = a.V + int64_t(col_s) * a.ldv + c * W;
-                for (int32_t cb = 0; cb < a.k; cb += C * W) {       // the tiles of k: the same register all along
-                    const int nv = min(max(a.k - cb - c * W, 0), W);
-                    if (nv > 0) {
-                        val_t u[W], v[W];
-                        load_cols<val_t, W>(u, up + cb, nv, a.u_vec != 0);
-                        load_cols<val_t, W>(v, vp + cb, nv, a.v_vec != 0);
-#pragma unroll
-                        for (int j = 0; j < W; ++j) part = sddmm_fma(u[j], v[j], part);
-                    }
-                }
-            }
-            // the dot of the slot's nonzero, in every lane of the slot: a fixed tree over its C lanes
-#pragma unroll
-            for (int d = 1; d < C; d <<= 1) part += __shfl_xor(part, d);
-            // back to the lane that loaded the nonzero: lane l holds nonzero l = t' * S + s', taken at step t' by slot s'
-            val_t mine = part;
-            if constexpr (C > 1) mine = __shfl(part, (lane % S) * C);
-            if (lane / S == t) dot = mine;
-        }
-        if (m < nn) {
-            val_t o;
-            if constexpr (VALUED) o = a.alpha * (ax * dot); else o = a.alpha * dot;
-            if (a.beta != val_t(0)) o += a.beta * a.out[n0 + m];
-            a.out[n0 + m] = o;
-        }
-    }
+    constexpr bool kWalkFmaInPlace = false;                         // what sddmm_slice_walk.inc asks its includer
+#include "slice_cut.inc"            // leaves lane, c, s, w, r0, n0, nn, nr, rel
+#include "sddmm_slice_walk.inc"     // the slice's nonzeros, 64 at a time: load_cols is slice_cut.hpp's
 }
 
 }  // namespace mi355
 
-using namespace mi355;
+#include "sddmm_half_kernel.hpp"    // (down here: its launch uses the handle and sddmm_args)
 
-struct mi355_spmv_sddmm {   // the opaque handle of include/mi355_spmv.h: host memory only, nothing on the device
-    int off_type = 0, val_type = 0;
-    int vec_type = 0;       // the type of U and V: val_type, or F16 / BF16 under F32 values (create_half)
-    int32_t n_rows = 0, n_cols = 0;
-    int64_t nnz = 0;
-    const void* Ap = nullptr;
-    const int32_t* Aj = nullptr;
-    double alpha = 1.0, beta = 0.0;
-    int64_t n_slices = 0;
-};
+using namespace mi355;
 
 namespace {
 
@@ -188,16 +156,7 @@ void sddmm_fill(mi355_spmv_sddmm& m, int off_type, int val_type, int vec_type, i
 template <typename off_t, typename val_t, bool VALUED>
 int sddmm_launch(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out,
                  int32_t k, hipStream_t s) {
-    SddmmArgs<val_t> a;
-    a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
-    a.Aj = m.Aj;
-    a.Ax = VALUED ? static_cast<const val_t*>(Ax) : nullptr;
-    a.U = static_cast<const val_t*>(U); a.V = static_cast<const val_t*>(V);
-    a.out = static_cast<val_t*>(out);
-    a.ldu = ldu; a.ldv = ldv; a.k = k;
-    a.u_vec = rows_aligned16<val_t>(U, ldu) ? 1 : 0;
-    a.v_vec = rows_aligned16<val_t>(V, ldv) ? 1 : 0;
-    a.alpha = val_t(m.alpha); a.beta = val_t(m.beta);
+    const SddmmArgs<val_t> a = sddmm_args<SddmmArgs<val_t>>(m, Ax, U, ldu, V, ldv, out, k);
     const off_t* Ap = static_cast<const off_t*>(m.Ap);
     const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
     constexpr int W = 16 / int(sizeof(val_t));
@@ -222,8 +181,7 @@ int sddmm_run(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64_t 
     if (m.vec_type != m.val_type) {     // 16-bit U and V under fp32 values
         const bool i32 = m.off_type == MI355_OFF_I32;
         auto run = [&](auto off, auto vec) {
-            return sddmm_half_launch<decltype(off), decltype(vec)>(m.n_rows, m.nnz, m.n_slices, m.Ap, m.Aj, m.alpha, m.beta, Ax, U, ldu, V,
-                                                                   ldv, out, k, s);
+            return sddmm_half_launch<decltype(off), decltype(vec)>(m, Ax, U, ldu, V, ldv, out, k, s);
         };
         if (m.vec_type == MI355_VAL_F16) return i32 ? run(int32_t(), F16()) : run(int64_t(), F16());
         return i32 ? run(int32_t(), Bf16()) : run(int64_t(), Bf16());

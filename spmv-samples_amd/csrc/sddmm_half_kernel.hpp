@@ -2,18 +2,18 @@
 // arithmetic (mi355_spmv_sddmm_create_half):
 //   out[n] = alpha * s[n] * sum_{j < k} float(U[r(n), j]) * float(V[Aj[n], j]) + beta * out[n]
 // Ax (s) and out are fp32.  Every stored 16-bit value is widened exactly (half_convert.hpp's widen); products and sums
-// are fp32; nothing is rounded to 16 bits anywhere.  Included by sddmm.hip, which owns the object and the entry points:
-// this header holds the kernel and its one launch.
+// are fp32; nothing is rounded to 16 bits anywhere.  Included by sddmm.hip, which owns the object and the entry points,
+// behind its handle and sddmm_args: this header holds the kernel and its one launch.
 //
-//   sddmm_half_slice_kernel   sddmm_slice_kernel's walk (sddmm.hip) over the same cut (slice_cut.hpp, slice_cut.inc,
-//                             slice_cut_row.inc) with a lane's 16 bytes being EIGHT columns: C = 1 / 2 / 4 / 8 lanes
+//   sddmm_half_slice_kernel   sddmm_slice_kernel's walk (the same text, sddmm_slice_walk.inc) over the same cut
+//                             (slice_cut.hpp, slice_cut.inc) with a lane's 16 bytes being EIGHT columns: C = 1 / 2 / 4 / 8 lanes
 //                             per slot from ceil(k / 8), tiles of 8 / 16 / 32 / 64 columns, the tile loop inside the
 //                             kernel for wider k.  A kernel of its own, with a name and an argument struct of its own:
 //                             a storage type among sddmm_slice_kernel's template arguments would rename the kernels on
 //                             record (profiles/sddmm_kernel_resources.txt).
 //
-// Order of addition, one piece of code behind the 16-byte and the element-by-element load (both fill the same eight
-// fp32 registers, half_cols.hpp): part = fma(u[j], v[j], part) over the lane's columns in ascending order, tile after
+// Order of addition, sddmm_slice_walk.inc's: one piece of code for this kernel and the fp32 / fp64 one, behind the 16-byte
+// and the element-by-element load (both fill the same eight fp32 registers, half_cols.hpp): part = fma(u[j], v[j], part) over the lane's columns in ascending order, tile after
 // tile, from +0 (a masked column is loaded as 0 and adds +0); the xor-shuffle tree over the C lanes at distance 1, 2,
 // 4; the hand-back to the lane that loaded the nonzero; alpha * (ax * dot), + beta * out_old when beta != 0; one store
 // of 64 contiguous fp32 values per group.  An element of out is a function of (U[r, :k], V[c, :k], s, alpha, beta,
@@ -44,86 +44,26 @@ struct SddmmHalfArgs {
 // C = lanes per nonzero slot (16-byte column groups of a tile); the wave holds S = 64 / C slots
 template <typename off_t, typename vec_t, int C, bool VALUED>
 __global__ __launch_bounds__(kBlock) void sddmm_half_slice_kernel(const SddmmHalfArgs<vec_t> a, const off_t* __restrict__ Ap) {
+    using acc_t = float;
+    using mh::load_cols;                // the walk's load_cols: the lane's eight 16-bit columns, widened
     constexpr int W = mh::kHalfV;       // columns of a lane per tile
     constexpr int S = kWave / C;
     constexpr bool kCutCarriedIn = false, kCutKeepsR1 = false;      // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = 0;
-#include "slice_cut.inc"        // leaves lane, c, s, w, r0, n0, nn, nr, rel
-
-    for (int base = 0; base < nn; base += kWave) {
-        // 64 nonzeros, one per lane, coalesced; each lane finds its nonzero's row in the slice's offsets
-        const int m = base + lane;
-        int32_t col = 0;
-        int row_i = 0;
-        [[maybe_unused]] float ax = 1.0f;
-        if (m < nn) {
-            col = a.Aj[n0 + m];
-            if constexpr (VALUED) ax = a.Ax[n0 + m];
-#include "slice_cut_row.inc"     // leaves lo: the nonzero's row, relative to r0
-            row_i = lo;
-        }
-        const int left = nn - base;
-        const int steps = slice_group_steps<C>(left);
-        float dot = 0.0f;               // of this lane's own nonzero m, handed back by the step that took it
-        for (int t = 0; t < steps; ++t) {
-            // slot s takes nonzero t * S + s of the 64
-            const int src = t * S + s;
-            int32_t col_s = col;
-            int row_s = row_i;
-            if constexpr (C > 1) {
-                col_s = __shfl(col, src);
-                row_s = __shfl(row_i, src);
-            }
-            float part = 0.0f;
-            if (src < left) {
-                const vec_t* up = a.U + (r0 + row_s) * a.ldu + c * W;
-                const vec_t* vp = a.V + int64_t(col_s) * a.ldv + c * W;
-                for (int32_t cb = 0; cb < a.k; cb += C * W) {       // the tiles of k: the same register all along
-                    const int nv = min(max(a.k - cb - c * W, 0), W);
-                    if (nv > 0) {
-                        float u[W], v[W];
-                        mh::load_cols<vec_t>(u, up + cb, nv, a.u_vec != 0);
-                        mh::load_cols<vec_t>(v, vp + cb, nv, a.v_vec != 0);
-#pragma unroll
-                        for (int j = 0; j < W; ++j) part = __builtin_fmaf(u[j], v[j], part);    // one rounding per column
-                    }
-                }
-            }
-            // the dot of the slot's nonzero, in every lane of the slot: a fixed tree over its C lanes
-#pragma unroll
-            for (int d = 1; d < C; d <<= 1) part += __shfl_xor(part, d);
-            // back to the lane that loaded the nonzero: lane l holds nonzero l = t' * S + s', taken at step t' by slot s'
-            float mine = part;
-            if constexpr (C > 1) mine = __shfl(part, (lane % S) * C);
-            if (lane / S == t) dot = mine;
-        }
-        if (m < nn) {
-            float o;
-            if constexpr (VALUED) o = a.alpha * (ax * dot); else o = a.alpha * dot;
-            if (a.beta != 0.0f) o += a.beta * a.out[n0 + m];
-            a.out[n0 + m] = o;
-        }
-    }
+    constexpr bool kWalkFmaInPlace = true;                          // what sddmm_slice_walk.inc asks its includer
+#include "slice_cut.inc"            // leaves lane, c, s, w, r0, n0, nn, nr, rel
+#include "sddmm_slice_walk.inc"     // the slice's nonzeros, 64 at a time: sddmm_slice_kernel's walk
 }
 
 // the one launch of a 16-bit execute: C from ceil(k / 8), valued / pattern from Ax.  A caller has checked the arguments
 // and that there is something to launch (nnz and n_rows above 0).
 template <typename off_t, typename vec_t>
-int sddmm_half_launch(int32_t n_rows, int64_t nnz, int64_t n_slices, const void* Ap, const int32_t* Aj, double alpha, double beta,
-                      const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out, int32_t k, hipStream_t s) {
+int sddmm_half_launch(const mi355_spmv_sddmm& m, const void* Ax, const void* U, int64_t ldu, const void* V, int64_t ldv, void* out,
+                      int32_t k, hipStream_t s) {
     static_assert(sizeof(vec_t) == 2, "16-bit U and V");
-    SddmmHalfArgs<vec_t> a;
-    a.n_rows = n_rows; a.nnz = nnz; a.n_slices = n_slices;
-    a.Aj = Aj;
-    a.Ax = static_cast<const float*>(Ax);
-    a.U = static_cast<const vec_t*>(U); a.V = static_cast<const vec_t*>(V);
-    a.out = static_cast<float*>(out);
-    a.ldu = ldu; a.ldv = ldv; a.k = k;
-    a.u_vec = rows_aligned16<vec_t>(U, ldu) ? 1 : 0;
-    a.v_vec = rows_aligned16<vec_t>(V, ldv) ? 1 : 0;
-    a.alpha = float(alpha); a.beta = float(beta);
-    const off_t* ap = static_cast<const off_t*>(Ap);
-    const dim3 grid(unsigned(slice_grid(n_slices))), block(kBlock);
+    const SddmmHalfArgs<vec_t> a = sddmm_args<SddmmHalfArgs<vec_t>>(m, Ax, U, ldu, V, ldv, out, k);
+    const off_t* ap = static_cast<const off_t*>(m.Ap);
+    const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
     with_slot_lanes((k + mh::kHalfV - 1) / mh::kHalfV, [&](auto lanes) {
         constexpr int C = decltype(lanes)::value;
         if (Ax) hipLaunchKernelGGL((sddmm_half_slice_kernel<off_t, vec_t, C, true>), grid, block, 0, s, a, ap);

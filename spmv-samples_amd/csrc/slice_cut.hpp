@@ -1,5 +1,5 @@
 // slice_cut.hpp — what the slice kinds share: multi-vector SpMV (multi_kernels.hpp, multi_half_kernels.hpp) and SDDMM
-// (sddmm.hip, sddmm_half_kernel.hpp).  Both cut A into slices of kSliceLen merge items (row ends + nonzeros: a run of empty rows cannot make
+// (sddmm.hip, sddmm_half_kernel.hpp; their one walk, sddmm_slice_walk.inc).  Both cut A into slices of kSliceLen merge items (row ends + nonzeros: a run of empty rows cannot make
 // the row range of a slice unbounded, a hub row is spread over as many waves as it has slices), give one WAVE a slice,
 // and spread a step's nonzeros over (nonzero slot x 16-byte column group) lanes.  Here: the geometry and its host
 // arithmetic, the 16-byte column access of a lane, and the steps of a group of 64 nonzeros.  The cut itself — the wave's

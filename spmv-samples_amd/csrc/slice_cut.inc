@@ -1,6 +1,7 @@
 // slice_cut.inc — from "wave w of the grid" to "rows r0 .. r0 + nr - 1, nonzeros n0 .. n0 + nn - 1, offsets in LDS": the
 // prologue of every slice kernel, included inside the kernel's braces by multi_slice_walk.inc (multi_slice_kernel,
-// mh::multi_half_slice_kernel) and by sddmm_slice_kernel (sddmm.hip) and sddmm_half_slice_kernel (sddmm_half_kernel.hpp).  Text and not a function, for multi_slice_walk.inc's
+// mh::multi_half_slice_kernel) and by sddmm_slice_kernel (sddmm.hip) and sddmm_half_slice_kernel (sddmm_half_kernel.hpp),
+// each in front of sddmm_slice_walk.inc.  Text and not a function, for multi_slice_walk.inc's
 // reason: the kernels compile to the device code on record only when this is compiled as part of them.
 //
 // In scope where it is included (kernel arguments and template arguments, or bound by the includer in front):

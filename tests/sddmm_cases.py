@@ -286,36 +286,44 @@ def table():
     return [c for f in FAMILIES for c in family(f)]
 
 
-# ---- the host program's batch file (tests/cpp/sddmm_sim.cpp) -------------------------------------------------------------
-def write_batch(path, cases):
+# ---- the host program's batch file (tests/cpp/sddmm_sim.cpp, whose header comment has the records) ------------------------
+NAN_BITS = {"f32": 0x7FC00000, "f64": 0x7FF8000000000000}
+
+
+def batch_operands(c):
+    """What write_batch asks of a case: its plan key, the MI355_VAL_* of U and V, (Ap, Aj, Ax, O0, U, V) as the program
+    reads them, and the bit pattern of a NaN of U's and V's type."""
+    return plan_key(c), ("f32", "f64").index(c.val), arrays(c.matrix, c.off, c.val, c.integer), NAN_BITS[c.val]
+
+
+def write_batch(path, cases, operands=batch_operands):
     """Cases in plan order; returns them in the order their results come back."""
     words = lambda *v: struct.pack("<%dq" % len(v), *v)
     last = None
     with open(path, "wb") as f:
         for c in cases:
-            Ap, Aj, Ax, O0, U, V = arrays(c.matrix, c.off, c.val, c.integer)
-            if plan_key(c) != last:
-                last = plan_key(c)
-                f.write(words(1, ("i32", "i64").index(c.off), ("f32", "f64").index(c.val), len(c.matrix.lens), c.matrix.n_cols,
-                              int(Ap[-1]), *c.shift[:3]))
+            key, type_word, (Ap, Aj, Ax, O0, U, V), nan_bits = operands(c)
+            if key != last:
+                last = key
+                f.write(words(1, ("i32", "i64").index(c.off), type_word, len(c.matrix.lens), c.matrix.n_cols, int(Ap[-1]), *c.shift[:3]))
                 for a in (Ap, Aj, Ax, O0):
                     f.write(a.tobytes())
-                f.write(words(2, KF))
+                f.write(words(2, U.shape[1]))
                 f.write(np.ascontiguousarray(U).tobytes())
                 f.write(np.ascontiguousarray(V).tobytes())
-            f.write(words(4, c.k, c.c0, c.ldu, c.ldv, c.shift[3], c.shift[4], c.shift[5], int(c.valued), int(c.beta == 0.0)))
+            f.write(words(4, c.k, c.c0, c.ldu, c.ldv, c.shift[3], c.shift[4], c.shift[5], int(c.valued), int(c.beta == 0.0), nan_bits))
             f.write(struct.pack("<2d", c.alpha, c.beta))
         f.write(words(0))
     return list(cases)
 
 
-def read_results(path, cases):
-    """[(status, out)] per case; raises if the file is not complete."""
+def read_results(path, cases, dtype=lambda c: NP[c.val]):
+    """[(status, out)] per case, out in dtype(c); raises if the file is not complete."""
     out = []
     with open(path, "rb") as f:
         for c in cases:
             st, count = struct.unpack("<2q", f.read(16))
             assert count == sum(c.matrix.lens), c.name
-            out.append((st, np.frombuffer(f.read(count * NP[c.val]().itemsize), dtype=NP[c.val])))
+            out.append((st, np.frombuffer(f.read(count * np.dtype(dtype(c)).itemsize), dtype=dtype(c))))
         assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
     return out

@@ -25,7 +25,6 @@ per column rounds once per column as the fp32 kernel's does, and the tree, the m
 what the bound already counts.  Padding columns of U and V hold NaN; with beta = 0, out starts as NaN and no NaN may
 remain; on the device a canary behind out[nnz - 1] must survive."""
 import collections
-import struct
 
 import numpy as np
 
@@ -295,40 +294,15 @@ def self_test():
     return t
 
 
-# ---- the host program's batch file (tests/cpp/sddmm_half_sim.cpp) --------------------------------------------------------
+# ---- the host program's batch file: sddmm_cases' records, with U and V as 16-bit patterns and fp32 results ---------------
+def batch_operands(c):
+    Ap, Aj, Ax, O0, U, V = arrays(c.matrix, c.off, c.vec, c.integer)
+    return plan_key(c), VAL_TYPE[c.vec], (Ap, Aj, Ax, O0, to_bits(U, c.vec), to_bits(V, c.vec)), NAN_BITS[c.vec]
+
+
 def write_batch(path, cases):
-    """Cases in plan order; returns them in the order their results come back.  Records (int64 words, then raw arrays):
-      1 matrix    off_type vec_type n_rows n_cols nnz ap_off aj_off ax_off | Ap[n_rows + 1] Aj[nnz] Ax[nnz] O0[nnz]   (Ax, O0: fp32)
-      2 operands  kf | U[n_rows * kf] V[n_cols * kf]                                          (16-bit patterns, row-major)
-      4 run       k c0 ldu ldv u_off v_off out_off valued out0_nan nan_bits | alpha beta (2 doubles)
-      0 end"""
-    words = lambda *v: struct.pack("<%dq" % len(v), *v)
-    last = None
-    with open(path, "wb") as f:
-        for c in cases:
-            Ap, Aj, Ax, O0, U, V = arrays(c.matrix, c.off, c.vec, c.integer)
-            if plan_key(c) != last:
-                last = plan_key(c)
-                f.write(words(1, OFFS.index(c.off), VAL_TYPE[c.vec], len(c.matrix.lens), c.matrix.n_cols, int(Ap[-1]), *c.shift[:3]))
-                for a in (Ap, Aj, Ax, O0):
-                    f.write(a.tobytes())
-                f.write(words(2, KF))
-                f.write(to_bits(U, c.vec).tobytes())
-                f.write(to_bits(V, c.vec).tobytes())
-            f.write(words(4, c.k, c.c0, c.ldu, c.ldv, c.shift[3], c.shift[4], c.shift[5], int(c.valued), int(c.beta == 0.0),
-                          NAN_BITS[c.vec]))
-            f.write(struct.pack("<2d", c.alpha, c.beta))
-        f.write(words(0))
-    return list(cases)
+    return sc.write_batch(path, cases, batch_operands)
 
 
 def read_results(path, cases):
-    """[(status, out)] per case; raises if the file is not complete."""
-    out = []
-    with open(path, "rb") as f:
-        for c in cases:
-            st, count = struct.unpack("<2q", f.read(16))
-            assert count == sum(c.matrix.lens), c.name
-            out.append((st, np.frombuffer(f.read(count * 4), dtype=np.float32)))
-        assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
-    return out
+    return sc.read_results(path, cases, lambda c: np.float32)

@@ -1,0 +1,86 @@
+"""What the host simulations' test files (tests/test_*_sim_cpu.py) share: building a program of tests/cpp with the
+sanitizers, dealing a table's plan groups to batches, and running the batches as concurrent child processes under a time
+limit.  Nothing is loaded into this process, and the children's environment is this process's own (the sanitizer runtimes
+are linked statically).  Each test file keeps its table, its geometry asserts, its weight function and its tests."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+CPP = os.path.join(ROOT, "tests", "cpp")
+TIME_LIMIT = 900        # seconds per child: ~30 x what the slowest batch of any table takes
+
+
+def build(target):
+    """The program, built on demand by the rule of tests/cpp/Makefile (its SIM_SAN flags).  Skips only where the host
+    compiler cannot link with those flags at all (a trivial program, the same flags); any other failure to build is a
+    failure."""
+    probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
+    if probe.returncode != 0:
+        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
+    subprocess.run(["make", "-s", "-C", CPP, target], check=True)
+    return os.path.join(CPP, target)
+
+
+def child_env():
+    return dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1")
+
+
+def source(name):
+    """The text of a file of csrc/."""
+    with open(os.path.join(ROOT, "spmv-samples_amd", "csrc", name)) as f:
+        return f.read()
+
+
+def kernel_constant(text, name):
+    return int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
+
+
+def groups_by(cases, key):
+    """The cases of each key together, in the order the keys first occur."""
+    groups = {}
+    for c in cases:
+        groups.setdefault(key(c), []).append(c)
+    return list(groups.values())
+
+
+def batches(groups, weight, n):
+    """Whole plan groups dealt to at most n batches, heaviest first onto the lightest batch."""
+    out = [[0, []] for _ in range(n)]
+    for g in sorted(groups, key=weight, reverse=True):
+        b = min(out, key=lambda b: b[0])
+        b[0] += weight(g)
+        b[1] += g
+    return [b[1] for b in out if b[1]]
+
+
+def run_table(exe, tmp, groups, weight, write_batch, read_results):
+    """Every case of the groups through the sanitized program, in at most min(8, CPUs) concurrent children:
+    ({case name: what read_results gives for it}, [(exit status, stdout + stderr) per child])."""
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    env = child_env()
+    children = []
+    for i, cases in enumerate(batches(groups, weight, max(1, min(8, cpus)))):
+        src, dst = str(tmp / ("batch%d.bin" % i)), str(tmp / ("out%d.bin" % i))
+        order = write_batch(src, cases)
+        children.append((subprocess.Popen([exe, src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env),
+                         order, dst))
+    results, reports = {}, []
+    for child, order, dst in children:
+        try:
+            out, err = child.communicate(timeout=TIME_LIMIT)
+        except subprocess.TimeoutExpired:
+            child.kill()
+            out, err = child.communicate()
+            err += "\n(killed after %d s)" % TIME_LIMIT
+        reports.append((child.returncode, out + err))
+        if child.returncode == 0:
+            for c, res in zip(order, read_results(dst, order)):
+                results[c.name] = res
+    return results, reports

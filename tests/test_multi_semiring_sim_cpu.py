@@ -10,69 +10,23 @@ linked statically).
 
 Cost: the table's ~3 000 executes run as concurrent child processes (at most 8): about a minute on 8 cores, plus the
 compilation once (every instantiation of the kernels: about four minutes)."""
-import os
-import subprocess
-
 import pytest
 
 import multi_cases as mc
 import multi_semiring_cases as sc
-from conftest import ROOT
-
-CPP = os.path.join(ROOT, "tests", "cpp")
-TIME_LIMIT = 900        # seconds per child
+import sim_runner as sr
 
 
-def build():
-    """The program, by the rule of tests/cpp/Makefile (its SIM_SAN flags).  Skips only where the host compiler cannot
-    link with those flags at all; any other failure to build is a failure."""
-    probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", CPP, "multi_semiring_sim"], check=True)
-    return os.path.join(CPP, "multi_semiring_sim")
-
-
-def batches(cases, n):
-    """Whole plan groups dealt to n batches, heaviest first onto the lightest batch (weight: merge items x columns)."""
-    weight = lambda g: sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (c.k + 8) for c in g)
-    out = [[0, []] for _ in range(n)]
-    for g in sorted(sc.groups(cases), key=weight, reverse=True):
-        b = min(out, key=lambda b: b[0])
-        b[0] += weight(g)
-        b[1] += g
-    return [b[1] for b in out if b[1]]
+def weight(g):
+    """Of a plan group: merge items x columns."""
+    return sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (c.k + 8) for c in g)
 
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, Y)}, and the children's reports."""
-    exe = build()
-    tmp = tmp_path_factory.mktemp("multi_semiring_sim")
-    env = dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1")
-    try:
-        cpus = len(os.sched_getaffinity(0))
-    except AttributeError:
-        cpus = os.cpu_count() or 1
-    children = []
-    for i, cases in enumerate(batches(sc.table(), max(1, min(8, cpus)))):
-        src, dst = str(tmp / ("batch%d.bin" % i)), str(tmp / ("y%d.bin" % i))
-        order = sc.write_batch(src, cases)
-        children.append((subprocess.Popen([exe, src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env),
-                         order, dst))
-    results, reports = {}, []
-    for child, order, dst in children:
-        try:
-            out, err = child.communicate(timeout=TIME_LIMIT)
-        except subprocess.TimeoutExpired:
-            child.kill()
-            out, err = child.communicate()
-            err += "\n(killed after %d s)" % TIME_LIMIT
-        reports.append((child.returncode, out + err))
-        if child.returncode == 0:
-            for c, res in zip(order, sc.read_results(dst, order)):
-                results[c.name] = res
-    return results, reports
+    return sr.run_table(sr.build("multi_semiring_sim"), tmp_path_factory.mktemp("multi_semiring_sim"), sc.groups(sc.table()), weight,
+                        sc.write_batch, sc.read_results)
 
 
 def test_the_children_end_clean_with_an_empty_sanitizer_log(run):

@@ -8,87 +8,30 @@ process's own (the sanitizer runtimes are linked statically).
 
 Cost: the table's 5 180 executes take ~4 minutes of one core under the sanitizers; the batches run as concurrent child
 processes (at most 8), so the file costs about a minute on 8 cores, plus ~20 s to compile the program once."""
-import os
-import re
 import subprocess
-import tempfile
 
 import pytest
 
 import multi_cases as mc
-from conftest import ROOT
-
-CPP = os.path.join(ROOT, "tests", "cpp")
-TIME_LIMIT = 900        # seconds per child: ~30 x what the slowest batch takes
+import sim_runner as sr
 
 
-def build(target):
-    """The program, built on demand with the Makefile's sanitizer flags.  Skips only where the host compiler cannot
-    link with those flags at all (a trivial program, the same flags); any other failure to build is a failure."""
-    probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", CPP, target], check=True)
-    return os.path.join(CPP, target)
-
-
-def child_env():
-    return dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1")
-
-
-def kernel_constant(text, name):
-    return int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
-
-
-def batches(cases, n):
-    """Whole plan groups dealt to n batches, heaviest first onto the lightest batch (weight: merge items x columns)."""
-    groups = {}
-    for c in cases:
-        groups.setdefault(mc.plan_key(c), []).append(c)
-    weight = lambda g: sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (c.k + 8) for c in g)
-    out = [[0, []] for _ in range(n)]
-    for g in sorted(groups.values(), key=weight, reverse=True):
-        b = min(out, key=lambda b: b[0])
-        b[0] += weight(g)
-        b[1] += g
-    return [b[1] for b in out if b[1]]
+def weight(g):
+    """Of a plan group: merge items x columns."""
+    return sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (c.k + 8) for c in g)
 
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, Y)}, and the children's reports."""
-    exe = build("multi_sim")
-    csrc = os.path.join(ROOT, "spmv-samples_amd", "csrc")
-    multi, common = open(os.path.join(csrc, "multi.hip")).read(), open(os.path.join(csrc, "common.hpp")).read()
-    assert kernel_constant(multi, "kMultiSlice") == mc.SLICE_LEN
-    assert kernel_constant(common, "kWave") == mc.STEP
-    assert kernel_constant(multi, "kMultiGroupsMax") == max(mc.LANES_PER_SLOT)
-    assert kernel_constant(common, "kBlock") % mc.STEP == 0
-    tmp = tmp_path_factory.mktemp("multi_sim")
-    env = child_env()
-    try:
-        cpus = len(os.sched_getaffinity(0))
-    except AttributeError:
-        cpus = os.cpu_count() or 1
-    children = []
-    for i, cases in enumerate(batches(mc.table(), max(1, min(8, cpus)))):
-        src, dst = str(tmp / ("batch%d.bin" % i)), str(tmp / ("y%d.bin" % i))
-        order = mc.write_batch(src, cases)
-        children.append((subprocess.Popen([exe, src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env),
-                         order, dst))
-    results, reports = {}, []
-    for child, order, dst in children:
-        try:
-            out, err = child.communicate(timeout=TIME_LIMIT)
-        except subprocess.TimeoutExpired:
-            child.kill()
-            out, err = child.communicate()
-            err += "\n(killed after %d s)" % TIME_LIMIT
-        reports.append((child.returncode, out + err))
-        if child.returncode == 0:
-            for c, res in zip(order, mc.read_results(dst, order)):
-                results[c.name] = res
-    return results, reports
+    exe = sr.build("multi_sim")
+    multi, common = sr.source("multi.hip"), sr.source("common.hpp")
+    assert sr.kernel_constant(multi, "kMultiSlice") == mc.SLICE_LEN
+    assert sr.kernel_constant(common, "kWave") == mc.STEP
+    assert sr.kernel_constant(multi, "kMultiGroupsMax") == max(mc.LANES_PER_SLOT)
+    assert sr.kernel_constant(common, "kBlock") % mc.STEP == 0
+    return sr.run_table(exe, tmp_path_factory.mktemp("multi_sim"), sr.groups_by(mc.table(), mc.plan_key), weight, mc.write_batch,
+                        mc.read_results)
 
 
 def test_the_children_end_clean_with_an_empty_sanitizer_log(run):
@@ -104,12 +47,12 @@ def test_every_case_of_the_table_has_a_name_of_its_own():
 def test_the_stand_in_keeps_its_own_promises():
     """tests/cpp/simt_selftest.cpp: shuffle, ballot and barrier semantics, block order and the hipMalloc fill; lanes out
     of step end the program with status 3 and a message naming the wave, not with a deadlock."""
-    exe = build("simt_selftest")
-    r = subprocess.run([exe, "semantics"], capture_output=True, text=True, timeout=60, env=child_env())
+    exe = sr.build("simt_selftest")
+    r = subprocess.run([exe, "semantics"], capture_output=True, text=True, timeout=60, env=sr.child_env())
     assert r.returncode == 0 and r.stderr == "", r.stderr[-2000:]
     for mode, message in (("returned", "lanes have returned while others of the wave wait"),
                           ("kind", "out of step"), ("size", "out of step")):
-        r = subprocess.run([exe, mode], capture_output=True, text=True, timeout=60, env=child_env())
+        r = subprocess.run([exe, mode], capture_output=True, text=True, timeout=60, env=sr.child_env())
         assert r.returncode == 3, (mode, r.returncode, r.stderr[-2000:])
         assert "wave 0, collective 0: " in r.stderr and message in r.stderr and "lane  7" in r.stderr, r.stderr[-2000:]
 

@@ -9,84 +9,29 @@ statically).
 
 Cost: the table's ~1 300 executes take a few minutes of one core under the sanitizers; the batches run as concurrent
 child processes (at most 8), plus ~15 s to compile the program once."""
-import os
-import re
-import subprocess
-
 import numpy as np
 import pytest
 
 import sddmm_cases as sc
-from conftest import ROOT
-
-CPP = os.path.join(ROOT, "tests", "cpp")
-TIME_LIMIT = 900        # seconds per child
+import sim_runner as sr
 
 
-def build():
-    """The program, built on demand with the sanitizer flags of the other host simulations.  Skips only where the host
-    compiler cannot link with those flags at all (a trivial program, the same flags); any other failure to build is a
-    failure."""
-    probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", CPP, "-f", "sddmm_sim.mk", "sddmm_sim"], check=True)
-    return os.path.join(CPP, "sddmm_sim")
-
-
-def kernel_constant(text, name):
-    return int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
-
-
-def batches(cases, n):
-    """Whole plan groups dealt to n batches, heaviest first onto the lightest batch (weight: merge items x lanes per slot)."""
-    groups = {}
-    for c in cases:
-        groups.setdefault(sc.plan_key(c), []).append(c)
-    weight = lambda g: sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (sc.lanes_per_slot(c.k, c.val) + 2) for c in g)
-    out = [[0, []] for _ in range(n)]
-    for g in sorted(groups.values(), key=weight, reverse=True):
-        b = min(out, key=lambda b: b[0])
-        b[0] += weight(g)
-        b[1] += g
-    return [b[1] for b in out if b[1]]
+def weight(g):
+    """Of a plan group: merge items x lanes per slot."""
+    return sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (sc.lanes_per_slot(c.k, c.val) + 2) for c in g)
 
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, out)}, and the children's reports."""
-    exe = build()
-    csrc = os.path.join(ROOT, "spmv-samples_amd", "csrc")
-    sddmm, common = open(os.path.join(csrc, "sddmm.hip")).read(), open(os.path.join(csrc, "common.hpp")).read()
-    assert kernel_constant(sddmm, "kSddmmSlice") == sc.SLICE_LEN
-    assert kernel_constant(common, "kWave") == sc.STEP
-    assert kernel_constant(sddmm, "kSddmmGroupsMax") == max(sc.LANES_PER_SLOT)
-    assert kernel_constant(common, "kBlock") % sc.STEP == 0
-    tmp = tmp_path_factory.mktemp("sddmm_sim")
-    env = dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1")
-    try:
-        cpus = len(os.sched_getaffinity(0))
-    except AttributeError:
-        cpus = os.cpu_count() or 1
-    children = []
-    for i, cases in enumerate(batches(sc.table(), max(1, min(8, cpus)))):
-        src, dst = str(tmp / ("batch%d.bin" % i)), str(tmp / ("out%d.bin" % i))
-        order = sc.write_batch(src, cases)
-        children.append((subprocess.Popen([exe, src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env),
-                         order, dst))
-    results, reports = {}, []
-    for child, order, dst in children:
-        try:
-            out, err = child.communicate(timeout=TIME_LIMIT)
-        except subprocess.TimeoutExpired:
-            child.kill()
-            out, err = child.communicate()
-            err += "\n(killed after %d s)" % TIME_LIMIT
-        reports.append((child.returncode, out + err))
-        if child.returncode == 0:
-            for c, res in zip(order, sc.read_results(dst, order)):
-                results[c.name] = res
-    return results, reports
+    exe = sr.build("sddmm_sim")
+    sddmm, common = sr.source("sddmm.hip"), sr.source("common.hpp")
+    assert sr.kernel_constant(sddmm, "kSddmmSlice") == sc.SLICE_LEN
+    assert sr.kernel_constant(common, "kWave") == sc.STEP
+    assert sr.kernel_constant(sddmm, "kSddmmGroupsMax") == max(sc.LANES_PER_SLOT)
+    assert sr.kernel_constant(common, "kBlock") % sc.STEP == 0
+    return sr.run_table(exe, tmp_path_factory.mktemp("sddmm_sim"), sr.groups_by(sc.table(), sc.plan_key), weight, sc.write_batch,
+                        sc.read_results)
 
 
 def test_the_children_end_clean_with_an_empty_sanitizer_log(run):
