@@ -219,7 +219,7 @@ def reference(orc, m, val, integer):
     return _refs[key]
 
 
-def _bits(a):
+def bits(a):
     """The bit patterns of a float array with -0 taken as +0: the sign of a zero sum follows the summation order (a lone
     product -0 is -0, the serial sum 0 + -0 is +0), every other value of integer data has one pattern."""
     a = np.ascontiguousarray(a) + a.dtype.type(0)
@@ -242,7 +242,7 @@ def check(orc, c, ybuf):
             want = V(c.alpha) * ref[c.c0 + j]
             if c.beta != 0.0:
                 want = want + V(c.beta) * Y0[:, j]
-            bad = np.nonzero(_bits(got[:, j]) != _bits(want))[0]
+            bad = np.nonzero(bits(got[:, j]) != bits(want))[0]
             assert bad.size == 0, "%s: column %d differs from the serial sum in rows %s (got %s, want %s)" % (
                 c.name, j, bad[:8], got[bad[:8], j], want[bad[:8]])
         return
@@ -338,39 +338,66 @@ def table(L=SLICE_LEN):
     return [c for f in FAMILIES for c in family(f, L)]
 
 
-# ---- the host program's batch file (tests/cpp/multi_sim.cpp) -------------------------------------------------------------
-def write_batch(path, cases):
+def weight(g):
+    """Of a plan group, to deal the groups of any multi-vector table to batches: merge items x columns."""
+    return sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (c.k + 8) for c in g)
+
+
+# ---- the host program's batch file (tests/cpp/multi_sim.cpp, whose header comment has the records) ------------------------
+VAL_TYPE = {"f32": 0, "f64": 1, "i32": 2, "f16": 4, "bf16": 5}      # MI355_VAL_*
+CREATE, CREATE_TYPED, CREATE_HALF = 0, 1, 2                         # the plan record's `how`
+# What write_batch asks of a case.  matrix_key: cases of one key share a matrix record; plan = (k_max, how, pattern): the
+# plan record, made anew where it changes; the MI355_VAL_* of X / Y and of Ax as stored; Ap, Aj, Ax, Xs (the variants of
+# X a run chooses from by x_kind) and Y0 as the program reads them; semiring = its number, or -1 for no set_semiring
+# call; x_pad, y_poison, canary: the bit patterns of what the padding of X, a poisoned Y and the padding of Y hold.
+Operands = collections.namedtuple("Operands", "matrix_key plan vec_type mat_type Ap Aj Ax Xs Y0 semiring x_kind x_pad y_poison canary")
+
+
+def word_of(value, dtype):
+    """The bit pattern of a value of dtype as an int64 word (its low bytes)."""
+    return int.from_bytes(np.asarray(value, dtype=dtype).tobytes().ljust(8, b"\0"), "little", signed=True)
+
+
+def batch_operands(c):
+    Ap, Aj, Ax, X, Y0 = arrays(c.matrix, c.off, c.val, c.integer)
+    nan = word_of(float("nan"), NP[c.val])
+    return Operands(plan_key(c)[:5], (c.k_max, CREATE, 0), VAL_TYPE[c.val], VAL_TYPE[c.val], Ap, Aj, Ax, (X,), Y0, -1, 0, nan, nan,
+                    word_of(CANARY, NP[c.val]))
+
+
+def write_batch(path, cases, operands=batch_operands):
     """Cases in plan order; returns them in the order their results come back."""
     words = lambda *v: struct.pack("<%dq" % len(v), *v)
     last_m = last_p = None
     with open(path, "wb") as f:
         for c in cases:
-            Ap, Aj, Ax, X, Y0 = arrays(c.matrix, c.off, c.val, c.integer)
-            if plan_key(c)[:5] != last_m:
-                last_m, last_p = plan_key(c)[:5], None
-                f.write(words(1, ("i32", "i64").index(c.off), ("f32", "f64").index(c.val), len(c.matrix.lens), c.matrix.n_cols,
-                              int(Ap[-1]), *c.shift[:3]))
-                for a in (Ap, Aj, Ax):
+            o = operands(c)
+            if o.matrix_key != last_m:
+                last_m, last_p = o.matrix_key, None
+                f.write(words(1, ("i32", "i64").index(c.off), o.vec_type, o.mat_type, len(c.matrix.lens), c.matrix.n_cols,
+                              int(o.Ap[-1]), *c.shift[:3]))
+                for a in (o.Ap, o.Aj, o.Ax):
                     f.write(a.tobytes())
-                f.write(words(2, KF))
-                f.write(np.ascontiguousarray(X).tobytes())
-                f.write(np.ascontiguousarray(Y0).tobytes())
-            if c.k_max != last_p:
-                last_p = c.k_max
-                f.write(words(3, c.k_max))
-            f.write(words(4, c.k, c.c0, c.ldx, c.ldy, c.shift[3], c.shift[4], int(c.beta == 0.0)))
+                f.write(words(2, o.Y0.shape[1], len(o.Xs)))
+                for a in o.Xs + (o.Y0,):
+                    f.write(np.ascontiguousarray(a).tobytes())
+            if o.plan != last_p:
+                last_p = o.plan
+                f.write(words(3, *o.plan))
+            f.write(words(4, c.k, c.c0, c.ldx, c.ldy, c.shift[3], c.shift[4], int(c.beta == 0.0), o.semiring, o.x_kind, o.x_pad,
+                          o.y_poison, o.canary))
             f.write(struct.pack("<2d", c.alpha, c.beta))
         f.write(words(0))
     return list(cases)
 
 
-def read_results(path, cases):
-    """[(status, Y buffer as n_rows x ldy)] per case; raises if the file is not complete."""
+def read_results(path, cases, dtype=lambda c: NP[c.val]):
+    """[(status, Y buffer as n_rows x ldy)] per case, Y in dtype(c); raises if the file is not complete."""
     out = []
     with open(path, "rb") as f:
         for c in cases:
             st, count = struct.unpack("<2q", f.read(16))
             assert count == len(c.matrix.lens) * c.ldy, c.name
-            out.append((st, np.frombuffer(f.read(count * NP[c.val]().itemsize), dtype=NP[c.val])))
+            out.append((st, np.frombuffer(f.read(count * np.dtype(dtype(c)).itemsize), dtype=dtype(c))))
         assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
     return out

@@ -23,7 +23,7 @@ result: 2^-11 * |want| for fp16 (11 significand bits), 2^-8 * |want| for bf16 (8
 subnormal spacing (2^-24).  Padding columns of X hold NaN, those of Y a canary that must survive; with beta = 0, Y0 is
 NaN."""
 import collections
-import struct
+import functools
 
 import numpy as np
 
@@ -280,17 +280,6 @@ def table():
     return list(_table)
 
 
-def groups(cases):
-    """Runs of consecutive cases of one plan key."""
-    out = []
-    for c in cases:
-        if out and plan_key(out[-1][0]) == plan_key(c):
-            out[-1].append(c)
-        else:
-            out.append([c])
-    return out
-
-
 def self_test():
     """What the table promises: names of their own, every combination, and carried hub rows with sums above 256."""
     t = table()
@@ -318,48 +307,24 @@ def self_test():
     return t
 
 
-# ---- the host program's batch file (tests/cpp/multi_half_sim.cpp) ------------------------------------------------------
+# ---- the host program's batch file: multi_cases' records, with X, Y0 and Y as 16-bit patterns, through create_half -------
+@functools.lru_cache(maxsize=1)     # cases come in plan order: the conversion is made once per matrix record
+def _stored_arrays(m, off, vec, mat, integer):
+    """arrays() as the program reads them: Ax in the matrix type, X (its one variant) and Y0 as 16-bit patterns."""
+    Ap, Aj, Ax, X, Y0 = arrays(m, off, vec, mat, integer)
+    return Ap, Aj, stored(Ax, vec if mat == "same" else "f32"), (to_bits(X, vec),), to_bits(Y0, vec)
+
+
+def batch_operands(c):
+    nan = NAN_BITS[c.vec]
+    return mc.Operands(plan_key(c)[:6], (c.k_max, mc.CREATE_HALF, 0), VAL_TYPE[c.vec], VAL_TYPE[mat_type(c)],
+                       *_stored_arrays(c.matrix, c.off, c.vec, c.mat, c.integer), -1, 0, nan, nan,
+                       int(to_bits(np.float32(CANARY), c.vec).ravel()[0]))
+
+
 def write_batch(path, cases):
-    """Cases in plan order; returns them in the order their results come back.  Records (int64 words, then raw arrays):
-      1 matrix   off_type vec_type mat_type n_rows n_cols nnz ap_off aj_off ax_off | Ap[n_rows + 1] Aj[nnz] Ax[nnz]
-      2 vectors  kf | X[n_cols * kf] Y0[n_rows * kf]                   (16-bit patterns, row-major)
-      3 plan     k_max
-      4 run      k c0 ldx ldy x_off y_off y0_poison x_pad_bits y_poison_bits canary_bits | alpha beta (2 doubles)
-      0 end"""
-    words = lambda *v: struct.pack("<%dq" % len(v), *v)
-    last_m = last_p = None
-    with open(path, "wb") as f:
-        for c in cases:
-            Ap, Aj, Ax, X, Y0 = arrays(c.matrix, c.off, c.vec, c.mat, c.integer)
-            mkey = plan_key(c)[:6]
-            if mkey != last_m:
-                last_m, last_p = mkey, None
-                f.write(words(1, OFFS.index(c.off), VAL_TYPE[c.vec], VAL_TYPE[mat_type(c)], len(c.matrix.lens), c.matrix.n_cols,
-                              int(Ap[-1]), *c.shift[:3]))
-                f.write(Ap.tobytes())
-                f.write(Aj.tobytes())
-                f.write(stored(Ax, mat_type(c)).tobytes())
-                f.write(words(2, KF))
-                f.write(to_bits(X, c.vec).tobytes())
-                f.write(to_bits(Y0, c.vec).tobytes())
-            if c.k_max != last_p:
-                last_p = c.k_max
-                f.write(words(3, c.k_max))
-            nan = NAN_BITS[c.vec]
-            f.write(words(4, c.k, c.c0, c.ldx, c.ldy, c.shift[3], c.shift[4], int(c.beta == 0.0), nan, nan,
-                          int(to_bits(np.float32(CANARY), c.vec).ravel()[0])))
-            f.write(struct.pack("<2d", c.alpha, c.beta))
-        f.write(words(0))
-    return list(cases)
+    return mc.write_batch(path, cases, batch_operands)
 
 
 def read_results(path, cases):
-    """[(status, Y buffer as n_rows x ldy 16-bit patterns)] per case; raises if the file is not complete."""
-    out = []
-    with open(path, "rb") as f:
-        for c in cases:
-            st, count = struct.unpack("<2q", f.read(16))
-            assert count == len(c.matrix.lens) * c.ldy, c.name
-            out.append((st, np.frombuffer(f.read(count * 2), dtype=np.uint16)))
-        assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
-    return out
+    return mc.read_results(path, cases, lambda c: np.uint16)

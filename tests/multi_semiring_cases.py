@@ -11,13 +11,12 @@ off a 16-byte boundary and — (+, *) on the float types only — alpha / beta r
 Data: integer-valued in {-3 .. 3} (zeros included: (or, and) sees both outcomes) or real-valued in (-1, 1); int32 is
 always integer-valued.  Under (min, +) on floats a tenth of X is +inf, under (max, +) -inf (unreached vertices); no
 infinities under the two x semirings, no NaN.  The reference is Oracle.spmv_genl_serial per column, with Ax = ones of
-the vector type for a pattern case.  Integer-valued data: bit for bit (-0 taken as +0, multi_cases._bits).
+the vector type for a pattern case.  Integer-valued data: bit for bit (-0 taken as +0, multi_cases.bits).
 Real-valued data under (min, +), (max, *), (max, +), (or, and): bit for bit as well — a product is one rounding and
 min / max do not round.  Real-valued (+, *): the per-row bound of multi_cases.check.  Padding columns of X hold NaN
 (int32: a large value), those of Y a canary that must survive; Y is poisoned before every call (NaN; int32: a value
 that would win the semiring's reduce), which under a semiring other than (+, *) also proves that Y is not read."""
 import collections
-import struct
 
 import numpy as np
 
@@ -109,9 +108,10 @@ def reference(orc, c, col):
     return _refs[key]
 
 
-def _bits(a):
+def bits(a):
+    """multi_cases.bits; int32 values as they are."""
     a = np.ascontiguousarray(a)
-    return a if a.dtype == np.int32 else mc._bits(a)
+    return a if a.dtype == np.int32 else mc.bits(a)
 
 
 def check(orc, c, ybuf):
@@ -132,7 +132,7 @@ def check(orc, c, ybuf):
                 want = V(c.alpha) * want
                 if c.beta != 0.0:
                     want = want + V(c.beta) * Y0[:, j]
-            bad = np.nonzero(_bits(got[:, j]) != _bits(want))[0]
+            bad = np.nonzero(bits(got[:, j]) != bits(want))[0]
             assert bad.size == 0, "%s: column %d differs from the serial oracle in rows %s (got %s, want %s)" % (
                 c.name, j, bad[:8], got[bad[:8], j], want[bad[:8]])
         return
@@ -218,57 +218,17 @@ def table():
     return list(_table)
 
 
-def groups(cases):
-    """Runs of consecutive cases of one plan key."""
-    out = []
-    for c in cases:
-        if out and plan_key(out[-1][0]) == plan_key(c):
-            out[-1].append(c)
-        else:
-            out.append([c])
-    return out
+# ---- the host program's batch file: multi_cases' records, through create_typed and set_semiring -------------------------
+def batch_operands(c):
+    Ap, Aj, Ax, _, Y0 = operands(c)
+    V = mc.NP[c.val]        # (the canary of an int32 Y is V(CANARY) = -777, as check() has it)
+    return mc.Operands((c.matrix.name, c.off, c.val, c.integer, c.shift[:3]), (c.k_max, mc.CREATE_TYPED, int(c.pattern)),
+                       VAL_TYPE[c.val], VAL_TYPE[c.val], Ap, Aj, Ax, x_variants(c.matrix, c.off, c.val, c.integer), Y0,
+                       SEMIRINGS.index(c.semiring), x_kind(c), mc.word_of(x_pad(c), V), mc.word_of(y_poison(c), V), mc.word_of(CANARY, V))
 
 
-# ---- the host program's batch file (tests/cpp/multi_semiring_sim.cpp) ----------------------------------------------------
 def write_batch(path, cases):
-    """Cases in plan order; returns them in the order their results come back.  Records (int64 words, then raw arrays):
-      1 matrix   off_type vec_type n_rows n_cols nnz ap_off aj_off ax_off | Ap[n_rows + 1] Aj[nnz] Ax[nnz]
-      2 vectors  kf | X[3][n_cols * kf] (as drawn, with +inf, with -inf) Y0[n_rows * kf]
-      3 plan     k_max pattern
-      4 run      k c0 ldx ldy x_off y_off y0_poison semiring x_kind y_poison_i32 x_pad_i32 | alpha beta (2 doubles)
-      0 end"""
-    words = lambda *v: struct.pack("<%dq" % len(v), *v)
-    last_m = last_p = None
-    with open(path, "wb") as f:
-        for c in cases:
-            Ap, Aj, Ax, _, Y0 = operands(c)
-            mkey = (c.matrix.name, c.off, c.val, c.integer, c.shift[:3])
-            if mkey != last_m:
-                last_m, last_p = mkey, None
-                f.write(words(1, OFFS.index(c.off), VAL_TYPE[c.val], len(c.matrix.lens), c.matrix.n_cols, int(Ap[-1]), *c.shift[:3]))
-                for a in (Ap, Aj, Ax):
-                    f.write(a.tobytes())
-                f.write(words(2, KF))
-                for X in x_variants(c.matrix, c.off, c.val, c.integer):
-                    f.write(np.ascontiguousarray(X).tobytes())
-                f.write(np.ascontiguousarray(Y0).tobytes())
-            if (c.k_max, c.pattern) != last_p:
-                last_p = (c.k_max, c.pattern)
-                f.write(words(3, c.k_max, int(c.pattern)))
-            f.write(words(4, c.k, c.c0, c.ldx, c.ldy, c.shift[3], c.shift[4], int(c.beta == 0.0), SEMIRINGS.index(c.semiring),
-                          x_kind(c), Y_POISON_I32[c.semiring], X_PAD_I32))
-            f.write(struct.pack("<2d", c.alpha, c.beta))
-        f.write(words(0))
-    return list(cases)
+    return mc.write_batch(path, cases, batch_operands)
 
 
-def read_results(path, cases):
-    """[(status, Y buffer as n_rows x ldy)] per case; raises if the file is not complete."""
-    out = []
-    with open(path, "rb") as f:
-        for c in cases:
-            st, count = struct.unpack("<2q", f.read(16))
-            assert count == len(c.matrix.lens) * c.ldy, c.name
-            out.append((st, np.frombuffer(f.read(count * mc.NP[c.val]().itemsize), dtype=mc.NP[c.val])))
-        assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
-    return out
+read_results = mc.read_results

@@ -22,7 +22,7 @@ import struct
 import numpy as np
 
 import multi_cases as mc
-from multi_cases import (AB_REDUCED, LANES_PER_SLOT, NP, SLICE_LEN, STEP, VEC, TILE, is_integer_pair, open_row_structures,  # noqa: F401
+from multi_cases import (AB_REDUCED, LANES_PER_SLOT, NP, SLICE_LEN, STEP, VEC, TILE, bits, is_integer_pair, open_row_structures,  # noqa: F401
                          ragged_structure, row_end_structures, slice_edge_structures, slices)
 
 CANARY = -777.25
@@ -138,12 +138,6 @@ def expected(c):
     eps = 2.0 ** -24 if c.val == "f32" else 2.0 ** -53
     bound = abs(c.alpha) * (c.k + 3) * eps * np.abs(s) * dabs + 2 * eps * (np.abs(c.alpha * s * dot) + np.abs(old) + np.abs(want))
     return want, bound
-
-
-def bits(a):
-    """The bit patterns of a float array with -0 taken as +0 (the sign of a zero follows the order of addition)."""
-    a = np.ascontiguousarray(a) + a.dtype.type(0)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
 
 
 def check(c, out):

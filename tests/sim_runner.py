@@ -1,7 +1,8 @@
 """What the host simulations' test files (tests/test_*_sim_cpu.py) share: building a program of tests/cpp with the
 sanitizers, dealing a table's plan groups to batches, and running the batches as concurrent child processes under a time
 limit.  Nothing is loaded into this process, and the children's environment is this process's own (the sanitizer runtimes
-are linked statically).  Each test file keeps its table, its geometry asserts, its weight function and its tests."""
+are linked statically).  Each test file keeps its table, its geometry asserts, its tests and its weight function (the three
+multi-vector files: the one multi_cases.weight)."""
 import os
 import re
 import subprocess
@@ -45,6 +46,18 @@ def groups_by(cases, key):
     for c in cases:
         groups.setdefault(key(c), []).append(c)
     return list(groups.values())
+
+
+def consecutive_runs(cases, key):
+    """Runs of consecutive cases of one key, in table order: for a table that ends in ordered sequences on one object,
+    whose cases must stay behind one another (the device files cut their tables the same way)."""
+    out = []
+    for c in cases:
+        if out and key(out[-1][0]) == key(c):
+            out[-1].append(c)
+        else:
+            out.append([c])
+    return out
 
 
 def batches(groups, weight, n):

@@ -10,6 +10,7 @@ import torch
 
 import multi_cases as mc
 import multi_half_cases as hc
+import sim_runner as sr
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +54,7 @@ def test_table(sp, family):
     """Every case on the structures of the family, the sequences on one object among them: objects are made per
     (structure, types, data, matrix offsets, k_max) and reused over k, alpha / beta, leading dimensions and the offsets
     of X and Y.  No case is skipped."""
-    groups = [g for g in hc.groups(hc.table()) if g[0].matrix.family == family]
+    groups = [g for g in sr.consecutive_runs(hc.table(), hc.plan_key) if g[0].matrix.family == family]
     assert groups
     for g in groups:
         c = g[0]

@@ -10,6 +10,7 @@ import torch
 
 import multi_cases as mc
 import multi_semiring_cases as sc
+import sim_runner as sr
 from conftest import random_csr
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,7 @@ def on_device(flat, shift):
 
 
 def bits(a):
-    return sc._bits(np.ascontiguousarray(a))
+    return sc.bits(np.ascontiguousarray(a))
 
 
 # ---- the table -----------------------------------------------------------------------------------------------------------
@@ -47,7 +48,7 @@ def test_table(sp, oracle, family):
     """Every case on the structures of the family, the sequences on one object among them: objects are made per
     (structure, types, valued / pattern, data, matrix offsets, k_max) and reused over k, semiring, alpha / beta,
     leading dimensions and the offsets of X and Y.  No case is skipped."""
-    groups = [g for g in sc.groups(sc.table()) if g[0].matrix.family == family]
+    groups = [g for g in sr.consecutive_runs(sc.table(), sc.plan_key) if g[0].matrix.family == family]
     assert groups
     for g in groups:
         c = g[0]

@@ -1,5 +1,6 @@
 """The multi-vector kernels over semirings, int32 values and pattern matrices executed on the host, lane by lane
-(tests/cpp/multi_semiring_sim.cpp over tests/cpp/simt): csrc/multi.hip with the headers it includes, unchanged, built
+(tests/cpp/multi_sim.cpp over tests/cpp/simt, the one program of tests/test_multi_sim_cpu.py,
+tests/test_multi_half_sim_cpu.py and this file): csrc/multi.hip with the headers it includes, unchanged, built
 with the address and undefined-behaviour sanitizers and run over the WHOLE table of tests/multi_semiring_cases.py
 through the real mi355_spmv_multi_create_typed / set_semiring / set_alpha_beta / execute / destroy.  Each Y is held to
 the serial oracle exactly as the device run of the same table is (tests/test_gpu_multi_semiring.py); the children must
@@ -8,8 +9,9 @@ that met combine() among them — and the stand-in's out-of-step check report), 
 Nothing is loaded into this process, and the children's environment is this process's own (the sanitizer runtimes are
 linked statically).
 
-Cost: the table's ~3 000 executes run as concurrent child processes (at most 8): about a minute on 8 cores, plus the
-compilation once (every instantiation of the kernels: about four minutes)."""
+Cost (profiles/multi_sim_merge.txt): the table's ~3 000 executes run as concurrent child processes (at most 8): about
+ten seconds on 8 cores, plus the compilation of the program where no other multi sim file has built it yet (every
+instantiation of the kernels: 287 s as measured)."""
 import pytest
 
 import multi_cases as mc
@@ -17,16 +19,11 @@ import multi_semiring_cases as sc
 import sim_runner as sr
 
 
-def weight(g):
-    """Of a plan group: merge items x columns."""
-    return sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (c.k + 8) for c in g)
-
-
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, Y)}, and the children's reports."""
-    return sr.run_table(sr.build("multi_semiring_sim"), tmp_path_factory.mktemp("multi_semiring_sim"), sc.groups(sc.table()), weight,
-                        sc.write_batch, sc.read_results)
+    return sr.run_table(sr.build("multi_sim"), tmp_path_factory.mktemp("multi_semiring_sim"),
+                        sr.consecutive_runs(sc.table(), sc.plan_key), mc.weight, sc.write_batch, sc.read_results)
 
 
 def test_the_children_end_clean_with_an_empty_sanitizer_log(run):

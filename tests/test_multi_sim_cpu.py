@@ -1,4 +1,5 @@
-"""csrc/multi.hip executed on the host, lane by lane (tests/cpp/multi_sim.cpp over tests/cpp/simt): the kernel source
+"""csrc/multi.hip executed on the host, lane by lane (tests/cpp/multi_sim.cpp over tests/cpp/simt, the one program of
+this file, tests/test_multi_semiring_sim_cpu.py and tests/test_multi_half_sim_cpu.py): the kernel source
 and its launch path, unchanged, built with the address and undefined-behaviour sanitizers and run over the WHOLE table
 of tests/multi_cases.py — every structure, every k of the crosses, both offset widths, both value types.  Each Y is
 held to the oracle exactly as the device run of the same table is (tests/test_gpu_multi.py), the children must end
@@ -6,19 +7,16 @@ with status 0 and must have written nothing to stderr (where the sanitizers and 
 report), and each runs under a time limit.  Nothing is loaded into this process, and the children's environment is this
 process's own (the sanitizer runtimes are linked statically).
 
-Cost: the table's 5 180 executes take ~4 minutes of one core under the sanitizers; the batches run as concurrent child
-processes (at most 8), so the file costs about a minute on 8 cores, plus ~20 s to compile the program once."""
+Cost (profiles/multi_sim_merge.txt): the table's 5 180 executes take ~4 minutes of one core under the sanitizers; the
+batches run as concurrent child processes (at most 8), so the file costs about a minute on 8 cores — the three multi sim
+files together 86 s — plus the compilation of the program, once for the three files: 287 s as measured (every
+instantiation of the kernels that multi.hip can launch; the three programs it replaced took 866 s together)."""
 import subprocess
 
 import pytest
 
 import multi_cases as mc
 import sim_runner as sr
-
-
-def weight(g):
-    """Of a plan group: merge items x columns."""
-    return sum((len(c.matrix.lens) + sum(c.matrix.lens) + 2000) * (c.k + 8) for c in g)
 
 
 @pytest.fixture(scope="module")
@@ -30,7 +28,7 @@ def run(tmp_path_factory):
     assert sr.kernel_constant(common, "kWave") == mc.STEP
     assert sr.kernel_constant(multi, "kMultiGroupsMax") == max(mc.LANES_PER_SLOT)
     assert sr.kernel_constant(common, "kBlock") % mc.STEP == 0
-    return sr.run_table(exe, tmp_path_factory.mktemp("multi_sim"), sr.groups_by(mc.table(), mc.plan_key), weight, mc.write_batch,
+    return sr.run_table(exe, tmp_path_factory.mktemp("multi_sim"), sr.groups_by(mc.table(), mc.plan_key), mc.weight, mc.write_batch,
                         mc.read_results)
 
 
