@@ -47,6 +47,7 @@ extern "C" {
 #define MI355_SPMV_HAS_MULTI_HALF 1 /* mi355_spmv_multi_create_half / _half_*: X and Y in binary16 / bfloat16, fp32 arithmetic */
 #define MI355_SPMV_HAS_SDDMM 1 /* mi355_spmv_sddmm_*: dot(U[r], V[c]) at every stored entry (r, c) of A in one pass over A */
 #define MI355_SPMV_HAS_SDDMM_HALF 1 /* mi355_spmv_sddmm_create_half / _get_types / _half_*: U and V in binary16 / bfloat16, fp32 Ax and out */
+#define MI355_SPMV_HAS_ROW_SOFTMAX 1 /* mi355_spmv_row_softmax_*: softmax over the stored entries of every row (edge softmax), and its gradient */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -746,6 +747,59 @@ int mi355_spmv_sddmm_half_i64_f16(int32_t n_rows, int32_t n_cols, int64_t nnz, c
     const void* U, int64_t ldu, const void* V, int64_t ldv, float* out, int32_t k, void* stream);
 int mi355_spmv_sddmm_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, const float* Ax,
     const void* U, int64_t ldu, const void* V, int64_t ldv, float* out, int32_t k, void* stream);
+
+/* ---- Row softmax over the stored entries of a CSR matrix, "edge softmax" (MI355_SPMV_HAS_ROW_SOFTMAX) ------------------
+ * For callers who attend over a graph: the step between the edge scores (SDDMM) and the aggregation (multi-vector SpMV
+ * with the result as Ax), and its gradient, without leaving the library for nnz-sized temporaries.
+ *   forward    v[n] = scale * x[n];  m_r = max over row r of v;  out[n] = exp(v[n] - m_r) / sum over row r of exp(v - m_r)
+ *   backward   t_r = sum over row r of p * dp;  dx[n] = scale * p[n] * (dp[n] - t_r)        (p = the forward's output)
+ * x, out, p, dp, dx: nnz values of the value type in CSR order.  Aj is retained for symmetry with the other objects and
+ * never read.  scale is 1 after create (the 1 / sqrt(d) of attention: set_scale).
+ * Empty rows write nothing.  A row of one entry gives exactly 1.  An entry x[n] = -inf (a masked edge; scale > 0) gives
+ * exactly +0, and a row whose entries are ALL -inf gives +0 everywhere, not NaN.
+ * In place is allowed: out may be x; dx may be dp or p.  Every element is read by the lane that writes it, and none is
+ * read after another wave has written it.  Any other overlap of operands is not allowed.
+ * No atomics: two executes on the same inputs give the same bits.  Unlike SDDMM's, the bits of an element depend on
+ * where the cuts fall in its row: a row's statistic ((max, sum) forward, the sum backward) is combined by group of 64
+ * nonzeros of a slice in ascending order, then by slice in ascending order.
+ * Types: {I32, I64} offsets x {F32, F64} values.  MI355_VAL_I32: MI355_SPMV_ENOTSUP; PATTERN / F16 / BF16 / unknown:
+ * MI355_SPMV_EINVAL.  16-bit x, a fused SDDMM-softmax-SpMM, a column (transposed) softmax and dist_* entry points are
+ * not built.
+ * The work is cut as the multi-vector kind's (slice_len merge items per wave).  Three kernels per execute, always the
+ * same three: the slices (every row inside a slice is finished from registers: x crosses memory once, out once), a
+ * fix-up of the rows that cross slices (one thread per slice), and a finish pass over those rows' pieces.
+ * Life cycle: create retains Ap / Aj (not copied, not read) and allocates scratch_bytes = O(n_slices) on the current
+ * device (its only device call; none when nnz or n_rows is 0); execute / backward are asynchronous on `stream`,
+ * allocate nothing, never synchronise and decide nothing from device data (graph-capturable; no launch when nnz or
+ * n_rows is 0); one stream at a time per object.  Every argument error is MI355_SPMV_EINVAL before any device call,
+ * and the text of the last error names the argument.                                                             */
+typedef struct mi355_spmv_row_softmax mi355_spmv_row_softmax;
+typedef struct mi355_spmv_row_softmax_info {
+    int32_t off_type, val_type;
+    int32_t slice_len;       /* merge items (row ends + nonzeros) per slice = per wave                    */
+    int32_t block_threads;
+    int64_t n_slices;
+    int64_t grid_blocks;     /* workgroups of the slice kernel (and of the finish kernel)                 */
+    int64_t scratch_bytes;   /* device memory the object owns                                             */
+    char main_kernel[64];
+} mi355_spmv_row_softmax_info;
+int mi355_spmv_row_softmax_create(mi355_spmv_row_softmax** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols,
+                                  int64_t nnz, const void* Ap, const int32_t* Aj);
+int mi355_spmv_row_softmax_set_scale(mi355_spmv_row_softmax* m, double scale);
+int mi355_spmv_row_softmax_execute(mi355_spmv_row_softmax* m, const void* x, void* out, void* stream);
+int mi355_spmv_row_softmax_backward(mi355_spmv_row_softmax* m, const void* p, const void* dp, void* dx, void* stream);
+int mi355_spmv_row_softmax_get_info(const mi355_spmv_row_softmax* m, mi355_spmv_row_softmax_info* info);
+int mi355_spmv_row_softmax_destroy(mi355_spmv_row_softmax* m);
+/* One-shots (forward): create, set_scale, execute, synchronise the stream, destroy — the scratch must outlive the
+ * kernels, as the multi-vector one-shots' does.                                                                    */
+int mi355_spmv_row_softmax_i32_f32(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const float* x, float* out, double scale, void* stream);
+int mi355_spmv_row_softmax_i32_f64(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const double* x, double* out, double scale, void* stream);
+int mi355_spmv_row_softmax_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const float* x, float* out, double scale, void* stream);
+int mi355_spmv_row_softmax_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const double* x, double* out, double scale, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

@@ -7,6 +7,7 @@ is missing or a call fails, a RuntimeError is raised.
 The reference interface this mirrors (same argument order and meaning):
     SpMV(kind_str, n_rows, n_cols, nnz, Ap, Aj, Ax, x, y)   include/spmv.h:29-34
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -58,6 +59,8 @@ EXPORTS = (
     + ["mi355_spmv_sddmm_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
     + ["mi355_spmv_sddmm_create_half", "mi355_spmv_sddmm_get_types"]
     + ["mi355_spmv_sddmm_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
+    + ["mi355_spmv_row_softmax_" + n for n in ("create", "set_scale", "execute", "backward", "get_info", "destroy")]
+    + ["mi355_spmv_row_softmax_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
 )
 
 
@@ -108,6 +111,12 @@ class MultiInfo(C.Structure):
 class SddmmInfo(C.Structure):
     _fields_ = [("off_type", C.c_int32), ("val_type", C.c_int32), ("slice_len", C.c_int32), ("block_threads", C.c_int32),
                 ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("main_kernel", C.c_char * 64)]
+
+
+class RowSoftmaxInfo(C.Structure):
+    _fields_ = [("off_type", C.c_int32), ("val_type", C.c_int32), ("slice_len", C.c_int32), ("block_threads", C.c_int32),
+                ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("scratch_bytes", C.c_int64),
+                ("main_kernel", C.c_char * 64)]
 
 
 EXCHANGES = {"auto": 0, "bcast": 1, "sendrecv": 2, "allgather": 3}
@@ -224,6 +233,16 @@ def lib():
         for o in ("i32", "i64"):
             for v in ("f16", "bf16"):
                 getattr(L, "mi355_spmv_sddmm_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_sddmm_%s_f32" % o).argtypes
+        L.mi355_spmv_row_softmax_create.argtypes = L.mi355_spmv_sddmm_create.argtypes
+        L.mi355_spmv_row_softmax_set_scale.argtypes = [C.c_void_p, C.c_double]
+        L.mi355_spmv_row_softmax_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355_spmv_row_softmax_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mi355_spmv_row_softmax_get_info.argtypes = [C.c_void_p, C.POINTER(RowSoftmaxInfo)]
+        L.mi355_spmv_row_softmax_destroy.argtypes = [C.c_void_p]
+        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
+            for v in ("f32", "f64"):
+                getattr(L, "mi355_spmv_row_softmax_%s_%s" % (o, v)).argtypes = [
+                    C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
         _lib = L
     return _lib
 
@@ -941,6 +960,109 @@ def sddmm_half(n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out=None, stream=None):
         st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
                                   C.c_void_p(Ax.data_ptr()) if Ax is not None else None, C.c_void_p(U.data_ptr()), ldu,
                                   C.c_void_p(V.data_ptr()), ldv, C.c_void_p(out.data_ptr()), k, _stream_ptr(stream))
+    _check(st, name)
+    return out
+
+
+def _edge_values(t, name, nnz, val_dtype):
+    """An operand of nnz values in CSR order: a contiguous 1-D device tensor of the plan's value type."""
+    _require_device(t)
+    if t.dtype != val_dtype:
+        raise TypeError("value type differs from the plan's (%s)" % name)
+    if t.dim() != 1 or t.numel() < nnz:
+        raise ValueError("operand shorter than the plan's sizes (%s)" % name)
+    return t
+
+
+class RowSoftmaxPlan:
+    """mi355_spmv_row_softmax_*: the softmax of scale * x over the stored entries of every row of A ("edge softmax"), and
+    its gradient.  x, out, p, dp and the gradient are contiguous 1-D device tensors of nnz values in CSR order, float32 or
+    float64 (val_dtype).  An entry of -inf is a masked edge and gives exactly 0; a row that is masked whole gives zeros;
+    empty rows write nothing.  In place is allowed: execute(x, out=x), backward(p, dp, out=dp) or out=p.  Holds
+    references to Ap and Aj (Aj is not read) so they outlive the object; creating one allocates O(n_slices) bytes of
+    scratch on Ap's device (info()["scratch_bytes"]).  Executes are asynchronous and never synchronise."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype):
+        _require_device(Ap, Aj)
+        if Aj.dtype != torch.int32:
+            raise TypeError("Aj must be int32")
+        if val_dtype not in (torch.float32, torch.float64):
+            raise TypeError("val_dtype must be float32 or float64")
+        self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
+        self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
+        self._h = C.c_void_p()
+        # (nothing stored: create makes no device call, and no device need exist)
+        with torch.cuda.device(Ap.device) if nnz > 0 and n_rows > 0 else contextlib.nullcontext():
+            st = lib().mi355_spmv_row_softmax_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols,
+                                                     nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()))
+        _check(st, "mi355_spmv_row_softmax_create")
+
+    def _out(self, out, like):
+        if out is None:
+            return torch.empty(self.nnz, dtype=self.val_dtype, device=like.device)
+        return _edge_values(out, "out", self.nnz, self.val_dtype)
+
+    def execute(self, x, out=None, stream=None):
+        """out = softmax over each row of scale * x; asynchronous on `stream` (default: torch's current stream); returns
+        out (made when None; out may be x)."""
+        x = _edge_values(x, "x", self.nnz, self.val_dtype)
+        out = self._out(out, x)
+        with torch.cuda.device(self.Ap.device):
+            st = lib().mi355_spmv_row_softmax_execute(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), _stream_ptr(stream))
+        _check(st, "mi355_spmv_row_softmax_execute")
+        return out
+
+    def backward(self, p, dp, out=None, stream=None):
+        """out = scale * p * (dp - sum over the row of p * dp), p an execute's output; returns out (made when None; out
+        may be dp or p)."""
+        p = _edge_values(p, "p", self.nnz, self.val_dtype)
+        dp = _edge_values(dp, "dp", self.nnz, self.val_dtype)
+        out = self._out(out, p)
+        with torch.cuda.device(self.Ap.device):
+            st = lib().mi355_spmv_row_softmax_backward(self._h, C.c_void_p(p.data_ptr()), C.c_void_p(dp.data_ptr()),
+                                                       C.c_void_p(out.data_ptr()), _stream_ptr(stream))
+        _check(st, "mi355_spmv_row_softmax_backward")
+        return out
+
+    def set_scale(self, s):
+        """scale for the following executes and backwards (default 1): the 1 / sqrt(d) of attention."""
+        _check(lib().mi355_spmv_row_softmax_set_scale(self._h, C.c_double(s)), "mi355_spmv_row_softmax_set_scale")
+
+    def info(self):
+        si = RowSoftmaxInfo()
+        _check(lib().mi355_spmv_row_softmax_get_info(self._h, C.byref(si)), "mi355_spmv_row_softmax_get_info")
+        d = {n: getattr(si, n) for n, _ in si._fields_}
+        d["main_kernel"] = d["main_kernel"].decode()
+        return d
+
+    def destroy(self):
+        if self._h:
+            lib().mi355_spmv_row_softmax_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def row_softmax(n_rows, n_cols, nnz, Ap, Aj, x, out=None, scale=1.0, stream=None):
+    """One-shot row softmax (mi355_spmv_row_softmax_<off>_<val>): out = softmax over each row of scale * x, x and out nnz
+    values in CSR order (out may be x).  Synchronises `stream` before returning: its scratch lives for the call."""
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if not getattr(x, "is_cuda", False):
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError("x must be float32 or float64")
+    x = _edge_values(x, "x", nnz, x.dtype)
+    out = torch.empty(nnz, dtype=x.dtype, device=x.device) if out is None else _edge_values(out, "out", nnz, x.dtype)
+    name = "mi355_spmv_row_softmax_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[x.dtype][1])
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), C.c_void_p(x.data_ptr()),
+                                  C.c_void_p(out.data_ptr()), C.c_double(scale), _stream_ptr(stream))
     _check(st, name)
     return out
 
