@@ -45,6 +45,7 @@ extern "C" {
 #define MI355_SPMV_HAS_MULTI 1   /* mi355_spmv_multi_*: Y = A X for k vectors in one pass over A */
 #define MI355_SPMV_HAS_MULTI_SEMIRING 1 /* mi355_spmv_multi_create_typed / _set_semiring / _get_types / _genl_* / _pattern_* */
 #define MI355_SPMV_HAS_MULTI_HALF 1 /* mi355_spmv_multi_create_half / _half_*: X and Y in binary16 / bfloat16, fp32 arithmetic */
+#define MI355_SPMV_HAS_MULTI_TRANSPOSED 1 /* mi355_spmv_csr_transpose, mi355_spmv_multi_create_permuted / _create_transposed / _transposed_* */
 #define MI355_SPMV_HAS_SDDMM 1 /* mi355_spmv_sddmm_*: dot(U[r], V[c]) at every stored entry (r, c) of A in one pass over A */
 #define MI355_SPMV_HAS_SDDMM_HALF 1 /* mi355_spmv_sddmm_create_half / _get_types / _half_*: U and V in binary16 / bfloat16, fp32 Ax and out */
 #define MI355_SPMV_HAS_ROW_SOFTMAX 1 /* mi355_spmv_row_softmax_*: softmax over the stored entries of every row (edge softmax), and its gradient */
@@ -665,6 +666,72 @@ int mi355_spmv_multi_half_i64_f16(int32_t n_rows, int32_t n_cols, int64_t nnz, c
     const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream);
 int mi355_spmv_multi_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
     const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, void* stream);
+
+/* ---- transposed multi-vector SpMV, Y = alpha * A^T X + beta * Y, in three layers (MI355_SPMV_HAS_MULTI_TRANSPOSED) ---
+ * For callers who train or attend over a graph: the gradient of multi-vector SpMV with respect to X is A^T dY, and the
+ * gradient of SDDMM with respect to V is (A o dOut)^T U — two products with the transpose of a matrix whose VALUES change
+ * on every step while its structure does not.  So the structure of A^T is built once, and the values are never moved:
+ * an execute reads the caller's Ax, in A's own CSR order, through a slot map.  DESIGN.md 3.14.
+ *
+ * 1. mi355_spmv_csr_transpose: the structure of A^T on the device, deterministic.
+ *   Ap, Aj        the CSR structure of A (n_rows + 1 device offsets of off_type, nnz device int32 columns)
+ *   Apt           n_cols + 1 device offsets of off_type;  Ajt: nnz int32, Ajt[t] = the row of A behind transposed slot t
+ *   perm          nnz 32-bit indices: perm[t] = the CSR slot of A behind transposed slot t (Axt = Ax[perm])
+ *   Inside a column the slots are in ASCENDING SOURCE SLOT order (a stable sort by column): rows ascend, duplicates keep
+ *   their order, two calls give identical outputs — never the order of atomics.
+ *   workspace     NULL: *workspace_bytes = the bytes needed, return OK (touches no device, needs no GPU); otherwise
+ *                 device memory of at least that many bytes; the call allocates nothing.
+ * Sizes as coo_to_csr: with MI355_OFF_I32 nnz <= INT32_MAX (else EINVAL); nnz >= 2^32 is MI355_SPMV_ENOTSUP.  Ap and Aj
+ * are checked first: offsets that do not ascend from 0 to nnz, or a column outside [0, n_cols), return MI355_SPMV_EINVAL,
+ * mi355_spmv_last_error() names the first offender, and no output is written.  The work is enqueued on `stream`, which
+ * is then synchronised once.                                                                                       */
+int mi355_spmv_csr_transpose(int off_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
+                             void* Apt, int32_t* Ajt, uint32_t* perm, void* workspace, size_t* workspace_bytes, void* stream);
+
+/* 2. mi355_spmv_multi_create_permuted: a multi-vector object whose matrix values are read through a permutation,
+ *   Y[r, j] = alpha * sum over the nonzeros n of row r of Ax[perm[n]] * X[Aj[n], j] + beta * Y[r, j]
+ * with Ax, at execute, an array of n_values values.  perm may repeat indices (the mirrors of a symmetric file share one
+ * value: the perm of mi355_spmv_coo_to_csr_symmetric) and may leave values unused.  The work is cut, carried and fixed
+ * up exactly as a plain object's; the result is, bit for bit, that of a plain object executed on Ax[perm].
+ *   perm_type     MI355_OFF_I32: 32-bit indices (what mi355_spmv_csr_transpose writes); MI355_OFF_I64: the int64 of
+ *                 mi355_spmv_coo_to_csr
+ *   perm          nnz device indices.  Create checks EVERY index against [0, n_values) on the device (on `stream`, which
+ *                 it synchronises): a bad one is MI355_SPMV_EINVAL, mi355_spmv_last_error() names the first, and no
+ *                 object is made.  The object keeps its own 4-byte copy (no execute can gather out of bounds, and the
+ *                 stream carries 4 bytes per nonzero): the caller's perm is not retained.  n_values >= 2^32: ENOTSUP.
+ * fp32 / fp64 values and the (+, *) semiring with alpha / beta only: MI355_VAL_I32, MI355_VAL_PATTERN, F16 and BF16 are
+ * MI355_SPMV_ENOTSUP (a pattern matrix has no values to permute), and so is mi355_spmv_multi_set_semiring to anything
+ * else.  Everything else — k_max, the argument checks before any device call, execute (asynchronous, allocation-free,
+ * kernels only: graph-capturable), set_alpha_beta, get_info (main_kernel = "multi_perm_slice_kernel"), destroy — is
+ * mi355_spmv_multi_create's.                                                                                       */
+int mi355_spmv_multi_create_permuted(mi355_spmv_multi** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols,
+                                     int64_t nnz, const void* Ap, const int32_t* Aj, int perm_type, const void* perm,
+                                     int64_t n_values, int32_t k_max, void* stream);
+/* What a permuted or transposed object holds besides its carries (any pointer may be NULL): the values its executes'
+ * Ax has (a plain object: nnz), the bytes of structure and permutation it owns (a plain object: 0), and whether its Ap
+ * and Aj are its own (a transposed object) or the caller's.                                                         */
+int mi355_spmv_multi_get_perm_info(const mi355_spmv_multi* multi, int64_t* n_values, int64_t* held_bytes, int* owns_structure);
+/* The object's Ap, Aj and perm copied to the caller's device arrays (rows + 1 offsets, nnz int32, nnz 32-bit indices; any
+ * of the three may be NULL), asynchronously on `stream`: of a transposed object, the CSR structure of A^T.            */
+int mi355_spmv_multi_copy_structure(const mi355_spmv_multi* multi, void* Ap, int32_t* Aj, uint32_t* perm, void* stream);
+
+/* 3. mi355_spmv_multi_create_transposed: layers 1 and 2 composed.  Ap and Aj describe A (n_rows x n_cols); the object
+ * owns Apt, Ajt and perm — (n_cols + 1) offsets + 8 nnz bytes, reported by get_perm_info and freed by destroy — and does
+ * not retain Ap / Aj.  Create allocates, runs the transpose on `stream` and synchronises it; a bad Ap or Aj is EINVAL as
+ * in layer 1.  mi355_spmv_multi_execute(multi, Ax, X, ldx, Y, ldy, k, stream) then takes Ax in A's CSR order (nnz
+ * values), X as n_rows x k and Y as n_cols x k; an empty column of A gives beta * Y.  Types as layer 2.
+ * Out of scope: a transposed single-vector plan, semirings / int32 / 16-bit types, dist_*, harness labels.           */
+int mi355_spmv_multi_create_transposed(mi355_spmv_multi** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols,
+                                       int64_t nnz, const void* Ap, const int32_t* Aj, int32_t k_max, void* stream);
+/* One-shots: create_transposed (k_max = k), execute, synchronise the stream, destroy.                              */
+int mi355_spmv_multi_transposed_i32_f32(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const float* Ax, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_transposed_i32_f64(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj,
+    const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_transposed_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const float* Ax, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t k, void* stream);
+int mi355_spmv_multi_transposed_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
+    const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy, int32_t k, void* stream);
 
 /* ---- SDDMM: the dot of a row of U and a row of V at every stored entry of A (MI355_SPMV_HAS_SDDMM) ------------------
  * For callers who train or attend over a graph: the gradient of multi-vector SpMV with respect to Ax

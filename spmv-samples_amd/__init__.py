@@ -14,11 +14,12 @@ Contents (only what the hot path needs):
     capi.py    ctypes binding used by tests and bench.py (also coo_to_csr: COO -> CSR on the device, symmetric expansion included;
                MultiPlan / spmm / spmm_pattern: Y = A X for k vectors in one pass over A, over a semiring; narrow_values: fp32 -> fp16 / bf16 matrix values;
                SddmmPlan / sddmm / sddmm_half: dot(U[r], V[c]) at every stored entry (r, c) of A in one pass over A, U and V in fp32 / fp64 or in 16 bits;
-               RowSoftmaxPlan / row_softmax: softmax over the stored entries of every row, and its gradient)
+               RowSoftmaxPlan / row_softmax: softmax over the stored entries of every row, and its gradient;
+               csr_transpose / MultiPlan(perm=) / TransposedMultiPlan / spmm_t: Y = A^T X with Ax read in place through a slot map)
     synth.py   seeded synthetic CSR matrices (stand-ins for the BASELINE configs)
     dist.py    row-block sharding + allgatherv(y) for one process per GPU
     load.py    ctypes binding of the Matrix Market loader (include/mi355_load.h, host/load.hpp)
 """
 from . import capi, dist, load, synth  # noqa: F401
 from .capi import (DistPlan, Functor, MultiPlan, Plan, PlanShape, RowSoftmaxPlan, SddmmPlan, coo_symmetric_nnz, coo_to_csr, spmm,  # noqa: F401
-                   spmv, narrow_values, row_softmax, sddmm, sddmm_half, spmm_pattern, spmv_genl, spmv_mixed, spmv_pattern)
+                   spmv, narrow_values, row_softmax, TransposedMultiPlan, csr_transpose, spmm_t, sddmm, sddmm_half, spmm_pattern, spmv_genl, spmv_mixed, spmv_pattern)

@@ -61,6 +61,9 @@ EXPORTS = (
     + ["mi355_spmv_sddmm_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
     + ["mi355_spmv_row_softmax_" + n for n in ("create", "set_scale", "execute", "backward", "get_info", "destroy")]
     + ["mi355_spmv_row_softmax_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
+    + ["mi355_spmv_csr_transpose"]
+    + ["mi355_spmv_multi_" + n for n in ("create_permuted", "create_transposed", "get_perm_info", "copy_structure")]
+    + ["mi355_spmv_multi_transposed_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
 )
 
 
@@ -243,6 +246,18 @@ def lib():
             for v in ("f32", "f64"):
                 getattr(L, "mi355_spmv_row_softmax_%s_%s" % (o, v)).argtypes = [
                     C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        L.mi355_spmv_csr_transpose.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]
+        L.mi355_spmv_multi_create_permuted.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64,
+                                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int32,
+                                                       C.c_void_p]
+        L.mi355_spmv_multi_create_transposed.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64,
+                                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.mi355_spmv_multi_get_perm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        L.mi355_spmv_multi_copy_structure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for o in ("i32", "i64"):
+            for v in ("f32", "f64"):
+                getattr(L, "mi355_spmv_multi_transposed_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_multi_%s_%s" % (o, v)).argtypes
         _lib = L
     return _lib
 
@@ -662,10 +677,21 @@ class MultiPlan:
     in 16 bits, fp32 arithmetic, Y rounded once; mat_dtype is then None or val_dtype (Ax in the same 16 bits) or
     torch.float32, and the semiring "plus_times".  Holds references to Ap and Aj so they outlive the object."""
 
-    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, mat_dtype=None, semiring="plus_times"):
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, mat_dtype=None, semiring="plus_times", perm=None,
+                 n_values=None, stream=None):
+        """perm (nnz int32 or int64 device indices) makes a PERMUTED plan (mi355_spmv_multi_create_permuted): execute reads
+        nonzero n's value as Ax[perm[n]], Ax holding n_values values (default nnz).  float32 / float64 under "plus_times"
+        only.  Every index is checked on the device at create (on `stream`, which is synchronised); the plan keeps its own
+        copy of perm."""
         _require_device(Ap, Aj)
         if Aj.dtype != torch.int32:
             raise TypeError("Aj must be int32")
+        self.n_values = nnz
+        if perm is not None:
+            self._init_permuted(n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, mat_dtype, semiring, perm, n_values, stream)
+            return
+        if n_values is not None:
+            raise TypeError("n_values comes with perm")
         pattern = isinstance(mat_dtype, str) and mat_dtype == "pattern"
         half = val_dtype in MAT_TYPES
         if half and mat_dtype not in (None, val_dtype, torch.float32):
@@ -703,9 +729,39 @@ class MultiPlan:
         if sr != 0:
             self.set_semiring(sr)
 
+    def _init_permuted(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, mat_dtype, semiring, perm, n_values, stream):
+        if val_dtype not in (torch.float32, torch.float64) or mat_dtype not in (None, val_dtype):
+            raise TypeError("a permuted plan is float32 or float64 (matrix and vectors alike)")
+        if _semiring_id(semiring) != 0:
+            raise TypeError('a permuted plan is built under the "plus_times" semiring only')
+        _require_device(perm)
+        if perm.dtype not in OFF_TYPES:
+            raise TypeError("perm must be int32 or int64")
+        if perm.dim() != 1 or perm.numel() < nnz:
+            raise ValueError("perm must hold nnz indices")
+        n_values = nnz if n_values is None else int(n_values)
+        if n_values < 0:
+            raise ValueError("n_values is negative")
+        self.n_rows, self.n_cols, self.nnz, self.k_max, self.n_values = n_rows, n_cols, nnz, k_max, n_values
+        self.Ap, self.Aj, self.val_dtype, self.pattern, self.mat_dtype = Ap, Aj, val_dtype, False, val_dtype
+        self.permuted = True
+        self._h = C.c_void_p()
+        with torch.cuda.device(Ap.device):
+            st = lib().mi355_spmv_multi_create_permuted(
+                C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()),
+                C.c_void_p(Aj.data_ptr()), OFF_TYPES[perm.dtype][0], C.c_void_p(perm.data_ptr()), n_values, k_max,
+                _stream_ptr(stream))
+        _check(st, "mi355_spmv_multi_create_permuted")
+
+    def perm_info(self):
+        """{"n_values", "held_bytes", "owns_structure"} (mi355_spmv_multi_get_perm_info)."""
+        n, b, o = C.c_int64(), C.c_int64(), C.c_int()
+        _check(lib().mi355_spmv_multi_get_perm_info(self._h, C.byref(n), C.byref(b), C.byref(o)), "mi355_spmv_multi_get_perm_info")
+        return {"n_values": n.value, "held_bytes": b.value, "owns_structure": o.value}
+
     def execute(self, Ax, X, Y, stream=None):
         """Asynchronous on `stream` (default: torch's current stream).  k = X.size(1) = Y.size(1).  Ax is None for a
-        pattern plan (one that is given is ignored)."""
+        pattern plan (one that is given is ignored); a permuted plan takes n_values values."""
         if getattr(self, "pattern", False):
             Ax = None       # ignored: never checked, never passed on
         elif Ax is None:
@@ -714,12 +770,14 @@ class MultiPlan:
             _require_device(Ax)
             if Ax.dtype != getattr(self, "mat_dtype", self.val_dtype):
                 raise TypeError("value type differs from the plan's")
-            if Ax.numel() < self.nnz:
+            if Ax.numel() < (self.n_values if getattr(self, "permuted", False) else self.nnz):
                 raise ValueError("operand shorter than the plan's sizes")
         ldx = _require_matrix(X, "X", self.n_cols, self.val_dtype)
         ldy = _require_matrix(Y, "Y", self.n_rows, self.val_dtype)
         if X.size(1) != Y.size(1):
             raise ValueError("X and Y hold different numbers of vectors")
+        if getattr(self, "permuted", False):
+            _refuse_alias(X, Y)
         st = lib().mi355_spmv_multi_execute(self._h, C.c_void_p(Ax.data_ptr()) if Ax is not None else None,
                                             C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, X.size(1),
                                             _stream_ptr(stream))
@@ -758,6 +816,116 @@ class MultiPlan:
             self.destroy()
         except Exception:
             pass
+
+
+def _refuse_alias(X, Y):
+    """Y must not lie over X: a slice writes rows of Y while other slices still gather rows of X."""
+    span = lambda t: (t.data_ptr(), t.data_ptr() + ((t.size(0) - 1) * t.stride(0) + t.size(1)) * t.element_size()) if t.numel() else (0, 0)
+    (x0, x1), (y0, y1) = span(X), span(Y)
+    if x0 < y1 and y0 < x1:
+        raise ValueError("Y aliases X")
+
+
+def csr_transpose(n_rows, n_cols, Ap, Aj, stream=None):
+    """The structure of A^T on the device (mi355_spmv_csr_transpose): (Apt, Ajt, perm) with Apt of n_cols + 1 offsets in
+    Ap's dtype, Ajt[t] = the row of A behind transposed slot t and perm[t] = its CSR slot in A (int32 tensors holding the
+    library's unsigned 32-bit indices), so that Axt = Ax[perm.long()].  Inside a column the slots ascend (a stable sort by
+    column): deterministic.  Synchronises the stream."""
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if Ap.dtype not in OFF_TYPES:
+        raise TypeError("Ap must be int32 or int64")
+    if Ap.dim() != 1 or Ap.numel() < n_rows + 1:
+        raise ValueError("Ap must hold n_rows + 1 offsets")
+    nnz = Aj.numel()
+    dev = Ap.device
+    Apt = torch.empty(n_cols + 1, dtype=Ap.dtype, device=dev)
+    Ajt = torch.empty(nnz, dtype=torch.int32, device=dev)
+    perm = torch.empty(nnz, dtype=torch.int32, device=dev)
+    nbytes = csr_transpose_workspace_bytes(n_cols, nnz, Ap.dtype)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    size = C.c_size_t(nbytes)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+    with torch.cuda.device(dev):
+        st = lib().mi355_spmv_csr_transpose(OFF_TYPES[Ap.dtype][0], n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), ptr(Aj),
+                                            C.c_void_p(Apt.data_ptr()), ptr(Ajt), ptr(perm), C.c_void_p(ws.data_ptr()),
+                                            C.byref(size), _stream_ptr(stream))
+    _check(st, "mi355_spmv_csr_transpose")
+    return Apt, Ajt, perm
+
+
+def csr_transpose_workspace_bytes(n_cols, nnz, off_dtype=torch.int32):
+    """Device workspace mi355_spmv_csr_transpose needs (the size query: no device is touched)."""
+    ws = C.c_size_t(0)
+    st = lib().mi355_spmv_csr_transpose(OFF_TYPES[off_dtype][0], 1 if nnz else 0, n_cols, nnz, None, None, None, None, None, None,
+                                        C.byref(ws), None)
+    _check(st, "mi355_spmv_csr_transpose (size query)")
+    return ws.value
+
+
+class TransposedMultiPlan(MultiPlan):
+    """mi355_spmv_multi_create_transposed: Y = alpha * A^T X + beta * Y for up to k_max vectors, with A given as it is held —
+    Ap, Aj (n_rows x n_cols) — and Ax, at execute, in A's own CSR order: the plan builds the structure of A^T once and
+    reads the values through a slot map, so values that change on every step are never gathered or copied.  X is
+    n_rows x k, Y is n_cols x k.  float32 / float64.  The plan owns its structure: Ap and Aj are not retained."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, stream=None):
+        _require_device(Ap, Aj)
+        if Aj.dtype != torch.int32:
+            raise TypeError("Aj must be int32")
+        if val_dtype not in (torch.float32, torch.float64):
+            raise TypeError("val_dtype must be float32 or float64")
+        if Ap.dtype not in OFF_TYPES:
+            raise TypeError("Ap must be int32 or int64")
+        if Ap.numel() < n_rows + 1 or Aj.numel() < nnz:
+            raise ValueError("Ap or Aj shorter than the matrix")
+        # as a MultiPlan sees it: the rows of A^T are the columns of A
+        self.n_rows, self.n_cols, self.nnz, self.k_max, self.n_values = n_cols, n_rows, nnz, k_max, nnz
+        self.val_dtype, self.mat_dtype, self.pattern, self.permuted = val_dtype, val_dtype, False, True
+        self.off_dtype, self.device = Ap.dtype, Ap.device
+        self.Ap = self.Aj = None
+        self._h = C.c_void_p()
+        with torch.cuda.device(Ap.device):
+            st = lib().mi355_spmv_multi_create_transposed(
+                C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()),
+                C.c_void_p(Aj.data_ptr()) if Aj.numel() else None, k_max, _stream_ptr(stream))
+        _check(st, "mi355_spmv_multi_create_transposed")
+
+    def structure(self, stream=None):
+        """(Apt, Ajt, perm): copies of the plan's CSR structure of A^T and its slot map, as csr_transpose returns them."""
+        Apt = torch.empty(self.n_rows + 1, dtype=self.off_dtype, device=self.device)
+        Ajt = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
+        perm = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        with torch.cuda.device(self.device):
+            st = lib().mi355_spmv_multi_copy_structure(self._h, ptr(Apt), ptr(Ajt), ptr(perm), _stream_ptr(stream))
+        _check(st, "mi355_spmv_multi_copy_structure")
+        return Apt, Ajt, perm
+
+
+def spmm_t(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None):
+    """One-shot Y = A^T X for the k = X.size(1) vectors of a row-major X (n_rows x k; Y is n_cols x k), Ax in A's CSR order:
+    mi355_spmv_multi_transposed_<off>_<val> — create, execute, synchronise the stream, destroy."""
+    _require_device(Ap, Aj, Ax)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if Ax.dtype not in (torch.float32, torch.float64):
+        raise TypeError("Ax must be float32 or float64")
+    if Ax.numel() < nnz or Aj.numel() < nnz or Ap.numel() < n_rows + 1:
+        raise ValueError("operand shorter than the matrix")
+    ldx = _require_matrix(X, "X", n_rows, Ax.dtype)
+    ldy = _require_matrix(Y, "Y", n_cols, Ax.dtype)
+    if X.size(1) != Y.size(1):
+        raise ValueError("X and Y hold different numbers of vectors")
+    _refuse_alias(X, Y)
+    name = "mi355_spmv_multi_transposed_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[Ax.dtype][1])
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
+                                  C.c_void_p(Ax.data_ptr()), C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy,
+                                  X.size(1), _stream_ptr(stream))
+    _check(st, name)
+    return Y
 
 
 def spmm(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None, semiring="plus_times"):

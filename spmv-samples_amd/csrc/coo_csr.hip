@@ -26,6 +26,10 @@
 // gather reads cols[i] or rows[i] by the bit, and vals[i], from the stored arrays.  check_count compares the true
 // expanded count with the caller's before anything is sized by it and stops every later kernel through the same word
 // the validation uses.
+//
+// mi355_spmv_csr_transpose gives the structure of A^T from the CSR structure of A by the same sort with the COLUMN as key
+// and the CSR slot as payload: Apt from the sorted keys, perm = the sorted payload, and Ajt = each slot's
+// row, found in Ap by slot_rows.  Inside a column the slots ascend: the sort is stable.
 #include "common.hpp"
 
 namespace mi355 {
@@ -577,6 +581,131 @@ extern "C" int mi355_spmv_coo_to_csr(int off_type, int val_type, int32_t n_rows,
     return off_type == MI355_OFF_I32
                ? coo::run<int32_t>(L, val_bytes, n_rows, n_cols, uint64_t(nnz), rows, cols, vals, Ap, Aj, Ax, perm, ws, s)
                : coo::run<int64_t>(L, val_bytes, n_rows, n_cols, uint64_t(nnz), rows, cols, vals, Ap, Aj, Ax, perm, ws, s);
+}
+
+// ---- the structure of A^T: a stable sort of the CSR slots by column ------------------------------------------------
+namespace mi355 {
+namespace coo {
+
+constexpr unsigned long long kBadOffsets = ~0ull - 1;   // csr_transpose: Ap is not 0 .. nnz ascending (word[1] names the place)
+
+// word[1] = the first i with Ap[i] out of order: Ap[0] != 0, Ap[i] < Ap[i - 1], or Ap[n_rows] != nnz (i = n_rows);
+// word[0] then stops every later kernel.  Compares only: no offset is used as an address.
+template <typename off_t>
+__global__ void __launch_bounds__(kBlock) validate_offsets(const off_t* __restrict__ Ap, uint32_t n_rows, uint64_t nnz,
+                                                           unsigned long long* word) {
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    for (uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x; i <= n_rows; i += stride) {
+        const bool bad = i == 0 ? Ap[0] != 0 : (Ap[i] < Ap[i - 1] || (i == n_rows && uint64_t(Ap[i]) != nnz));
+        if (bad) {
+            atomicMin(word + 1, (unsigned long long)i);
+            atomicMin(word, kBadOffsets);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) validate_columns(const int32_t* __restrict__ Aj, uint64_t nnz, uint32_t n_cols,
+                                                           unsigned long long* bad) {
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    for (uint64_t k = uint64_t(blockIdx.x) * kBlock + threadIdx.x; k < nnz; k += stride)
+        if (uint32_t(Aj[k]) >= n_cols) atomicMin(bad, (unsigned long long)k);
+}
+
+// perm[t] = the CSR slot behind transposed slot t (the sorted payload; pay == nullptr: the identity, no pass ran) and
+// Ajt[t] = that slot's row: the last r with Ap[r] <= slot (rows without entries are stepped over by the search).
+template <typename off_t>
+__global__ void __launch_bounds__(kBlock) slot_rows(const uint32_t* __restrict__ pay, uint64_t nnz, const off_t* __restrict__ Ap,
+                                                    uint32_t n_rows, int32_t* __restrict__ Ajt, uint32_t* __restrict__ perm,
+                                                    const unsigned long long* bad) {
+    if (*bad != kNoBad) return;
+    const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    for (uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x; t < nnz; t += stride) {
+        const uint64_t p = pay ? pay[t] : t;
+        uint32_t lo = 0, hi = n_rows;           // the first r in (0, n_rows] with Ap[r] > p, minus one
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (uint64_t(Ap[mid + 1]) <= p) lo = mid + 1; else hi = mid;
+        }
+        Ajt[t] = int32_t(lo);
+        perm[t] = uint32_t(p);
+    }
+}
+
+template <typename off_t>
+static int run_transpose(const Layout& L, int32_t n_rows, int32_t n_cols, uint64_t nnz, const off_t* Ap, const int32_t* Aj,
+                         off_t* Apt, int32_t* Ajt, uint32_t* perm, char* ws, hipStream_t s) {
+    auto* bad = reinterpret_cast<unsigned long long*>(ws);   // [0] the validation word, [1] the first offset out of order
+    MI355_HIP_TRY(hipMemsetAsync(bad, 0xff, 2 * sizeof(unsigned long long), s));
+    if (n_rows > 0) MI355_COO_LAUNCH(validate_offsets<off_t>, grid_for(uint64_t(n_rows) + 1), Ap, uint32_t(n_rows), nnz, bad);
+    if (nnz) MI355_COO_LAUNCH(validate_columns, grid_for(nnz), Aj, nnz, uint32_t(n_cols), bad);
+    const uint32_t* keys = nullptr;
+    const uint32_t* pay = nullptr;
+    uint32_t* counts = reinterpret_cast<uint32_t*>(ws + L.o_counts);
+    uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + L.o_bsum);
+    for (int p = 0; p < L.passes; ++p) {        // the column is the key, the slot its payload
+        const int shift = 8 * p;
+        const uint32_t* keys_in = p == 0 ? reinterpret_cast<const uint32_t*>(Aj) : keys;
+        uint32_t* keys_out = reinterpret_cast<uint32_t*>(ws + L.o_keys[p & 1]);
+        uint32_t* pay_out = reinterpret_cast<uint32_t*>(ws + L.o_pay[p & 1]);
+        MI355_COO_LAUNCH(count_digits, unsigned(L.n_tiles), keys_in, nnz, shift, L.n_tiles, counts, bad);
+        MI355_COO_LAUNCH(scan_reduce, unsigned(L.n_scan_blocks), counts, L.n_counts, bsum, bad);
+        MI355_COO_LAUNCH(scan_sums, 1u, bsum, L.n_scan_blocks, bad);
+        MI355_COO_LAUNCH(scan_apply, unsigned(L.n_scan_blocks), counts, L.n_counts, bsum, bad);
+        MI355_COO_LAUNCH(scatter, unsigned(L.n_tiles), keys_in, pay, nnz, shift, L.n_tiles, counts, keys_out, pay_out, bad);
+        keys = keys_out;
+        pay = pay_out;
+    }
+    MI355_COO_LAUNCH(row_offsets<off_t>, grid_for(uint64_t(n_cols) + 1), keys, nnz, uint32_t(n_cols), Apt, bad);
+    if (nnz) MI355_COO_LAUNCH(slot_rows<off_t>, grid_for(nnz), pay, nnz, Ap, uint32_t(n_rows), Ajt, perm, bad);
+    // the one synchronisation: the validation words
+    unsigned long long word[2] = {kNoBad, kNoBad};
+    MI355_HIP_TRY(hipMemcpyAsync(word, bad, sizeof(word), hipMemcpyDeviceToHost, s));
+    MI355_HIP_TRY(hipStreamSynchronize(s));
+    if (word[1] != kNoBad) {
+        const uint64_t i = word[1];
+        off_t at = 0, before = 0;
+        MI355_HIP_TRY(hipMemcpy(&at, Ap + i, sizeof(at), hipMemcpyDeviceToHost));
+        if (i > 0) MI355_HIP_TRY(hipMemcpy(&before, Ap + i - 1, sizeof(before), hipMemcpyDeviceToHost));
+        if (i == 0) set_error("csr_transpose: Ap[0] is %lld, not 0", (long long)at);
+        else if (at < before) set_error("csr_transpose: Ap[%llu] = %lld is below Ap[%llu] = %lld (offsets must ascend)", (unsigned long long)i, (long long)at, (unsigned long long)(i - 1), (long long)before);
+        else set_error("csr_transpose: Ap[%llu] = %lld, the last offset, is not nnz = %llu", (unsigned long long)i, (long long)at, (unsigned long long)nnz);
+        return MI355_SPMV_EINVAL;
+    }
+    if (word[0] != kNoBad) {
+        int32_t c = 0;
+        MI355_HIP_TRY(hipMemcpy(&c, Aj + word[0], sizeof(c), hipMemcpyDeviceToHost));
+        set_error("csr_transpose: entry %llu of Aj is column %d, outside the %d x %d matrix", word[0], c, n_rows, n_cols);
+        return MI355_SPMV_EINVAL;
+    }
+    return MI355_SPMV_OK;
+}
+
+}  // namespace coo
+}  // namespace mi355
+
+extern "C" int mi355_spmv_csr_transpose(int off_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
+                                        const int32_t* Aj, void* Apt, int32_t* Ajt, uint32_t* perm, void* workspace,
+                                        size_t* workspace_bytes, void* stream) {
+    using namespace mi355;
+    const char* const fn = "csr_transpose";
+    set_error("%s", "");
+    if (off_type != MI355_OFF_I32 && off_type != MI355_OFF_I64) { set_error("%s: unknown offset type %d", fn, off_type); return MI355_SPMV_EINVAL; }
+    if (n_rows < 0 || n_cols < 0 || nnz < 0) { set_error("%s: negative size", fn); return MI355_SPMV_EINVAL; }
+    if (off_type == MI355_OFF_I32 && nnz > INT32_MAX) { set_error("%s: nnz does not fit 32-bit offsets (use 64-bit offsets)", fn); return MI355_SPMV_EINVAL; }
+    if (uint64_t(nnz) >= (1ull << 32)) { set_error("%s: 2^32 or more entries (the sort's payload is 32-bit)", fn); return MI355_SPMV_ENOTSUP; }
+    if (nnz > 0 && (n_rows == 0 || n_cols == 0)) { set_error("%s: nnz > 0 but n_rows or n_cols is 0", fn); return MI355_SPMV_EINVAL; }
+    if (!workspace_bytes) { set_error("%s: null workspace_bytes", fn); return MI355_SPMV_EINVAL; }
+    const coo::Layout L = coo::layout(n_cols, uint64_t(nnz));
+    if (!workspace) { *workspace_bytes = L.bytes; return MI355_SPMV_OK; }
+    if (*workspace_bytes < L.bytes) { set_error("%s: workspace of %zu bytes, %zu needed", fn, *workspace_bytes, L.bytes); return MI355_SPMV_EINVAL; }
+    if (!Apt) { set_error("%s: null Apt", fn); return MI355_SPMV_EINVAL; }
+    if (n_rows > 0 && !Ap) { set_error("%s: null Ap", fn); return MI355_SPMV_EINVAL; }
+    if (nnz > 0 && (!Aj || !Ajt || !perm)) { set_error("%s: null Aj, Ajt or perm", fn); return MI355_SPMV_EINVAL; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    return off_type == MI355_OFF_I32
+               ? coo::run_transpose<int32_t>(L, n_rows, n_cols, uint64_t(nnz), static_cast<const int32_t*>(Ap), Aj, static_cast<int32_t*>(Apt), Ajt, perm, ws, s)
+               : coo::run_transpose<int64_t>(L, n_rows, n_cols, uint64_t(nnz), static_cast<const int64_t*>(Ap), Aj, static_cast<int64_t*>(Apt), Ajt, perm, ws, s);
 }
 
 extern "C" int mi355_spmv_coo_symmetric_nnz(int64_t nnz_stored, const int32_t* rows, const int32_t* cols, void* stream,

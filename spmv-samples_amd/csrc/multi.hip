@@ -4,7 +4,9 @@
 // per value type: the multi_<type>.hip units, which include this file with MI355_MULTI_TU set to the value type (the
 // library's build, MI355_MULTI_SPLIT_UNITS; without it this unit instantiates what it launches and stands alone).
 // 16-bit vectors (mi355_spmv_multi_create_half): multi_half_kernels.hpp, instantiated by multi_h16.hip, which includes
-// this file with MI355_MULTI_HALF_TU set.  The slice geometry and the cut are the slice kinds' own, shared with SDDMM:
+// this file with MI355_MULTI_HALF_TU set.  Permuted and transposed objects are made by multi_perm.hip and
+// multi_transposed.hip on an object of this unit (multi_attach_perm) and executed here; their kernels are instantiated by
+// multi_perm_f32.hip / multi_perm_f64.hip, which include this file with MI355_MULTI_PERM_TU set.  The slice geometry and the cut are the slice kinds' own, shared with SDDMM:
 // slice_cut.hpp, slice_cut.inc.  DESIGN.md §3.10, §3.10.1, §3.10.2.
 #include <algorithm>
 #include <new>
@@ -28,6 +30,10 @@ MI355_MULTI_EACH_SEMIRING(MI355_MULTI_DEFINE, MI355_MULTI_TU)
 namespace mi355 {
 MI355_MULTI_HALF_EACH(MI355_MULTI_HALF_DEFINE)
 }  // namespace mi355
+#elif defined(MI355_MULTI_PERM_TU)   // ... or the launch_multi_perm of one value type (multi_perm_f32.hip, multi_perm_f64.hip)
+namespace mi355 {
+MI355_MULTI_PERM_EACH(MI355_MULTI_PERM_DEFINE, MI355_MULTI_PERM_TU)
+}  // namespace mi355
 #else
 
 using namespace mi355;
@@ -41,6 +47,12 @@ struct mi355_spmv_multi {   // the opaque handle of include/mi355_spmv.h
     MultiShape shape;               // what an execute reads (multi_kernels.hpp)
     void* scratch = nullptr;        // carry_row, then carry_val (16-bit vectors: carry_val, tail_val, then carry_row)
     size_t scratch_bytes = 0;
+    // a permuted object (multi_attach_perm): shape.perm, and
+    bool permuted = false;
+    int64_t n_values = 0;           // values of the Ax of an execute (a plain object: nnz)
+    void* held = nullptr;           // the object's copy of perm; a transposed object's perm, Aj and Ap
+    size_t held_bytes = 0;
+    bool owns_structure = false;    // shape.Ap / shape.Aj lie in `held`
 };
 
 namespace {
@@ -187,6 +199,9 @@ int launch_half(const mi355_spmv_multi& m, const void* Ax, const void* X, int64_
 
 template <typename off_t>
 int launch_offsets(const mi355_spmv_multi& m, const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, hipStream_t s) {
+    if (m.permuted)     // fp32 / fp64 under (+, *): multi_attach_perm and set_semiring see to it
+        return m.val_type == MI355_VAL_F64 ? launch_multi_perm<off_t, double>(m.shape, Ax, X, ldx, Y, ldy, k, s)
+                                           : launch_multi_perm<off_t, float>(m.shape, Ax, X, ldx, Y, ldy, k, s);
     switch (m.val_type) {
         case MI355_VAL_F16: return launch_half<off_t, mh::F16>(m, Ax, X, ldx, Y, ldy, k, s);
         case MI355_VAL_BF16: return launch_half<off_t, Bf16>(m, Ax, X, ldx, Y, ldy, k, s);
@@ -218,6 +233,26 @@ int multi_one_shot(const char* who, CreateHow how, int off_type, int mat_type, i
 }
 
 }  // namespace
+
+namespace mi355 {
+
+int multi_attach_perm(mi355_spmv_multi* m, const uint32_t* perm, int64_t n_values, void* held, size_t held_bytes, bool owns_structure) {
+    if (!m || m->permuted || n_values < 0 || (m->shape.nnz > 0 && !perm)) { set_error("multi_attach_perm: bad argument"); return MI355_SPMV_EINVAL; }
+    if (m->mat_type != m->val_type || (m->val_type != MI355_VAL_F32 && m->val_type != MI355_VAL_F64) ||
+        m->semiring != MI355_SEMIRING_PLUS_TIMES) {
+        set_error("multi_attach_perm: a permuted object is fp32 or fp64 under (+, *)");
+        return MI355_SPMV_ENOTSUP;
+    }
+    m->permuted = true;
+    m->shape.perm = perm;
+    m->n_values = n_values;
+    m->held = held; m->held_bytes = held_bytes; m->owns_structure = owns_structure;
+    return MI355_SPMV_OK;
+}
+
+const MultiShape& multi_shape_of(const mi355_spmv_multi* m) { return m->shape; }
+
+}  // namespace mi355
 
 extern "C" {
 
@@ -254,6 +289,10 @@ int mi355_spmv_multi_set_semiring(mi355_spmv_multi* m, int semiring) {
     if (!known_semiring(semiring)) { set_error("multi_set_semiring: unknown semiring %d", semiring); return MI355_SPMV_EINVAL; }
     if (semiring != MI355_SEMIRING_PLUS_TIMES && is_half_matrix(m->val_type)) {
         set_error("multi_set_semiring: 16-bit vectors are built under the (+, *) semiring only");
+        return MI355_SPMV_ENOTSUP;
+    }
+    if (semiring != MI355_SEMIRING_PLUS_TIMES && m->permuted) {
+        set_error("multi_set_semiring: a permuted or transposed object is built under the (+, *) semiring only");
         return MI355_SPMV_ENOTSUP;
     }
     if (semiring != MI355_SEMIRING_PLUS_TIMES && (m->shape.alpha != 1.0 || m->shape.beta != 0.0)) {
@@ -312,7 +351,17 @@ int mi355_spmv_multi_get_info(const mi355_spmv_multi* m, mi355_spmv_multi_info* 
     info->n_slices = m->shape.n_slices;
     info->grid_blocks = slice_grid(m->shape.n_slices);
     info->scratch_bytes = int64_t(m->scratch_bytes);
-    snprintf(info->main_kernel, sizeof(info->main_kernel), is_half_matrix(m->val_type) ? "multi_half_slice_kernel" : "multi_slice_kernel");
+    snprintf(info->main_kernel, sizeof(info->main_kernel), m->permuted                    ? "multi_perm_slice_kernel"
+                                                           : is_half_matrix(m->val_type) ? "multi_half_slice_kernel"
+                                                                                         : "multi_slice_kernel");
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_multi_get_perm_info(const mi355_spmv_multi* m, int64_t* n_values, int64_t* held_bytes, int* owns_structure) {
+    if (!m) { set_error("multi_get_perm_info: null object"); return MI355_SPMV_EINVAL; }
+    if (n_values) *n_values = m->permuted ? m->n_values : m->shape.nnz;
+    if (held_bytes) *held_bytes = int64_t(m->held_bytes);
+    if (owns_structure) *owns_structure = m->owns_structure ? 1 : 0;
     return MI355_SPMV_OK;
 }
 
@@ -321,6 +370,10 @@ int mi355_spmv_multi_destroy(mi355_spmv_multi* m) {
     int st = MI355_SPMV_OK;
     if (m->scratch) {
         const hipError_t e = hipFree(m->scratch);
+        if (e != hipSuccess) { set_error("hipFree -> %s", hipGetErrorString(e)); st = MI355_SPMV_EHIP; }
+    }
+    if (m->held) {
+        const hipError_t e = hipFree(m->held);
         if (e != hipSuccess) { set_error("hipFree -> %s", hipGetErrorString(e)); st = MI355_SPMV_EHIP; }
     }
     delete m;

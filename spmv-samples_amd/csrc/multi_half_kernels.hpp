@@ -88,7 +88,7 @@ struct MultiHalfPolicy {
     using SR = Semiring<MI355_SEMIRING_PLUS_TIMES, float>;
     using Args = MultiHalfArgs<vec_t, mat_t>;
     static constexpr int V = kHalfV;
-    static constexpr bool kValued = true, kMaskCombine = false, kTails = true;
+    static constexpr bool kValued = true, kMaskCombine = false, kTails = true, kPermuted = false;
     __device__ static __forceinline__ float ax(mat_t v) { return widen(v); }
     __device__ static __forceinline__ void load_cols(float (&v)[V], const vec_t* p, int nv, bool vec) { mh::load_cols<vec_t>(v, p, nv, vec); }
     static constexpr bool kFields = true;

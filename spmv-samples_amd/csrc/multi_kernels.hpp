@@ -101,7 +101,7 @@ struct MultiTypedPolicy {
     using SR = Semiring<SRI, val_t>;
     using Args = MultiArgs<val_t>;
     static constexpr int V = 16 / int(sizeof(val_t));
-    static constexpr bool kValued = !PATTERN, kMaskCombine = SRI != MI355_SEMIRING_PLUS_TIMES, kTails = false;
+    static constexpr bool kValued = !PATTERN, kMaskCombine = SRI != MI355_SEMIRING_PLUS_TIMES, kTails = false, kPermuted = false;
     __device__ static __forceinline__ val_t ax(val_t v) { return v; }
     __device__ static __forceinline__ void load_cols(val_t (&v)[V], const val_t* p, int nv, bool vec) {
         mi355::load_cols<val_t, V>(v, p, nv, vec);
@@ -116,6 +116,25 @@ struct MultiTypedPolicy {
 template <typename off_t, typename val_t, int C, int SRI, bool PATTERN>
 __global__ __launch_bounds__(kBlock) void multi_slice_kernel(const MultiArgs<val_t> a, const off_t* __restrict__ Ap) {
     using P = MultiTypedPolicy<val_t, SRI, PATTERN>;
+#include "multi_slice_walk.inc"
+}
+
+// The permuted kernels (mi355_spmv_multi_create_permuted): the typed walk under (+, *) on a valued fp32 /
+// fp64 matrix, with nonzero n's value read as Ax[perm[n]].  perm is the object's own validated 4-byte copy: every index
+// is inside the n_values values of Ax, so the gather cannot leave the caller's array.
+template <typename val_t>
+struct MultiPermArgs : MultiArgs<val_t> {
+    const uint32_t* perm;   // [nnz]
+};
+template <typename val_t>
+struct MultiPermPolicy : MultiTypedPolicy<val_t, MI355_SEMIRING_PLUS_TIMES, false> {
+    using Args = MultiPermArgs<val_t>;
+    static constexpr bool kPermuted = true;
+};
+
+template <typename off_t, typename val_t, int C>
+__global__ __launch_bounds__(kBlock) void multi_perm_slice_kernel(const MultiPermArgs<val_t> a, const off_t* __restrict__ Ap) {
+    using P = MultiPermPolicy<val_t>;
 #include "multi_slice_walk.inc"
 }
 
@@ -150,6 +169,7 @@ struct MultiShape {
     int32_t* carry_row = nullptr;
     void* carry_val = nullptr;
     void* tail_val = nullptr;       // 16-bit vectors only (multi_half_kernels.hpp): [n_slices][carry_ld] fp32
+    const uint32_t* perm = nullptr; // a permuted object only: [nnz] indices into the Ax of an execute, each below n_values
 };
 
 // what both argument structs (MultiArgs, mh::MultiHalfArgs) hold alike, of the object and of one execute's operands
@@ -201,6 +221,33 @@ int launch_multi(const MultiShape& m, const void* Ax, const void* X, int64_t ldx
     return MI355_SPMV_OK;
 }
 
+// the same for a permuted object: the permuted slice passes, then the typed fix-up of (+, *)
+template <typename off_t, typename val_t>
+int launch_multi_perm(const MultiShape& m, const void* Ax, const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t k, hipStream_t s) {
+    if (m.n_slices == 0) return MI355_SPMV_OK;
+    MultiPermArgs<val_t> a;
+    multi_fill_args<MultiPermArgs<val_t>, val_t>(a, m, X, ldx, Y, ldy);
+    a.Ax = static_cast<const val_t*>(Ax);
+    a.perm = m.perm;
+    const off_t* Ap = static_cast<const off_t*>(m.Ap);
+    const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
+    if (const int st = multi_passes<16 / int(sizeof(val_t))>(a, k, [&](auto lanes) {
+            hipLaunchKernelGGL((multi_perm_slice_kernel<off_t, val_t, decltype(lanes)::value>), grid, block, 0, s, a, Ap);
+        }))
+        return st;
+    if (m.n_slices > 1) {
+        const int64_t threads = m.n_slices * k;
+        hipLaunchKernelGGL((multi_fixup_kernel<val_t, MI355_SEMIRING_PLUS_TIMES>), dim3(unsigned((threads + kBlock - 1) / kBlock)), block, 0, s,
+                           m.n_slices, k, m.carry_row, a.carry_val, m.carry_ld, a.Y, ldy, a.alpha);
+        MI355_HIP_TRY(hipGetLastError());
+    }
+    return MI355_SPMV_OK;
+}
+#define MI355_MULTI_PERM_DEFINE(OFF, VAL) \
+    template int launch_multi_perm<OFF, VAL>(const MultiShape&, const void*, const void*, int64_t, void*, int64_t, int32_t, hipStream_t);
+#define MI355_MULTI_PERM_EACH(X, VAL) X(int32_t, VAL) X(int64_t, VAL)
+#define MI355_MULTI_PERM_DECLARE(OFF, VAL) extern MI355_MULTI_PERM_DEFINE(OFF, VAL)
+
 // MI355_MULTI_EACH(X, val_t, SRI): X(off_t, val_t, SRI, PATTERN) for both offset widths, valued and pattern — the four
 // launch_multi (sixteen slice kernels) of one value type under one semiring
 #define MI355_MULTI_EACH(X, VAL, SRI) \
@@ -217,6 +264,16 @@ int launch_multi(const MultiShape& m, const void* Ax, const void* X, int64_t ldx
 MI355_MULTI_EACH_SEMIRING(MI355_MULTI_DECLARE, float)
 MI355_MULTI_EACH_SEMIRING(MI355_MULTI_DECLARE, double)
 MI355_MULTI_EACH_SEMIRING(MI355_MULTI_DECLARE, int32_t)
+MI355_MULTI_PERM_EACH(MI355_MULTI_PERM_DECLARE, float)      // multi_perm_f32.hip, multi_perm_f64.hip
+MI355_MULTI_PERM_EACH(MI355_MULTI_PERM_DECLARE, double)
 #endif
+
+// What the units that make permuted objects (multi_perm.hip, multi_transposed.hip) ask of multi.hip, which defines both.
+// multi_attach_perm turns a new object of mi355_spmv_multi_create into a permuted one: its executes read Ax[perm[n]] for
+// n_values values of Ax.  `held` (device memory of held_bytes bytes that holds perm and, with owns_structure, the object's
+// Ap and Aj too) becomes the object's and is freed by its destroy.  The caller has checked every index of perm.
+int multi_attach_perm(::mi355_spmv_multi* m, const uint32_t* perm, int64_t n_values, void* held, size_t held_bytes,
+                      bool owns_structure);
+const MultiShape& multi_shape_of(const ::mi355_spmv_multi* m);
 
 }  // namespace mi355

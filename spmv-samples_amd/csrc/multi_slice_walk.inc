@@ -13,6 +13,9 @@
 //   kValued, kAxFill           Ax is loaded, converted by P::ax and shuffled; otherwise every entry is kAxFill (one).  A valued
 //                              kernel's kAxFill is what a lane past the slice's last nonzero holds: never used, and kept as
 //                              each family wrote it so that its kernels compile as on record
+//   kPermuted                  (a valued policy) nonzero n's value is a.Ax[a.perm[n]], not a.Ax[n]: the index is loaded
+//                              coalesced next to Aj and the value gathered through it (multi_perm_slice_kernel).  A constant
+//                              under `if constexpr`: the other policies' kernels see the line they always had
 //   kMaskCombine               combine() must not see a masked column (every semiring except (+, *), whose product with
 //                              the 0 that a masked column is loaded as is the identity already)
 //   kTails                     the last piece of a row that began in an earlier slice goes to a.tail_val, not to Y
@@ -48,7 +51,8 @@
         int ie = nr * 2;    // row * 2 + (1 = this nonzero is the last of its row); nr = no nonzero
         if (m < nn) {
             col = a.Aj[n0 + m];
-            if constexpr (P::kValued) ax = P::ax(a.Ax[n0 + m]);
+            if constexpr (P::kPermuted) ax = P::ax(a.Ax[a.perm[n0 + m]]);
+            else if constexpr (P::kValued) ax = P::ax(a.Ax[n0 + m]);
 #include "slice_cut_row.inc"     // leaves lo: the nonzero's row, relative to r0
             ie = lo * 2 + (rel[lo + 1] == m + 1 ? 1 : 0);
         }
