@@ -23,20 +23,7 @@
 
 #include "../../spmv-samples_amd/csrc/multi.hip"
 
-// What csrc/multi_perm.hip uses of the HIP runtime and the stand-in leaves out (multi.hip copies nothing between host and
-// device and has no atomics).  Device memory is host memory here, a stream runs at once, and the lanes of a kernel are
-// fibers of one thread: an atomic is its plain operation.
-enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
-inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) { memcpy(dst, src, bytes); return hipSuccess; }
-inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t) { memcpy(dst, src, bytes); return hipSuccess; }
-inline hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t) { memset(dst, value, bytes); return hipSuccess; }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v) {
-    const unsigned long long old = *p;
-    if (v < old) *p = v;
-    return old;
-}
-
+#include "sim_runtime.hpp"     // what csrc/multi_perm.hip uses of the HIP runtime and the stand-in leaves out
 #include "../../spmv-samples_amd/csrc/multi_perm.hip"
 
 #define SIM_NAME "multi_perm_sim"

@@ -7,5 +7,5 @@
 #                         make -C tests/cpp -f multi_perm_sim.mk multi_perm_sim
 include Makefile
 
-multi_perm_sim: multi_perm_sim.cpp $(MULTI_SRC) $(CSRC)/multi_perm.hip $(SIM_HDRS)
+multi_perm_sim: multi_perm_sim.cpp sim_runtime.hpp $(MULTI_SRC) $(CSRC)/multi_perm.hip $(SIM_HDRS)
 	$(CXX) -std=c++17 -O1 -g -fno-omit-frame-pointer $(SIM_SAN) -Isimt -o $@ $<

@@ -2,7 +2,7 @@
 // kernel source compiles UNCHANGED with the host compiler and executes lane by lane (tests/cpp/multi_sim.cpp).
 //
 //   lanes      every lane of a workgroup is a fiber with a stack of its own, all in one host thread.  A lane runs until
-//              its next collective (__shfl, __shfl_xor, __shfl_up, __ballot, __syncthreads), posts its operand and
+//              its next collective (__shfl, __shfl_xor, __shfl_up, __shfl_down, __ballot, __syncthreads), posts its operand and
 //              yields; when every lane of its wave has arrived the wave goes on.  Width 64.
 //   out of step  every collective records its kind and operand size, and the lanes of a wave are compared after each
 //              exchange: a mismatch, or a lane that has returned while others wait in a collective, ends the program
@@ -13,7 +13,8 @@
 //              (a row far outside any Y of a test), a float as 1.5e16, a double as 1.7e127.
 //   alignment  float4 / double2 are alignas(16): the host's alignment check fires on a 16-byte access to an address
 //              that is not 16-byte aligned.
-// Covered: what csrc/multi.hip and csrc/common.hpp use.  No LDS-staging builtins, no sched_barrier, no atomics.
+// Covered: what csrc/multi.hip, csrc/coo_csr.hip and csrc/common.hpp use.  No LDS-staging builtins, no sched_barrier; the
+// atomics and copies of the units that have them are in tests/cpp/sim_runtime.hpp.
 #pragma once
 
 #include <sys/mman.h>
@@ -78,6 +79,7 @@ inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 inline int min(int a, int b) { return b < a ? b : a; }
 inline int max(int a, int b) { return a < b ? b : a; }
 inline int __clzll(unsigned long long v) { return v ? __builtin_clzll(v) : 64; }
+inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 
 namespace simt {
 
@@ -87,10 +89,10 @@ constexpr size_t kStackBytes = 256 * 1024;
 
 struct Index { unsigned x, y, z; };
 
-enum Kind : uint8_t { kRunning = 0, kShfl, kShflXor, kShflUp, kBallot, kSync };
+enum Kind : uint8_t { kRunning = 0, kShfl, kShflXor, kShflUp, kBallot, kSync, kShflDown };
 inline const char* kind_name(uint8_t k) {
-    static const char* const names[] = {"(no collective)", "__shfl", "__shfl_xor", "__shfl_up", "__ballot", "__syncthreads"};
-    return k < 6 ? names[k] : "?";
+    static const char* const names[] = {"(no collective)", "__shfl", "__shfl_xor", "__shfl_up", "__ballot", "__syncthreads", "__shfl_down"};
+    return k < 7 ? names[k] : "?";
 }
 
 struct Lane {
@@ -336,6 +338,13 @@ inline T __shfl_up(T v, unsigned delta, int width = simt::kWidth) {
     const int lane = simt::g.cur & (simt::kWidth - 1);
     const uint64_t* w = simt::collective(simt::kShflUp, sizeof(T), simt::to_bits(v));
     return simt::from_bits<T>(w[unsigned(lane) < delta ? lane : lane - int(delta)]);
+}
+template <typename T>
+inline T __shfl_down(T v, unsigned delta, int width = simt::kWidth) {
+    (void)width;
+    const int lane = simt::g.cur & (simt::kWidth - 1);
+    const uint64_t* w = simt::collective(simt::kShflDown, sizeof(T), simt::to_bits(v));
+    return simt::from_bits<T>(w[unsigned(lane) + delta >= unsigned(simt::kWidth) ? lane : lane + int(delta)]);
 }
 inline unsigned long long __ballot(int pred) {
     const uint64_t* w = simt::collective(simt::kBallot, sizeof(int), pred ? 1 : 0);

@@ -1,9 +1,11 @@
 // simt_selftest — TEST CODE.  What tests/cpp/simt/hip/hip_runtime.h promises, on kernels of a few lines: the host
 // execution of csrc/multi.hip (multi_sim.cpp) means what it says only while these hold.
-//   simt_selftest semantics   shuffles, ballot, barrier, __shared__, block order, the hipMalloc fill: exit status 0
+//   simt_selftest semantics   shuffles, ballot, barrier, __shared__ and its reuse behind a second barrier, block order, the
+//                             hipMalloc fill:                                                   exit status 0
 //   simt_selftest returned    a lane returns while the others of its wave wait in a collective: exit status 3
 //   simt_selftest kind        one lane calls another collective than the others:                exit status 3
 //   simt_selftest size        one lane's operand has another size:                              exit status 3
+//   simt_selftest down        one lane calls __shfl_down where the others call __shfl_up:       exit status 3
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -14,6 +16,9 @@ __global__ void semantics(int* ok, int* order) {
     bool good = true;
     for (unsigned d = 0; d < 64; d = d ? d * 2 : 1)         // __shfl_up: the lane's own value where lane < d
         good = good && __shfl_up(lane + 100, d) == (unsigned(lane) < d ? lane + 100 : lane + 100 - int(d));
+    for (unsigned d = 0; d < 64; d = d ? d * 2 : 1)         // __shfl_down: lanes 64 - d .. 63 keep their own value
+        good = good && __shfl_down(lane + 100, d) == (unsigned(lane) + d >= 64 ? lane + 100 : lane + 100 + int(d));
+    good = good && __shfl_down(int64_t(lane) << 40, 3) == int64_t(lane < 61 ? lane + 3 : lane) << 40 && __popcll(~0ull) == 64 && __popcll(0) == 0;
     good = good && __shfl(lane, 64 + 3) == 3 && __shfl(lane, 63) == 63 && __shfl(lane, -1) == 63;   // src & 63
     good = good && __shfl_xor(lane, 8) == (lane ^ 8) && __shfl_xor(double(lane), 1) == double(lane ^ 1);
     good = good && __shfl(int64_t(lane) << 40, 5) == int64_t(5) << 40 && __shfl(float(lane) / 4, 9) == 2.25f;
@@ -26,14 +31,40 @@ __global__ void semantics(int* ok, int* order) {
     if (threadIdx.x == 0) order[blockIdx.x] = order[gridDim.x]++;      // blocks run one after another, in order
 }
 
+// block_exclusive_scan of csrc/coo_csr.hip in small: a __shared__ array that lane 63 of each of the four waves writes, all
+// read behind a barrier, and the next call writes again behind a second one
+__device__ inline int sum_before(int own) {
+    __shared__ int wave_sum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = own;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) wave_sum[wave] = inc;
+    __syncthreads();
+    int before = inc - own;
+    for (int w = 0; w < wave; ++w) before += wave_sum[w];
+    __syncthreads();
+    return before;
+}
+
+__global__ void lds_reuse(int* ok) {
+    const int t = threadIdx.x, b = blockIdx.x;
+    const int ones = sum_before(1), ramp = sum_before(t + b), again = sum_before(2);
+    ok[b * blockDim.x + t] = ones == t && ramp == t * (t - 1) / 2 + b * t && again == 2 * t;
+}
+
 __global__ void out_of_step(int mode) {
     const int lane = threadIdx.x & 63;
     if (lane == 7) {
         if (mode == 0) return;
         if (mode == 1) { __ballot(1); return; }
         if (mode == 2) { __shfl(double(lane), 0); return; }
+        if (mode == 3) { __shfl_down(lane, 1); return; }
     }
-    __shfl(lane, 0);
+    if (mode == 3) __shfl_up(lane, 1);
+    else __shfl(lane, 0);
 }
 
 int main(int argc, char** argv) {
@@ -51,10 +82,14 @@ int main(int argc, char** argv) {
             if (!ok[i]) { fprintf(stderr, "a collective's result is wrong in thread %d\n", i); return 1; }
         for (int b = 0; b < 3; ++b)
             if (order[b] != b) { fprintf(stderr, "block %d ran out of order\n", b); return 1; }
+        memset(ok, 0, sizeof(ok));
+        hipLaunchKernelGGL(lds_reuse, dim3(3), dim3(256), 0, nullptr, ok);
+        for (int i = 0; i < 3 * 256; ++i)
+            if (!ok[i]) { fprintf(stderr, "a sum over __shared__ reused behind a second barrier is wrong in thread %d\n", i); return 1; }
         return alignof(float4) == 16 && alignof(double2) == 16 ? 0 : 1;
     }
-    const int mode = !strcmp(what, "returned") ? 0 : !strcmp(what, "kind") ? 1 : !strcmp(what, "size") ? 2 : -1;
-    if (mode < 0) { fprintf(stderr, "usage: simt_selftest semantics | returned | kind | size\n"); return 2; }
+    const int mode = !strcmp(what, "returned") ? 0 : !strcmp(what, "kind") ? 1 : !strcmp(what, "size") ? 2 : !strcmp(what, "down") ? 3 : -1;
+    if (mode < 0) { fprintf(stderr, "usage: simt_selftest semantics | returned | kind | size | down\n"); return 2; }
     hipLaunchKernelGGL(out_of_step, dim3(1), dim3(128), 0, nullptr, mode);
     return 0;   // not reached: the stand-in ends the program with status 3
 }

@@ -49,7 +49,7 @@ def test_the_stand_in_keeps_its_own_promises():
     r = subprocess.run([exe, "semantics"], capture_output=True, text=True, timeout=60, env=sr.child_env())
     assert r.returncode == 0 and r.stderr == "", r.stderr[-2000:]
     for mode, message in (("returned", "lanes have returned while others of the wave wait"),
-                          ("kind", "out of step"), ("size", "out of step")):
+                          ("kind", "out of step"), ("size", "out of step"), ("down", "out of step")):
         r = subprocess.run([exe, mode], capture_output=True, text=True, timeout=60, env=sr.child_env())
         assert r.returncode == 3, (mode, r.returncode, r.stderr[-2000:])
         assert "wave 0, collective 0: " in r.stderr and message in r.stderr and "lane  7" in r.stderr, r.stderr[-2000:]
