@@ -49,6 +49,7 @@ extern "C" {
 #define MI355_SPMV_HAS_SDDMM 1 /* mi355_spmv_sddmm_*: dot(U[r], V[c]) at every stored entry (r, c) of A in one pass over A */
 #define MI355_SPMV_HAS_SDDMM_HALF 1 /* mi355_spmv_sddmm_create_half / _get_types / _half_*: U and V in binary16 / bfloat16, fp32 Ax and out */
 #define MI355_SPMV_HAS_ROW_SOFTMAX 1 /* mi355_spmv_row_softmax_*: softmax over the stored entries of every row (edge softmax), and its gradient */
+#define MI355_SPMV_HAS_ATTENTION 1 /* mi355_spmv_attention_*: O = softmax(scale Q K^T + bias, on the stored entries of A) V in one pass over A */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -867,6 +868,74 @@ int mi355_spmv_row_softmax_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, 
     const float* x, float* out, double scale, void* stream);
 int mi355_spmv_row_softmax_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj,
     const double* x, double* out, double scale, void* stream);
+
+/* ---- Fused sparse attention on the structure of a CSR matrix (MI355_SPMV_HAS_ATTENTION) --------------------------------
+ * The chain mi355_spmv_sddmm -> mi355_spmv_row_softmax -> mi355_spmv_multi in ONE pass over A, for callers who need O
+ * alone (inference, graph-attention layers): nothing of nnz size is written or allocated.
+ *   v[n]      = scale * sum_{j < d} Q[r(n) * ldq + j] * K[Aj[n] * ldk + j]  +  bias[n]      for every stored entry n
+ *   m_r       = max over row r of v;   l_r = sum over row r of exp(v - m_r)
+ *   O[r, :dv] = (sum over row r of exp(v[n] - m_r) * V[Aj[n] * ldv + :dv]) / l_r
+ *   lse[r]    = m_r + log(l_r)                                                  (lse NULL: not written)
+ *   Q         n_rows x d, K n_cols x d, V n_cols x dv, O n_rows x dv: row-major, leading dimensions ldq, ldk >= d and
+ *             ldv, ldo >= dv, all in the object's val_type; bias: nnz values in CSR order, or NULL for none.
+ * scale is 1 after create (the 1 / sqrt(d) of attention: set_scale).  There is no alpha / beta: O and lse are never read.
+ * bias[n] = -inf is a masked edge and contributes exactly +0 (its row of V is not multiplied in).  A row that is empty
+ * or masked whole gets O[r, :dv] = +0 and lse[r] = -inf, never NaN.  A row of one unmasked entry gives O[r] = V[c] and
+ * lse[r] = v exactly.  Columns >= d of Q / K and >= dv of V are never read, columns >= dv of O never written.
+ * Operands may have any alignment (16-byte accesses where the pointer and ld * sizeof allow, element accesses otherwise:
+ * both fill the same registers and give the same bits).  O and lse must not overlap an input or each other; this is not
+ * checked.  With lse a caller who trains forms P[n] = exp(v[n] - lse[r]) from one mi355_spmv_sddmm and runs the backward
+ * call by call.
+ * No atomics: two executes on the same inputs give the same bits.  The bits of O depend on where the step and slice
+ * edges fall in a row (states are combined by step, then by slice, in ascending order), as row softmax's do.
+ * Types: {I32, I64} offsets x {F32, F64} values.  MI355_VAL_I32: MI355_SPMV_ENOTSUP; PATTERN / F16 / BF16 / unknown:
+ * MI355_SPMV_EINVAL.  16-bit operands, a fused backward, heads in one call and dist_* are not built.
+ * The work is cut as the multi-vector kind's (slice_len merge items per wave, lanes_per_slot lanes per nonzero from the
+ * tile of dv).  An execute launches ceil(dv / widest_tile) slice kernels (each recomputes the scores; widest_tile is 32
+ * fp32 / 16 fp64 columns) and, with more than one slice, one fix-up of the rows that cross slices.
+ * Life cycle: create retains Ap / Aj (not copied, not read) and allocates scratch_bytes = O(n_slices * dv_max) on the
+ * current device (its only device call; none when n_rows is 0); execute is asynchronous on `stream`, allocates nothing,
+ * never synchronises and decides nothing from device data (graph-capturable; no launch when n_rows is 0); one stream at a
+ * time per object.  Every argument error — a null pointer, d or dv below 1 or above d_max / dv_max, a leading dimension
+ * below its width, a type word that is not F32 / F64 — is refused before any device call, and the text of the last
+ * error names the argument.                                                                                        */
+typedef struct mi355_spmv_attention mi355_spmv_attention;
+typedef struct mi355_spmv_attention_info {
+    int32_t off_type, val_type;
+    int32_t slice_len;       /* merge items (row ends + nonzeros) per slice = per wave                    */
+    int32_t block_threads;
+    int32_t d_max, dv_max;
+    int32_t widest_tile;     /* columns of dv per slice pass                                              */
+    int32_t passes;          /* slice kernels of an execute at dv = dv_max                                */
+    int32_t lanes_per_slot;  /* C of the first pass at dv = dv_max                                        */
+    int32_t reserved;
+    int64_t n_slices;
+    int64_t grid_blocks;     /* workgroups of a slice kernel                                              */
+    int64_t scratch_bytes;   /* device memory the object owns                                             */
+    char main_kernel[64];
+} mi355_spmv_attention_info;
+int mi355_spmv_attention_create(int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj, int off_type,
+                                int val_type, int32_t d_max, int32_t dv_max, mi355_spmv_attention** out);
+int mi355_spmv_attention_set_scale(mi355_spmv_attention* m, double scale);
+int mi355_spmv_attention_execute(mi355_spmv_attention* m, int32_t d, int32_t dv, const void* Q, int64_t ldq, const void* K,
+                                 int64_t ldk, const void* V, int64_t ldv, const void* bias, void* O, int64_t ldo, void* lse,
+                                 void* stream);
+int mi355_spmv_attention_get_info(const mi355_spmv_attention* m, mi355_spmv_attention_info* info);
+int mi355_spmv_attention_destroy(mi355_spmv_attention* m);
+/* One-shots: create (d_max = d, dv_max = dv), set_scale, execute, synchronise the stream, destroy — the scratch must
+ * outlive the kernels, as the multi-vector one-shots' does.                                                         */
+int mi355_spmv_attention_i32_f32(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* V, int64_t ldv, const float* bias, double scale,
+    float* O, int64_t ldo, float* lse, void* stream);
+int mi355_spmv_attention_i32_f64(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const double* Q, int64_t ldq, const double* K, int64_t ldk, const double* V, int64_t ldv, const double* bias, double scale,
+    double* O, int64_t ldo, double* lse, void* stream);
+int mi355_spmv_attention_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* V, int64_t ldv, const float* bias, double scale,
+    float* O, int64_t ldo, float* lse, void* stream);
+int mi355_spmv_attention_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const double* Q, int64_t ldq, const double* K, int64_t ldk, const double* V, int64_t ldv, const double* bias, double scale,
+    double* O, int64_t ldo, double* lse, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

@@ -61,6 +61,8 @@ EXPORTS = (
     + ["mi355_spmv_sddmm_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
     + ["mi355_spmv_row_softmax_" + n for n in ("create", "set_scale", "execute", "backward", "get_info", "destroy")]
     + ["mi355_spmv_row_softmax_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
+    + ["mi355_spmv_attention_" + n for n in ("create", "set_scale", "execute", "get_info", "destroy")]
+    + ["mi355_spmv_attention_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
     + ["mi355_spmv_csr_transpose"]
     + ["mi355_spmv_multi_" + n for n in ("create_permuted", "create_transposed", "get_perm_info", "copy_structure")]
     + ["mi355_spmv_multi_transposed_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
@@ -118,6 +120,14 @@ class SddmmInfo(C.Structure):
 
 class RowSoftmaxInfo(C.Structure):
     _fields_ = [("off_type", C.c_int32), ("val_type", C.c_int32), ("slice_len", C.c_int32), ("block_threads", C.c_int32),
+                ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("scratch_bytes", C.c_int64),
+                ("main_kernel", C.c_char * 64)]
+
+
+class AttentionInfo(C.Structure):
+    _fields_ = [("off_type", C.c_int32), ("val_type", C.c_int32), ("slice_len", C.c_int32), ("block_threads", C.c_int32),
+                ("d_max", C.c_int32), ("dv_max", C.c_int32), ("widest_tile", C.c_int32), ("passes", C.c_int32),
+                ("lanes_per_slot", C.c_int32), ("reserved", C.c_int32),
                 ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("scratch_bytes", C.c_int64),
                 ("main_kernel", C.c_char * 64)]
 
@@ -246,6 +256,18 @@ def lib():
             for v in ("f32", "f64"):
                 getattr(L, "mi355_spmv_row_softmax_%s_%s" % (o, v)).argtypes = [
                     C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        L.mi355_spmv_attention_create.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32,
+                                                  C.c_int32, C.POINTER(C.c_void_p)]
+        L.mi355_spmv_attention_set_scale.argtypes = [C.c_void_p, C.c_double]
+        L.mi355_spmv_attention_execute.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mi355_spmv_attention_get_info.argtypes = [C.c_void_p, C.POINTER(AttentionInfo)]
+        L.mi355_spmv_attention_destroy.argtypes = [C.c_void_p]
+        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
+            for v in ("f32", "f64"):
+                getattr(L, "mi355_spmv_attention_%s_%s" % (o, v)).argtypes = [
+                    C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                    C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.mi355_spmv_csr_transpose.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]
         L.mi355_spmv_multi_create_permuted.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64,
@@ -1231,6 +1253,114 @@ def row_softmax(n_rows, n_cols, nnz, Ap, Aj, x, out=None, scale=1.0, stream=None
     with torch.cuda.device(Ap.device):
         st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), C.c_void_p(x.data_ptr()),
                                   C.c_void_p(out.data_ptr()), C.c_double(scale), _stream_ptr(stream))
+    _check(st, name)
+    return out
+
+
+def _attention_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, out, lse, bias, d_max=None, dv_max=None):
+    """The operand checks of a fused sparse attention: (d, dv, ldq, ldk, ldv, out, ldo).  Q, K, V and out are 2-D device
+    tensors of the value type with unit stride along their columns (any row stride >= the width: a column slice of a
+    wider tensor is taken as it is); bias and lse are contiguous 1-D tensors of nnz and n_rows values, or None."""
+    ldq, ldk, ldv = _require_matrix(Q, "Q", n_rows, val_dtype), _require_matrix(K, "K", n_cols, val_dtype), _require_matrix(V, "V", n_cols, val_dtype)
+    d, dv = Q.size(1), V.size(1)
+    if K.size(1) != d:
+        raise ValueError("Q and K differ in their columns (%d, %d)" % (d, K.size(1)))
+    if d < 1 or dv < 1:
+        raise ValueError("Q, K and V need at least one column")
+    if (d_max is not None and d > d_max) or (dv_max is not None and dv > dv_max):
+        raise ValueError("d = %d or dv = %d above the plan's d_max = %s, dv_max = %s" % (d, dv, d_max, dv_max))
+    if out is None:
+        out = torch.empty((n_rows, dv), dtype=val_dtype, device=Q.device)
+    ldo = _require_matrix(out, "out", n_rows, val_dtype)
+    if out.size(1) != dv:
+        raise ValueError("out has %d columns, V has %d" % (out.size(1), dv))
+    if lse is not None:
+        _edge_values(lse, "lse", n_rows, val_dtype)
+    if bias is not None:
+        _edge_values(bias, "bias", nnz, val_dtype)
+    return d, dv, ldq, ldk, ldv, out, ldo
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class SparseAttentionPlan:
+    """mi355_spmv_attention_*: fused sparse attention on the structure of A, O = softmax(scale * Q K^T + bias, over the
+    stored entries of every row) V in ONE pass over A — the chain SddmmPlan -> RowSoftmaxPlan -> MultiPlan without the
+    nnz-sized scores and probabilities.  Q is n_rows x d, K n_cols x d, V n_cols x dv (row-major device tensors of
+    val_dtype, float32 or float64; d <= d_max, dv <= dv_max; a row stride above the width is taken as the leading
+    dimension), bias nnz values in CSR order or None; bias[n] = -inf masks an edge.  A row that is empty or masked whole
+    gives zeros and lse = -inf.  out and lse must not overlap an input.  Holds references to Ap and Aj so they outlive the
+    object; creating one allocates O(n_slices * dv_max) bytes of scratch on Ap's device (info()["scratch_bytes"]).
+    Executes are asynchronous and never synchronise."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, d_max, dv_max):
+        _require_device(Ap, Aj)
+        if Aj.dtype != torch.int32:
+            raise TypeError("Aj must be int32")
+        if val_dtype not in (torch.float32, torch.float64):
+            raise TypeError("val_dtype must be float32 or float64")
+        self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
+        self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
+        self.d_max, self.dv_max = d_max, dv_max
+        self._h = C.c_void_p()
+        # (no rows: create makes no device call, and no device need exist)
+        with torch.cuda.device(Ap.device) if n_rows > 0 else contextlib.nullcontext():
+            st = lib().mi355_spmv_attention_create(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
+                                                   OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], d_max, dv_max, C.byref(self._h))
+        _check(st, "mi355_spmv_attention_create")
+
+    def execute(self, Q, K, V, out=None, lse=None, bias=None, stream=None):
+        """out[r] = sum over the row of softmax(scale * Q[r] . K[c] + bias)[n] * V[c]; lse (n_rows values, optional) takes
+        the row's log-sum-exp.  Asynchronous on `stream` (default: torch's current stream); returns out (made when None)."""
+        d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(self.n_rows, self.n_cols, self.nnz, self.val_dtype, Q, K, V, out, lse, bias,
+                                                             self.d_max, self.dv_max)
+        with torch.cuda.device(self.Ap.device):
+            st = lib().mi355_spmv_attention_execute(self._h, d, dv, _ptr(Q), ldq, _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), _ptr(out), ldo,
+                                                    _ptr(lse), _stream_ptr(stream))
+        _check(st, "mi355_spmv_attention_execute")
+        return out
+
+    def set_scale(self, s):
+        """scale for the following executes (default 1): the 1 / sqrt(d) of attention."""
+        _check(lib().mi355_spmv_attention_set_scale(self._h, C.c_double(s)), "mi355_spmv_attention_set_scale")
+
+    def info(self):
+        si = AttentionInfo()
+        _check(lib().mi355_spmv_attention_get_info(self._h, C.byref(si)), "mi355_spmv_attention_get_info")
+        d = {n: getattr(si, n) for n, _ in si._fields_ if n != "reserved"}
+        d["main_kernel"] = d["main_kernel"].decode()
+        return d
+
+    def destroy(self):
+        if self._h:
+            lib().mi355_spmv_attention_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def sparse_attention(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias=None, scale=1.0, out=None, lse=None, stream=None):
+    """One-shot fused sparse attention (mi355_spmv_attention_<off>_<val>): SparseAttentionPlan's execute on a plan made for
+    the call.  Synchronises `stream` before returning: its scratch lives for the call."""
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if not getattr(Q, "is_cuda", False):
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if Q.dtype not in (torch.float32, torch.float64):
+        raise TypeError("Q must be float32 or float64")
+    d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(n_rows, n_cols, nnz, Q.dtype, Q, K, V, out, lse, bias)
+    name = "mi355_spmv_attention_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[Q.dtype][1])
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq,
+                                  _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(out), ldo, _ptr(lse),
+                                  _stream_ptr(stream))
     _check(st, name)
     return out
 
