@@ -50,6 +50,7 @@ extern "C" {
 #define MI355_SPMV_HAS_SDDMM_HALF 1 /* mi355_spmv_sddmm_create_half / _get_types / _half_*: U and V in binary16 / bfloat16, fp32 Ax and out */
 #define MI355_SPMV_HAS_ROW_SOFTMAX 1 /* mi355_spmv_row_softmax_*: softmax over the stored entries of every row (edge softmax), and its gradient */
 #define MI355_SPMV_HAS_ATTENTION 1 /* mi355_spmv_attention_*: O = softmax(scale Q K^T + bias, on the stored entries of A) V in one pass over A */
+#define MI355_SPMV_HAS_ATTENTION_HALF 1 /* mi355_spmv_attention_create_half / _get_types / _half_*: Q, K, V and O in binary16 / bfloat16, fp32 bias, lse and arithmetic */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -889,7 +890,8 @@ int mi355_spmv_row_softmax_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, 
  * No atomics: two executes on the same inputs give the same bits.  The bits of O depend on where the step and slice
  * edges fall in a row (states are combined by step, then by slice, in ascending order), as row softmax's do.
  * Types: {I32, I64} offsets x {F32, F64} values.  MI355_VAL_I32: MI355_SPMV_ENOTSUP; PATTERN / F16 / BF16 / unknown:
- * MI355_SPMV_EINVAL.  16-bit operands, a fused backward, heads in one call and dist_* are not built.
+ * MI355_SPMV_EINVAL.  16-bit Q, K, V and O under fp32 everything else are an object of their own
+ * (mi355_spmv_attention_create_half, below).  A fused backward, heads in one call and dist_* are not built.
  * The work is cut as the multi-vector kind's (slice_len merge items per wave, lanes_per_slot lanes per nonzero from the
  * tile of dv).  An execute launches ceil(dv / widest_tile) slice kernels (each recomputes the scores; widest_tile is 32
  * fp32 / 16 fp64 columns) and, with more than one slice, one fix-up of the rows that cross slices.
@@ -936,6 +938,43 @@ int mi355_spmv_attention_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, co
 int mi355_spmv_attention_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
     const double* Q, int64_t ldq, const double* K, int64_t ldk, const double* V, int64_t ldv, const double* bias, double scale,
     double* O, int64_t ldo, double* lse, void* stream);
+
+/* ---- Fused sparse attention with 16-bit Q, K, V and O (MI355_SPMV_HAS_ATTENTION_HALF) ----------------------------------
+ * For callers who keep features in 16 bits (mi355_spmv_multi_create_half, mi355_spmv_sddmm_create_half): no widening of
+ * Q, K, V and no narrowing of O around the fused call.  The arithmetic is the fp32 object's, unchanged:
+ *   Q, K, V, O   in ONE 16-bit type, vec_type = MI355_VAL_F16 or MI355_VAL_BF16 (2-byte elements; ld* in elements)
+ *   bias, lse    float; scale, the scores, the (m, l, acc) states, the scratch and every operation are fp32
+ * Every stored value is widened exactly.  An element of O is rounded to the 16-bit type exactly ONCE, from the fp32
+ * acc / l, to nearest even — also in a row that crosses slices: the slices leave fp32 states and the fix-up narrows.
+ * Masked edges, empty and whole-masked rows (O = +0, lse = -inf), "one live entry gives O[r] = V[c] bit for bit and
+ * lse[r] = v", two executes giving the same bits, any ld* and any alignment hold as above (a row is 16-byte aligned when
+ * the pointer and ld * 2 allow; both access paths fill the same registers).  No atomics, nothing of nnz size, nothing
+ * decided from device data (graph-capturable).
+ * A lane's 16 bytes are EIGHT columns: widest_tile = 64, lanes_per_slot from ceil(min(dv_max, 64) / 8), an execute
+ * launches ceil(dv / 64) slice kernels.  info reports val_type = MI355_VAL_F32 and main_kernel =
+ * "attention_half_slice_kernel"; the type of Q, K, V and O is get_types' vec_type (which equals val_type on an object
+ * of mi355_spmv_attention_create).  The object is the same: set_scale, execute, get_info and destroy serve both.
+ * create_half: vec_type outside {F16, BF16} is MI355_SPMV_EINVAL ("vec_type" in the text); every other check is
+ * create's, before any device call, and *out stays NULL.
+ * Out of scope: an fp32 O under 16-bit inputs, mixed Q / K / V types, a 16-bit bias or lse, fp8, the fused backward,
+ * heads in one call, dist_*, harness labels, an autograd.Function.                                                  */
+int mi355_spmv_attention_create_half(mi355_spmv_attention** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols,
+                                     int64_t nnz, const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max);
+int mi355_spmv_attention_get_types(const mi355_spmv_attention* m, int* val_type, int* vec_type);
+/* One-shots (Q, K, V, O: binary16 / bfloat16 as stored): create_half (d_max = d, dv_max = dv), set_scale, execute,
+ * synchronise the stream, destroy.                                                                                  */
+int mi355_spmv_attention_half_i32_f16(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
+    void* O, int64_t ldo, float* lse, void* stream);
+int mi355_spmv_attention_half_i32_bf16(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
+    void* O, int64_t ldo, float* lse, void* stream);
+int mi355_spmv_attention_half_i64_f16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
+    void* O, int64_t ldo, float* lse, void* stream);
+int mi355_spmv_attention_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
+    void* O, int64_t ldo, float* lse, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

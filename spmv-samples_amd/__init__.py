@@ -15,12 +15,12 @@ Contents (only what the hot path needs):
                MultiPlan / spmm / spmm_pattern: Y = A X for k vectors in one pass over A, over a semiring; narrow_values: fp32 -> fp16 / bf16 matrix values;
                SddmmPlan / sddmm / sddmm_half: dot(U[r], V[c]) at every stored entry (r, c) of A in one pass over A, U and V in fp32 / fp64 or in 16 bits;
                RowSoftmaxPlan / row_softmax: softmax over the stored entries of every row, and its gradient;
-               SparseAttentionPlan / sparse_attention: O = softmax(Q K^T on A) V fused into one pass over A;
+               SparseAttentionPlan / sparse_attention / sparse_attention_half: O = softmax(Q K^T on A) V fused into one pass over A, Q, K, V and O in fp32 / fp64 or in 16 bits;
                csr_transpose / MultiPlan(perm=) / TransposedMultiPlan / spmm_t: Y = A^T X with Ax read in place through a slot map)
     synth.py   seeded synthetic CSR matrices (stand-ins for the BASELINE configs)
     dist.py    row-block sharding + allgatherv(y) for one process per GPU
     load.py    ctypes binding of the Matrix Market loader (include/mi355_load.h, host/load.hpp)
 """
 from . import capi, dist, load, synth  # noqa: F401
-from .capi import (DistPlan, Functor, MultiPlan, Plan, PlanShape, RowSoftmaxPlan, SddmmPlan, SparseAttentionPlan, sparse_attention, coo_symmetric_nnz, coo_to_csr, spmm,  # noqa: F401
+from .capi import (DistPlan, Functor, MultiPlan, Plan, PlanShape, RowSoftmaxPlan, SddmmPlan, SparseAttentionPlan, sparse_attention, sparse_attention_half, coo_symmetric_nnz, coo_to_csr, spmm,  # noqa: F401
                    spmv, narrow_values, row_softmax, TransposedMultiPlan, csr_transpose, spmm_t, sddmm, sddmm_half, spmm_pattern, spmv_genl, spmv_mixed, spmv_pattern)

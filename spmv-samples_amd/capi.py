@@ -63,6 +63,8 @@ EXPORTS = (
     + ["mi355_spmv_row_softmax_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
     + ["mi355_spmv_attention_" + n for n in ("create", "set_scale", "execute", "get_info", "destroy")]
     + ["mi355_spmv_attention_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
+    + ["mi355_spmv_attention_create_half", "mi355_spmv_attention_get_types"]
+    + ["mi355_spmv_attention_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
     + ["mi355_spmv_csr_transpose"]
     + ["mi355_spmv_multi_" + n for n in ("create_permuted", "create_transposed", "get_perm_info", "copy_structure")]
     + ["mi355_spmv_multi_transposed_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
@@ -268,6 +270,12 @@ def lib():
                 getattr(L, "mi355_spmv_attention_%s_%s" % (o, v)).argtypes = [
                     C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                     C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.mi355_spmv_attention_create_half.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
+                                                       C.c_void_p, C.c_int32, C.c_int32]
+        L.mi355_spmv_attention_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        for o in ("i32", "i64"):
+            for v in ("f16", "bf16"):
+                getattr(L, "mi355_spmv_attention_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_attention_%s_f32" % o).argtypes
         L.mi355_spmv_csr_transpose.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]
         L.mi355_spmv_multi_create_permuted.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64,
@@ -1257,11 +1265,13 @@ def row_softmax(n_rows, n_cols, nnz, Ap, Aj, x, out=None, scale=1.0, stream=None
     return out
 
 
-def _attention_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, out, lse, bias, d_max=None, dv_max=None):
+def _attention_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, out, lse, bias, d_max=None, dv_max=None, vec_dtype=None):
     """The operand checks of a fused sparse attention: (d, dv, ldq, ldk, ldv, out, ldo).  Q, K, V and out are 2-D device
-    tensors of the value type with unit stride along their columns (any row stride >= the width: a column slice of a
-    wider tensor is taken as it is); bias and lse are contiguous 1-D tensors of nnz and n_rows values, or None."""
-    ldq, ldk, ldv = _require_matrix(Q, "Q", n_rows, val_dtype), _require_matrix(K, "K", n_cols, val_dtype), _require_matrix(V, "V", n_cols, val_dtype)
+    tensors of vec_dtype (the value type when None) with unit stride along their columns (any row stride >= the width: a
+    column slice of a wider tensor is taken as it is); bias and lse are contiguous 1-D tensors of nnz and n_rows values of
+    the value type, or None."""
+    vec_dtype = val_dtype if vec_dtype is None else vec_dtype
+    ldq, ldk, ldv = _require_matrix(Q, "Q", n_rows, vec_dtype), _require_matrix(K, "K", n_cols, vec_dtype), _require_matrix(V, "V", n_cols, vec_dtype)
     d, dv = Q.size(1), V.size(1)
     if K.size(1) != d:
         raise ValueError("Q and K differ in their columns (%d, %d)" % (d, K.size(1)))
@@ -1270,8 +1280,8 @@ def _attention_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, out, lse, bias,
     if (d_max is not None and d > d_max) or (dv_max is not None and dv > dv_max):
         raise ValueError("d = %d or dv = %d above the plan's d_max = %s, dv_max = %s" % (d, dv, d_max, dv_max))
     if out is None:
-        out = torch.empty((n_rows, dv), dtype=val_dtype, device=Q.device)
-    ldo = _require_matrix(out, "out", n_rows, val_dtype)
+        out = torch.empty((n_rows, dv), dtype=vec_dtype, device=Q.device)
+    ldo = _require_matrix(out, "out", n_rows, vec_dtype)
     if out.size(1) != dv:
         raise ValueError("out has %d columns, V has %d" % (out.size(1), dv))
     if lse is not None:
@@ -1293,29 +1303,45 @@ class SparseAttentionPlan:
     dimension), bias nnz values in CSR order or None; bias[n] = -inf masks an edge.  A row that is empty or masked whole
     gives zeros and lse = -inf.  out and lse must not overlap an input.  Holds references to Ap and Aj so they outlive the
     object; creating one allocates O(n_slices * dv_max) bytes of scratch on Ap's device (info()["scratch_bytes"]).
-    Executes are asynchronous and never synchronise."""
+    Executes are asynchronous and never synchronise.
+    vec_dtype=torch.float16 / torch.bfloat16 (mi355_spmv_attention_create_half; val_dtype must be float32): Q, K, V and out
+    are held in that type; bias, lse, the scale and every operation stay float32, every stored value is widened exactly and
+    an element of out is rounded to vec_dtype once.  plan.vec_dtype is the type of Q, K, V and out (val_dtype without the
+    argument)."""
 
-    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, d_max, dv_max):
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, d_max, dv_max, vec_dtype=None):
         _require_device(Ap, Aj)
         if Aj.dtype != torch.int32:
             raise TypeError("Aj must be int32")
         if val_dtype not in (torch.float32, torch.float64):
             raise TypeError("val_dtype must be float32 or float64")
+        if vec_dtype is not None:
+            if vec_dtype not in MAT_TYPES:
+                raise TypeError("vec_dtype must be float16 or bfloat16 (or None: Q, K, V and out in val_dtype)")
+            if val_dtype != torch.float32:
+                raise TypeError("vec_dtype needs val_dtype float32 (16-bit Q, K, V and out under float32 bias and lse)")
         self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
         self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
+        self.vec_dtype = val_dtype if vec_dtype is None else vec_dtype
         self.d_max, self.dv_max = d_max, dv_max
         self._h = C.c_void_p()
         # (no rows: create makes no device call, and no device need exist)
         with torch.cuda.device(Ap.device) if n_rows > 0 else contextlib.nullcontext():
-            st = lib().mi355_spmv_attention_create(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
-                                                   OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], d_max, dv_max, C.byref(self._h))
-        _check(st, "mi355_spmv_attention_create")
+            if vec_dtype is None:
+                st, name = lib().mi355_spmv_attention_create(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
+                                                             OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], d_max, dv_max,
+                                                             C.byref(self._h)), "mi355_spmv_attention_create"
+            else:
+                st, name = lib().mi355_spmv_attention_create_half(C.byref(self._h), OFF_TYPES[Ap.dtype][0], MAT_TYPES[vec_dtype][0], n_rows,
+                                                                  n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d_max,
+                                                                  dv_max), "mi355_spmv_attention_create_half"
+        _check(st, name)
 
     def execute(self, Q, K, V, out=None, lse=None, bias=None, stream=None):
         """out[r] = sum over the row of softmax(scale * Q[r] . K[c] + bias)[n] * V[c]; lse (n_rows values, optional) takes
         the row's log-sum-exp.  Asynchronous on `stream` (default: torch's current stream); returns out (made when None)."""
         d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(self.n_rows, self.n_cols, self.nnz, self.val_dtype, Q, K, V, out, lse, bias,
-                                                             self.d_max, self.dv_max)
+                                                             self.d_max, self.dv_max, self.vec_dtype)
         with torch.cuda.device(self.Ap.device):
             st = lib().mi355_spmv_attention_execute(self._h, d, dv, _ptr(Q), ldq, _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), _ptr(out), ldo,
                                                     _ptr(lse), _stream_ptr(stream))
@@ -1357,6 +1383,27 @@ def sparse_attention(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias=None, scale=1.0,
         raise TypeError("Q must be float32 or float64")
     d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(n_rows, n_cols, nnz, Q.dtype, Q, K, V, out, lse, bias)
     name = "mi355_spmv_attention_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[Q.dtype][1])
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq,
+                                  _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(out), ldo, _ptr(lse),
+                                  _stream_ptr(stream))
+    _check(st, name)
+    return out
+
+
+def sparse_attention_half(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias=None, scale=1.0, out=None, lse=None, stream=None):
+    """One-shot fused sparse attention on 16-bit Q, K, V and out (mi355_spmv_attention_half_<off>_<f16|bf16>):
+    sparse_attention's arguments with Q, K, V (and out) in one of float16 / bfloat16, bias and lse in float32.  Synchronises
+    `stream` before returning: its scratch lives for the call."""
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if not getattr(Q, "is_cuda", False):
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if Q.dtype not in MAT_TYPES:
+        raise TypeError("Q must be float16 or bfloat16")
+    d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(n_rows, n_cols, nnz, torch.float32, Q, K, V, out, lse, bias, vec_dtype=Q.dtype)
+    name = "mi355_spmv_attention_half_%s_%s" % (OFF_TYPES[Ap.dtype][1], MAT_TYPES[Q.dtype][1])
     with torch.cuda.device(Ap.device):
         st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq,
                                   _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(out), ldo, _ptr(lse),

@@ -31,7 +31,10 @@
 //                            monoid — tails in slice order, then the ending slice's head — and writes O[r] = acc / l;
 //                            column 0 writes lse[r].
 //
-// dv above the widest tile (32 fp32 / 16 fp64 columns): ceil(dv / widest) launches of the slice kernel inside the one
+// Q, K, V and O in 16 bits under fp32 bias, lse, scale, states and arithmetic (mi355_spmv_attention_create_half, §3.15.1):
+// the same object and the same walk (attention_slice_walk.inc) in a kernel of its own, attention_half_kernel.hpp.
+//
+// dv above the widest tile (32 fp32 / 16 fp64 / 64 16-bit columns): ceil(dv / widest) launches of the slice kernel inside the one
 // execute.  Each recomputes the scores (the same bits: the score does not depend on the tile); only the first stores lse
 // and the pieces' (row, m, l).  d is unbounded: the tile loop.
 // No atomics, no finish pass, nothing of nnz size written, the host decides nothing from device data: an execute launches
@@ -45,6 +48,7 @@
 
 struct mi355_spmv_attention {       // the opaque handle of include/mi355_spmv.h
     int off_type = 0, val_type = 0;
+    int vec_type = 0;               // the type of Q, K, V and O: val_type, or F16 / BF16 under F32 everything else (create_half)
     int32_t n_rows = 0, n_cols = 0;
     int64_t nnz = 0;
     const void* Ap = nullptr;
@@ -168,251 +172,29 @@ __device__ __forceinline__ void attn_reduce_slots(val_t& m, val_t& l, val_t (&ac
 // C = lanes per nonzero slot (16-byte column groups of this pass's tile of dv); the wave holds S = 64 / C slots
 template <typename off_t, typename val_t, int C>
 __global__ __launch_bounds__(kBlock) void attention_slice_kernel(const AttnArgs<val_t> a, const off_t* __restrict__ Ap) {
+    using acc_t = val_t;                            // what attention_slice_walk.inc asks its includer
     constexpr int W = 16 / int(sizeof(val_t));      // columns of a lane per tile
     constexpr int S = kWave / C;
     constexpr val_t kNegInf = -std::numeric_limits<val_t>::infinity();
     constexpr bool kCutCarriedIn = true, kCutKeepsR1 = true;        // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = -1;
 #include "slice_cut.inc"            // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
-
-    const bool first_pass = a.col_begin == 0;
-    const bool biased = a.bias != nullptr;
-    const int nv = min(max(a.cols - c * W, 0), W);
-    // the row carried in ends here with nonzeros of its own (a slice inside one row is a tail; a row whose last nonzero
-    // was the slice before's last item has nothing here)
-    const bool has_head = carried_in && nr >= 1 && rel[1] >= 1 && rel[1] <= nn;
-
-    // per-slot state of the open row (the row whose nonzeros are not all seen yet)
-    val_t m_o = kNegInf, l_o = val_t(0), acc[W];
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[j] = val_t(0);
-    int open_i = -1;        // that row, relative to r0; -1 = none (the state is the identity)
-    int holder = -1;        // >= 0: the state is not the identity in this slot only; -2: spread over the slots
-
-    for (int base = 0; base < nn; base += kWave) {
-        // 64 nonzeros, one per lane, coalesced; each lane finds its nonzero's row in the slice's offsets
-        const int m = base + lane;
-        int32_t col = 0;
-        val_t bias = val_t(0);
-        int ie = nr * 2;    // row * 2 + (1 = this nonzero is the last of its row); nr = no nonzero
-        if (m < nn) {
-            col = a.Aj[n0 + m];
-            if (biased) bias = a.bias[n0 + m];
-#include "slice_cut_row.inc"     // leaves lo: the nonzero's row, relative to r0
-            ie = lo * 2 + (rel[lo + 1] == m + 1 ? 1 : 0);
-        }
-        const int left = nn - base;
-        const int steps = slice_group_steps<C>(left);
-        for (int t = 0; t < steps; ++t) {
-            // slot s takes nonzero t * S + s of the 64
-            int32_t col_s = col;
-            val_t bias_s = bias;
-            int ie_s = ie;
-            if constexpr (C > 1) {
-                const int src = t * S + s;
-                col_s = __shfl(col, src);
-                bias_s = __shfl(bias, src);
-                ie_s = __shfl(ie, src);
-            }
-            const int i_s = ie_s >> 1;
-            const bool live = i_s < nr;
-
-            // the score: SDDMM's tile loop over d, then a fixed tree over the slot's C lanes
-            val_t part = val_t(0);
-            if (live) {
-                const val_t* qp = a.Q + (r0 + i_s) * a.ldq + c * W;
-                const val_t* kp = a.K + int64_t(col_s) * a.ldk + c * W;
-                for (int32_t cb = 0; cb < a.d; cb += C * W) {       // the tiles of d: the same register all along
-                    const int nd = min(max(a.d - cb - c * W, 0), W);
-                    if (nd > 0) {
-                        val_t q[W], k[W];
-                        load_cols<val_t, W>(q, qp + cb, nd, a.q_vec != 0);
-                        load_cols<val_t, W>(k, kp + cb, nd, a.k_vec != 0);
-#pragma unroll
-                        for (int j = 0; j < W; ++j) part = attn_fma(q[j], k[j], part);
-                    }
-                }
-            }
-#pragma unroll
-            for (int dd = 1; dd < C; dd <<= 1) part += __shfl_xor(part, dd);
-            val_t v = kNegInf;
-            val_t xv[W];
-#pragma unroll
-            for (int j = 0; j < W; ++j) xv[j] = val_t(0);
-            if (live) {
-                v = a.scale * part;
-                if (biased) v = v + bias_s;
-                // (a masked edge contributes +0 whatever its row of V holds)
-                if (v != kNegInf) load_cols<val_t, W>(xv, a.V + int64_t(col_s) * a.ldv + a.col_begin + c * W, nv, a.v_vec != 0);
-            }
-
-            const int i_first = __shfl(ie_s, 0) >> 1;
-            const int ie_last = __shfl(ie_s, kWave - 1);
-            if (i_first == (ie_last >> 1) && !(ie_last & 1)) {
-                // every slot is inside one row, and the row goes on: the entry joins its slot's state, one exp
-                const bool up = v > m_o;
-                const val_t low = up ? m_o : v;
-                const val_t f = low == kNegInf ? val_t(0) : attn_exp_diff(up ? m_o - v : v - m_o);
-                const val_t e = up ? f : val_t(1), ev = v == kNegInf ? val_t(0) : up ? val_t(1) : f;
-                l_o = l_o * e + ev;
-#pragma unroll
-                for (int j = 0; j < W; ++j) acc[j] = acc[j] * e + ev * xv[j];
-                if (up) m_o = v;
-                open_i = i_first;
-                holder = -2;
-                continue;
-            }
-            // a row ends in this step (or the slice does).  The open row's state, folded once, joins slot 0, whose
-            // nonzero is the next of that row.
-            const bool joins = open_i >= 0 && s == 0;
-            if (open_i >= 0) {
-                if (holder >= 0) {
-                    m_o = __shfl(m_o, holder * C + c);
-                    l_o = __shfl(l_o, holder * C + c);
-#pragma unroll
-                    for (int j = 0; j < W; ++j) acc[j] = __shfl(acc[j], holder * C + c);
-                } else {
-                    attn_reduce_slots<val_t, W, C>(m_o, l_o, acc);
-                }
-            }
-            // the runs of one row over the slots, and each run's maximum M in every one of its lanes
-            const int i_prev = __shfl_up(i_s, C);
-            const bool head = s == 0 || i_prev != i_s;
-            const unsigned long long heads = __ballot(head && c == 0);
-            const int start = 63 - __clzll(heads & (~0ull >> (63 - lane)));   // lane c == 0 of the slot that starts this run
-            const int behind = lane - c + C;
-            const unsigned long long later = behind >= kWave ? 0ull : heads >> behind;
-            const int end = later ? behind + __builtin_ctzll(later) - C : kWave - C;     // lane c == 0 of its last slot
-            val_t mx = joins && m_o > v ? m_o : v;
-#pragma unroll
-            for (int dd = C; dd < kWave; dd <<= 1) {
-                const val_t o = __shfl_up(mx, dd);
-                if (lane - c - dd >= start && o > mx) mx = o;
-            }
-            const val_t M = __shfl(mx, end + c);
-            // one exp per entry; the open row's state is rescaled into slot 0
-            const val_t e = attn_side(v, M);
-            val_t lp = e, p[W];
-#pragma unroll
-            for (int j = 0; j < W; ++j) p[j] = e * xv[j];
-            if (joins) {
-                const val_t eo = attn_side(m_o, M);
-                lp = l_o * eo + lp;
-#pragma unroll
-                for (int j = 0; j < W; ++j) p[j] = acc[j] * eo + p[j];
-            }
-            m_o = kNegInf;
-            l_o = val_t(0);
-#pragma unroll
-            for (int j = 0; j < W; ++j) acc[j] = val_t(0);
-            // the segmented inclusive sum scan of the multi-vector walk, l beside the W columns
-#pragma unroll
-            for (int dd = C; dd < kWave; dd <<= 1) {
-                const val_t ol = __shfl_up(lp, dd);
-                const bool in_run = lane - c - dd >= start;
-                if (in_run) lp = lp + ol;
-#pragma unroll
-                for (int j = 0; j < W; ++j) {
-                    const val_t o = __shfl_up(p[j], dd);
-                    if (in_run) p[j] = p[j] + o;
-                }
-            }
-            if (live && lane - c == end && (ie_s & 1)) {
-                if (i_s == 0 && carried_in) {
-                    // the HEAD piece: the state as computed, for the fix-up (whole tiles fit carry_ld)
-                    val_t* hv = a.sc.acc + (w * 2 + 0) * a.sc.carry_ld + a.col_begin + c * W;
-#pragma unroll
-                    for (int j = 0; j < W; ++j) hv[j] = p[j];
-                    if (c == 0 && first_pass) {
-                        a.sc.ml[(w * 2 + 0) * 2 + 0] = M;
-                        a.sc.ml[(w * 2 + 0) * 2 + 1] = lp;
-                    }
-                } else {
-                    const int64_t r = r0 + i_s;
-                    if (nv > 0) {
-                        val_t o[W];
-#pragma unroll
-                        for (int j = 0; j < W; ++j) o[j] = attn_out(p[j], lp);
-                        store_cols<val_t, W>(o, a.O + r * a.ldo + a.col_begin + c * W, nv, a.o_vec != 0);
-                    }
-                    if (c == 0 && first_pass && a.lse) a.lse[r] = attn_lse(M, lp);
-                }
-            }
-            // the last nonzero of the step: if its row goes on, its run's state is the new open state
-            const int lv = min(S - 1, left - t * S - 1);
-            const int ie_lv = __shfl(ie_s, lv * C);
-            if (!(ie_lv & 1)) {
-                open_i = ie_lv >> 1;
-                holder = lv;
-                if (s == lv) {
-                    m_o = M;
-                    l_o = lp;
-#pragma unroll
-                    for (int j = 0; j < W; ++j) acc[j] = p[j];
-                }
-            } else {
-                open_i = -1;
-                holder = -1;
-            }
-        }
-    }
-
-    // the TAIL piece: what this slice holds of a row that ends in a later one
-    if (open_i >= 0) {
-        if (holder >= 0) {
-            m_o = __shfl(m_o, holder * C + c);
-            l_o = __shfl(l_o, holder * C + c);
-#pragma unroll
-            for (int j = 0; j < W; ++j) acc[j] = __shfl(acc[j], holder * C + c);
-        } else {
-            attn_reduce_slots<val_t, W, C>(m_o, l_o, acc);
-        }
-        if (s == 0) {
-            val_t* tv = a.sc.acc + (w * 2 + 1) * a.sc.carry_ld + a.col_begin + c * W;      // (carry_ld covers whole tiles)
-#pragma unroll
-            for (int j = 0; j < W; ++j) tv[j] = acc[j];
-        }
-    }
-    if (lane == 0 && first_pass) {
-        a.sc.row[w * 2 + 0] = has_head ? int32_t(r0) : -1;
-        a.sc.row[w * 2 + 1] = open_i >= 0 ? int32_t(r0 + open_i) : -1;
-        if (open_i >= 0) {
-            a.sc.ml[(w * 2 + 1) * 2 + 0] = m_o;
-            a.sc.ml[(w * 2 + 1) * 2 + 1] = l_o;
-        }
-    }
-
-    // empty rows whose end lies in this slice: O = +0 and lse = -inf; a row with nonzeros is stored where its last one is
-    // (and a row carried in has nonzeros: an empty row is never a piece)
-    if (nv > 0 || (c == 0 && first_pass && a.lse)) {
-        val_t none[W];
-#pragma unroll
-        for (int j = 0; j < W; ++j) none[j] = val_t(0);
-        for (int64_t r = r0 + s; r < r1; r += S) {
-            if (Ap[r] == Ap[r + 1]) {
-                if (nv > 0) store_cols<val_t, W>(none, a.O + r * a.ldo + a.col_begin + c * W, nv, a.o_vec != 0);
-                if (c == 0 && first_pass && a.lse) a.lse[r] = kNegInf;
-            }
-        }
-    }
+#include "attention_slice_walk.inc"     // the slice's nonzeros, 64 at a time, and its empty rows
 }
 
-// one thread per (slice, column): the first slice that carries a row folds the row's pieces in slice order — the tails,
-// then the head of the slice the row ends in — and writes the row of O; column 0 writes lse
-template <typename val_t>
-__global__ __launch_bounds__(kBlock) void attention_fixup_kernel(int64_t n_slices, int32_t dv, const AttnScratch<val_t> sc, val_t* __restrict__ O,
-                                                                 int64_t ldo, val_t* __restrict__ lse) {
-    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-    const int64_t t = gid / dv;
-    const int j = int(gid % dv);
-    if (t >= n_slices) return;
-    const int32_t r = sc.row[t * 2 + 1];
-    if (r < 0 || (t > 0 && sc.row[(t - 1) * 2 + 1] == r)) return;
-    val_t m = sc.ml[(t * 2 + 1) * 2], l = sc.ml[(t * 2 + 1) * 2 + 1], acc = sc.acc[(t * 2 + 1) * sc.carry_ld + j];
+// the fix-up's thread of (slice t, column j): if t is the first slice that carries a row, that row and its state folded
+// over the row's pieces in slice order — the tails, then the head of the slice the row ends in; otherwise false
+template <typename acc_t>
+__device__ __forceinline__ bool attn_fixup_fold(int64_t n_slices, const AttnScratch<acc_t>& sc, int64_t t, int j, int32_t& r, acc_t& m, acc_t& l,
+                                                acc_t& acc) {
+    if (t >= n_slices) return false;
+    r = sc.row[t * 2 + 1];
+    if (r < 0 || (t > 0 && sc.row[(t - 1) * 2 + 1] == r)) return false;
+    m = sc.ml[(t * 2 + 1) * 2]; l = sc.ml[(t * 2 + 1) * 2 + 1]; acc = sc.acc[(t * 2 + 1) * sc.carry_ld + j];
     const auto fold = [&](int64_t piece) {      // (m, l, acc) + the piece's state, the piece being the later side
-        const val_t m2 = sc.ml[piece * 2], l2 = sc.ml[piece * 2 + 1], a2 = sc.acc[piece * sc.carry_ld + j];
-        const val_t M = m < m2 ? m2 : m;
-        const val_t e = attn_side(m, M), e2 = attn_side(m2, M);
+        const acc_t m2 = sc.ml[piece * 2], l2 = sc.ml[piece * 2 + 1], a2 = sc.acc[piece * sc.carry_ld + j];
+        const acc_t M = m < m2 ? m2 : m;
+        const acc_t e = attn_side(m, M), e2 = attn_side(m2, M);
         l = l * e + l2 * e2;
         acc = acc * e + a2 * e2;
         m = M;
@@ -420,11 +202,56 @@ __global__ __launch_bounds__(kBlock) void attention_fixup_kernel(int64_t n_slice
     int64_t u = t + 1;
     for (; u < n_slices && sc.row[u * 2 + 1] == r; ++u) fold(u * 2 + 1);
     if (u < n_slices && sc.row[u * 2 + 0] == r) fold(u * 2 + 0);
+    return true;
+}
+
+// one thread per (slice, column): the first slice that carries a row folds the row's pieces and writes the row of O;
+// column 0 writes lse
+template <typename val_t>
+__global__ __launch_bounds__(kBlock) void attention_fixup_kernel(int64_t n_slices, int32_t dv, const AttnScratch<val_t> sc, val_t* __restrict__ O,
+                                                                 int64_t ldo, val_t* __restrict__ lse) {
+    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    const int j = int(gid % dv);
+    int32_t r;
+    val_t m, l, acc;
+    if (!attn_fixup_fold(n_slices, sc, gid / dv, j, r, m, l, acc)) return;
     O[int64_t(r) * ldo + j] = attn_out(acc, l);
     if (j == 0 && lse) lse[r] = attn_lse(m, l);
 }
 
+// the operands of an execute as the entry points take them
+struct AttnOperands {
+    int32_t d, dv;
+    const void* Q; int64_t ldq;
+    const void* K; int64_t ldk;
+    const void* V; int64_t ldv;
+    const void* bias;
+    void* O; int64_t ldo;
+    void* lse;
+};
+
+// the arguments of an execute but the pass's tile (col_begin, cols), Args = AttnArgs<val_t> or AttnHalfArgs<vec_t>
+// (attention_half_kernel.hpp): elem_t is the type of Q, K, V and O, acc_t that of bias, lse, scale and the scratch
+template <typename elem_t, typename acc_t, typename Args>
+void attn_fill_args(Args& a, const mi355_spmv_attention& m, const AttnOperands& o) {
+    a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
+    a.Aj = m.Aj;
+    a.Q = static_cast<const elem_t*>(o.Q); a.K = static_cast<const elem_t*>(o.K); a.V = static_cast<const elem_t*>(o.V);
+    a.bias = static_cast<const acc_t*>(o.bias);
+    a.O = static_cast<elem_t*>(o.O); a.lse = static_cast<acc_t*>(o.lse);
+    a.ldq = o.ldq; a.ldk = o.ldk; a.ldv = o.ldv; a.ldo = o.ldo;
+    a.d = o.d;
+    a.q_vec = rows_aligned16<elem_t>(o.Q, o.ldq) ? 1 : 0;
+    a.k_vec = rows_aligned16<elem_t>(o.K, o.ldk) ? 1 : 0;
+    a.v_vec = rows_aligned16<elem_t>(o.V, o.ldv) ? 1 : 0;
+    a.o_vec = rows_aligned16<elem_t>(o.O, o.ldo) ? 1 : 0;
+    a.scale = acc_t(m.scale);
+    a.sc = attn_scratch<acc_t>(m.scratch, m.n_slices, m.carry_ld);
+}
+
 }  // namespace mi355
+
+#include "attention_half_kernel.hpp"    // (down here: its launch uses the handle, AttnOperands and attn_fill_args)
 
 using namespace mi355;
 
@@ -447,6 +274,16 @@ int attention_check_create(const char* who, int off_type, int val_type, int32_t 
     return check_csr_structure(who, off_type, n_rows, n_cols, nnz, Ap, Aj);
 }
 
+// the checks of create_half (and of the 16-bit one-shots): vec_type first, then what a create of fp32 values checks
+int attention_check_create_half(const char* who, int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
+                                const int32_t* Aj, int32_t d_max, int32_t dv_max) {
+    if (vec_type != MI355_VAL_F16 && vec_type != MI355_VAL_BF16) {
+        set_error("%s: vec_type %d is not a 16-bit type of Q, K, V and O (MI355_VAL_F16 or MI355_VAL_BF16)", who, vec_type);
+        return MI355_SPMV_EINVAL;
+    }
+    return attention_check_create(who, off_type, MI355_VAL_F32, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max);
+}
+
 // argument-only checks of an execute (bias and lse may be null)
 int attention_check_execute(const char* who, int32_t n_rows, int64_t nnz, int32_t d_max, int32_t dv_max, int32_t d, int32_t dv, const void* Q,
                             int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const void* O, int64_t ldo) {
@@ -465,19 +302,21 @@ int attention_check_execute(const char* who, int32_t n_rows, int64_t nnz, int32_
     return MI355_SPMV_OK;
 }
 
-int attention_widest(int val_type) { return (val_type == MI355_VAL_F64 ? 2 : 4) * kSliceGroupsMax; }
+// columns of a lane's 16 bytes of a row of Q, K, V and O, and the widest tile of dv
+int attention_lane_cols(int vec_type) { return vec_type == MI355_VAL_F64 ? 2 : vec_type == MI355_VAL_F32 ? 4 : mh::kHalfV; }
+int attention_widest(int vec_type) { return attention_lane_cols(vec_type) * kSliceGroupsMax; }
 
 // the object of checked arguments: the slices and their scratch (the only device call of a create: one hipMalloc)
-int attention_make(const char* who, mi355_spmv_attention** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+int attention_make(const char* who, mi355_spmv_attention** out, int off_type, int val_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
                    const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max) {
     mi355_spmv_attention* m = new (std::nothrow) mi355_spmv_attention();
     if (!m) { set_error("%s: host allocation failed", who); return MI355_SPMV_ENOMEM; }
-    m->off_type = off_type; m->val_type = val_type;
+    m->off_type = off_type; m->val_type = val_type; m->vec_type = vec_type;
     m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
     m->Ap = Ap; m->Aj = Aj;
     m->d_max = d_max; m->dv_max = dv_max;
     m->n_slices = slice_count(n_rows, nnz);
-    const int widest = attention_widest(val_type);
+    const int widest = attention_widest(vec_type);
     m->carry_ld = (int64_t(dv_max) + widest - 1) / widest * widest;
     if (m->n_slices > 0) {      // (no rows: nothing is ever launched, nothing allocated)
         m->scratch_bytes = attn_scratch_bytes(m->n_slices, m->carry_ld, val_type == MI355_VAL_F64 ? 8 : 4);
@@ -492,35 +331,13 @@ int attention_make(const char* who, mi355_spmv_attention** out, int off_type, in
     return MI355_SPMV_OK;
 }
 
-struct AttnOperands {
-    int32_t d, dv;
-    const void* Q; int64_t ldq;
-    const void* K; int64_t ldk;
-    const void* V; int64_t ldv;
-    const void* bias;
-    void* O; int64_t ldo;
-    void* lse;
-};
-
 // the passes over the tiles of dv, then the fix-up
 template <typename off_t, typename val_t>
 int attention_launch(const mi355_spmv_attention& m, const AttnOperands& o, hipStream_t s) {
     constexpr int W = 16 / int(sizeof(val_t));
     constexpr int kWidest = W * kSliceGroupsMax;
     AttnArgs<val_t> a;
-    a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
-    a.Aj = m.Aj;
-    a.Q = static_cast<const val_t*>(o.Q); a.K = static_cast<const val_t*>(o.K); a.V = static_cast<const val_t*>(o.V);
-    a.bias = static_cast<const val_t*>(o.bias);
-    a.O = static_cast<val_t*>(o.O); a.lse = static_cast<val_t*>(o.lse);
-    a.ldq = o.ldq; a.ldk = o.ldk; a.ldv = o.ldv; a.ldo = o.ldo;
-    a.d = o.d;
-    a.q_vec = rows_aligned16<val_t>(o.Q, o.ldq) ? 1 : 0;
-    a.k_vec = rows_aligned16<val_t>(o.K, o.ldk) ? 1 : 0;
-    a.v_vec = rows_aligned16<val_t>(o.V, o.ldv) ? 1 : 0;
-    a.o_vec = rows_aligned16<val_t>(o.O, o.ldo) ? 1 : 0;
-    a.scale = val_t(m.scale);
-    a.sc = attn_scratch<val_t>(m.scratch, m.n_slices, m.carry_ld);
+    attn_fill_args<val_t, val_t>(a, m, o);
     const off_t* Ap = static_cast<const off_t*>(m.Ap);
     const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
     for (int32_t cb = 0; cb < o.dv; cb += kWidest) {
@@ -543,6 +360,12 @@ int attention_launch(const mi355_spmv_attention& m, const AttnOperands& o, hipSt
 int attention_run(const mi355_spmv_attention& m, const AttnOperands& o, void* stream) {
     if (m.n_rows == 0) return MI355_SPMV_OK;        // no rows: nothing to write, nothing launched
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (m.vec_type != m.val_type) {     // 16-bit Q, K, V and O under fp32 everything else
+        const bool i32 = m.off_type == MI355_OFF_I32;
+        auto run = [&](auto off, auto vec) { return attention_half_launch<decltype(off), decltype(vec)>(m, o, s); };
+        if (m.vec_type == MI355_VAL_F16) return i32 ? run(int32_t(), F16()) : run(int64_t(), F16());
+        return i32 ? run(int32_t(), Bf16()) : run(int64_t(), Bf16());
+    }
     if (m.off_type == MI355_OFF_I32)
         return m.val_type == MI355_VAL_F64 ? attention_launch<int32_t, double>(m, o, s) : attention_launch<int32_t, float>(m, o, s);
     return m.val_type == MI355_VAL_F64 ? attention_launch<int64_t, double>(m, o, s) : attention_launch<int64_t, float>(m, o, s);
@@ -550,15 +373,17 @@ int attention_run(const mi355_spmv_attention& m, const AttnOperands& o, void* st
 
 // create, execute, synchronise, destroy (the scratch must outlive the kernels, as the multi-vector one-shots' does);
 // every argument check comes before any device call
-int attention_one_shot(int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
+int attention_one_shot(int off_type, int val_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
                        const AttnOperands& o, double scale, void* stream) {
     set_error("%s", "");
     if (const int st = attention_check_execute("attention", n_rows, nnz, o.d, o.dv, o.d, o.dv, o.Q, o.ldq, o.K, o.ldk, o.V, o.ldv, o.O, o.ldo))
         return st;
-    if (const int st = attention_check_create("attention", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv)) return st;
+    if (const int st = vec_type != val_type ? attention_check_create_half("attention_half", off_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv)
+                                            : attention_check_create("attention", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv))
+        return st;
     if (n_rows == 0) return MI355_SPMV_OK;
     mi355_spmv_attention* m = nullptr;
-    int st = attention_make("attention", &m, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv);
+    int st = attention_make("attention", &m, off_type, val_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv);
     if (st != MI355_SPMV_OK) return st;
     m->scale = scale;
     st = attention_run(*m, o, stream);
@@ -577,7 +402,23 @@ int mi355_spmv_attention_create(int32_t n_rows, int32_t n_cols, int64_t nnz, con
     if (!out) { set_error("attention_create: null object pointer (out)"); return MI355_SPMV_EINVAL; }
     *out = nullptr;
     if (const int st = attention_check_create("attention_create", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max)) return st;
-    return attention_make("attention_create", out, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max);
+    return attention_make("attention_create", out, off_type, val_type, val_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max);
+}
+
+int mi355_spmv_attention_create_half(mi355_spmv_attention** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+                                     const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max) {
+    set_error("%s", "");
+    if (!out) { set_error("attention_create_half: null object pointer (out)"); return MI355_SPMV_EINVAL; }
+    *out = nullptr;
+    if (const int st = attention_check_create_half("attention_create_half", off_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max)) return st;
+    return attention_make("attention_create_half", out, off_type, MI355_VAL_F32, vec_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max);
+}
+
+int mi355_spmv_attention_get_types(const mi355_spmv_attention* m, int* val_type, int* vec_type) {
+    if (!m || !val_type || !vec_type) { set_error("attention_get_types: null argument"); return MI355_SPMV_EINVAL; }
+    *val_type = m->val_type;
+    *vec_type = m->vec_type;
+    return MI355_SPMV_OK;
 }
 
 int mi355_spmv_attention_set_scale(mi355_spmv_attention* m, double scale) {
@@ -604,7 +445,7 @@ int mi355_spmv_attention_get_info(const mi355_spmv_attention* m, mi355_spmv_atte
     info->slice_len = kSliceLen;
     info->block_threads = kBlock;
     info->d_max = m->d_max; info->dv_max = m->dv_max;
-    info->widest_tile = attention_widest(m->val_type);
+    info->widest_tile = attention_widest(m->vec_type);
     info->passes = (m->dv_max + info->widest_tile - 1) / info->widest_tile;
     const int cols = m->dv_max < info->widest_tile ? m->dv_max : info->widest_tile;
     const int per_lane = info->widest_tile / kSliceGroupsMax;
@@ -612,7 +453,7 @@ int mi355_spmv_attention_get_info(const mi355_spmv_attention* m, mi355_spmv_atte
     info->n_slices = m->n_slices;
     info->grid_blocks = slice_grid(m->n_slices);
     info->scratch_bytes = int64_t(m->scratch_bytes);
-    snprintf(info->main_kernel, sizeof(info->main_kernel), "attention_slice_kernel");
+    snprintf(info->main_kernel, sizeof(info->main_kernel), m->vec_type != m->val_type ? "attention_half_slice_kernel" : "attention_slice_kernel");
     return MI355_SPMV_OK;
 }
 
@@ -632,11 +473,23 @@ int mi355_spmv_attention_destroy(mi355_spmv_attention* m) {
                                    const VAL* Q, int64_t ldq, const VAL* K, int64_t ldk, const VAL* V, int64_t ldv, const VAL* bias, \
                                    double scale, VAL* O, int64_t ldo, VAL* lse, void* stream) {                               \
         const AttnOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, lse};                                               \
-        return attention_one_shot(OFFENUM, VALENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, o, scale, stream);                  \
+        return attention_one_shot(OFFENUM, VALENUM, VALENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, o, scale, stream);                  \
     }
 MI355_SPMV_DEFINE_ATTENTION(i32_f32, int32_t, MI355_OFF_I32, float, MI355_VAL_F32)
 MI355_SPMV_DEFINE_ATTENTION(i32_f64, int32_t, MI355_OFF_I32, double, MI355_VAL_F64)
 MI355_SPMV_DEFINE_ATTENTION(i64_f32, int64_t, MI355_OFF_I64, float, MI355_VAL_F32)
 MI355_SPMV_DEFINE_ATTENTION(i64_f64, int64_t, MI355_OFF_I64, double, MI355_VAL_F64)
+
+#define MI355_SPMV_DEFINE_ATTENTION_HALF(SUF, OFF, OFFENUM, VECENUM)                                                          \
+    int mi355_spmv_attention_half_##SUF(int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap, const int32_t* Aj, int32_t d, int32_t dv, \
+                                        const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,   \
+                                        const float* bias, double scale, void* O, int64_t ldo, float* lse, void* stream) {    \
+        const AttnOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, lse};                                               \
+        return attention_one_shot(OFFENUM, MI355_VAL_F32, VECENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, o, scale, stream);   \
+    }
+MI355_SPMV_DEFINE_ATTENTION_HALF(i32_f16, int32_t, MI355_OFF_I32, MI355_VAL_F16)
+MI355_SPMV_DEFINE_ATTENTION_HALF(i32_bf16, int32_t, MI355_OFF_I32, MI355_VAL_BF16)
+MI355_SPMV_DEFINE_ATTENTION_HALF(i64_f16, int64_t, MI355_OFF_I64, MI355_VAL_F16)
+MI355_SPMV_DEFINE_ATTENTION_HALF(i64_bf16, int64_t, MI355_OFF_I64, MI355_VAL_BF16)
 
 }  // extern "C"

@@ -1,0 +1,110 @@
+// attention_half_kernel.hpp — fused sparse attention with Q, K, V and O stored in ONE 16-bit type (MI355_VAL_F16 /
+// MI355_VAL_BF16) and fp32 everything else (mi355_spmv_attention_create_half): bias, lse, scale, the
+// scores, the (m, l, acc) states, the scratch pieces and every operation are fp32, exactly attention.hip's arithmetic.
+// Every stored 16-bit value is widened exactly (half_convert.hpp's widen); an element of O is rounded to the 16-bit type
+// exactly ONCE, from the fp32 acc / l (narrow_to: nearest even) — by the slot that holds the row's last nonzero, or, for a
+// row that crosses slices, by the fix-up: the slices leave fp32 states, as the fp32 kernel's do.  Included by
+// attention.hip, which owns the object and the entry points, behind its handle, AttnScratch, AttnOperands and
+// attn_fill_args: this header holds the kernels and their one launch.
+//
+//   attention_half_slice_kernel   attention_slice_kernel's walk (the same text, attention_slice_walk.inc) over the same cut
+//                                 (slice_cut.hpp, slice_cut.inc, slice_cut_row.inc) with a lane's 16 bytes being EIGHT
+//                                 columns: C = 1 / 2 / 4 / 8 lanes per slot from ceil(cols / 8), tiles of 8 / 16 / 32 / 64
+//                                 columns, so dv = 64 is one pass and dv = 32 runs 16 nonzeros a step.  dv above 64:
+//                                 ceil(dv / 64) passes, the scores recomputed, only the first storing lse and the pieces'
+//                                 (row, m, l).  d is unbounded: the tile loop runs over C * 8 columns per round.  A kernel
+//                                 of its own, with a name and an argument struct of its own: a storage type among
+//                                 attention_slice_kernel's template arguments would rename the kernels on record
+//                                 (profiles/attention_kernel_resources.txt).
+//   attention_half_fixup_kernel   attention_fixup_kernel's fold (attn_fixup_fold) and the one narrowing of a crossing row.
+//
+// The aligned and the element-by-element accesses fill the same eight fp32 registers (half_cols.hpp), so unaligned
+// operands give the aligned bits.  The lane partition differs from the fp32 kernel's (8 columns per lane against 4): C and
+// the step edges of one width differ, so on real data the two kinds do not agree bit for bit.
+#pragma once
+
+#include "half_cols.hpp"
+#include "slice_cut.hpp"
+
+namespace mi355 {
+
+#ifdef __clang__
+#pragma clang fp contract(off)      // attention.hip's reason: the walk's v = scale * dot, then + bias, and a e + a' e' stay as written
+#endif
+
+template <typename vec_t>
+struct AttnHalfArgs {
+    int32_t n_rows;
+    int64_t nnz, n_slices;
+    const int32_t* Aj;
+    const vec_t* Q;
+    const vec_t* K;
+    const vec_t* V;
+    const float* bias;      // null: none
+    vec_t* O;
+    float* lse;             // null: not asked for
+    int64_t ldq, ldk, ldv, ldo;
+    int32_t d;
+    int32_t col_begin;      // first column of this pass's tile of dv (0: the pass that stores lse and the pieces' row, m, l)
+    int32_t cols;           // columns of it that exist (<= 64): the others are masked on load and store
+    int32_t q_vec, k_vec, v_vec, o_vec;     // 1 = rows are 16-byte aligned: one 16-byte access per lane
+    float scale;
+    AttnScratch<float> sc;
+};
+
+// C = lanes per nonzero slot (16-byte column groups of this pass's tile of dv); the wave holds S = 64 / C slots
+template <typename off_t, typename vec_t, int C>
+__global__ __launch_bounds__(kBlock) void attention_half_slice_kernel(const AttnHalfArgs<vec_t> a, const off_t* __restrict__ Ap) {
+    using acc_t = float;                // what attention_slice_walk.inc asks its includer
+    using mh::load_cols;                // the lane's eight 16-bit columns, widened
+    using mh::store_cols;               // and narrowed, once each
+    constexpr int W = mh::kHalfV;       // columns of a lane per tile
+    constexpr int S = kWave / C;
+    constexpr float kNegInf = -std::numeric_limits<float>::infinity();
+    constexpr bool kCutCarriedIn = true, kCutKeepsR1 = true;        // what slice_cut.inc asks its includer
+    constexpr int kCutNrInit = -1;
+#include "slice_cut.inc"            // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
+#include "attention_slice_walk.inc"     // the slice's nonzeros, 64 at a time: attention_slice_kernel's walk
+}
+
+// one thread per (slice, column), as attention_fixup_kernel: the row's only rounding to 16 bits
+template <typename vec_t>
+__global__ __launch_bounds__(kBlock) void attention_half_fixup_kernel(int64_t n_slices, int32_t dv, const AttnScratch<float> sc,
+                                                                      vec_t* __restrict__ O, int64_t ldo, float* __restrict__ lse) {
+    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    const int j = int(gid % dv);
+    int32_t r;
+    float m, l, acc;
+    if (!attn_fixup_fold(n_slices, sc, gid / dv, j, r, m, l, acc)) return;
+    O[int64_t(r) * ldo + j] = narrow_to(attn_out(acc, l), vec_t());
+    if (j == 0 && lse) lse[r] = attn_lse(m, l);
+}
+
+// the passes over the tiles of dv (64 columns each), then the fix-up.  A caller has checked the arguments and that there
+// are rows.
+template <typename off_t, typename vec_t>
+int attention_half_launch(const mi355_spmv_attention& m, const AttnOperands& o, hipStream_t s) {
+    static_assert(sizeof(vec_t) == 2, "16-bit Q, K, V and O");
+    constexpr int kWidest = mh::kHalfV * kSliceGroupsMax;
+    AttnHalfArgs<vec_t> a;
+    attn_fill_args<vec_t, float>(a, m, o);
+    const off_t* Ap = static_cast<const off_t*>(m.Ap);
+    const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
+    for (int32_t cb = 0; cb < o.dv; cb += kWidest) {
+        a.col_begin = cb;
+        a.cols = o.dv - cb < kWidest ? o.dv - cb : kWidest;
+        with_slot_lanes((a.cols + mh::kHalfV - 1) / mh::kHalfV, [&](auto lanes) {
+            hipLaunchKernelGGL((attention_half_slice_kernel<off_t, vec_t, decltype(lanes)::value>), grid, block, 0, s, a, Ap);
+        });
+        MI355_HIP_TRY(hipGetLastError());
+    }
+    if (m.n_slices > 1) {
+        const int64_t threads = m.n_slices * o.dv;
+        hipLaunchKernelGGL((attention_half_fixup_kernel<vec_t>), dim3(unsigned((threads + kBlock - 1) / kBlock)), block, 0, s, m.n_slices, o.dv,
+                           a.sc, a.O, o.ldo, a.lse);
+        MI355_HIP_TRY(hipGetLastError());
+    }
+    return MI355_SPMV_OK;
+}
+
+}  // namespace mi355

@@ -16,8 +16,8 @@
 //     tail, reads Yold only when beta != 0 and stores the rounded row.  It is the row's only writer.
 //   - every execute rewrites carry_row of every slice, and the carry / tail of every slice that has one, for the k
 //     columns of the execute: the fix-up reads nothing that an earlier (wider) execute left.
-// The conversions: half_convert.hpp; the widening load of a lane's eight columns (mh::load_cols, U32x4, kHalfV):
-// half_cols.hpp, shared with SDDMM's 16-bit kernel.
+// The conversions: half_convert.hpp; the widening load and the narrowing store of a lane's eight columns (mh::load_cols,
+// mh::store_cols, U32x4, kHalfV): half_cols.hpp, shared with SDDMM's and fused attention's 16-bit kernels.
 #pragma once
 
 #include "half_cols.hpp"
@@ -46,21 +46,6 @@ struct MultiHalfArgs {
     float* tail_val;        // [n_slices][carry_ld]: the partial of the slice's first row, when that row began earlier and ends here
     int64_t carry_ld;
 };
-
-template <typename vec_t>
-__device__ __forceinline__ void store_cols(const float (&v)[kHalfV], vec_t* p, int nv, bool vec) {
-    if (vec && nv == kHalfV) {
-        uint32_t w[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            w[q] = uint32_t(bits_of(narrow_to(v[2 * q], vec_t()))) | (uint32_t(bits_of(narrow_to(v[2 * q + 1], vec_t()))) << 16);
-        *reinterpret_cast<U32x4*>(p) = U32x4{w[0], w[1], w[2], w[3]};
-    } else {
-#pragma unroll
-        for (int j = 0; j < kHalfV; ++j)
-            if (j < nv) p[j] = narrow_to(v[j], vec_t());
-    }
-}
 
 // Y[r, tile] = round(alpha * sum + beta * float(Y[r, tile])), Y read only when beta != 0: the one rounding of the row
 template <typename vec_t>
