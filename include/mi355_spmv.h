@@ -51,6 +51,7 @@ extern "C" {
 #define MI355_SPMV_HAS_ROW_SOFTMAX 1 /* mi355_spmv_row_softmax_*: softmax over the stored entries of every row (edge softmax), and its gradient */
 #define MI355_SPMV_HAS_ATTENTION 1 /* mi355_spmv_attention_*: O = softmax(scale Q K^T + bias, on the stored entries of A) V in one pass over A */
 #define MI355_SPMV_HAS_ATTENTION_HALF 1 /* mi355_spmv_attention_create_half / _get_types / _half_*: Q, K, V and O in binary16 / bfloat16, fp32 bias, lse and arithmetic */
+#define MI355_SPMV_HAS_ATTENTION_BACKWARD 1 /* mi355_spmv_attention_bwd_*: dQ, dK, dV (and dbias) of fused sparse attention from O, dO and lse, nothing of nnz size kept */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -891,7 +892,8 @@ int mi355_spmv_row_softmax_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, 
  * edges fall in a row (states are combined by step, then by slice, in ascending order), as row softmax's do.
  * Types: {I32, I64} offsets x {F32, F64} values.  MI355_VAL_I32: MI355_SPMV_ENOTSUP; PATTERN / F16 / BF16 / unknown:
  * MI355_SPMV_EINVAL.  16-bit Q, K, V and O under fp32 everything else are an object of their own
- * (mi355_spmv_attention_create_half, below).  A fused backward, heads in one call and dist_* are not built.
+ * (mi355_spmv_attention_create_half, below).  The fused backward is mi355_spmv_attention_bwd_* (below); heads in one call and
+ * dist_* are not built.
  * The work is cut as the multi-vector kind's (slice_len merge items per wave, lanes_per_slot lanes per nonzero from the
  * tile of dv).  An execute launches ceil(dv / widest_tile) slice kernels (each recomputes the scores; widest_tile is 32
  * fp32 / 16 fp64 columns) and, with more than one slice, one fix-up of the rows that cross slices.
@@ -975,6 +977,87 @@ int mi355_spmv_attention_half_i64_f16(int32_t n_rows, int32_t n_cols, int64_t nn
 int mi355_spmv_attention_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
     const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
     void* O, int64_t ldo, float* lse, void* stream);
+
+/* ---- The fused backward of sparse attention (MI355_SPMV_HAS_ATTENTION_BACKWARD) ---------------------------------------
+ * For a caller who trains on mi355_spmv_attention: the step saves O and lse (n_rows-sized) instead of P (nnz-sized), and
+ * one object per STRUCTURE — shared by every head, layer and step — holds the transpose.  For every stored entry
+ * n = (r, c) of A:
+ *   v[n]     = scale * dot(Q[r, :d], K[c, :d]) + bias[n]         (rounded before + bias, as the forward)
+ *   p[n]     = v[n] == -inf ? +0 : exp(v[n] - lse[r])            (the test comes before the subtraction)
+ *   delta[r] = dot(dO[r, :dv], O[r, :dv]);  dp[n] = dot(dO[r, :dv], V[c, :dv]);  ds[n] = p[n] * (dp[n] - delta[r])
+ *   dQ[r, :d]  = sum over row r    of (scale * ds[n]) * K[c, :d]
+ *   dK[c, :d]  = sum over column c of (scale * ds[n]) * Q[r, :d]
+ *   dV[c, :dv] = sum over column c of p[n] * dO[r, :dv]
+ *   dbias[n]   = ds[n]                                           (optional; nnz values in A's CSR order)
+ * Q, K, V, bias, O, dO and lse are inputs, all of the object's val_type; O and lse are whatever the caller passes (nothing
+ * assumes they came from this library's forward).  Every matrix is row-major with its own leading dimension >= its width
+ * (Q, dQ: n_rows x d; K, dK: n_cols x d; V, dV: n_cols x dv; O, dO: n_rows x dv) and may have any alignment (16-byte
+ * accesses where the pointer and ld * sizeof allow, element accesses otherwise: same registers, same bits).  Outputs are
+ * never read (no alpha / beta) and must not overlap an input or each other; this is not checked.
+ * A masked edge (bias[n] = -inf) has p = ds = dbias = +0, and its rows of K, V, Q and dO are not loaded: a NaN there
+ * contributes nothing.  A row of A without entries gets dQ[r] = +0, a column without entries dK[c] = dV[c] = +0.  Every
+ * element of every requested output is written by every execute.
+ * The work: one kernel for delta (into the object's scratch), then ONE slice walk in three roles — DQ on A; DK and DV on
+ * A^T with bias read through the slot map — each cut as the multi-vector kind's (slice_len merge items per wave,
+ * lanes_per_slot lanes per entry from the tile of the role's OUTPUT), each taking ceil(width / widest_tile) launches that
+ * recompute the coefficient, and each followed, when its structure has more than one slice, by a fix-up of the lines
+ * that cross slices.  A role whose output is NULL is not launched.  No atomics; nothing of nnz size is allocated or
+ * written (dbias apart).  Order of addition: within a step the scan tree, then steps ascending, then slices ascending:
+ * two executes give the same bits, and the bits of a line depend only on where step and slice edges fall in that line of
+ * A (dQ) or A^T (dK, dV).
+ * Life cycle: create builds Apt / Ajt / perm with mi355_spmv_csr_transpose on `stream` (which it synchronises) and holds
+ * them in one allocation of held_bytes = 8 nnz + (n_cols + 1) offsets, allocates scratch_bytes = O(n_rows + slices *
+ * max(d_max, dv_max)), and retains Ap / Aj (not copied).  2^32 or more entries: MI355_SPMV_ENOTSUP.  Type refusals as
+ * mi355_spmv_attention_create (the 16-bit object has no backward).  execute is asynchronous on `stream`, launches kernels
+ * only, never synchronises and decides nothing from device data (graph-capturable); one stream at a time per object.
+ * Any of dQ / dK / dV may be NULL; all three NULL is MI355_SPMV_EINVAL, and so is dbias without dQ (it comes from the DQ
+ * walk).  Every argument error is refused before any device call, and the text of the last error names the argument.
+ * Out of scope: 16-bit operands, heads in one call, dist_*, harness labels, semirings, sharing the held transpose with a
+ * transposed multi-vector object.                                                                 */
+typedef struct mi355_spmv_attention_bwd mi355_spmv_attention_bwd;
+typedef struct mi355_spmv_attention_bwd_info {
+    int32_t off_type, val_type;
+    int32_t slice_len;          /* merge items (line ends + entries) per slice = per wave                 */
+    int32_t block_threads;
+    int32_t d_max, dv_max;
+    int32_t widest_tile;        /* columns of an output per slice pass                                    */
+    int32_t reserved;
+    int32_t lanes_per_slot[3];  /* C of the first pass of DQ, DK, DV at d = d_max, dv = dv_max            */
+    int32_t passes[3];          /* slice kernels of DQ, DK, DV at the maxima                              */
+    int64_t n_slices;           /* of A (the DQ walk)                                                     */
+    int64_t grid_blocks;
+    int64_t n_slices_t;         /* of A^T (the DK and DV walks)                                           */
+    int64_t grid_blocks_t;
+    int64_t scratch_bytes;      /* delta and the slices' pieces                                           */
+    int64_t held_bytes;         /* Apt, Ajt and perm                                                      */
+    char main_kernel[64];
+} mi355_spmv_attention_bwd_info;
+int mi355_spmv_attention_bwd_create(mi355_spmv_attention_bwd** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols,
+                                    int64_t nnz, const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max, void* stream);
+int mi355_spmv_attention_bwd_set_scale(mi355_spmv_attention_bwd* m, double scale);
+int mi355_spmv_attention_bwd_execute(mi355_spmv_attention_bwd* m, int32_t d, int32_t dv, const void* Q, int64_t ldq, const void* K,
+                                     int64_t ldk, const void* V, int64_t ldv, const void* bias, const void* O, int64_t ldo,
+                                     const void* dO, int64_t lddo, const void* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk,
+                                     void* dV, int64_t lddv, void* dbias, void* stream);
+int mi355_spmv_attention_bwd_get_info(const mi355_spmv_attention_bwd* m, mi355_spmv_attention_bwd_info* info);
+int mi355_spmv_attention_bwd_destroy(mi355_spmv_attention_bwd* m);
+/* One-shots: create (d_max = d, dv_max = dv), set_scale, execute, synchronise the stream, destroy.                   */
+int mi355_spmv_attention_bwd_i32_f32(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* V, int64_t ldv, const float* bias, double scale,
+    const float* O, int64_t ldo, const float* dO, int64_t lddo, const float* lse, float* dQ, int64_t lddq, float* dK, int64_t lddk,
+    float* dV, int64_t lddv, float* dbias, void* stream);
+int mi355_spmv_attention_bwd_i32_f64(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const double* Q, int64_t ldq, const double* K, int64_t ldk, const double* V, int64_t ldv, const double* bias, double scale,
+    const double* O, int64_t ldo, const double* dO, int64_t lddo, const double* lse, double* dQ, int64_t lddq, double* dK, int64_t lddk,
+    double* dV, int64_t lddv, double* dbias, void* stream);
+int mi355_spmv_attention_bwd_i64_f32(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* V, int64_t ldv, const float* bias, double scale,
+    const float* O, int64_t ldo, const float* dO, int64_t lddo, const float* lse, float* dQ, int64_t lddq, float* dK, int64_t lddk,
+    float* dV, int64_t lddv, float* dbias, void* stream);
+int mi355_spmv_attention_bwd_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const double* Q, int64_t ldq, const double* K, int64_t ldk, const double* V, int64_t ldv, const double* bias, double scale,
+    const double* O, int64_t ldo, const double* dO, int64_t lddo, const double* lse, double* dQ, int64_t lddq, double* dK, int64_t lddk,
+    double* dV, int64_t lddv, double* dbias, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "spmv-samples_amd", "csrc")
 TUS = ["csr_vector.hip", "csr_vector_f64.hip", "light_rows.hip", "light_rows_f64.hip", "merge_plan.hip", "merge_path_f32.hip", "merge_path_f64.hip",
        "merge_path_i32.hip", "merge_path_pattern.hip", "analyze.hip", "rows_plan.hip",
-       "dist.hip", "coo_csr.hip", "multi.hip", "multi_f32.hip", "multi_f64.hip", "multi_i32.hip", "multi_h16.hip", "csr_vector_h16.hip", "sddmm.hip", "row_softmax.hip", "attention.hip",
+       "dist.hip", "coo_csr.hip", "multi.hip", "multi_f32.hip", "multi_f64.hip", "multi_i32.hip", "multi_h16.hip", "csr_vector_h16.hip", "sddmm.hip", "row_softmax.hip", "attention.hip", "attention_bwd.hip",
        "multi_perm.hip", "multi_perm_f32.hip", "multi_perm_f64.hip"]
 
 

@@ -11,7 +11,7 @@
 # is blanked.  UNITS="a b" in the environment limits both commands to those units.
 set -euo pipefail
 
-UNITS=${UNITS:-"csr_vector csr_vector_f64 csr_vector_h16 light_rows light_rows_f64 merge_path_f32 merge_path_f64 merge_path_i32 merge_path_pattern rows_plan multi_f32 multi_f64 multi_i32 multi_h16 sddmm multi_perm_f32 multi_perm_f64 multi_perm attention"}
+UNITS=${UNITS:-"csr_vector csr_vector_f64 csr_vector_h16 light_rows light_rows_f64 merge_path_f32 merge_path_f64 merge_path_i32 merge_path_pattern rows_plan multi_f32 multi_f64 multi_i32 multi_h16 sddmm multi_perm_f32 multi_perm_f64 multi_perm attention attention_bwd"}
 unit_flags() {  # what the Makefile adds for one unit
     case "$1" in multi_*) echo -DMI355_MULTI_SPLIT_UNITS ;; esac
 }

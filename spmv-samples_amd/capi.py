@@ -68,6 +68,8 @@ EXPORTS = (
     + ["mi355_spmv_csr_transpose"]
     + ["mi355_spmv_multi_" + n for n in ("create_permuted", "create_transposed", "get_perm_info", "copy_structure")]
     + ["mi355_spmv_multi_transposed_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
+    + ["mi355_spmv_attention_bwd_" + n for n in ("create", "set_scale", "execute", "get_info", "destroy")]
+    + ["mi355_spmv_attention_bwd_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
 )
 
 
@@ -132,6 +134,14 @@ class AttentionInfo(C.Structure):
                 ("lanes_per_slot", C.c_int32), ("reserved", C.c_int32),
                 ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("scratch_bytes", C.c_int64),
                 ("main_kernel", C.c_char * 64)]
+
+
+class AttentionBackwardInfo(C.Structure):
+    _fields_ = [("off_type", C.c_int32), ("val_type", C.c_int32), ("slice_len", C.c_int32), ("block_threads", C.c_int32),
+                ("d_max", C.c_int32), ("dv_max", C.c_int32), ("widest_tile", C.c_int32), ("reserved", C.c_int32),
+                ("lanes_per_slot", C.c_int32 * 3), ("passes", C.c_int32 * 3),
+                ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("n_slices_t", C.c_int64), ("grid_blocks_t", C.c_int64),
+                ("scratch_bytes", C.c_int64), ("held_bytes", C.c_int64), ("main_kernel", C.c_char * 64)]
 
 
 EXCHANGES = {"auto": 0, "bcast": 1, "sendrecv": 2, "allgather": 3}
@@ -288,6 +298,21 @@ def lib():
         for o in ("i32", "i64"):
             for v in ("f32", "f64"):
                 getattr(L, "mi355_spmv_multi_transposed_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_multi_%s_%s" % (o, v)).argtypes
+        L.mi355_spmv_attention_bwd_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.mi355_spmv_attention_bwd_set_scale.argtypes = [C.c_void_p, C.c_double]
+        # d, dv, (Q, ldq), (K, ldk), (V, ldv), bias, (O, ldo), (dO, lddo), lse, (dQ, lddq), (dK, lddk), (dV, lddv), dbias, stream
+        bwd_operands = ([C.c_void_p, C.c_int64] * 3 + [C.c_void_p] + [C.c_void_p, C.c_int64] * 2 + [C.c_void_p] + [C.c_void_p, C.c_int64] * 3
+                        + [C.c_void_p, C.c_void_p])
+        L.mi355_spmv_attention_bwd_execute.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + bwd_operands
+        L.mi355_spmv_attention_bwd_get_info.argtypes = [C.c_void_p, C.POINTER(AttentionBackwardInfo)]
+        L.mi355_spmv_attention_bwd_destroy.argtypes = [C.c_void_p]
+        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
+            for v in ("f32", "f64"):
+                # ... bias, scale, (O, ldo), ...: the one-shots take the scale behind bias
+                getattr(L, "mi355_spmv_attention_bwd_%s_%s" % (o, v)).argtypes = (
+                    [C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + bwd_operands[:7] + [C.c_double]
+                    + bwd_operands[7:])
         _lib = L
     return _lib
 
@@ -1410,6 +1435,132 @@ def sparse_attention_half(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias=None, scale
                                   _stream_ptr(stream))
     _check(st, name)
     return out
+
+
+def _attention_backward_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, d_max=None, dv_max=None):
+    """The operand checks of a fused attention backward: (d, dv, the leading dimensions of Q, K, V, O, dO, then dQ, dK, dV,
+    dbias — made where asked for by `need` and not given — and their leading dimensions, 0 for an output that is None)."""
+    ldq, ldk, ldv = _require_matrix(Q, "Q", n_rows, val_dtype), _require_matrix(K, "K", n_cols, val_dtype), _require_matrix(V, "V", n_cols, val_dtype)
+    ldo, lddo = _require_matrix(O, "O", n_rows, val_dtype), _require_matrix(dO, "dO", n_rows, val_dtype)
+    d, dv = Q.size(1), V.size(1)
+    if K.size(1) != d:
+        raise ValueError("Q and K differ in their columns (%d, %d)" % (d, K.size(1)))
+    if O.size(1) != dv or dO.size(1) != dv:
+        raise ValueError("O and dO need V's %d columns (%d, %d)" % (dv, O.size(1), dO.size(1)))
+    if d < 1 or dv < 1:
+        raise ValueError("Q, K and V need at least one column")
+    if (d_max is not None and d > d_max) or (dv_max is not None and dv > dv_max):
+        raise ValueError("d = %d or dv = %d above the plan's d_max = %s, dv_max = %s" % (d, dv, d_max, dv_max))
+    _edge_values(lse, "lse", n_rows, val_dtype)
+    if bias is not None:
+        _edge_values(bias, "bias", nnz, val_dtype)
+    need = tuple(bool(x) for x in need)
+    if len(need) != 3:
+        raise ValueError("need is (dQ, dK, dV)")
+    outs, lds = [], []
+    for t, name, want, rows, width in ((dQ, "dQ", need[0], n_rows, d), (dK, "dK", need[1], n_cols, d), (dV, "dV", need[2], n_cols, dv)):
+        if t is None and want:
+            t = torch.empty((rows, width), dtype=val_dtype, device=Q.device)
+        if t is not None:
+            lds.append(_require_matrix(t, name, rows, val_dtype))
+            if t.size(1) != width:
+                raise ValueError("%s has %d columns, not %d" % (name, t.size(1), width))
+        else:
+            lds.append(0)
+        outs.append(t)
+    if not any(t is not None for t in outs):
+        raise ValueError("none of dQ, dK and dV is asked for")
+    if dbias is True:
+        dbias = torch.empty((nnz,), dtype=val_dtype, device=Q.device)
+    if dbias is not None:
+        if outs[0] is None:
+            raise ValueError("dbias needs dQ (it comes from the walk that makes dQ)")
+        _edge_values(dbias, "dbias", nnz, val_dtype)
+    return d, dv, ldq, ldk, ldv, ldo, lddo, outs[0], outs[1], outs[2], dbias, lds
+
+
+class SparseAttentionBackwardPlan:
+    """mi355_spmv_attention_bwd_*: the fused backward of SparseAttentionPlan — dQ, dK, dV (and dbias) from Q, K, V, bias, the
+    forward's O and lse, and dO, with nothing of nnz size kept between forward and backward.  One plan per STRUCTURE: it
+    holds the transpose of A (info()["held_bytes"]), built at create on `stream` (which is synchronised), and serves every
+    head, layer and step on that structure.  dtype is float32 or float64; Q is n_rows x d, K n_cols x d, V n_cols x dv, O
+    and dO n_rows x dv (row-major device tensors, d <= d_max, dv <= dv_max, a row stride above the width is the leading
+    dimension); lse n_rows values, bias nnz values in CSR order or None.  Holds references to Ap and Aj.  Executes are
+    asynchronous and never synchronise."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, dtype, d_max, dv_max, stream=None):
+        _require_device(Ap, Aj)
+        if Aj.dtype != torch.int32:
+            raise TypeError("Aj must be int32")
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError("dtype must be float32 or float64 (the 16-bit object has no backward)")
+        self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
+        self.Ap, self.Aj, self.val_dtype = Ap, Aj, dtype
+        self.d_max, self.dv_max = d_max, dv_max
+        self._h = C.c_void_p()
+        with torch.cuda.device(Ap.device):
+            st = lib().mi355_spmv_attention_bwd_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[dtype][0], n_rows, n_cols, nnz,
+                                                       C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d_max, dv_max, _stream_ptr(stream))
+        _check(st, "mi355_spmv_attention_bwd_create")
+
+    def execute(self, Q, K, V, O, dO, lse, bias=None, dQ=None, dK=None, dV=None, dbias=None, need=(True, True, True), stream=None):
+        """-> (dQ, dK, dV, dbias).  need = which of dQ, dK, dV to compute (a given tensor is computed whatever need says; an
+        output neither given nor needed is None and its walk is not launched).  dbias: a tensor of nnz values, True to have
+        one made, or None.  Asynchronous on `stream` (default: torch's current stream)."""
+        d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
+            self.n_rows, self.n_cols, self.nnz, self.val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, self.d_max, self.dv_max)
+        with torch.cuda.device(self.Ap.device):
+            st = lib().mi355_spmv_attention_bwd_execute(self._h, d, dv, _ptr(Q), ldq, _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), _ptr(O), ldo,
+                                                        _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0], _ptr(dK), lds[1], _ptr(dV), lds[2],
+                                                        _ptr(dbias), _stream_ptr(stream))
+        _check(st, "mi355_spmv_attention_bwd_execute")
+        return dQ, dK, dV, dbias
+
+    def set_scale(self, s):
+        """scale for the following executes (default 1): the forward plan's."""
+        _check(lib().mi355_spmv_attention_bwd_set_scale(self._h, C.c_double(s)), "mi355_spmv_attention_bwd_set_scale")
+
+    def info(self):
+        si = AttentionBackwardInfo()
+        _check(lib().mi355_spmv_attention_bwd_get_info(self._h, C.byref(si)), "mi355_spmv_attention_bwd_get_info")
+        d = {n: getattr(si, n) for n, _ in si._fields_ if n != "reserved"}
+        d["main_kernel"] = d["main_kernel"].decode()
+        d["lanes_per_slot"] = dict(zip(("dq", "dk", "dv"), d["lanes_per_slot"]))
+        d["passes"] = dict(zip(("dq", "dk", "dv"), d["passes"]))
+        return d
+
+    def destroy(self):
+        if self._h:
+            lib().mi355_spmv_attention_bwd_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def sparse_attention_backward(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, bias=None, scale=1.0, dQ=None, dK=None, dV=None, dbias=None,
+                              need=(True, True, True), stream=None):
+    """One-shot fused attention backward (mi355_spmv_attention_bwd_<off>_<val>): SparseAttentionBackwardPlan's execute on a
+    plan made for the call -> (dQ, dK, dV, dbias).  Synchronises `stream` before returning."""
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if not getattr(Q, "is_cuda", False):
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if Q.dtype not in (torch.float32, torch.float64):
+        raise TypeError("Q must be float32 or float64")
+    d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
+        n_rows, n_cols, nnz, Q.dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need)
+    name = "mi355_spmv_attention_bwd_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[Q.dtype][1])
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq, _ptr(K), ldk,
+                                  _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(O), ldo, _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0],
+                                  _ptr(dK), lds[1], _ptr(dV), lds[2], _ptr(dbias), _stream_ptr(stream))
+    _check(st, name)
+    return dQ, dK, dV, dbias
 
 
 C_TYPE_NAMES = {torch.float32: "float", torch.float64: "double", torch.int32: "int", torch.int64: "long long"}
