@@ -52,6 +52,7 @@ extern "C" {
 #define MI355_SPMV_HAS_ATTENTION 1 /* mi355_spmv_attention_*: O = softmax(scale Q K^T + bias, on the stored entries of A) V in one pass over A */
 #define MI355_SPMV_HAS_ATTENTION_HALF 1 /* mi355_spmv_attention_create_half / _get_types / _half_*: Q, K, V and O in binary16 / bfloat16, fp32 bias, lse and arithmetic */
 #define MI355_SPMV_HAS_ATTENTION_BACKWARD 1 /* mi355_spmv_attention_bwd_*: dQ, dK, dV (and dbias) of fused sparse attention from O, dO and lse, nothing of nnz size kept */
+#define MI355_SPMV_HAS_ATTENTION_BACKWARD_HALF 1 /* mi355_spmv_attention_bwd_create_half / _get_types / _half_*: the eight matrices in binary16 / bfloat16, fp32 bias, lse, dbias and arithmetic */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
 /* status codes */
@@ -958,8 +959,9 @@ int mi355_spmv_attention_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, co
  * of mi355_spmv_attention_create).  The object is the same: set_scale, execute, get_info and destroy serve both.
  * create_half: vec_type outside {F16, BF16} is MI355_SPMV_EINVAL ("vec_type" in the text); every other check is
  * create's, before any device call, and *out stays NULL.
- * Out of scope: an fp32 O under 16-bit inputs, mixed Q / K / V types, a 16-bit bias or lse, fp8, the fused backward,
- * heads in one call, dist_*, harness labels, an autograd.Function.                                                  */
+ * The fused backward on the same 16-bit type is mi355_spmv_attention_bwd_create_half (below).
+ * Out of scope: an fp32 O under 16-bit inputs, mixed Q / K / V types, a 16-bit bias or lse, fp8, heads in one call,
+ * dist_*, harness labels.                                                                                           */
 int mi355_spmv_attention_create_half(mi355_spmv_attention** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols,
                                      int64_t nnz, const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max);
 int mi355_spmv_attention_get_types(const mi355_spmv_attention* m, int* val_type, int* vec_type);
@@ -1008,12 +1010,12 @@ int mi355_spmv_attention_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t n
  * Life cycle: create builds Apt / Ajt / perm with mi355_spmv_csr_transpose on `stream` (which it synchronises) and holds
  * them in one allocation of held_bytes = 8 nnz + (n_cols + 1) offsets, allocates scratch_bytes = O(n_rows + slices *
  * max(d_max, dv_max)), and retains Ap / Aj (not copied).  2^32 or more entries: MI355_SPMV_ENOTSUP.  Type refusals as
- * mi355_spmv_attention_create (the 16-bit object has no backward).  execute is asynchronous on `stream`, launches kernels
+ * mi355_spmv_attention_create (16-bit operands: mi355_spmv_attention_bwd_create_half, below).  execute is asynchronous on `stream`, launches kernels
  * only, never synchronises and decides nothing from device data (graph-capturable); one stream at a time per object.
  * Any of dQ / dK / dV may be NULL; all three NULL is MI355_SPMV_EINVAL, and so is dbias without dQ (it comes from the DQ
  * walk).  Every argument error is refused before any device call, and the text of the last error names the argument.
- * Out of scope: 16-bit operands, heads in one call, dist_*, harness labels, semirings, sharing the held transpose with a
- * transposed multi-vector object.                                                                 */
+ * Out of scope: heads in one call, dist_*, harness labels, semirings, sharing the held transpose with a transposed
+ * multi-vector object.                                                                            */
 typedef struct mi355_spmv_attention_bwd mi355_spmv_attention_bwd;
 typedef struct mi355_spmv_attention_bwd_info {
     int32_t off_type, val_type;
@@ -1058,6 +1060,52 @@ int mi355_spmv_attention_bwd_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz
     const double* Q, int64_t ldq, const double* K, int64_t ldk, const double* V, int64_t ldv, const double* bias, double scale,
     const double* O, int64_t ldo, const double* dO, int64_t lddo, const double* lse, double* dQ, int64_t lddq, double* dK, int64_t lddk,
     double* dV, int64_t lddv, double* dbias, void* stream);
+
+/* ---- The fused backward with 16-bit operands (MI355_SPMV_HAS_ATTENTION_BACKWARD_HALF) ----------------------------------
+ * For callers who train on mi355_spmv_attention_create_half: no widening of Q, K, V, O, dO and no narrowing of dQ, dK, dV
+ * around the fused call.  The arithmetic is the fp32 object's, operation for operation:
+ *   Q, K, V, O, dO, dQ, dK, dV   in ONE 16-bit type, vec_type = MI355_VAL_F16 or MI355_VAL_BF16 (2-byte elements; ld* in
+ *                                elements)
+ *   bias, lse, dbias             float; delta, scale, the scores, p, dp, ds, the coefficients, the per-slot partials, the
+ *                                slices' pieces in scratch and every operation are fp32
+ * Every stored value is widened exactly.  An element of dQ, dK or dV is rounded to the 16-bit type exactly ONCE, from the
+ * fp32 sum of its line, to nearest even: by the slot that holds the line's last entry, or, for a line that crosses
+ * slices, by the fix-up after it has added the fp32 pieces in slice order.  A line without a live entry is the 16-bit +0
+ * bit pattern.  Masked edges (exactly +0, no row loaded), the test on v before the subtraction, every requested element
+ * written by every execute, two executes giving the same bits, any ld* and any alignment (a row is 16-byte aligned when
+ * the pointer and ld * 2 allow; both access paths fill the same registers, so an unaligned operand gives the aligned
+ * bits), NULL roles not launched and dbias without dQ refused hold as above.  No atomics, nothing of nnz size apart from
+ * dbias, kernels only (graph-capturable).
+ * A lane's 16 bytes are EIGHT columns: widest_tile = 64, lanes_per_slot from ceil(min(width, 64) / 8) of each role's
+ * output, ceil(width / 64) launches per role (d = dv = 64 is one pass per role).  get_info reports val_type =
+ * MI355_VAL_F32 and main_kernel = "attention_bwd_half_slice_kernel"; the type of the matrices is get_types' vec_type
+ * (which equals val_type on an object of mi355_spmv_attention_bwd_create).  The object is the same: set_scale, execute,
+ * get_info and destroy serve both.
+ * create_half: vec_type outside {F16, BF16} is MI355_SPMV_EINVAL ("vec_type" in the text); every other check is
+ * mi355_spmv_attention_bwd_create's, before any device call, and *out stays NULL.
+ * Out of scope: fp32 gradients under 16-bit inputs, mixed 16-bit types, a 16-bit bias / lse / dbias, fp8, heads in one
+ * call, dist_*, harness labels, a 16-bit transposed multi-vector object.                                             */
+int mi355_spmv_attention_bwd_create_half(mi355_spmv_attention_bwd** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols,
+                                         int64_t nnz, const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max, void* stream);
+int mi355_spmv_attention_bwd_get_types(const mi355_spmv_attention_bwd* m, int* val_type, int* vec_type);
+/* One-shots (the eight matrices: binary16 / bfloat16 as stored): create_half (d_max = d, dv_max = dv), set_scale, execute,
+ * synchronise the stream, destroy.                                                                                  */
+int mi355_spmv_attention_bwd_half_i32_f16(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
+    const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk,
+    void* dV, int64_t lddv, float* dbias, void* stream);
+int mi355_spmv_attention_bwd_half_i32_bf16(int32_t n_rows, int32_t n_cols, int32_t nnz, const int32_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
+    const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk,
+    void* dV, int64_t lddv, float* dbias, void* stream);
+int mi355_spmv_attention_bwd_half_i64_f16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
+    const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk,
+    void* dV, int64_t lddv, float* dbias, void* stream);
+int mi355_spmv_attention_bwd_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t nnz, const int64_t* Ap, const int32_t* Aj, int32_t d, int32_t dv,
+    const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
+    const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk,
+    void* dV, int64_t lddv, float* dbias, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

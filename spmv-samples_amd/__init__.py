@@ -17,6 +17,7 @@ Contents (only what the hot path needs):
                RowSoftmaxPlan / row_softmax: softmax over the stored entries of every row, and its gradient;
                SparseAttentionPlan / sparse_attention / sparse_attention_half: O = softmax(Q K^T on A) V fused into one pass over A, Q, K, V and O in fp32 / fp64 or in 16 bits;
                SparseAttentionBackwardPlan / sparse_attention_backward: dQ, dK, dV (and dbias) of that attention from O, dO and lse, nothing of nnz size kept;
+               SparseAttentionBackwardHalfPlan / sparse_attention_backward_half: the same with the eight matrices in 16 bits;
                csr_transpose / MultiPlan(perm=) / TransposedMultiPlan / spmm_t: Y = A^T X with Ax read in place through a slot map)
     autograd.py  sparse_attention_function: the two attention plans as one torch.autograd.Function-backed callable
     synth.py   seeded synthetic CSR matrices (stand-ins for the BASELINE configs)
@@ -25,5 +26,5 @@ Contents (only what the hot path needs):
 """
 from . import autograd, capi, dist, load, synth  # noqa: F401
 from .autograd import sparse_attention_function  # noqa: F401
-from .capi import (DistPlan, Functor, MultiPlan, Plan, PlanShape, RowSoftmaxPlan, SddmmPlan, SparseAttentionPlan, SparseAttentionBackwardPlan, sparse_attention, sparse_attention_backward, sparse_attention_half, coo_symmetric_nnz, coo_to_csr, spmm,  # noqa: F401
+from .capi import (DistPlan, Functor, MultiPlan, Plan, PlanShape, RowSoftmaxPlan, SddmmPlan, SparseAttentionPlan, SparseAttentionBackwardPlan, SparseAttentionBackwardHalfPlan, sparse_attention_backward_half, sparse_attention, sparse_attention_backward, sparse_attention_half, coo_symmetric_nnz, coo_to_csr, spmm,  # noqa: F401
                    spmv, narrow_values, row_softmax, TransposedMultiPlan, csr_transpose, spmm_t, sddmm, sddmm_half, spmm_pattern, spmv_genl, spmv_mixed, spmv_pattern)

@@ -6,11 +6,13 @@ import torch
 def sparse_attention_function(fwd_plan, bwd_plan):
     """f(Q, K, V, bias=None) -> O = softmax(scale * Q K^T + bias, on the stored entries of A) V, differentiable in Q, K, V and
     (where it requires grad) bias.  The forward saves Q, K, V, bias, O and lse — nothing of nnz size but the caller's own
-    bias.  Both plans are made on the same structure and value type, and the caller sets the same scale on both."""
+    bias.  Both plans are made on the same structure and value type, and the caller sets the same scale on both.  A 16-bit
+    pair — SparseAttentionPlan(vec_dtype=) with a SparseAttentionBackwardHalfPlan of the same vec_dtype — takes Q, K, V in
+    that type and returns O and the gradients in it; bias, lse and dbias are float32."""
     if (fwd_plan.n_rows, fwd_plan.n_cols, fwd_plan.nnz, fwd_plan.val_dtype) != (bwd_plan.n_rows, bwd_plan.n_cols, bwd_plan.nnz, bwd_plan.val_dtype):
         raise ValueError("the forward and the backward plan differ in structure or value type")
-    if fwd_plan.vec_dtype != fwd_plan.val_dtype:
-        raise TypeError("a 16-bit forward plan has no backward")
+    if fwd_plan.vec_dtype != bwd_plan.vec_dtype:
+        raise TypeError("the forward plan holds Q, K, V and O in %s, the backward plan in %s" % (fwd_plan.vec_dtype, bwd_plan.vec_dtype))
 
     class SparseAttention(torch.autograd.Function):
         @staticmethod

@@ -70,6 +70,8 @@ EXPORTS = (
     + ["mi355_spmv_multi_transposed_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
     + ["mi355_spmv_attention_bwd_" + n for n in ("create", "set_scale", "execute", "get_info", "destroy")]
     + ["mi355_spmv_attention_bwd_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
+    + ["mi355_spmv_attention_bwd_create_half", "mi355_spmv_attention_bwd_get_types"]
+    + ["mi355_spmv_attention_bwd_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
 )
 
 
@@ -313,6 +315,11 @@ def lib():
                 getattr(L, "mi355_spmv_attention_bwd_%s_%s" % (o, v)).argtypes = (
                     [C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + bwd_operands[:7] + [C.c_double]
                     + bwd_operands[7:])
+        L.mi355_spmv_attention_bwd_create_half.argtypes = L.mi355_spmv_attention_bwd_create.argtypes
+        L.mi355_spmv_attention_bwd_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        for o in ("i32", "i64"):
+            for v in ("f16", "bf16"):
+                getattr(L, "mi355_spmv_attention_bwd_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_attention_bwd_%s_f32" % o).argtypes
         _lib = L
     return _lib
 
@@ -1437,11 +1444,18 @@ def sparse_attention_half(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias=None, scale
     return out
 
 
-def _attention_backward_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, d_max=None, dv_max=None):
+def _attention_backward_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, d_max=None, dv_max=None,
+                                 vec_dtype=None):
     """The operand checks of a fused attention backward: (d, dv, the leading dimensions of Q, K, V, O, dO, then dQ, dK, dV,
-    dbias — made where asked for by `need` and not given — and their leading dimensions, 0 for an output that is None)."""
-    ldq, ldk, ldv = _require_matrix(Q, "Q", n_rows, val_dtype), _require_matrix(K, "K", n_cols, val_dtype), _require_matrix(V, "V", n_cols, val_dtype)
-    ldo, lddo = _require_matrix(O, "O", n_rows, val_dtype), _require_matrix(dO, "dO", n_rows, val_dtype)
+    dbias — made where asked for by `need` and not given — and their leading dimensions, 0 for an output that is None).
+    Q, K, V, O, dO and dQ, dK, dV are of vec_dtype (the value type when None); lse, bias and dbias of the value type."""
+    vec_dtype = val_dtype if vec_dtype is None else vec_dtype
+    if vec_dtype != val_dtype:      # the 16-bit object: which of the eight matrices is in another type
+        for t, name in ((Q, "Q"), (K, "K"), (V, "V"), (O, "O"), (dO, "dO"), (dQ, "dQ"), (dK, "dK"), (dV, "dV")):
+            if t is not None and getattr(t, "dtype", vec_dtype) != vec_dtype:
+                raise TypeError("%s is %s: the plan's vec_dtype is %s" % (name, t.dtype, vec_dtype))
+    ldq, ldk, ldv = _require_matrix(Q, "Q", n_rows, vec_dtype), _require_matrix(K, "K", n_cols, vec_dtype), _require_matrix(V, "V", n_cols, vec_dtype)
+    ldo, lddo = _require_matrix(O, "O", n_rows, vec_dtype), _require_matrix(dO, "dO", n_rows, vec_dtype)
     d, dv = Q.size(1), V.size(1)
     if K.size(1) != d:
         raise ValueError("Q and K differ in their columns (%d, %d)" % (d, K.size(1)))
@@ -1460,9 +1474,9 @@ def _attention_backward_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, O, dO,
     outs, lds = [], []
     for t, name, want, rows, width in ((dQ, "dQ", need[0], n_rows, d), (dK, "dK", need[1], n_cols, d), (dV, "dV", need[2], n_cols, dv)):
         if t is None and want:
-            t = torch.empty((rows, width), dtype=val_dtype, device=Q.device)
+            t = torch.empty((rows, width), dtype=vec_dtype, device=Q.device)
         if t is not None:
-            lds.append(_require_matrix(t, name, rows, val_dtype))
+            lds.append(_require_matrix(t, name, rows, vec_dtype))
             if t.size(1) != width:
                 raise ValueError("%s has %d columns, not %d" % (name, t.size(1), width))
         else:
@@ -1493,22 +1507,28 @@ class SparseAttentionBackwardPlan:
         if Aj.dtype != torch.int32:
             raise TypeError("Aj must be int32")
         if dtype not in (torch.float32, torch.float64):
-            raise TypeError("dtype must be float32 or float64 (the 16-bit object has no backward)")
+            raise TypeError("dtype must be float32 or float64 (16-bit operands: SparseAttentionBackwardHalfPlan)")
+        self._create("mi355_spmv_attention_bwd_create", VAL_TYPES[dtype][0], n_rows, n_cols, nnz, Ap, Aj, dtype, dtype, d_max, dv_max, stream)
+
+    def _create(self, entry, type_code, n_rows, n_cols, nnz, Ap, Aj, val_dtype, vec_dtype, d_max, dv_max, stream):
+        """The object of checked arguments: `entry` is create (type_code a value type) or create_half (a 16-bit type)."""
         self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
-        self.Ap, self.Aj, self.val_dtype = Ap, Aj, dtype
+        self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
+        self.vec_dtype = vec_dtype
         self.d_max, self.dv_max = d_max, dv_max
         self._h = C.c_void_p()
         with torch.cuda.device(Ap.device):
-            st = lib().mi355_spmv_attention_bwd_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[dtype][0], n_rows, n_cols, nnz,
-                                                       C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d_max, dv_max, _stream_ptr(stream))
-        _check(st, "mi355_spmv_attention_bwd_create")
+            st = getattr(lib(), entry)(C.byref(self._h), OFF_TYPES[Ap.dtype][0], type_code, n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()),
+                                       C.c_void_p(Aj.data_ptr()), d_max, dv_max, _stream_ptr(stream))
+        _check(st, entry)
 
     def execute(self, Q, K, V, O, dO, lse, bias=None, dQ=None, dK=None, dV=None, dbias=None, need=(True, True, True), stream=None):
         """-> (dQ, dK, dV, dbias).  need = which of dQ, dK, dV to compute (a given tensor is computed whatever need says; an
         output neither given nor needed is None and its walk is not launched).  dbias: a tensor of nnz values, True to have
         one made, or None.  Asynchronous on `stream` (default: torch's current stream)."""
         d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
-            self.n_rows, self.n_cols, self.nnz, self.val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, self.d_max, self.dv_max)
+            self.n_rows, self.n_cols, self.nnz, self.val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, self.d_max, self.dv_max,
+            self.vec_dtype)
         with torch.cuda.device(self.Ap.device):
             st = lib().mi355_spmv_attention_bwd_execute(self._h, d, dv, _ptr(Q), ldq, _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), _ptr(O), ldo,
                                                         _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0], _ptr(dK), lds[1], _ptr(dV), lds[2],
@@ -1555,6 +1575,45 @@ def sparse_attention_backward(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, 
     d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
         n_rows, n_cols, nnz, Q.dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need)
     name = "mi355_spmv_attention_bwd_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[Q.dtype][1])
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq, _ptr(K), ldk,
+                                  _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(O), ldo, _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0],
+                                  _ptr(dK), lds[1], _ptr(dV), lds[2], _ptr(dbias), _stream_ptr(stream))
+    _check(st, name)
+    return dQ, dK, dV, dbias
+
+
+class SparseAttentionBackwardHalfPlan(SparseAttentionBackwardPlan):
+    """mi355_spmv_attention_bwd_create_half: SparseAttentionBackwardPlan with Q, K, V, O, dO and dQ, dK, dV held in vec_dtype
+    (torch.float16 or torch.bfloat16) — the backward of SparseAttentionPlan(vec_dtype=).  lse, bias and dbias are float32
+    (val_dtype), and so is every operation; every stored value is widened exactly and an element of dQ, dK or dV is rounded
+    to vec_dtype once, from the float32 sum of its line.  execute, set_scale, info and destroy are the base class's."""
+
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, vec_dtype, d_max, dv_max, stream=None):
+        if vec_dtype not in MAT_TYPES:
+            raise TypeError("vec_dtype must be float16 or bfloat16 (float32 / float64 operands: SparseAttentionBackwardPlan)")
+        _require_device(Ap, Aj)
+        if Aj.dtype != torch.int32:
+            raise TypeError("Aj must be int32")
+        self._create("mi355_spmv_attention_bwd_create_half", MAT_TYPES[vec_dtype][0], n_rows, n_cols, nnz, Ap, Aj, torch.float32, vec_dtype, d_max,
+                     dv_max, stream)
+
+
+def sparse_attention_backward_half(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, bias=None, scale=1.0, dQ=None, dK=None, dV=None, dbias=None,
+                                   need=(True, True, True), stream=None):
+    """One-shot fused attention backward on 16-bit matrices (mi355_spmv_attention_bwd_half_<off>_<f16|bf16>):
+    sparse_attention_backward's arguments with Q, K, V, O, dO (and dQ, dK, dV) in one of float16 / bfloat16, lse, bias and
+    dbias in float32 -> (dQ, dK, dV, dbias).  Synchronises `stream` before returning."""
+    _require_device(Ap, Aj)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+    if not getattr(Q, "is_cuda", False):
+        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    if Q.dtype not in MAT_TYPES:
+        raise TypeError("Q must be float16 or bfloat16")
+    d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
+        n_rows, n_cols, nnz, torch.float32, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, vec_dtype=Q.dtype)
+    name = "mi355_spmv_attention_bwd_half_%s_%s" % (OFF_TYPES[Ap.dtype][1], MAT_TYPES[Q.dtype][1])
     with torch.cuda.device(Ap.device):
         st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq, _ptr(K), ldk,
                                   _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(O), ldo, _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0],

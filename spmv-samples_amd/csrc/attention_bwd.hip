@@ -33,7 +33,11 @@
 //   attention_bwd_fixup_kernel   one thread per (slice, column): the first slice that carries a line adds its pieces in
 //                                slice order — the tails, then the head of the slice it ends in — and stores the line.
 //
-// An output wider than the widest tile (32 fp32 / 16 fp64 columns) takes ceil(width / widest) launches of its role, each
+// Q, K, V, O, dO, dQ, dK and dV in 16 bits under fp32 bias, lse, dbias, delta, scale, partials, pieces and arithmetic
+// (mi355_spmv_attention_bwd_create_half, §3.15.3): the same object and the same walk (attention_bwd_slice_walk.inc) in
+// kernels of their own, attention_bwd_half_kernel.hpp.
+//
+// An output wider than the widest tile (32 fp32 / 16 fp64 / 64 16-bit columns) takes ceil(width / widest) launches of its role, each
 // recomputing the coefficient.  A role whose output pointer is NULL is not launched.  No atomics, nothing allocated by an
 // execute, nothing decided from device data: an execute launches kernels only (graph-capturable), and two executes give
 // the same bits.  Order of addition: within a step the scan tree, then steps ascending, then slices ascending; the bits of
@@ -47,6 +51,7 @@
 
 struct mi355_spmv_attention_bwd {   // the opaque handle of include/mi355_spmv.h
     int off_type = 0, val_type = 0;
+    int vec_type = 0;               // the type of Q, K, V, O, dO, dQ, dK, dV: val_type, or F16 / BF16 under F32 everything else (create_half)
     int32_t n_rows = 0, n_cols = 0;
     int64_t nnz = 0;
     const void* Ap = nullptr;
@@ -165,235 +170,39 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_delta_kernel(int32_t n_r
 // C = lanes per nonzero slot (16-byte column groups of this pass's tile of out); the wave holds S = 64 / C slots
 template <typename off_t, typename val_t, int C, int ROLE>
 __global__ __launch_bounds__(kBlock) void attention_bwd_slice_kernel(const AttnBwdArgs<val_t> a, const off_t* __restrict__ Ap) {
+    using acc_t = val_t;                            // what attention_bwd_slice_walk.inc asks its includer
     constexpr int W = 16 / int(sizeof(val_t));      // columns of a lane per tile
     constexpr int S = kWave / C;
     constexpr val_t kNegInf = -std::numeric_limits<val_t>::infinity();
     constexpr bool kCutCarriedIn = true, kCutKeepsR1 = true;        // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = -1;
 #include "slice_cut.inc"            // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
-    const bool first_pass = a.col_begin == 0;
-    const bool biased = a.bias != nullptr;
-    const int nv = min(max(a.cols - c * W, 0), W);
-    // the line carried in ends here with entries of its own (a slice inside one line is a tail; a line whose last entry
-    // was the slice before's last item has nothing here)
-    const bool has_head = carried_in && nr >= 1 && rel[1] >= 1 && rel[1] <= nn;
-
-    val_t acc[W];           // per-slot partial of the open line (the line whose entries are not all seen yet)
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[j] = val_t(0);
-    int open_i = -1;        // that line, relative to r0; -1 = none (acc is +0)
-    int holder = -1;        // >= 0: acc is not +0 in this slot only; -2: spread over the slots
-
-    for (int base = 0; base < nn; base += kWave) {
-        // 64 entries, one per lane, coalesced; each lane finds its entry's line in the slice's offsets
-        const int m = base + lane;
-        int32_t col = 0;
-        val_t bias = val_t(0);
-        int ie = nr * 2;    // line * 2 + (1 = this entry is the last of its line); nr = no entry
-        if (m < nn) {
-            col = a.Aj[n0 + m];
-            if (biased) {
-                if constexpr (ROLE == kBwdDQ) bias = a.bias[n0 + m];
-                else bias = a.bias[a.perm[n0 + m]];
-            }
-#include "slice_cut_row.inc"     // leaves lo: the entry's line, relative to r0
-            ie = lo * 2 + (rel[lo + 1] == m + 1 ? 1 : 0);
-        }
-        const int left = nn - base;
-        const int steps = slice_group_steps<C>(left);
-        for (int t = 0; t < steps; ++t) {
-            // slot s takes entry t * S + s of the 64
-            int32_t col_s = col;
-            val_t bias_s = bias;
-            int ie_s = ie;
-            if constexpr (C > 1) {
-                const int src = t * S + s;
-                col_s = __shfl(col, src);
-                bias_s = __shfl(bias, src);
-                ie_s = __shfl(ie, src);
-            }
-            const int i_s = ie_s >> 1;
-            const bool live = i_s < nr;
-            // the entry's query and key: the line and the gathered index, or the other way round on A^T
-            const int64_t qi = ROLE == kBwdDQ ? r0 + i_s : int64_t(col_s);
-            const int64_t ki = ROLE == kBwdDQ ? int64_t(col_s) : r0 + i_s;
-            // a masked edge loads nothing and contributes exactly +0
-            const bool seen = live && !(biased && bias_s == kNegInf);
-
-            // the two dots, each SDDMM's tile loop and then a fixed tree over the slot's C lanes: the score over d, dp over dv
-            val_t part = val_t(0), dpart = val_t(0);
-            if (seen) {
-                const val_t* qp = a.Q + qi * a.ldq + c * W;
-                const val_t* kp = a.K + ki * a.ldk + c * W;
-                for (int32_t cb = 0; cb < a.d; cb += C * W) {       // the tiles of d: the same register all along
-                    const int nd = min(max(a.d - cb - c * W, 0), W);
-                    if (nd > 0) {
-                        val_t q[W], k[W];
-                        load_cols(q, qp + cb, nd, a.q_vec != 0);
-                        load_cols(k, kp + cb, nd, a.k_vec != 0);
-#pragma unroll
-                        for (int j = 0; j < W; ++j) part = attn_bwd_fma(q[j], k[j], part);
-                    }
-                }
-                const val_t* gp = a.dO + qi * a.lddo + c * W;
-                const val_t* vp = a.V + ki * a.ldv + c * W;
-                for (int32_t cb = 0; cb < a.dv; cb += C * W) {      // the tiles of dv
-                    const int nd = min(max(a.dv - cb - c * W, 0), W);
-                    if (nd > 0) {
-                        val_t g[W], x[W];
-                        load_cols(g, gp + cb, nd, a.do_vec != 0);
-                        load_cols(x, vp + cb, nd, a.v_vec != 0);
-#pragma unroll
-                        for (int j = 0; j < W; ++j) dpart = attn_bwd_fma(g[j], x[j], dpart);
-                    }
-                }
-            }
-#pragma unroll
-            for (int dd = 1; dd < C; dd <<= 1) {
-                part += __shfl_xor(part, dd);
-                dpart += __shfl_xor(dpart, dd);
-            }
-            // one exp; the coefficient of this role and the lane's W columns of the row it multiplies
-            val_t coef = val_t(0), ds = val_t(0);
-            val_t xv[W];
-#pragma unroll
-            for (int j = 0; j < W; ++j) xv[j] = val_t(0);
-            if (seen) {
-                val_t v = a.scale * part;
-                if (biased) v = v + bias_s;
-                if (v != kNegInf) {     // (the test comes before the subtraction)
-                    const val_t p = attn_bwd_exp(v - a.lse[qi]);
-                    ds = p * (dpart - a.delta[qi]);
-                    if constexpr (ROLE == kBwdDQ) {
-                        coef = a.scale * ds;
-                        load_cols(xv, a.K + ki * a.ldk + a.col_begin + c * W, nv, a.k_vec != 0);
-                    } else if constexpr (ROLE == kBwdDK) {
-                        coef = a.scale * ds;
-                        load_cols(xv, a.Q + qi * a.ldq + a.col_begin + c * W, nv, a.q_vec != 0);
-                    } else {
-                        coef = p;
-                        load_cols(xv, a.dO + qi * a.lddo + a.col_begin + c * W, nv, a.do_vec != 0);
-                    }
-                }
-            }
-            if constexpr (ROLE == kBwdDQ) {
-                // one writer per element: lane 0 of the slot, on the first pass
-                if (live && c == 0 && first_pass && a.dbias) a.dbias[n0 + base + t * S + s] = ds;
-            }
-            val_t p[W];
-#pragma unroll
-            for (int j = 0; j < W; ++j) p[j] = coef * xv[j];
-
-            const int i_first = __shfl(ie_s, 0) >> 1;
-            const int ie_last = __shfl(ie_s, kWave - 1);
-            if (i_first == (ie_last >> 1) && !(ie_last & 1)) {
-                // every slot is inside one line, and the line goes on: partials stay per slot
-#pragma unroll
-                for (int j = 0; j < W; ++j) acc[j] = acc[j] + p[j];
-                open_i = i_first;
-                holder = -2;
-                continue;
-            }
-            // a line ends in this step (or the slice does).  The open line's partial joins slot 0, whose entry is the
-            // next of that line; then a segmented inclusive scan over the slots sums each line's run of products.
-            if (open_i >= 0) {
-                if (holder >= 0) {
-#pragma unroll
-                    for (int j = 0; j < W; ++j) acc[j] = __shfl(acc[j], holder * C + c);
-                } else {
-                    attn_bwd_reduce_slots<val_t, W, C>(acc);
-                }
-                if (s == 0) {
-#pragma unroll
-                    for (int j = 0; j < W; ++j) p[j] = p[j] + acc[j];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < W; ++j) acc[j] = val_t(0);
-            const int i_prev = __shfl_up(i_s, C);
-            const bool head = s == 0 || i_prev != i_s;
-            const unsigned long long heads = __ballot(head && c == 0);
-            const int start = 63 - __clzll(heads & (~0ull >> (63 - lane)));   // lane c == 0 of the slot that starts this run
-#pragma unroll
-            for (int dd = C; dd < kWave; dd <<= 1) {
-#pragma unroll
-                for (int j = 0; j < W; ++j) {
-                    const val_t o = __shfl_up(p[j], dd);
-                    if (lane - c - dd >= start) p[j] = p[j] + o;
-                }
-            }
-            const bool tail = s == S - 1 || ((heads >> (lane - c + C)) & 1ull);
-            if (live && tail && (ie_s & 1)) {
-                if (i_s == 0 && carried_in) {
-                    // the HEAD piece: as computed, for the fix-up (whole tiles fit carry_ld)
-                    val_t* hv = a.sc.acc + (w * 2 + 0) * a.sc.carry_ld + a.col_begin + c * W;
-#pragma unroll
-                    for (int j = 0; j < W; ++j) hv[j] = p[j];
-                } else if (nv > 0) {
-                    store_cols(p, a.out + (r0 + i_s) * a.ldout + a.col_begin + c * W, nv, a.out_vec != 0);
-                }
-            }
-            // the last entry of the step: if its line goes on, its run's sum is the new open partial
-            const int lv = min(S - 1, left - t * S - 1);
-            const int ie_lv = __shfl(ie_s, lv * C);
-            if (!(ie_lv & 1)) {
-                open_i = ie_lv >> 1;
-                holder = lv;
-                if (s == lv) {
-#pragma unroll
-                    for (int j = 0; j < W; ++j) acc[j] = p[j];
-                }
-            } else {
-                open_i = -1;
-                holder = -1;
-            }
-        }
-    }
-
-    // the TAIL piece: what this slice holds of a line that ends in a later one
-    if (open_i >= 0) {
-        if (holder >= 0) {
-#pragma unroll
-            for (int j = 0; j < W; ++j) acc[j] = __shfl(acc[j], holder * C + c);
-        } else {
-            attn_bwd_reduce_slots<val_t, W, C>(acc);
-        }
-        if (s == 0) {
-            val_t* tv = a.sc.acc + (w * 2 + 1) * a.sc.carry_ld + a.col_begin + c * W;      // (carry_ld covers whole tiles)
-#pragma unroll
-            for (int j = 0; j < W; ++j) tv[j] = acc[j];
-        }
-    }
-    if (lane == 0 && first_pass) {
-        a.sc.row[w * 2 + 0] = has_head ? int32_t(r0) : -1;
-        a.sc.row[w * 2 + 1] = open_i >= 0 ? int32_t(r0 + open_i) : -1;
-    }
-
-    // lines without entries whose end lies in this slice: +0; a line with entries is stored where its last one is
-    if (nv > 0) {
-        val_t none[W];
-#pragma unroll
-        for (int j = 0; j < W; ++j) none[j] = val_t(0);
-        for (int64_t r = r0 + s; r < r1; r += S)
-            if (Ap[r] == Ap[r + 1]) store_cols(none, a.out + r * a.ldout + a.col_begin + c * W, nv, a.out_vec != 0);
-    }
+#include "attention_bwd_slice_walk.inc"     // the slice's entries, 64 at a time, and its lines without entries
 }
 
-// one thread per (slice, column): the first slice that carries a line adds the line's pieces in slice order — the tails,
-// then the head of the slice the line ends in — and stores the line of out
+// the fix-up's thread of (slice t, column j): if t is the first slice that carries a line, that line and the sum of its
+// pieces in slice order — the tails, then the head of the slice the line ends in; otherwise false
+template <typename acc_t>
+__device__ __forceinline__ bool attn_bwd_fixup_sum(int64_t n_slices, const AttnBwdScratch<acc_t>& sc, int64_t t, int j, int32_t& r, acc_t& sum) {
+    if (t >= n_slices) return false;
+    r = sc.row[t * 2 + 1];
+    if (r < 0 || (t > 0 && sc.row[(t - 1) * 2 + 1] == r)) return false;
+    sum = sc.acc[(t * 2 + 1) * sc.carry_ld + j];
+    int64_t u = t + 1;
+    for (; u < n_slices && sc.row[u * 2 + 1] == r; ++u) sum = sum + sc.acc[(u * 2 + 1) * sc.carry_ld + j];
+    if (u < n_slices && sc.row[u * 2 + 0] == r) sum = sum + sc.acc[(u * 2 + 0) * sc.carry_ld + j];
+    return true;
+}
+
+// one thread per (slice, column): the first slice that carries a line adds the line's pieces and stores the line of out
 template <typename val_t>
 __global__ __launch_bounds__(kBlock) void attention_bwd_fixup_kernel(int64_t n_slices, int32_t width, const AttnBwdScratch<val_t> sc,
                                                                      val_t* __restrict__ out, int64_t ldout) {
     const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-    const int64_t t = gid / width;
     const int j = int(gid % width);
-    if (t >= n_slices) return;
-    const int32_t r = sc.row[t * 2 + 1];
-    if (r < 0 || (t > 0 && sc.row[(t - 1) * 2 + 1] == r)) return;
-    val_t sum = sc.acc[(t * 2 + 1) * sc.carry_ld + j];
-    int64_t u = t + 1;
-    for (; u < n_slices && sc.row[u * 2 + 1] == r; ++u) sum = sum + sc.acc[(u * 2 + 1) * sc.carry_ld + j];
-    if (u < n_slices && sc.row[u * 2 + 0] == r) sum = sum + sc.acc[(u * 2 + 0) * sc.carry_ld + j];
+    int32_t r;
+    val_t sum;
+    if (!attn_bwd_fixup_sum(n_slices, sc, gid / width, j, r, sum)) return;
     out[int64_t(r) * ldout + j] = sum;
 }
 
@@ -415,6 +224,8 @@ struct AttnBwdOperands {
 
 }  // namespace mi355
 
+#include "attention_bwd_half_kernel.hpp"    // (down here: its kernels use AttnBwdScratch, the fold and kDeltaLanes)
+
 using namespace mi355;
 
 namespace {
@@ -429,7 +240,7 @@ int attention_bwd_check_create(const char* who, int off_type, int val_type, int3
         return MI355_SPMV_ENOTSUP;
     }
     if (val_type != MI355_VAL_F32 && val_type != MI355_VAL_F64) {
-        set_error("%s: val_type %d is not a type of Q, K, V, O and dO (F32 or F64; a 16-bit backward is not built)", who, val_type);
+        set_error("%s: val_type %d is not a type of Q, K, V, O and dO (F32 or F64; 16-bit operands: mi355_spmv_attention_bwd_create_half)", who, val_type);
         return MI355_SPMV_EINVAL;
     }
     if (d_max < 1) { set_error("%s: d_max = %d below 1", who, d_max); return MI355_SPMV_EINVAL; }
@@ -437,6 +248,16 @@ int attention_bwd_check_create(const char* who, int off_type, int val_type, int3
     if (const int st = check_csr_structure(who, off_type, n_rows, n_cols, nnz, Ap, Aj)) return st;
     if (uint64_t(nnz) >= (1ull << 32)) { set_error("%s: nnz of 2^32 or more entries (the slot map is 32-bit)", who); return MI355_SPMV_ENOTSUP; }
     return MI355_SPMV_OK;
+}
+
+// the checks of create_half (and of the 16-bit one-shots): vec_type first, then what a create of fp32 values checks
+int attention_bwd_check_create_half(const char* who, int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
+                                    const int32_t* Aj, int32_t d_max, int32_t dv_max) {
+    if (vec_type != MI355_VAL_F16 && vec_type != MI355_VAL_BF16) {
+        set_error("%s: vec_type %d is not a 16-bit type of Q, K, V, O, dO, dQ, dK and dV (MI355_VAL_F16 or MI355_VAL_BF16)", who, vec_type);
+        return MI355_SPMV_EINVAL;
+    }
+    return attention_bwd_check_create(who, off_type, MI355_VAL_F32, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max);
 }
 
 // argument-only checks of an execute (bias may be null; so may any of dQ, dK, dV, but not all three)
@@ -466,8 +287,9 @@ int attention_bwd_check_execute(const char* who, int32_t n_rows, int32_t n_cols,
     return MI355_SPMV_OK;
 }
 
-int attention_bwd_lane_cols(int val_type) { return val_type == MI355_VAL_F64 ? 2 : 4; }
-int attention_bwd_widest(int val_type) { return attention_bwd_lane_cols(val_type) * kSliceGroupsMax; }
+// columns of a lane's 16 bytes of a row of the eight matrices, and the widest tile of an output
+int attention_bwd_lane_cols(int vec_type) { return vec_type == MI355_VAL_F64 ? 2 : vec_type == MI355_VAL_F32 ? 4 : mh::kHalfV; }
+int attention_bwd_widest(int vec_type) { return attention_bwd_lane_cols(vec_type) * kSliceGroupsMax; }
 
 int attention_bwd_free(mi355_spmv_attention_bwd* m) {
     int st = MI355_SPMV_OK;
@@ -482,17 +304,17 @@ int attention_bwd_free(mi355_spmv_attention_bwd* m) {
 
 // the object of checked arguments: the structure of A^T and the slot map in one allocation (the transpose synchronises
 // the stream), the slices of both structures and the scratch
-int attention_bwd_make(const char* who, mi355_spmv_attention_bwd** out, int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+int attention_bwd_make(const char* who, mi355_spmv_attention_bwd** out, int off_type, int val_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
                        const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max, hipStream_t s) {
     mi355_spmv_attention_bwd* m = new (std::nothrow) mi355_spmv_attention_bwd();
     if (!m) { set_error("%s: host allocation failed", who); return MI355_SPMV_ENOMEM; }
-    m->off_type = off_type; m->val_type = val_type;
+    m->off_type = off_type; m->val_type = val_type; m->vec_type = vec_type;
     m->n_rows = n_rows; m->n_cols = n_cols; m->nnz = nnz;
     m->Ap = Ap; m->Aj = Aj;
     m->d_max = d_max; m->dv_max = dv_max;
     m->n_slices = slice_count(n_rows, nnz);
     m->n_slices_t = slice_count(n_cols, nnz);
-    const int widest = attention_bwd_widest(val_type);
+    const int widest = attention_bwd_widest(vec_type);
     const int64_t wide = d_max > dv_max ? d_max : dv_max;
     m->carry_ld = (wide + widest - 1) / widest * widest;
     const size_t ob = off_type == MI355_OFF_I64 ? 8 : 4;
@@ -525,71 +347,91 @@ int attention_bwd_make(const char* who, mi355_spmv_attention_bwd** out, int off_
     return MI355_SPMV_OK;
 }
 
+// The kernels of one storage type as the launch path below names them: elem_t is the type of the eight matrices, acc_t that
+// of bias, lse, dbias, scale and the scratch, W a lane's columns.  AttnBwdHalfKernels<vec_t> (attention_bwd_half_kernel.hpp)
+// has the same members.
+template <typename val_t>
+struct AttnBwdKernels {
+    using elem_t = val_t;
+    using acc_t = val_t;
+    using Args = AttnBwdArgs<val_t>;
+    static constexpr int W = 16 / int(sizeof(val_t));
+    static void delta(dim3 grid, hipStream_t s, int32_t n_rows, int32_t dv, const val_t* dO, int64_t lddo, const val_t* O, int64_t ldo, val_t* delta) {
+        hipLaunchKernelGGL((attention_bwd_delta_kernel<val_t>), grid, dim3(kBlock), 0, s, n_rows, dv, dO, lddo, O, ldo, delta);
+    }
+    template <typename off_t, int C, int ROLE>
+    static void slice(dim3 grid, hipStream_t s, const Args& a, const off_t* Ap) {
+        hipLaunchKernelGGL((attention_bwd_slice_kernel<off_t, val_t, C, ROLE>), grid, dim3(kBlock), 0, s, a, Ap);
+    }
+    static void fixup(dim3 grid, hipStream_t s, const Args& a, int32_t width) {
+        hipLaunchKernelGGL((attention_bwd_fixup_kernel<val_t>), grid, dim3(kBlock), 0, s, a.n_slices, width, a.sc, a.out, a.ldout);
+    }
+};
+
 // the passes of one role over the tiles of its output, then its fix-up
-template <typename off_t, typename val_t, int ROLE>
-int attention_bwd_role(AttnBwdArgs<val_t>& a, const off_t* Ap, int32_t width, hipStream_t s) {
-    constexpr int W = 16 / int(sizeof(val_t));
+template <typename off_t, typename K, int ROLE>
+int attention_bwd_role(typename K::Args& a, const off_t* Ap, int32_t width, hipStream_t s) {
+    constexpr int W = K::W;
     constexpr int kWidest = W * kSliceGroupsMax;
     if (a.n_slices == 0) return MI355_SPMV_OK;      // no lines: nothing to write
-    const dim3 grid(unsigned(slice_grid(a.n_slices))), block(kBlock);
+    const dim3 grid(unsigned(slice_grid(a.n_slices)));
     for (int32_t cb = 0; cb < width; cb += kWidest) {
         a.col_begin = cb;
         a.cols = width - cb < kWidest ? width - cb : kWidest;
-        with_slot_lanes((a.cols + W - 1) / W, [&](auto lanes) {
-            hipLaunchKernelGGL((attention_bwd_slice_kernel<off_t, val_t, decltype(lanes)::value, ROLE>), grid, block, 0, s, a, Ap);
-        });
+        with_slot_lanes((a.cols + W - 1) / W, [&](auto lanes) { K::template slice<off_t, decltype(lanes)::value, ROLE>(grid, s, a, Ap); });
         MI355_HIP_TRY(hipGetLastError());
     }
     if (a.n_slices > 1) {
         const int64_t threads = a.n_slices * width;
-        hipLaunchKernelGGL((attention_bwd_fixup_kernel<val_t>), dim3(unsigned((threads + kBlock - 1) / kBlock)), block, 0, s, a.n_slices, width, a.sc,
-                           a.out, a.ldout);
+        K::fixup(dim3(unsigned((threads + kBlock - 1) / kBlock)), s, a, width);
         MI355_HIP_TRY(hipGetLastError());
     }
     return MI355_SPMV_OK;
 }
 
 // delta, then the roles that are asked for, one behind the other on the stream (they share the pieces' scratch)
-template <typename off_t, typename val_t>
+template <typename off_t, typename K>
 int attention_bwd_launch(const mi355_spmv_attention_bwd& m, const AttnBwdOperands& o, hipStream_t s) {
+    using elem_t = typename K::elem_t;
+    using acc_t = typename K::acc_t;
     const int64_t slices = m.n_slices > m.n_slices_t ? m.n_slices : m.n_slices_t;
-    AttnBwdArgs<val_t> a;
+    typename K::Args a;
     a.nnz = m.nnz;
-    a.Q = static_cast<const val_t*>(o.Q); a.K = static_cast<const val_t*>(o.K); a.V = static_cast<const val_t*>(o.V);
-    a.dO = static_cast<const val_t*>(o.dO);
-    a.bias = static_cast<const val_t*>(o.bias);
-    a.lse = static_cast<const val_t*>(o.lse);
+    a.Q = static_cast<const elem_t*>(o.Q); a.K = static_cast<const elem_t*>(o.K); a.V = static_cast<const elem_t*>(o.V);
+    a.dO = static_cast<const elem_t*>(o.dO);
+    a.bias = static_cast<const acc_t*>(o.bias);
+    a.lse = static_cast<const acc_t*>(o.lse);
     a.ldq = o.ldq; a.ldk = o.ldk; a.ldv = o.ldv; a.lddo = o.lddo;
     a.d = o.d; a.dv = o.dv;
-    a.q_vec = rows_aligned16<val_t>(o.Q, o.ldq) ? 1 : 0;
-    a.k_vec = rows_aligned16<val_t>(o.K, o.ldk) ? 1 : 0;
-    a.v_vec = rows_aligned16<val_t>(o.V, o.ldv) ? 1 : 0;
-    a.do_vec = rows_aligned16<val_t>(o.dO, o.lddo) ? 1 : 0;
-    a.scale = val_t(m.scale);
-    a.sc = attn_bwd_scratch<val_t>(m.scratch, m.n_rows, slices, m.carry_ld);
+    a.q_vec = rows_aligned16<elem_t>(o.Q, o.ldq) ? 1 : 0;
+    a.k_vec = rows_aligned16<elem_t>(o.K, o.ldk) ? 1 : 0;
+    a.v_vec = rows_aligned16<elem_t>(o.V, o.ldv) ? 1 : 0;
+    a.do_vec = rows_aligned16<elem_t>(o.dO, o.lddo) ? 1 : 0;
+    a.scale = acc_t(m.scale);
+    a.sc = attn_bwd_scratch<acc_t>(m.scratch, m.n_rows, slices, m.carry_ld);
     a.delta = a.sc.delta;
     a.col_begin = 0; a.cols = 0;
     if (m.n_rows > 0 && m.nnz > 0) {
-        hipLaunchKernelGGL((attention_bwd_delta_kernel<val_t>), dim3(unsigned((int64_t(m.n_rows) * kDeltaLanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, m.n_rows,
-                           o.dv, a.dO, o.lddo, static_cast<const val_t*>(o.O), o.ldo, a.sc.delta);
+        K::delta(dim3(unsigned((int64_t(m.n_rows) * kDeltaLanes + kBlock - 1) / kBlock)), s, m.n_rows, o.dv, a.dO, o.lddo, static_cast<const elem_t*>(o.O),
+                 o.ldo, a.sc.delta);
         MI355_HIP_TRY(hipGetLastError());
     }
     const auto role = [&](auto which, void* out, int64_t ldout, int32_t width) {
-        a.out = static_cast<val_t*>(out);
+        a.out = static_cast<elem_t*>(out);
         a.ldout = ldout;
-        a.out_vec = rows_aligned16<val_t>(out, ldout) ? 1 : 0;
+        a.out_vec = rows_aligned16<elem_t>(out, ldout) ? 1 : 0;
         constexpr int ROLE = decltype(which)::value;
         if constexpr (ROLE == kBwdDQ) {
             a.n_rows = m.n_rows; a.n_slices = m.n_slices;
             a.Aj = m.Aj; a.perm = nullptr;
-            a.dbias = static_cast<val_t*>(o.dbias);
-            return attention_bwd_role<off_t, val_t, ROLE>(a, static_cast<const off_t*>(m.Ap), width, s);
+            a.dbias = static_cast<acc_t*>(o.dbias);
+            return attention_bwd_role<off_t, K, ROLE>(a, static_cast<const off_t*>(m.Ap), width, s);
         } else {
             a.n_rows = m.n_cols; a.n_slices = m.n_slices_t;
             a.perm = reinterpret_cast<const uint32_t*>(m.held);
             a.Aj = reinterpret_cast<const int32_t*>(m.held + size_t(m.nnz) * 4);
             a.dbias = nullptr;
-            return attention_bwd_role<off_t, val_t, ROLE>(a, reinterpret_cast<const off_t*>(m.held + size_t(m.nnz) * 8), width, s);
+            return attention_bwd_role<off_t, K, ROLE>(a, reinterpret_cast<const off_t*>(m.held + size_t(m.nnz) * 8), width, s);
         }
     };
     if (o.dQ)
@@ -603,20 +445,26 @@ int attention_bwd_launch(const mi355_spmv_attention_bwd& m, const AttnBwdOperand
 
 int attention_bwd_run(const mi355_spmv_attention_bwd& m, const AttnBwdOperands& o, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (m.off_type == MI355_OFF_I32)
-        return m.val_type == MI355_VAL_F64 ? attention_bwd_launch<int32_t, double>(m, o, s) : attention_bwd_launch<int32_t, float>(m, o, s);
-    return m.val_type == MI355_VAL_F64 ? attention_bwd_launch<int64_t, double>(m, o, s) : attention_bwd_launch<int64_t, float>(m, o, s);
+    const bool i32 = m.off_type == MI355_OFF_I32;
+    auto run = [&](auto off, auto kernels) { return attention_bwd_launch<decltype(off), decltype(kernels)>(m, o, s); };
+    auto either = [&](auto kernels) { return i32 ? run(int32_t(), kernels) : run(int64_t(), kernels); };
+    if (m.vec_type == MI355_VAL_F16) return either(AttnBwdHalfKernels<F16>());      // 16-bit matrices under fp32 everything else
+    if (m.vec_type == MI355_VAL_BF16) return either(AttnBwdHalfKernels<Bf16>());
+    return m.val_type == MI355_VAL_F64 ? either(AttnBwdKernels<double>()) : either(AttnBwdKernels<float>());
 }
 
 // create, execute, synchronise, destroy; every argument check comes before any device call
-int attention_bwd_one_shot(int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
+int attention_bwd_one_shot(int off_type, int val_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
                            const AttnBwdOperands& o, double scale, void* stream) {
-    const char* const who = "attention_bwd";
+    const char* const who = vec_type != val_type ? "attention_bwd_half" : "attention_bwd";
     set_error("%s", "");
-    if (const int st = attention_bwd_check_create(who, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, o.d < 1 ? 1 : o.d, o.dv < 1 ? 1 : o.dv)) return st;
+    const int32_t d1 = o.d < 1 ? 1 : o.d, dv1 = o.dv < 1 ? 1 : o.dv;
+    if (const int st = vec_type != val_type ? attention_bwd_check_create_half(who, off_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, d1, dv1)
+                                            : attention_bwd_check_create(who, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, d1, dv1))
+        return st;
     if (const int st = attention_bwd_check_execute(who, n_rows, n_cols, nnz, o.d, o.dv, o)) return st;
     mi355_spmv_attention_bwd* m = nullptr;
-    int st = attention_bwd_make(who, &m, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv, static_cast<hipStream_t>(stream));
+    int st = attention_bwd_make(who, &m, off_type, val_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv, static_cast<hipStream_t>(stream));
     if (st != MI355_SPMV_OK) return st;
     m->scale = scale;
     st = attention_bwd_run(*m, o, stream);
@@ -635,8 +483,26 @@ int mi355_spmv_attention_bwd_create(mi355_spmv_attention_bwd** out, int off_type
     if (!out) { set_error("attention_bwd_create: null object pointer (out)"); return MI355_SPMV_EINVAL; }
     *out = nullptr;
     if (const int st = attention_bwd_check_create("attention_bwd_create", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max)) return st;
-    return attention_bwd_make("attention_bwd_create", out, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max,
+    return attention_bwd_make("attention_bwd_create", out, off_type, val_type, val_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max,
                               static_cast<hipStream_t>(stream));
+}
+
+int mi355_spmv_attention_bwd_create_half(mi355_spmv_attention_bwd** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
+                                         const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max, void* stream) {
+    set_error("%s", "");
+    if (!out) { set_error("attention_bwd_create_half: null object pointer (out)"); return MI355_SPMV_EINVAL; }
+    *out = nullptr;
+    if (const int st = attention_bwd_check_create_half("attention_bwd_create_half", off_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max))
+        return st;
+    return attention_bwd_make("attention_bwd_create_half", out, off_type, MI355_VAL_F32, vec_type, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max,
+                              static_cast<hipStream_t>(stream));
+}
+
+int mi355_spmv_attention_bwd_get_types(const mi355_spmv_attention_bwd* m, int* val_type, int* vec_type) {
+    if (!m || !val_type || !vec_type) { set_error("attention_bwd_get_types: null argument"); return MI355_SPMV_EINVAL; }
+    *val_type = m->val_type;
+    *vec_type = m->vec_type;
+    return MI355_SPMV_OK;
 }
 
 int mi355_spmv_attention_bwd_set_scale(mi355_spmv_attention_bwd* m, double scale) {
@@ -664,8 +530,8 @@ int mi355_spmv_attention_bwd_get_info(const mi355_spmv_attention_bwd* m, mi355_s
     info->slice_len = kSliceLen;
     info->block_threads = kBlock;
     info->d_max = m->d_max; info->dv_max = m->dv_max;
-    info->widest_tile = attention_bwd_widest(m->val_type);
-    const int per_lane = attention_bwd_lane_cols(m->val_type);
+    info->widest_tile = attention_bwd_widest(m->vec_type);
+    const int per_lane = attention_bwd_lane_cols(m->vec_type);
     const int32_t widths[3] = {m->d_max, m->d_max, m->dv_max};      // the outputs of DQ, DK, DV
     for (int i = 0; i < 3; ++i) {
         info->passes[i] = (widths[i] + info->widest_tile - 1) / info->widest_tile;
@@ -678,7 +544,7 @@ int mi355_spmv_attention_bwd_get_info(const mi355_spmv_attention_bwd* m, mi355_s
     info->grid_blocks_t = slice_grid(m->n_slices_t);
     info->scratch_bytes = int64_t(m->scratch_bytes);
     info->held_bytes = int64_t(m->held_bytes);
-    snprintf(info->main_kernel, sizeof(info->main_kernel), "attention_bwd_slice_kernel");
+    snprintf(info->main_kernel, sizeof(info->main_kernel), m->vec_type != m->val_type ? "attention_bwd_half_slice_kernel" : "attention_bwd_slice_kernel");
     return MI355_SPMV_OK;
 }
 
@@ -693,11 +559,25 @@ int mi355_spmv_attention_bwd_destroy(mi355_spmv_attention_bwd* m) {
                                        double scale, const VAL* O, int64_t ldo, const VAL* dO, int64_t lddo, const VAL* lse, VAL* dQ, \
                                        int64_t lddq, VAL* dK, int64_t lddk, VAL* dV, int64_t lddv, VAL* dbias, void* stream) {  \
         const AttnBwdOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, dbias}; \
-        return attention_bwd_one_shot(OFFENUM, VALENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, o, scale, stream);               \
+        return attention_bwd_one_shot(OFFENUM, VALENUM, VALENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, o, scale, stream);      \
     }
 MI355_SPMV_DEFINE_ATTENTION_BWD(i32_f32, int32_t, MI355_OFF_I32, float, MI355_VAL_F32)
 MI355_SPMV_DEFINE_ATTENTION_BWD(i32_f64, int32_t, MI355_OFF_I32, double, MI355_VAL_F64)
 MI355_SPMV_DEFINE_ATTENTION_BWD(i64_f32, int64_t, MI355_OFF_I64, float, MI355_VAL_F32)
 MI355_SPMV_DEFINE_ATTENTION_BWD(i64_f64, int64_t, MI355_OFF_I64, double, MI355_VAL_F64)
+
+#define MI355_SPMV_DEFINE_ATTENTION_BWD_HALF(SUF, OFF, OFFENUM, VECENUM)                                                       \
+    int mi355_spmv_attention_bwd_half_##SUF(int32_t n_rows, int32_t n_cols, OFF nnz, const OFF* Ap, const int32_t* Aj, int32_t d, int32_t dv, \
+                                            const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,    \
+                                            const float* bias, double scale, const void* O, int64_t ldo, const void* dO, int64_t lddo, \
+                                            const float* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, \
+                                            float* dbias, void* stream) {                                                      \
+        const AttnBwdOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, dbias}; \
+        return attention_bwd_one_shot(OFFENUM, MI355_VAL_F32, VECENUM, n_rows, n_cols, (int64_t)nnz, Ap, Aj, o, scale, stream); \
+    }
+MI355_SPMV_DEFINE_ATTENTION_BWD_HALF(i32_f16, int32_t, MI355_OFF_I32, MI355_VAL_F16)
+MI355_SPMV_DEFINE_ATTENTION_BWD_HALF(i32_bf16, int32_t, MI355_OFF_I32, MI355_VAL_BF16)
+MI355_SPMV_DEFINE_ATTENTION_BWD_HALF(i64_f16, int64_t, MI355_OFF_I64, MI355_VAL_F16)
+MI355_SPMV_DEFINE_ATTENTION_BWD_HALF(i64_bf16, int64_t, MI355_OFF_I64, MI355_VAL_BF16)
 
 }  // extern "C"
