@@ -58,7 +58,7 @@ import numpy as np
 
 import attention_cases as ac
 import row_softmax_cases as rc
-from multi_cases import LANES_PER_SLOT, NP, SLICE_LEN, STEP, TILE, VEC, bits  # noqa: F401
+from multi_cases import LANES_PER_SLOT, NP, SLICE_LEN, STEP, TILE, VEC, bits, word_of  # noqa: F401
 
 CANARY = -777.25
 E_EXP = 3
@@ -466,49 +466,58 @@ def weight(g):
 # ---- the host program's batch file (tests/cpp/attention_bwd_sim.cpp, whose header comment has the records) ----------------
 NAN_BITS = ac.NAN_BITS
 ORDER = ("Q", "K", "V", "O", "dO")
+# What write_batch and read_results ask of a case.  plan_key: cases of one key share a matrix record; feat_type: the
+# MI355_VAL_* of the eight matrices; csr and ops: what csr() and operands() give; to_bits, which makes the bytes of a matrix
+# of ORDER of it; d_max, dv_max; dtype / side_dtype: an element of dQ, dK, dV / of dbias as the program writes it; nan,
+# canary, side_canary: the bit patterns that the padding of the inputs, all of dQ, dK, dV and dbias start with.
+Batch = collections.namedtuple("Batch", "plan_key feat_type csr ops to_bits d_max dv_max dtype side_dtype nan canary side_canary")
 
 
-def write_batch(path, cases):
+def batch_operands(c):
+    T = NP[c.val]
+    return Batch(plan_key(c), ac.VAL_TYPE[c.val], csr(c), operands(c), np.ascontiguousarray, D_MAX[c.val], DV_MAX[c.val], T, T, NAN_BITS[c.val],
+                 word_of(CANARY, T), word_of(CANARY, T))
+
+
+def write_batch(path, cases, operands=batch_operands):
     """Cases in plan order; returns them in the order their results come back."""
     words = lambda *v: struct.pack("<%dq" % len(v), *v)
     last = None
     with open(path, "wb") as f:
         for c in cases:
-            n_rows, n_cols, Ap, Aj, _ = csr(c)
-            if plan_key(c) != last:
-                last = plan_key(c)
-                f.write(words(1, ("i32", "i64").index(c.off), ("f32", "f64").index(c.val), n_rows, n_cols, len(Aj), D_MAX[c.val], DV_MAX[c.val]))
+            o = operands(c)
+            n_rows, n_cols, Ap, Aj, _ = o.csr
+            if o.plan_key != last:
+                last = o.plan_key
+                f.write(words(1, ("i32", "i64").index(c.off), o.feat_type, n_rows, n_cols, len(Aj), o.d_max, o.dv_max))
                 f.write(Ap.tobytes())
                 f.write(Aj.tobytes())
-            ops = operands(c)
-            f.write(words(4, c.d, c.dv, *c.pad, c.shift, int(ops["bias"] is not None), *c.need, int(c.want_dbias), NAN_BITS[c.val]))
+            bias = o.ops["bias"]
+            f.write(words(4, c.d, c.dv, *c.pad, c.shift, int(bias is not None), *c.need, int(c.want_dbias), o.nan, o.canary, o.side_canary))
             f.write(struct.pack("<d", c.scale))
             for name in ORDER:
-                f.write(np.ascontiguousarray(ops[name]).tobytes())
-            f.write(ops["lse"].tobytes())
-            if ops["bias"] is not None:
-                f.write(ops["bias"].tobytes())
+                f.write(o.to_bits(o.ops[name]).tobytes())
+            for a in (o.ops["lse"], bias):
+                if a is not None:
+                    assert a.dtype == o.side_dtype
+                    f.write(a.tobytes())
         f.write(words(0))
     return list(cases)
 
 
-def read_results(path, cases):
+def read_results(path, cases, operands=batch_operands):
     """[(status, padding elements of the outputs that lost their canary, dQ, dK, dV, dbias)] per case (None where not asked
     for); raises if the file is not complete."""
     out = []
     with open(path, "rb") as f:
         for c in cases:
+            o = operands(c)
             st, bad = struct.unpack("<2q", f.read(16))
-            n_rows, n_cols, Ap, Aj, _ = csr(c)
-            T = NP[c.val]
-            item = np.dtype(T).itemsize
+            n_rows, n_cols, Ap, Aj, _ = o.csr
             res = [st, bad]
-            for want, shape in ((c.need[0], (n_rows, c.d)), (c.need[1], (n_cols, c.d)), (c.need[2], (n_cols, c.dv)), (c.want_dbias, (len(Aj),))):
-                if want:
-                    count = int(np.prod(shape))
-                    res.append(np.frombuffer(f.read(count * item), dtype=T).reshape(shape))
-                else:
-                    res.append(None)
+            for want, shape, T in ((c.need[0], (n_rows, c.d), o.dtype), (c.need[1], (n_cols, c.d), o.dtype), (c.need[2], (n_cols, c.dv), o.dtype),
+                                   (c.want_dbias, (len(Aj),), o.side_dtype)):
+                res.append(np.frombuffer(f.read(int(np.prod(shape)) * np.dtype(T).itemsize), dtype=T).reshape(shape) if want else None)
             out.append(tuple(res))
         assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
     return out

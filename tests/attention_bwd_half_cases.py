@@ -50,9 +50,10 @@ What the outputs are held to, per kind of data (attention_bwd_cases' kinds):
            own tests (tests/test_gpu_attention_half.py on tests/attention_half_cases.py) separately hold |O' - O| to
            (1 + u16) B_O + u16 |O| + sub16 and |lse' - lse| to the forward table's lse bound.
 Padding columns of the inputs hold the type's NaN bits; the outputs start as a canary that must survive in their padding
-columns (and, on the device, behind every operand)."""
+columns (and, on the device, behind every operand).  The host program and its batch file are attention_bwd_cases'
+(tests/cpp/attention_bwd_sim.cpp): batch_operands() says what differs."""
 import collections
-import struct
+import functools
 
 import numpy as np
 
@@ -60,7 +61,7 @@ import attention_bwd_cases as bc
 import attention_cases as ac
 import attention_half_cases as hc
 from attention_bwd_cases import STRUCTURE_FAMILIES, structures, transpose  # noqa: F401
-from multi_cases import LANES_PER_SLOT, SLICE_LEN, STEP
+from multi_cases import LANES_PER_SLOT, SLICE_LEN, STEP, word_of
 from multi_half_cases import CANARY, NAN_BITS, VAL_TYPE, from_bits, to_bits  # noqa: F401
 
 VECS = ("f16", "bf16")
@@ -393,50 +394,11 @@ def weight(g):
                * (2 + (c.d + c.dv) // 16) + 3000 for c in g)
 
 
-# ---- the host program's batch file (tests/cpp/attention_bwd_half_sim.cpp, whose header comment has the records) ------------
-def write_batch(path, cases):
-    """Cases in plan order; returns them in the order their results come back."""
-    words = lambda *v: struct.pack("<%dq" % len(v), *v)
-    last = None
-    with open(path, "wb") as f:
-        for c in cases:
-            n_rows, n_cols, Ap, Aj, _ = csr(c)
-            if plan_key(c) != last:
-                last = plan_key(c)
-                f.write(words(1, OFFS.index(c.off), VAL_TYPE[c.vec], n_rows, n_cols, len(Aj), D_MAX, DV_MAX))
-                f.write(Ap.tobytes())
-                f.write(Aj.tobytes())
-            ops = operands(c)
-            f.write(words(4, c.d, c.dv, *c.pad, c.shift, int(ops["bias"] is not None), *c.need, int(c.want_dbias), NAN_BITS[c.vec],
-                          int(to_bits(np.float32(CANARY), c.vec).reshape(-1)[0])))
-            f.write(struct.pack("<d", c.scale))
-            for name in ORDER:
-                f.write(to_bits(ops[name], c.vec).tobytes())
-            assert ops["lse"].dtype == np.float32
-            f.write(ops["lse"].tobytes())
-            if ops["bias"] is not None:
-                assert ops["bias"].dtype == np.float32
-                f.write(ops["bias"].tobytes())
-        f.write(words(0))
-    return list(cases)
+# ---- the host program's batch file: attention_bwd_cases.write_batch and read_results on what differs here ------------------
+def batch_operands(c):
+    return bc.Batch(plan_key(c), VAL_TYPE[c.vec], csr(c), operands(c), lambda a: to_bits(a, c.vec), D_MAX, DV_MAX, np.uint16, np.float32,
+                    NAN_BITS[c.vec], int(to_bits(np.float32(CANARY), c.vec).reshape(-1)[0]), word_of(CANARY, np.float32))
 
 
-def read_results(path, cases):
-    """[(status, padding elements of the outputs that lost their canary, dQ, dK, dV bits, dbias)] per case (None where not
-    asked for); raises if the file is not complete."""
-    out = []
-    with open(path, "rb") as f:
-        for c in cases:
-            st, bad = struct.unpack("<2q", f.read(16))
-            n_rows, n_cols, Ap, Aj, _ = csr(c)
-            res = [st, bad]
-            for want, shape, T in ((c.need[0], (n_rows, c.d), np.uint16), (c.need[1], (n_cols, c.d), np.uint16), (c.need[2], (n_cols, c.dv), np.uint16),
-                                   (c.want_dbias, (len(Aj),), np.float32)):
-                if want:
-                    count = int(np.prod(shape))
-                    res.append(np.frombuffer(f.read(count * np.dtype(T).itemsize), dtype=T).reshape(shape))
-                else:
-                    res.append(None)
-            out.append(tuple(res))
-        assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
-    return out
+write_batch = functools.partial(bc.write_batch, operands=batch_operands)
+read_results = functools.partial(bc.read_results, operands=batch_operands)

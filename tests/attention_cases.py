@@ -389,45 +389,58 @@ def weight(g):
 
 # ---- the host program's batch file (tests/cpp/attention_sim.cpp, whose header comment has the records) -------------------
 NAN_BITS = {"f32": 0x7FC00000, "f64": 0x7FF8000000000000}
+VAL_TYPE = mc.VAL_TYPE
+# What write_batch and read_results ask of a case.  plan_key / data_key: cases of one key share a matrix / data record;
+# feat_type: the MI355_VAL_* of Q, K, V and O; Ap, Aj; Q, K, V (kf, kf and kv columns) and bias (or None) as operands() has
+# them, and to_bits, which makes the bytes of Q, K and V of them; dtype / side_dtype: an element of O / of lse as the
+# program writes it; nan, canary, side_nan: the bit patterns that the padding of Q, K and V, all of O and lse start with.
+Batch = collections.namedtuple("Batch", "plan_key data_key feat_type Ap Aj Q K V bias to_bits dtype side_dtype nan canary side_nan")
 
 
-def write_batch(path, cases):
+def batch_operands(c):
+    T = NP[c.val]
+    return Batch(plan_key(c), data_key(c), VAL_TYPE[c.val], *csr(c.matrix, c.off), *operands(c), np.ascontiguousarray, T, T, NAN_BITS[c.val],
+                 mc.word_of(CANARY, T), NAN_BITS[c.val])
+
+
+def write_batch(path, cases, operands=batch_operands):
     """Cases in plan order; returns them in the order their results come back."""
     words = lambda *v: struct.pack("<%dq" % len(v), *v)
     last, last_data = None, None
     with open(path, "wb") as f:
         for c in cases:
-            n_rows, n_cols = len(c.matrix.lens), c.matrix.n_cols
-            if plan_key(c) != last:
-                last, last_data = plan_key(c), None
-                Ap, Aj = csr(c.matrix, c.off)
-                f.write(words(1, ("i32", "i64").index(c.off), ("f32", "f64").index(c.val), n_rows, n_cols, int(Ap[-1]), c.shift[0], c.shift[1],
-                              KF, KV))
-                f.write(Ap.tobytes())
-                f.write(Aj.tobytes())
-            Q, K, V, bias = operands(c)
-            if data_key(c) != last_data:
-                last_data = data_key(c)
-                f.write(words(2, KF, KV, int(bias is not None)))
-                for a in (Q, K, V):
-                    f.write(np.ascontiguousarray(a).tobytes())
-                if bias is not None:
-                    f.write(bias.tobytes())
-            f.write(words(4, c.d, c.dv, c.c0, c.cv0, c.ldq, c.ldk, c.ldv, c.ldo, *c.shift[2:], int(c.want_lse), NAN_BITS[c.val]))
+            o = operands(c)
+            if o.plan_key != last:
+                last, last_data = o.plan_key, None
+                f.write(words(1, ("i32", "i64").index(c.off), o.feat_type, len(c.matrix.lens), c.matrix.n_cols, int(o.Ap[-1]), c.shift[0], c.shift[1],
+                              o.Q.shape[1], o.V.shape[1]))
+                f.write(o.Ap.tobytes())
+                f.write(o.Aj.tobytes())
+            if o.data_key != last_data:
+                last_data = o.data_key
+                f.write(words(2, o.Q.shape[1], o.V.shape[1], int(o.bias is not None)))
+                for a in (o.Q, o.K, o.V):
+                    f.write(o.to_bits(a).tobytes())
+                if o.bias is not None:
+                    assert o.bias.dtype == o.side_dtype
+                    f.write(o.bias.tobytes())
+            f.write(words(4, c.d, c.dv, c.c0, c.cv0, c.ldq, c.ldk, c.ldv, c.ldo, *c.shift[2:], int(c.want_lse), o.nan, o.canary, o.side_nan))
             f.write(struct.pack("<d", c.scale))
         f.write(words(0))
     return list(cases)
 
 
-def read_results(path, cases):
+def read_results(path, cases, operands=batch_operands):
     """[(status, padding elements of O that lost their canary, O, lse or None)] per case; raises if the file is not complete."""
     out = []
     with open(path, "rb") as f:
         for c in cases:
+            o = operands(c)
             st, bad, count = struct.unpack("<3q", f.read(24))
-            n_rows, T = len(c.matrix.lens), NP[c.val]
-            assert count == n_rows * (c.dv + 1), c.name
-            a = np.frombuffer(f.read(count * np.dtype(T).itemsize), dtype=T)
-            out.append((st, bad, a[:n_rows * c.dv].reshape(n_rows, c.dv), a[n_rows * c.dv:] if c.want_lse else None))
+            n_rows = len(c.matrix.lens)
+            assert count == n_rows * c.dv, c.name
+            O = np.frombuffer(f.read(count * np.dtype(o.dtype).itemsize), dtype=o.dtype).reshape(n_rows, c.dv)
+            lse = np.frombuffer(f.read(n_rows * np.dtype(o.side_dtype).itemsize), dtype=o.side_dtype)
+            out.append((st, bad, O, lse if c.want_lse else None))
         assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
     return out

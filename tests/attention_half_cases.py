@@ -38,9 +38,10 @@ What O and lse are held to, per kind of data (attention_cases' kinds):
            lse is fp32 throughout: attention_cases' fp32 bound unchanged.
 In EVERY case a row of one live entry must give O[r] = V[c] bit for bit (V[c] is widened exactly, multiplied by
 exp(0) = 1, divided by l = 1 and narrowed back), and on const / masked data lse[r] = v exactly.  Padding columns of Q, K
-and V hold the type's NaN bits; O starts as a canary that must survive in its padding columns; lse starts as NaN."""
+and V hold the type's NaN bits; O starts as a canary that must survive in its padding columns; lse starts as NaN.  The host
+program and its batch file are attention_cases' (tests/cpp/attention_sim.cpp): batch_operands() says what differs."""
 import collections
-import struct
+import functools
 
 import numpy as np
 
@@ -335,46 +336,11 @@ def weight(g):
     return sum((len(c.matrix.lens) + sum(c.matrix.lens)) * -(-c.dv // TILE) * (2 + c.d // 16) + 3000 for c in g)
 
 
-# ---- the host program's batch file (tests/cpp/attention_half_sim.cpp, whose header comment has the records) ----------------
-def write_batch(path, cases):
-    """Cases in plan order; returns them in the order their results come back."""
-    words = lambda *v: struct.pack("<%dq" % len(v), *v)
-    last, last_data = None, None
-    with open(path, "wb") as f:
-        for c in cases:
-            n_rows, n_cols = len(c.matrix.lens), c.matrix.n_cols
-            if plan_key(c) != last:
-                last, last_data = plan_key(c), None
-                Ap, Aj = csr(c.matrix, c.off)
-                f.write(words(1, OFFS.index(c.off), VAL_TYPE[c.vec], n_rows, n_cols, int(Ap[-1]), c.shift[0], c.shift[1], KF, KV))
-                f.write(Ap.tobytes())
-                f.write(Aj.tobytes())
-            Q, K, V, bias = operands(c)
-            if data_key(c) != last_data:
-                last_data = data_key(c)
-                f.write(words(2, KF, KV, int(bias is not None)))
-                for a in (Q, K, V):
-                    f.write(to_bits(a, c.vec).tobytes())
-                if bias is not None:
-                    assert bias.dtype == np.float32
-                    f.write(bias.tobytes())
-            f.write(words(4, c.d, c.dv, c.c0, c.cv0, c.ldq, c.ldk, c.ldv, c.ldo, *c.shift[2:], int(c.want_lse), NAN_BITS[c.vec],
-                          int(to_bits(np.float32(CANARY), c.vec).reshape(-1)[0])))
-            f.write(struct.pack("<d", c.scale))
-        f.write(words(0))
-    return list(cases)
+# ---- the host program's batch file: attention_cases.write_batch and read_results on what differs here ----------------------
+def batch_operands(c):
+    return ac.Batch(plan_key(c), data_key(c), VAL_TYPE[c.vec], *csr(c.matrix, c.off), *operands(c), lambda a: to_bits(a, c.vec), np.uint16,
+                    np.float32, NAN_BITS[c.vec], int(to_bits(np.float32(CANARY), c.vec).reshape(-1)[0]), ac.NAN_BITS["f32"])
 
 
-def read_results(path, cases):
-    """[(status, padding elements of O that lost their canary, O bits, lse or None)] per case; raises if the file is not complete."""
-    out = []
-    with open(path, "rb") as f:
-        for c in cases:
-            st, bad, count = struct.unpack("<3q", f.read(24))
-            n_rows = len(c.matrix.lens)
-            assert count == n_rows * c.dv, c.name
-            O = np.frombuffer(f.read(count * 2), dtype=np.uint16).reshape(n_rows, c.dv)
-            lse = np.frombuffer(f.read(n_rows * 4), dtype=np.float32)
-            out.append((st, bad, O, lse if c.want_lse else None))
-        assert struct.unpack("<q", f.read(8))[0] == -1 and f.read() == b""
-    return out
+write_batch = functools.partial(ac.write_batch, operands=batch_operands)
+read_results = functools.partial(ac.read_results, operands=batch_operands)

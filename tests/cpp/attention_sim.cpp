@@ -1,36 +1,39 @@
-// attention_sim — TEST CODE.  csrc/attention.hip, unchanged, compiled with the HOST compiler over tests/cpp/simt (a stand-in
-// <hip/hip_runtime.h> that runs every lane of a workgroup as a fiber) and driven through the real extern "C" entry points:
-// mi355_spmv_attention_create, then the object's set_scale / execute / destroy, so the slice passes, the fix-up and the
-// object's scratch run as well.  Built with -fsanitize=address,undefined (tests/cpp/attention_sim.mk).
+// attention_sim — TEST CODE.  csrc/attention.hip with what it includes (attention_slice_walk.inc, attention_half_kernel.hpp),
+// unchanged, compiled with the HOST compiler over tests/cpp/simt (a stand-in <hip/hip_runtime.h> that runs every lane of a
+// workgroup as a fiber) and driven through the real extern "C" entry points: mi355_spmv_attention_create or _create_half,
+// then the object's set_scale / execute / destroy, so the slice passes, the fix-up (with its one narrowing under 16-bit
+// features) and the object's scratch run as well.  One program for the two tables (tests/attention_cases.py,
+// tests/attention_half_cases.py): the matrix record says which create it is.  The program only moves bit patterns: element
+// sizes come from the type word and every fill value arrives as bits.  Built with -fsanitize=address,undefined
+// (tests/cpp/Makefile).
 //
 //   attention_sim BATCH OUT      reads records from BATCH, writes one result per run record to OUT
 //
 // Records are int64 words followed by raw little-endian arrays (tests/attention_cases.py writes them, write_batch):
-//   1  matrix    off_type val_type n_rows n_cols nnz ap_off aj_off d_max dv_max | Ap[n_rows + 1] Aj[nnz]
+//   1  matrix    off_type feat_type n_rows n_cols nnz ap_off aj_off d_max dv_max | Ap[n_rows + 1] Aj[nnz]
 //   2  data      kf kv has_bias | Q[n_rows * kf] K[n_cols * kf] V[n_cols * kv], and bias[nnz] with has_bias
-//   4  run       d dv c0 cv0 ldq ldk ldv ldo q_off k_off v_off bias_off o_off lse_off want_lse nan_bits | scale (1 double)
+//   4  run       d dv c0 cv0 ldq ldk ldv ldo q_off k_off v_off bias_off o_off lse_off want_lse nan_bits canary_bits
+//                side_nan_bits | scale (1 double)
 //   0  end
-// A run takes columns c0 .. c0 + d of Q and K and cv0 .. cv0 + dv of V.  *_off = elements between a 64-byte boundary and
-// the operand's base.  Every operand is an allocation of its own, exactly as long as the call may touch: (rows - 1) * ld +
-// width elements, the padding columns of Q, K and V filled with NaN and all of O with a canary — so a read or write one
-// element outside is a report, and a write into O's padding is counted.  A result is: status, the padding elements of O
-// that lost their canary, count = n_rows * (dv + 1), then O compact (n_rows x dv) and lse (n_rows; NaN where not asked).
-#include <cstring>
-#include <limits>
-#include <vector>
-
+// feat_type = the MI355_VAL_* of Q, K, V and O: F32 / F64 go through _create, F16 / BF16 through _create_half.  An element of
+// Q, K, V and O has that type's bytes; one of bias and lse (the side arrays) 8 under F64 and 4 otherwise.  A run takes
+// columns c0 .. c0 + d of Q and K and cv0 .. cv0 + dv of V.  *_off = elements between a 64-byte boundary and the operand's
+// base.  Every operand is an allocation of its own, exactly as long as the call may touch: (rows - 1) * ld + width elements,
+// the padding columns of Q, K and V filled with nan_bits, all of O with canary_bits and lse with side_nan_bits — so a read
+// or write one element outside is a report, and a write into O's padding is counted.  A result is: status, the padding
+// elements of O that lost their canary, count = n_rows * dv, then O compact (count elements) and lse (n_rows side elements;
+// side_nan_bits where not asked).
 #include "../../spmv-samples_amd/csrc/attention.hip"
 
 #define SIM_NAME "attention_sim"
 #include "sim_io.hpp"
+#include "sim_operand.hpp"
 
 namespace {
 
-constexpr double kCanary = -777.25;
-
 struct State {
-    int off_type = 0, val_type = 0;
-    size_t vb = 0;
+    int off_type = 0, feat_type = 0;
+    size_t eb = 0, sb = 0;          // bytes of an element of Q, K, V and O; of bias and lse
     int64_t n_rows = 0, n_cols = 0, nnz = 0;
     Buf Ap, Aj;
     int64_t kf = 0, kv = 0;
@@ -39,60 +42,31 @@ struct State {
     mi355_spmv_attention* plan = nullptr;
 };
 
-void fill(char* p, size_t elems, size_t vb, double v64, int64_t bits, bool use_bits) {
-    const float v32 = float(v64);
-    for (size_t i = 0; i < elems; ++i) {
-        if (use_bits) memcpy(p + i * vb, &bits, vb);
-        else memcpy(p + i * vb, vb == 8 ? static_cast<const void*>(&v64) : &v32, vb);
-    }
-}
-
-size_t span(int64_t rows, int64_t ld, int64_t width) { return rows > 0 ? size_t((rows - 1) * ld + width) : 0; }
-
-// columns col0 .. col0 + width of the full rows x full_ld array, as an operand of leading dimension ld with NaN padding
-void slice_operand(Buf& b, const std::vector<char>& full, int64_t rows, int64_t full_ld, int64_t col0, int64_t width, int64_t ld, size_t vb,
-                   int64_t off, int64_t nan_bits) {
-    b.alloc(span(rows, ld, width), vb, size_t(off));
-    fill(b.p, span(rows, ld, width), vb, 0.0, nan_bits, true);
-    for (int64_t r = 0; r < rows; ++r) memcpy(b.p + size_t(r * ld) * vb, full.data() + size_t(r * full_ld + col0) * vb, size_t(width) * vb);
-}
-
 void run(State& s) {
     const int64_t d = word(), dv = word(), c0 = word(), cv0 = word(), ldq = word(), ldk = word(), ldv = word(), ldo = word();
     const int64_t q_off = word(), k_off = word(), v_off = word(), b_off = word(), o_off = word(), lse_off = word();
-    const int64_t want_lse = word(), nan_bits = word();
+    const int64_t want_lse = word(), nan_bits = word(), canary_bits = word(), side_nan_bits = word();
     double scale;
     get(&scale, sizeof(scale));
     if (!s.plan || s.kf == 0 || c0 + d > s.kf || cv0 + dv > s.kv) { fprintf(stderr, "attention_sim: bad run record\n"); exit(4); }
-    Buf bq, bk, bv, bb, bo, bl;
-    slice_operand(bq, s.Q, s.n_rows, s.kf, c0, d, ldq, s.vb, q_off, nan_bits);
-    slice_operand(bk, s.K, s.n_cols, s.kf, c0, d, ldk, s.vb, k_off, nan_bits);
-    slice_operand(bv, s.V, s.n_cols, s.kv, cv0, dv, ldv, s.vb, v_off, nan_bits);
-    if (s.has_bias) {
-        bb.alloc(size_t(s.nnz), s.vb, size_t(b_off));
-        memcpy(bb.p, s.bias.data(), size_t(s.nnz) * s.vb);
-    }
-    bo.alloc(span(s.n_rows, ldo, dv), s.vb, size_t(o_off));
-    fill(bo.p, span(s.n_rows, ldo, dv), s.vb, kCanary, 0, false);
-    bl.alloc(size_t(s.n_rows), s.vb, size_t(lse_off));
-    fill(bl.p, size_t(s.n_rows), s.vb, 0.0, nan_bits, true);
+    Operand Q, K, V, bias, O, lse;
+    Q.make(s.n_rows, d, ldq, s.eb, q_off, nan_bits, s.Q.data(), s.kf, c0);
+    K.make(s.n_cols, d, ldk, s.eb, k_off, nan_bits, s.K.data(), s.kf, c0);
+    V.make(s.n_cols, dv, ldv, s.eb, v_off, nan_bits, s.V.data(), s.kv, cv0);
+    if (s.has_bias) bias.make(s.nnz, 1, 1, s.sb, b_off, 0, s.bias.data(), 1);
+    O.make(s.n_rows, dv, ldo, s.eb, o_off, canary_bits);
+    lse.make(s.n_rows, 1, 1, s.sb, lse_off, side_nan_bits);
     int64_t st = mi355_spmv_attention_set_scale(s.plan, scale);
     if (st == MI355_SPMV_OK)
-        st = mi355_spmv_attention_execute(s.plan, int32_t(d), int32_t(dv), bq.p, ldq, bk.p, ldk, bv.p, ldv, s.has_bias ? bb.p : nullptr, bo.p, ldo,
-                                          want_lse ? bl.p : nullptr, nullptr);
+        st = mi355_spmv_attention_execute(s.plan, int32_t(d), int32_t(dv), Q.p, ldq, K.p, ldk, V.p, ldv, bias.p, O.p, ldo, want_lse ? lse.p : nullptr,
+                                          nullptr);
     if (st != MI355_SPMV_OK) fprintf(stderr, "attention_sim: execute -> %d (%s)\n", int(st), mi355::g_error);
-    // the canary in O's padding columns
-    int64_t bad = 0;
-    std::vector<char> canary(s.vb);
-    fill(canary.data(), 1, s.vb, kCanary, 0, false);
-    for (int64_t r = 0; r + 1 < s.n_rows; ++r)
-        for (int64_t j = dv; j < ldo; ++j) bad += memcmp(bo.p + size_t(r * ldo + j) * s.vb, canary.data(), s.vb) != 0;
-    const int64_t count = s.n_rows * (dv + 1);
+    const int64_t bad = O.lost(), count = s.n_rows * dv;
     put(&st, 8);
     put(&bad, 8);
     put(&count, 8);
-    for (int64_t r = 0; r < s.n_rows; ++r) put(bo.p + size_t(r * ldo) * s.vb, size_t(dv) * s.vb);
-    put(bl.p, size_t(s.n_rows) * s.vb);
+    O.write();
+    lse.write();
 }
 
 }  // namespace
@@ -108,31 +82,40 @@ int main(int argc, char** argv) {
         if (tag == 0) break;
         if (tag == 1) {
             if (s.plan) { mi355_spmv_attention_destroy(s.plan); s.plan = nullptr; }
-            s.off_type = int(word()); s.val_type = int(word());
+            s.off_type = int(word()); s.feat_type = int(word());
             s.n_rows = word(); s.n_cols = word(); s.nnz = word();
             const int64_t ap_off = word(), aj_off = word(), d_max = word(), dv_max = word();
             const size_t ob = s.off_type == MI355_OFF_I64 ? 8 : 4;
-            s.vb = s.val_type == MI355_VAL_F64 ? 8 : 4;
+            const bool half = s.feat_type == MI355_VAL_F16 || s.feat_type == MI355_VAL_BF16;
+            s.eb = type_bytes(s.feat_type);
+            s.sb = s.feat_type == MI355_VAL_F64 ? 8 : 4;
             s.kf = 0;
             s.Ap.alloc(size_t(s.n_rows) + 1, ob, size_t(ap_off));
             s.Aj.alloc(size_t(s.nnz), 4, size_t(aj_off));
             get(s.Ap.p, (size_t(s.n_rows) + 1) * ob);
             get(s.Aj.p, size_t(s.nnz) * 4);
-            const int st = mi355_spmv_attention_create(int32_t(s.n_rows), int32_t(s.n_cols), s.nnz, s.Ap.p, reinterpret_cast<const int32_t*>(s.Aj.p),
-                                                       s.off_type, s.val_type, int32_t(d_max), int32_t(dv_max), &s.plan);
-            if (st != MI355_SPMV_OK) { fprintf(stderr, "attention_sim: create -> %d (%s)\n", st, mi355::g_error); return 5; }
+            const int32_t* Aj = reinterpret_cast<const int32_t*>(s.Aj.p);
+            const int st = half ? mi355_spmv_attention_create_half(&s.plan, s.off_type, s.feat_type, int32_t(s.n_rows), int32_t(s.n_cols), s.nnz, s.Ap.p,
+                                                                   Aj, int32_t(d_max), int32_t(dv_max))
+                                : mi355_spmv_attention_create(int32_t(s.n_rows), int32_t(s.n_cols), s.nnz, s.Ap.p, Aj, s.off_type, s.feat_type,
+                                                              int32_t(d_max), int32_t(dv_max), &s.plan);
+            if (st != MI355_SPMV_OK) { fprintf(stderr, "attention_sim: create (type %d) -> %d (%s)\n", s.feat_type, st, mi355::g_error); return 5; }
             mi355_spmv_attention_info info;
+            int val_type = -1, vec_type = -1;
             if (mi355_spmv_attention_get_info(s.plan, &info) != MI355_SPMV_OK || info.n_slices != (s.n_rows + s.nnz + info.slice_len - 1) / info.slice_len ||
-                info.passes != (dv_max + info.widest_tile - 1) / info.widest_tile) {
+                info.passes != (dv_max + info.widest_tile - 1) / info.widest_tile ||
+                (half && (info.widest_tile != 64 || info.val_type != MI355_VAL_F32 ||
+                          mi355_spmv_attention_get_types(s.plan, &val_type, &vec_type) != MI355_SPMV_OK || val_type != MI355_VAL_F32 ||
+                          vec_type != s.feat_type))) {
                 fprintf(stderr, "attention_sim: get_info\n");
                 return 5;
             }
         } else if (tag == 2) {
             s.kf = word(); s.kv = word(); s.has_bias = word() != 0;
-            s.Q.resize(size_t(s.n_rows * s.kf) * s.vb);
-            s.K.resize(size_t(s.n_cols * s.kf) * s.vb);
-            s.V.resize(size_t(s.n_cols * s.kv) * s.vb);
-            s.bias.resize(s.has_bias ? size_t(s.nnz) * s.vb : 0);
+            s.Q.resize(size_t(s.n_rows * s.kf) * s.eb);
+            s.K.resize(size_t(s.n_cols * s.kf) * s.eb);
+            s.V.resize(size_t(s.n_cols * s.kv) * s.eb);
+            s.bias.resize(s.has_bias ? size_t(s.nnz) * s.sb : 0);
             get(s.Q.data(), s.Q.size());
             get(s.K.data(), s.K.size());
             get(s.V.data(), s.V.size());

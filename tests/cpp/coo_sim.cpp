@@ -2,7 +2,7 @@
 // <hip/hip_runtime.h> that runs every lane of a workgroup as a fiber) and driven through the real extern "C" entry points:
 // mi355_spmv_coo_to_csr, mi355_spmv_coo_to_csr_symmetric (after mi355_spmv_coo_symmetric_nnz) and mi355_spmv_csr_transpose,
 // each with its size query first.  Because the unit is included as text, the kernels of mi355::coo are also launched alone,
-// at sizes the entry points reach only with 2^28 entries.  Built with -fsanitize=address,undefined (tests/cpp/coo_sim.mk).
+// at sizes the entry points reach only with 2^28 entries.  Built with -fsanitize=address,undefined (tests/cpp/Makefile).
 //
 //   coo_sim BATCH OUT      reads records from BATCH, writes one result per record to OUT
 //

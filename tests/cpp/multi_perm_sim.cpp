@@ -2,7 +2,7 @@
 // unchanged, compiled with the HOST compiler over tests/cpp/simt and driven through the real entry points:
 // mi355_spmv_multi_create_permuted / _execute / _destroy, and beside it, in the same program, mi355_spmv_multi_create on the
 // same structure executed on Ax[perm] materialised.  Both results are written; tests/test_multi_perm_sim_cpu.py holds
-// them to each other bit for bit.  Built with -fsanitize=address,undefined (tests/cpp/multi_perm_sim.mk).
+// them to each other bit for bit.  Built with -fsanitize=address,undefined (tests/cpp/Makefile).
 //
 //   multi_perm_sim BATCH OUT
 //

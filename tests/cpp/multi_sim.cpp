@@ -28,6 +28,7 @@
 // element outside is a report.  *_bits = the bit pattern of a value of vec_type: padding columns of X hold x_pad_bits,
 // of Y canary_bits; with y0_poison the k columns of Y hold y_poison_bits.
 // A result is: status, count = n_rows * ldy, then Y as count values (the missing tail of the last row as canary).
+// type_bytes and fill are sim_operand.hpp's.
 #include <cstring>
 #include <vector>
 
@@ -35,6 +36,7 @@
 
 #define SIM_NAME "multi_sim"
 #include "sim_io.hpp"
+#include "sim_operand.hpp"
 
 namespace {
 
@@ -48,18 +50,6 @@ struct State {
     std::vector<char> Y0;               // kf columns, dense
     mi355_spmv_multi* plan = nullptr;
 };
-
-size_t type_bytes(int type) { return type == MI355_VAL_F64 ? 8 : type == MI355_VAL_F16 || type == MI355_VAL_BF16 ? 2 : 4; }
-
-// n elements at dst, each the low sizeof(W) bytes of bits (a copy of constant size: no call per element)
-template <typename W>
-void fill_as(char* dst, size_t n, int64_t bits) {
-    const W w = W(bits);
-    for (size_t i = 0; i < n; ++i) memcpy(dst + i * sizeof(W), &w, sizeof(W));
-}
-void fill(char* dst, size_t n, int64_t bits, size_t eb) {
-    eb == 8 ? fill_as<uint64_t>(dst, n, bits) : eb == 4 ? fill_as<uint32_t>(dst, n, bits) : fill_as<uint16_t>(dst, n, bits);
-}
 
 // `rows` rows of k elements at stride ld in dst, every other element pad_bits: columns c0 .. c0 + k of the dense src, or
 // row_bits where there is no src

@@ -2,7 +2,7 @@
 // stand-in <hip/hip_runtime.h> that runs every lane of a workgroup as a fiber) and driven through the real extern "C"
 // entry points: mi355_spmv_row_softmax_create, then the object's set_scale / execute / backward / destroy, so the three
 // launches of an execute and the object's scratch run as well.  Built with -fsanitize=address,undefined
-// (tests/cpp/row_softmax_sim.mk).
+// (tests/cpp/Makefile).
 //
 //   row_softmax_sim BATCH OUT      reads records from BATCH, writes one result per run record to OUT
 //

@@ -1,5 +1,5 @@
-// sim_io.hpp — TEST CODE shared by multi_sim and sddmm_sim (each defines SIM_NAME, its own name in its messages, and
-// includes csrc/multi.hip or csrc/sddmm.hip first): the two functions that those call and the library defines in other
+// sim_io.hpp — TEST CODE shared by the host simulation programs (each defines SIM_NAME, its own name in its messages, and
+// includes its unit of csrc/ first): the two functions that those call and the library defines in other
 // units, an allocation placed against a 64-byte boundary, and the reading and writing of the batch and result files.
 #pragma once
 

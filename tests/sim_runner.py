@@ -1,12 +1,13 @@
 """What the host simulations' test files (tests/test_*_sim_cpu.py) share: building a program of tests/cpp with the
-sanitizers, dealing a table's plan groups to batches, and running the batches as concurrent child processes under a time
-limit.  Nothing is loaded into this process, and the children's environment is this process's own (the sanitizer runtimes
-are linked statically).  Each test file keeps its table, its geometry asserts, its tests and its weight function (the three
-multi-vector files: the one multi_cases.weight)."""
+sanitizers, dealing a table's plan groups to batches, running the batches as concurrent child processes under a time
+limit, and comparing two results bit for bit.  Nothing is loaded into this process, and the children's environment is this
+process's own (the sanitizer runtimes are linked statically).  Each test file keeps its table, its geometry asserts, its
+tests and its weight function (the three multi-vector files: the one multi_cases.weight)."""
 import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -16,14 +17,18 @@ TIME_LIMIT = 900        # seconds per child: ~30 x what the slowest batch of any
 
 
 def build(target):
-    """The program, built on demand by the rule of tests/cpp/Makefile (its SIM_SAN flags).  Skips only where the host
-    compiler cannot link with those flags at all (a trivial program, the same flags); any other failure to build is a
-    failure."""
+    """The program, built on demand by the one rule of tests/cpp/Makefile for every host simulation (its SIM_SAN flags).
+    Skips only where the host compiler cannot link with those flags at all (a trivial program, the same flags); any other
+    failure to build is a failure."""
     probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
     if probe.returncode != 0:
         pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
     subprocess.run(["make", "-s", "-C", CPP, target], check=True)
     return os.path.join(CPP, target)
+
+
+def same_bits(x, y):
+    return np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
 
 
 def child_env():

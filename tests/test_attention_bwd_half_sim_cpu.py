@@ -1,6 +1,6 @@
 """csrc/attention_bwd.hip with its 16-bit kernels (attention_bwd_half_kernel.hpp, attention_bwd_slice_walk.inc) executed on the
-host, lane by lane (tests/cpp/attention_bwd_half_sim.cpp over tests/cpp/simt): the kernel source and its launch path,
-unchanged, built with the address and undefined-behaviour sanitizers as a stand-alone program and run over the WHOLE table of
+host, lane by lane (tests/cpp/attention_bwd_sim.cpp, the fp32 / fp64 table's program, over tests/cpp/simt): the kernel source
+and its launch path, unchanged, built with the address and undefined-behaviour sanitizers as a stand-alone program and run over the WHOLE table of
 tests/attention_bwd_half_cases.py — every structure as A and as A^T, every width pair, both offset widths, both 16-bit types
 — through the real create_half (whose transpose is csrc/coo_csr.hip compiled the same way) / set_scale / execute / destroy.
 Every operand is an allocation exactly as long as the call may touch.  Each result is checked exactly as the device run of
@@ -8,10 +8,6 @@ the same table is (tests/test_gpu_attention_bwd_half.py), the children must end 
 to stderr (where the sanitizers and the stand-in's out-of-step check report), and each runs under a time limit.  Nothing is
 loaded into this process, and the children's environment is this process's own (the sanitizer runtimes are linked
 statically)."""
-import os
-import subprocess
-
-import numpy as np
 import pytest
 
 import attention_bwd_half_cases as bh
@@ -20,19 +16,11 @@ import sim_runner as sr
 RATIOS = []
 
 
-def build():
-    probe = subprocess.run(["make", "-s", "-C", sr.CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", sr.CPP, "-f", "attention_bwd_half_sim.mk", "attention_bwd_half_sim"], check=True)
-    return os.path.join(sr.CPP, "attention_bwd_half_sim")
-
-
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, bad canaries, dQ, dK, dV, dbias)}, and the
     children's reports."""
-    exe = build()
+    exe = sr.build("attention_bwd_sim")
     return sr.run_table(exe, tmp_path_factory.mktemp("attention_bwd_half_sim"), sr.groups_by(bh.table(), bh.plan_key), bh.weight, bh.write_batch,
                         bh.read_results)
 
@@ -64,24 +52,20 @@ def test_the_largest_error_over_bound_of_the_real_cases(run):
     assert max(RATIOS) <= 1.0
 
 
-def same_bits(x, y):
-    return np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
-
-
 def test_unaligned_operands_equal_aligned_ones_bit_for_bit(run):
     results = run[0]
     pairs = bh.alignment_pairs()
     assert pairs
     for a, b in pairs:
         for i in range(2, 6):
-            assert same_bits(results[a.name][i], results[b.name][i]), b.name
+            assert sr.same_bits(results[a.name][i], results[b.name][i]), b.name
 
 
 def test_two_executes_give_equal_bits(run):
     results = run[0]
     for a, b in bh.repeat_pairs():
         for i in range(2, 6):
-            assert same_bits(results[a.name][i], results[b.name][i]), a.name
+            assert sr.same_bits(results[a.name][i], results[b.name][i]), a.name
 
 
 def test_each_output_alone_equals_the_all_three_execute_and_dbias_leaves_dq_unchanged(run):
@@ -91,4 +75,4 @@ def test_each_output_alone_equals_the_all_three_execute_and_dbias_leaves_dq_unch
     for both, dq, dk, dv in groups:
         assert results[dq.name][5] is None and results[both.name][5] is not None
         for alone, i in ((dq, 2), (dk, 3), (dv, 4)):
-            assert same_bits(results[both.name][i], results[alone.name][i]), alone.name
+            assert sr.same_bits(results[both.name][i], results[alone.name][i]), alone.name

@@ -7,29 +7,17 @@ the device run of the same table is (tests/test_gpu_attention_bwd.py), the child
 written nothing to stderr (where the sanitizers and the stand-in's out-of-step check report), and each runs under a time
 limit.  Nothing is loaded into this process, and the children's environment is this process's own (the sanitizer runtimes are
 linked statically)."""
-import os
-import subprocess
-
-import numpy as np
 import pytest
 
 import attention_bwd_cases as bc
 import sim_runner as sr
 
 
-def build():
-    probe = subprocess.run(["make", "-s", "-C", sr.CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", sr.CPP, "-f", "attention_bwd_sim.mk", "attention_bwd_sim"], check=True)
-    return os.path.join(sr.CPP, "attention_bwd_sim")
-
-
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, bad canaries, dQ, dK, dV, dbias)}, and the
     children's reports."""
-    exe = build()
+    exe = sr.build("attention_bwd_sim")
     return sr.run_table(exe, tmp_path_factory.mktemp("attention_bwd_sim"), sr.groups_by(bc.table(), bc.plan_key), bc.weight, bc.write_batch,
                         bc.read_results)
 
@@ -52,24 +40,20 @@ def test_family(run, family):
         bc.check(c, dQ, dK, dV, dbias)
 
 
-def same_bits(x, y):
-    return np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
-
-
 def test_unaligned_operands_equal_aligned_ones_bit_for_bit(run):
     results = run[0]
     pairs = bc.alignment_pairs()
     assert pairs
     for a, b in pairs:
         for i in range(2, 6):
-            assert same_bits(results[a.name][i], results[b.name][i]), b.name
+            assert sr.same_bits(results[a.name][i], results[b.name][i]), b.name
 
 
 def test_two_executes_give_equal_bits(run):
     results = run[0]
     for a, b in bc.repeat_pairs():
         for i in range(2, 6):
-            assert same_bits(results[a.name][i], results[b.name][i]), a.name
+            assert sr.same_bits(results[a.name][i], results[b.name][i]), a.name
 
 
 def test_each_output_alone_equals_the_all_three_execute_and_dbias_leaves_dq_unchanged(run):
@@ -79,4 +63,4 @@ def test_each_output_alone_equals_the_all_three_execute_and_dbias_leaves_dq_unch
     for both, dq, dk, dv in groups:
         assert results[dq.name][5] is None and results[both.name][5] is not None
         for alone, i in ((dq, 2), (dk, 3), (dv, 4)):
-            assert same_bits(results[both.name][i], results[alone.name][i]), alone.name
+            assert sr.same_bits(results[both.name][i], results[alone.name][i]), alone.name

@@ -1,6 +1,6 @@
 """csrc/attention.hip's 16-bit kind (csrc/attention_half_kernel.hpp over csrc/attention_slice_walk.inc) executed on the host,
-lane by lane (tests/cpp/attention_half_sim.cpp over tests/cpp/simt): the kernel source and its launch path, unchanged, built
-with the address and undefined-behaviour sanitizers and run over the WHOLE table of tests/attention_half_cases.py — every
+lane by lane (tests/cpp/attention_sim.cpp, the fp32 / fp64 table's program, over tests/cpp/simt): the kernel source and its
+launch path, unchanged, built with the address and undefined-behaviour sanitizers and run over the WHOLE table of tests/attention_half_cases.py — every
 structure, every width, both offset widths, both 16-bit types — through the real create_half / set_scale / execute /
 destroy.  Every operand is an allocation exactly as long as the call may touch.  Each result is checked exactly as the device
 run of the same table is (tests/test_gpu_attention_half.py), the children must end with status 0 and must have written
@@ -8,31 +8,18 @@ nothing to stderr (where the sanitizers and the stand-in's out-of-step check rep
 Nothing is loaded into this process, and the children's environment is this process's own (the sanitizer runtimes are
 linked statically).
 
-The program has a rule of its own, tests/cpp/attention_half_sim.mk (which includes tests/cpp/Makefile), built behind that
-Makefile's sanitizer_probe."""
-import os
-import subprocess
-
-import numpy as np
+sim_runner.build makes the program by the rule of tests/cpp/Makefile, behind that Makefile's sanitizer_probe."""
 import pytest
 
 import attention_half_cases as hc
 import sim_runner as sr
 
 
-def build():
-    probe = subprocess.run(["make", "-s", "-C", sr.CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", sr.CPP, "-f", "attention_half_sim.mk", "attention_half_sim"], check=True)
-    return os.path.join(sr.CPP, "attention_half_sim")
-
-
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, bad canaries, O bits, lse)}, and the
     children's reports."""
-    exe = build()
+    exe = sr.build("attention_sim")
     unit, cut, common, cols = sr.source("attention.hip"), sr.source("slice_cut.hpp"), sr.source("common.hpp"), sr.source("half_cols.hpp")
     assert sr.kernel_constant(unit, "kAttentionSlice") == sr.kernel_constant(cut, "kSliceLen") == hc.SLICE_LEN
     assert sr.kernel_constant(unit, "kAttentionGroupsMax") == sr.kernel_constant(cut, "kSliceGroupsMax") == max(hc.LANES_PER_SLOT)
@@ -61,19 +48,15 @@ def test_family(run, family):
         hc.check(c, O, lse)
 
 
-def same_bits(x, y):
-    return np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
-
-
 def test_unaligned_operands_equal_aligned_ones_bit_for_bit(run):
     results = run[0]
     pairs = hc.alignment_pairs()
     assert pairs
     for a, b in pairs:
-        assert same_bits(results[a.name][2], results[b.name][2]) and same_bits(results[a.name][3], results[b.name][3]), b.name
+        assert sr.same_bits(results[a.name][2], results[b.name][2]) and sr.same_bits(results[a.name][3], results[b.name][3]), b.name
 
 
 def test_two_executes_give_equal_bits(run):
     results = run[0]
     for a, b in hc.repeat_pairs():
-        assert same_bits(results[a.name][2], results[b.name][2]) and same_bits(results[a.name][3], results[b.name][3]), a.name
+        assert sr.same_bits(results[a.name][2], results[b.name][2]) and sr.same_bits(results[a.name][3], results[b.name][3]), a.name

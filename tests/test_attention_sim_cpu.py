@@ -7,31 +7,19 @@ and must have written nothing to stderr (where the sanitizers and the stand-in's
 under a time limit.  Nothing is loaded into this process, and the children's environment is this process's own (the
 sanitizer runtimes are linked statically).
 
-The program has a rule of its own, tests/cpp/attention_sim.mk (which includes tests/cpp/Makefile), built behind that
-Makefile's sanitizer_probe."""
-import os
-import subprocess
-
-import numpy as np
+The program is the 16-bit table's too (tests/test_attention_half_sim_cpu.py); sim_runner.build makes it by the rule of
+tests/cpp/Makefile, behind that Makefile's sanitizer_probe."""
 import pytest
 
 import attention_cases as ac
 import sim_runner as sr
 
 
-def build():
-    probe = subprocess.run(["make", "-s", "-C", sr.CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", sr.CPP, "-f", "attention_sim.mk", "attention_sim"], check=True)
-    return os.path.join(sr.CPP, "attention_sim")
-
-
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, bad canaries, O, lse)}, and the
     children's reports."""
-    exe = build()
+    exe = sr.build("attention_sim")
     unit, cut, common = sr.source("attention.hip"), sr.source("slice_cut.hpp"), sr.source("common.hpp")
     assert sr.kernel_constant(unit, "kAttentionSlice") == sr.kernel_constant(cut, "kSliceLen") == ac.SLICE_LEN
     assert sr.kernel_constant(unit, "kAttentionGroupsMax") == sr.kernel_constant(cut, "kSliceGroupsMax") == max(ac.LANES_PER_SLOT)
@@ -59,19 +47,15 @@ def test_family(run, family):
         ac.check(c, O, lse)
 
 
-def same_bits(x, y):
-    return np.array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
-
-
 def test_unaligned_operands_equal_aligned_ones_bit_for_bit(run):
     results = run[0]
     pairs = ac.alignment_pairs()
     assert pairs
     for a, b in pairs:
-        assert same_bits(results[a.name][2], results[b.name][2]) and same_bits(results[a.name][3], results[b.name][3]), b.name
+        assert sr.same_bits(results[a.name][2], results[b.name][2]) and sr.same_bits(results[a.name][3], results[b.name][3]), b.name
 
 
 def test_two_executes_give_equal_bits(run):
     results = run[0]
     for a, b in ac.repeat_pairs():
-        assert same_bits(results[a.name][2], results[b.name][2]) and same_bits(results[a.name][3], results[b.name][3]), a.name
+        assert sr.same_bits(results[a.name][2], results[b.name][2]) and sr.same_bits(results[a.name][3], results[b.name][3]), a.name

@@ -13,9 +13,7 @@ What the host execution cannot show is stated in the header of tests/cpp/coo_sim
 wave provides.  tests/test_gpu_coo_edges.py runs the same table on the device.  profiles/coo_edges_mutations.txt records the
 one-token errors this file catches.
 
-The program has a rule of its own, tests/cpp/coo_sim.mk (which includes tests/cpp/Makefile), built behind that Makefile's
-sanitizer_probe."""
-import os
+sim_runner.build makes the program by the rule of tests/cpp/Makefile, behind that Makefile's sanitizer_probe."""
 import re
 import subprocess
 
@@ -34,17 +32,9 @@ assert sr.kernel_constant(_unit, "kScanItems") * sr.kernel_constant(_common, "kB
 assert re.search(r"constexpr int kTile = kBlock \* kSteps;", _unit) and re.search(r"constexpr int kScanChunk = kBlock \* kScanItems;", _unit)
 
 
-def build():
-    probe = subprocess.run(["make", "-s", "-C", sr.CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", sr.CPP, "-f", "coo_sim.mk", "coo_sim"], check=True)
-    return os.path.join(sr.CPP, "coo_sim")
-
-
 @pytest.fixture(scope="module")
 def exe():
-    return build()
+    return sr.build("coo_sim")
 
 
 @pytest.fixture(scope="module")

@@ -8,9 +8,7 @@ the same program — the same walk on the same values, so any difference is a bu
 must have written nothing to stderr (where the sanitizers and the stand-in's out-of-step check report).  Nothing is loaded
 into this process, and the children's environment is this process's own (the sanitizer runtimes are linked statically).
 
-The program has a rule of its own, tests/cpp/multi_perm_sim.mk (which includes tests/cpp/Makefile), built behind that
-Makefile's sanitizer_probe."""
-import os
+sim_runner.build makes the program by the rule of tests/cpp/Makefile, behind that Makefile's sanitizer_probe."""
 import subprocess
 
 import pytest
@@ -20,17 +18,9 @@ import multi_perm_cases as pc
 import sim_runner as sr
 
 
-def build():
-    probe = subprocess.run(["make", "-s", "-C", sr.CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", sr.CPP, "-f", "multi_perm_sim.mk", "multi_perm_sim"], check=True)
-    return os.path.join(sr.CPP, "multi_perm_sim")
-
-
 @pytest.fixture(scope="module")
 def exe():
-    path = build()
+    path = sr.build("multi_perm_sim")
     multi, common = sr.source("multi.hip"), sr.source("common.hpp")
     assert sr.kernel_constant(multi, "kMultiSlice") == mc.SLICE_LEN
     assert sr.kernel_constant(common, "kWave") == mc.STEP

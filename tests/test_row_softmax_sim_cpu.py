@@ -7,10 +7,7 @@ stderr (where the sanitizers and the stand-in's out-of-step check report), and e
 loaded into this process, and the children's environment is this process's own (the sanitizer runtimes are linked
 statically).
 
-The program has a rule of its own, tests/cpp/row_softmax_sim.mk (which includes tests/cpp/Makefile), built behind that
-Makefile's sanitizer_probe."""
-import os
-import subprocess
+sim_runner.build makes the program by the rule of tests/cpp/Makefile, behind that Makefile's sanitizer_probe."""
 
 import numpy as np
 import pytest
@@ -19,18 +16,10 @@ import row_softmax_cases as rc
 import sim_runner as sr
 
 
-def build():
-    probe = subprocess.run(["make", "-s", "-C", sr.CPP, "sanitizer_probe"], capture_output=True, text=True)
-    if probe.returncode != 0:
-        pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", sr.CPP, "-f", "row_softmax_sim.mk", "row_softmax_sim"], check=True)
-    return os.path.join(sr.CPP, "row_softmax_sim")
-
-
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
     """Every case of the table through the sanitized program: {case name: (status, out)}, and the children's reports."""
-    exe = build()
+    exe = sr.build("row_softmax_sim")
     unit, common = sr.source("row_softmax.hip"), sr.source("common.hpp")
     assert sr.kernel_constant(unit, "kRowSoftmaxSlice") == rc.SLICE_LEN
     assert sr.kernel_constant(unit, "kRowSoftmaxGroups") == rc.GROUPS
