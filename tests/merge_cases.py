@@ -8,7 +8,8 @@ a tile walks items T * IPT .. T * IPT + IPT of it, 64 threads are a wave, and a 
 MI355_MERGE_TPS consecutive tiles.  (BLOCK, IPT) is (256, 8) or, under MI355_MERGE_BLOCK=512 and plus-times, (512, 4).
 
 census() restates that DECOMPOSITION only (which thread sees which items, and what the kernel's predicates make of
-them); it never computes a y.  Expected values come from the serial oracle alone.
+them); it never computes a y.  Expected values come from the serial oracle alone.  The row-parallel run kernel
+(merge_rows_kernel), which this table keeps away with MI355_MERGE_ROWS=0, has its own in tests/merge_run_cases.py.
 
 Data: integer-valued ({-3..3} x {-2..2}: exact in any order), and for the float types a second, real-valued pass over
 the thread-edge, tail and run families.  In float cases the columns of x that no row references hold NaN."""
