@@ -3,8 +3,9 @@
 //   v[n]     = scale * dot(Q[r, :d], K[c, :d]) + bias[n]              for every stored entry n = (r, c) of A
 //   m_r      = max over the row of v,   l_r = sum over the row of exp(v - m_r)
 //   O[r,:dv] = (sum over the row of exp(v[n] - m_r) * V[c, :dv]) / l_r,        lse[r] = m_r + log(l_r)     (optional)
-// An object of its own beside mi355_spmv_sddmm / _row_softmax / _multi: the kernels, their launch and the extern "C" entry
-// points, all in this unit.
+// An object of its own beside mi355_spmv_sddmm / _row_softmax / _multi: the kernels, the one launch path of both storage
+// types and the extern "C" entry points, in this unit; what it shares with the backward (the checks, the pieces' walk, the
+// loop over the tiles) is attention_common.hpp's.
 //
 // Masked edges: bias[n] = -inf contributes exactly +0 (its row of V is not multiplied in).  A row that is empty or masked
 // whole gets O = +0 and lse = -inf, not NaN.  A row of one unmasked entry gives O = V[c] and lse = v exactly.
@@ -44,7 +45,7 @@
 #include <limits>
 #include <new>
 
-#include "slice_cut.hpp"
+#include "attention_common.hpp"
 
 struct mi355_spmv_attention {       // the opaque handle of include/mi355_spmv.h
     int off_type = 0, val_type = 0;
@@ -120,13 +121,6 @@ struct AttnArgs {
     AttnScratch<val_t> sc;
 };
 
-__device__ __forceinline__ float attn_fma(float x, float y, float z) { return __builtin_fmaf(x, y, z); }
-__device__ __forceinline__ double attn_fma(double x, double y, double z) { return __builtin_fma(x, y, z); }
-__device__ __forceinline__ float attn_exp(float d) { return expf(d); }
-__device__ __forceinline__ double attn_exp(double d) { return exp(d); }
-__device__ __forceinline__ float attn_log(float d) { return logf(d); }
-__device__ __forceinline__ double attn_log(double d) { return log(d); }
-
 // exp of a difference d = m - M <= 0: exactly 1 at 0 and exactly +0 at -inf, whatever the math library gives at its ends
 template <typename val_t>
 __device__ __forceinline__ val_t attn_exp_diff(val_t d) {
@@ -183,26 +177,20 @@ __global__ __launch_bounds__(kBlock) void attention_slice_kernel(const AttnArgs<
 }
 
 // the fix-up's thread of (slice t, column j): if t is the first slice that carries a row, that row and its state folded
-// over the row's pieces in slice order — the tails, then the head of the slice the row ends in; otherwise false
+// over the row's pieces in the order of attn_piece_chain; otherwise false
 template <typename acc_t>
 __device__ __forceinline__ bool attn_fixup_fold(int64_t n_slices, const AttnScratch<acc_t>& sc, int64_t t, int j, int32_t& r, acc_t& m, acc_t& l,
                                                 acc_t& acc) {
-    if (t >= n_slices) return false;
-    r = sc.row[t * 2 + 1];
-    if (r < 0 || (t > 0 && sc.row[(t - 1) * 2 + 1] == r)) return false;
-    m = sc.ml[(t * 2 + 1) * 2]; l = sc.ml[(t * 2 + 1) * 2 + 1]; acc = sc.acc[(t * 2 + 1) * sc.carry_ld + j];
-    const auto fold = [&](int64_t piece) {      // (m, l, acc) + the piece's state, the piece being the later side
-        const acc_t m2 = sc.ml[piece * 2], l2 = sc.ml[piece * 2 + 1], a2 = sc.acc[piece * sc.carry_ld + j];
-        const acc_t M = m < m2 ? m2 : m;
-        const acc_t e = attn_side(m, M), e2 = attn_side(m2, M);
-        l = l * e + l2 * e2;
-        acc = acc * e + a2 * e2;
-        m = M;
-    };
-    int64_t u = t + 1;
-    for (; u < n_slices && sc.row[u * 2 + 1] == r; ++u) fold(u * 2 + 1);
-    if (u < n_slices && sc.row[u * 2 + 0] == r) fold(u * 2 + 0);
-    return true;
+    return attn_piece_chain(
+        n_slices, sc.row, t, r, [&](int64_t piece) { m = sc.ml[piece * 2]; l = sc.ml[piece * 2 + 1]; acc = sc.acc[piece * sc.carry_ld + j]; },
+        [&](int64_t piece) {      // (m, l, acc) + the piece's state, the piece being the later side
+            const acc_t m2 = sc.ml[piece * 2], l2 = sc.ml[piece * 2 + 1], a2 = sc.acc[piece * sc.carry_ld + j];
+            const acc_t M = m < m2 ? m2 : m;
+            const acc_t e = attn_side(m, M), e2 = attn_side(m2, M);
+            l = l * e + l2 * e2;
+            acc = acc * e + a2 * e2;
+            m = M;
+        });
 }
 
 // one thread per (slice, column): the first slice that carries a row folds the row's pieces and writes the row of O;
@@ -230,28 +218,9 @@ struct AttnOperands {
     void* lse;
 };
 
-// the arguments of an execute but the pass's tile (col_begin, cols), Args = AttnArgs<val_t> or AttnHalfArgs<vec_t>
-// (attention_half_kernel.hpp): elem_t is the type of Q, K, V and O, acc_t that of bias, lse, scale and the scratch
-template <typename elem_t, typename acc_t, typename Args>
-void attn_fill_args(Args& a, const mi355_spmv_attention& m, const AttnOperands& o) {
-    a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
-    a.Aj = m.Aj;
-    a.Q = static_cast<const elem_t*>(o.Q); a.K = static_cast<const elem_t*>(o.K); a.V = static_cast<const elem_t*>(o.V);
-    a.bias = static_cast<const acc_t*>(o.bias);
-    a.O = static_cast<elem_t*>(o.O); a.lse = static_cast<acc_t*>(o.lse);
-    a.ldq = o.ldq; a.ldk = o.ldk; a.ldv = o.ldv; a.ldo = o.ldo;
-    a.d = o.d;
-    a.q_vec = rows_aligned16<elem_t>(o.Q, o.ldq) ? 1 : 0;
-    a.k_vec = rows_aligned16<elem_t>(o.K, o.ldk) ? 1 : 0;
-    a.v_vec = rows_aligned16<elem_t>(o.V, o.ldv) ? 1 : 0;
-    a.o_vec = rows_aligned16<elem_t>(o.O, o.ldo) ? 1 : 0;
-    a.scale = acc_t(m.scale);
-    a.sc = attn_scratch<acc_t>(m.scratch, m.n_slices, m.carry_ld);
-}
-
 }  // namespace mi355
 
-#include "attention_half_kernel.hpp"    // (down here: its launch uses the handle, AttnOperands and attn_fill_args)
+#include "attention_half_kernel.hpp"    // (down here: its kernels use AttnScratch and the fold)
 
 using namespace mi355;
 
@@ -260,15 +229,7 @@ namespace {
 // argument-only checks of a create (also run by the one-shots before they make anything)
 int attention_check_create(const char* who, int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
                            const int32_t* Aj, int32_t d_max, int32_t dv_max) {
-    if (off_type != MI355_OFF_I32 && off_type != MI355_OFF_I64) { set_error("%s: unknown off_type %d", who, off_type); return MI355_SPMV_EINVAL; }
-    if (val_type == MI355_VAL_I32) {
-        set_error("%s: val_type MI355_VAL_I32 is not built (fp32 / fp64 values)", who);
-        return MI355_SPMV_ENOTSUP;
-    }
-    if (val_type != MI355_VAL_F32 && val_type != MI355_VAL_F64) {
-        set_error("%s: val_type %d is not a type of Q, K, V and O (F32 or F64; 16-bit values are not built)", who, val_type);
-        return MI355_SPMV_EINVAL;
-    }
+    if (const int st = attn_check_types(who, off_type, val_type, "Q, K, V and O", "mi355_spmv_attention_create_half")) return st;
     if (d_max < 1) { set_error("%s: d_max = %d below 1", who, d_max); return MI355_SPMV_EINVAL; }
     if (dv_max < 1) { set_error("%s: dv_max = %d below 1", who, dv_max); return MI355_SPMV_EINVAL; }
     return check_csr_structure(who, off_type, n_rows, n_cols, nnz, Ap, Aj);
@@ -277,34 +238,15 @@ int attention_check_create(const char* who, int off_type, int val_type, int32_t 
 // the checks of create_half (and of the 16-bit one-shots): vec_type first, then what a create of fp32 values checks
 int attention_check_create_half(const char* who, int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
                                 const int32_t* Aj, int32_t d_max, int32_t dv_max) {
-    if (vec_type != MI355_VAL_F16 && vec_type != MI355_VAL_BF16) {
-        set_error("%s: vec_type %d is not a 16-bit type of Q, K, V and O (MI355_VAL_F16 or MI355_VAL_BF16)", who, vec_type);
-        return MI355_SPMV_EINVAL;
-    }
+    if (const int st = attn_check_half_type(who, vec_type, "Q, K, V and O")) return st;
     return attention_check_create(who, off_type, MI355_VAL_F32, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max);
 }
 
 // argument-only checks of an execute (bias and lse may be null)
-int attention_check_execute(const char* who, int32_t n_rows, int64_t nnz, int32_t d_max, int32_t dv_max, int32_t d, int32_t dv, const void* Q,
-                            int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const void* O, int64_t ldo) {
-    if (d < 1) { set_error("%s: d = %d below 1", who, d); return MI355_SPMV_EINVAL; }
-    if (dv < 1) { set_error("%s: dv = %d below 1", who, dv); return MI355_SPMV_EINVAL; }
-    if (d > d_max) { set_error("%s: d = %d above d_max = %d", who, d, d_max); return MI355_SPMV_EINVAL; }
-    if (dv > dv_max) { set_error("%s: dv = %d above dv_max = %d", who, dv, dv_max); return MI355_SPMV_EINVAL; }
-    if (ldq < d) { set_error("%s: ldq = %lld below d = %d", who, (long long)ldq, d); return MI355_SPMV_EINVAL; }
-    if (ldk < d) { set_error("%s: ldk = %lld below d = %d", who, (long long)ldk, d); return MI355_SPMV_EINVAL; }
-    if (ldv < dv) { set_error("%s: ldv = %lld below dv = %d", who, (long long)ldv, dv); return MI355_SPMV_EINVAL; }
-    if (ldo < dv) { set_error("%s: ldo = %lld below dv = %d", who, (long long)ldo, dv); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && !Q) { set_error("%s: null Q", who); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && !K) { set_error("%s: null K", who); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && !V) { set_error("%s: null V", who); return MI355_SPMV_EINVAL; }
-    if (n_rows > 0 && !O) { set_error("%s: null O", who); return MI355_SPMV_EINVAL; }
-    return MI355_SPMV_OK;
+int attention_check_execute(const char* who, int32_t n_rows, int64_t nnz, int32_t d_max, int32_t dv_max, const AttnOperands& o) {
+    if (const int st = attn_check_widths(who, o.d, o.dv, d_max, dv_max, o.ldq, o.ldk, o.ldv, o.ldo)) return st;
+    return attn_check_inputs(who, n_rows, nnz, o.Q, o.K, o.V, o.O);
 }
-
-// columns of a lane's 16 bytes of a row of Q, K, V and O, and the widest tile of dv
-int attention_lane_cols(int vec_type) { return vec_type == MI355_VAL_F64 ? 2 : vec_type == MI355_VAL_F32 ? 4 : mh::kHalfV; }
-int attention_widest(int vec_type) { return attention_lane_cols(vec_type) * kSliceGroupsMax; }
 
 // the object of checked arguments: the slices and their scratch (the only device call of a create: one hipMalloc)
 int attention_make(const char* who, mi355_spmv_attention** out, int off_type, int val_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz,
@@ -316,7 +258,7 @@ int attention_make(const char* who, mi355_spmv_attention** out, int off_type, in
     m->Ap = Ap; m->Aj = Aj;
     m->d_max = d_max; m->dv_max = dv_max;
     m->n_slices = slice_count(n_rows, nnz);
-    const int widest = attention_widest(vec_type);
+    const int widest = attn_widest(vec_type);
     m->carry_ld = (int64_t(dv_max) + widest - 1) / widest * widest;
     if (m->n_slices > 0) {      // (no rows: nothing is ever launched, nothing allocated)
         m->scratch_bytes = attn_scratch_bytes(m->n_slices, m->carry_ld, val_type == MI355_VAL_F64 ? 8 : 4);
@@ -331,44 +273,57 @@ int attention_make(const char* who, mi355_spmv_attention** out, int off_type, in
     return MI355_SPMV_OK;
 }
 
+// The kernels of one storage type as the launch path below names them: elem_t is the type of Q, K, V and O, acc_t that of
+// bias, lse, scale and the scratch, W a lane's columns.  AttnHalfKernels<vec_t> (attention_half_kernel.hpp) has the same members.
+template <typename val_t>
+struct AttnKernels {
+    using elem_t = val_t;
+    using acc_t = val_t;
+    using Args = AttnArgs<val_t>;
+    static constexpr int W = 16 / int(sizeof(val_t));
+    template <typename off_t, int C>
+    static void slice(dim3 grid, hipStream_t s, const Args& a, const off_t* Ap) {
+        hipLaunchKernelGGL((attention_slice_kernel<off_t, val_t, C>), grid, dim3(kBlock), 0, s, a, Ap);
+    }
+    static void fixup(dim3 grid, hipStream_t s, const Args& a, int32_t dv) {
+        hipLaunchKernelGGL((attention_fixup_kernel<val_t>), grid, dim3(kBlock), 0, s, a.n_slices, dv, a.sc, a.O, a.ldo, a.lse);
+    }
+};
+
 // the passes over the tiles of dv, then the fix-up
-template <typename off_t, typename val_t>
+template <typename off_t, typename K>
 int attention_launch(const mi355_spmv_attention& m, const AttnOperands& o, hipStream_t s) {
-    constexpr int W = 16 / int(sizeof(val_t));
-    constexpr int kWidest = W * kSliceGroupsMax;
-    AttnArgs<val_t> a;
-    attn_fill_args<val_t, val_t>(a, m, o);
+    using elem_t = typename K::elem_t;
+    using acc_t = typename K::acc_t;
+    typename K::Args a;
+    a.n_rows = m.n_rows; a.nnz = m.nnz; a.n_slices = m.n_slices;
+    a.Aj = m.Aj;
+    a.Q = static_cast<const elem_t*>(o.Q); a.K = static_cast<const elem_t*>(o.K); a.V = static_cast<const elem_t*>(o.V);
+    a.bias = static_cast<const acc_t*>(o.bias);
+    a.O = static_cast<elem_t*>(o.O); a.lse = static_cast<acc_t*>(o.lse);
+    a.ldq = o.ldq; a.ldk = o.ldk; a.ldv = o.ldv; a.ldo = o.ldo;
+    a.d = o.d;
+    a.q_vec = rows_aligned16<elem_t>(o.Q, o.ldq) ? 1 : 0;
+    a.k_vec = rows_aligned16<elem_t>(o.K, o.ldk) ? 1 : 0;
+    a.v_vec = rows_aligned16<elem_t>(o.V, o.ldv) ? 1 : 0;
+    a.o_vec = rows_aligned16<elem_t>(o.O, o.ldo) ? 1 : 0;
+    a.scale = acc_t(m.scale);
+    a.sc = attn_scratch<acc_t>(m.scratch, m.n_slices, m.carry_ld);
     const off_t* Ap = static_cast<const off_t*>(m.Ap);
-    const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
-    for (int32_t cb = 0; cb < o.dv; cb += kWidest) {
-        a.col_begin = cb;
-        a.cols = o.dv - cb < kWidest ? o.dv - cb : kWidest;
-        with_slot_lanes((a.cols + W - 1) / W, [&](auto lanes) {
-            hipLaunchKernelGGL((attention_slice_kernel<off_t, val_t, decltype(lanes)::value>), grid, block, 0, s, a, Ap);
-        });
-        MI355_HIP_TRY(hipGetLastError());
-    }
-    if (m.n_slices > 1) {
-        const int64_t threads = m.n_slices * o.dv;
-        hipLaunchKernelGGL((attention_fixup_kernel<val_t>), dim3(unsigned((threads + kBlock - 1) / kBlock)), block, 0, s, m.n_slices, o.dv, a.sc,
-                           a.O, o.ldo, a.lse);
-        MI355_HIP_TRY(hipGetLastError());
-    }
-    return MI355_SPMV_OK;
+    return attn_tile_passes<K::W>(
+        a, o.dv, [&](dim3 grid, auto lanes) { K::template slice<off_t, decltype(lanes)::value>(grid, s, a, Ap); },
+        [&](dim3 grid) { K::fixup(grid, s, a, o.dv); });
 }
 
 int attention_run(const mi355_spmv_attention& m, const AttnOperands& o, void* stream) {
     if (m.n_rows == 0) return MI355_SPMV_OK;        // no rows: nothing to write, nothing launched
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (m.vec_type != m.val_type) {     // 16-bit Q, K, V and O under fp32 everything else
-        const bool i32 = m.off_type == MI355_OFF_I32;
-        auto run = [&](auto off, auto vec) { return attention_half_launch<decltype(off), decltype(vec)>(m, o, s); };
-        if (m.vec_type == MI355_VAL_F16) return i32 ? run(int32_t(), F16()) : run(int64_t(), F16());
-        return i32 ? run(int32_t(), Bf16()) : run(int64_t(), Bf16());
-    }
-    if (m.off_type == MI355_OFF_I32)
-        return m.val_type == MI355_VAL_F64 ? attention_launch<int32_t, double>(m, o, s) : attention_launch<int32_t, float>(m, o, s);
-    return m.val_type == MI355_VAL_F64 ? attention_launch<int64_t, double>(m, o, s) : attention_launch<int64_t, float>(m, o, s);
+    const bool i32 = m.off_type == MI355_OFF_I32;
+    auto run = [&](auto off, auto kernels) { return attention_launch<decltype(off), decltype(kernels)>(m, o, s); };
+    auto either = [&](auto kernels) { return i32 ? run(int32_t(), kernels) : run(int64_t(), kernels); };
+    if (m.vec_type == MI355_VAL_F16) return either(AttnHalfKernels<F16>());     // 16-bit Q, K, V and O under fp32 everything else
+    if (m.vec_type == MI355_VAL_BF16) return either(AttnHalfKernels<Bf16>());
+    return m.val_type == MI355_VAL_F64 ? either(AttnKernels<double>()) : either(AttnKernels<float>());
 }
 
 // create, execute, synchronise, destroy (the scratch must outlive the kernels, as the multi-vector one-shots' does);
@@ -376,8 +331,7 @@ int attention_run(const mi355_spmv_attention& m, const AttnOperands& o, void* st
 int attention_one_shot(int off_type, int val_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap, const int32_t* Aj,
                        const AttnOperands& o, double scale, void* stream) {
     set_error("%s", "");
-    if (const int st = attention_check_execute("attention", n_rows, nnz, o.d, o.dv, o.d, o.dv, o.Q, o.ldq, o.K, o.ldk, o.V, o.ldv, o.O, o.ldo))
-        return st;
+    if (const int st = attention_check_execute("attention", n_rows, nnz, o.d, o.dv, o)) return st;
     if (const int st = vec_type != val_type ? attention_check_create_half("attention_half", off_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv)
                                             : attention_check_create("attention", off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv))
         return st;
@@ -432,9 +386,8 @@ int mi355_spmv_attention_execute(mi355_spmv_attention* m, int32_t d, int32_t dv,
                                  const void* V, int64_t ldv, const void* bias, void* O, int64_t ldo, void* lse, void* stream) {
     set_error("%s", "");
     if (!m) { set_error("attention_execute: null object"); return MI355_SPMV_EINVAL; }
-    if (const int st = attention_check_execute("attention_execute", m->n_rows, m->nnz, m->d_max, m->dv_max, d, dv, Q, ldq, K, ldk, V, ldv, O, ldo))
-        return st;
     const AttnOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, lse};
+    if (const int st = attention_check_execute("attention_execute", m->n_rows, m->nnz, m->d_max, m->dv_max, o)) return st;
     return attention_run(*m, o, stream);
 }
 
@@ -445,7 +398,7 @@ int mi355_spmv_attention_get_info(const mi355_spmv_attention* m, mi355_spmv_atte
     info->slice_len = kSliceLen;
     info->block_threads = kBlock;
     info->d_max = m->d_max; info->dv_max = m->dv_max;
-    info->widest_tile = attention_widest(m->vec_type);
+    info->widest_tile = attn_widest(m->vec_type);
     info->passes = (m->dv_max + info->widest_tile - 1) / info->widest_tile;
     const int cols = m->dv_max < info->widest_tile ? m->dv_max : info->widest_tile;
     const int per_lane = info->widest_tile / kSliceGroupsMax;

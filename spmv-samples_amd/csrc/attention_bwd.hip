@@ -8,7 +8,8 @@
 //   dK[c, :d]  = sum over column c of (scale * ds[n]) * Q[r, :d]
 //   dV[c, :dv] = sum over column c of p[n] * dO[r, :dv]
 //   dbias[n]   = ds[n]                                              (optional; nnz values in CSR order)
-// O and lse are whatever the caller passes: nothing here assumes they came from this library's forward.
+// O and lse are whatever the caller passes: nothing here assumes they came from this library's forward.  What the two
+// directions share (the checks, the pieces' walk, the loop over the tiles) is attention_common.hpp's.
 //
 //   attention_bwd_delta_kernel   eight lanes per row: delta[r] into the object's scratch; each lane one fma chain from +0 over
 //                                its columns in ascending order, then a fixed xor tree (one order of addition per row).
@@ -47,7 +48,7 @@
 #include <limits>
 #include <new>
 
-#include "slice_cut.hpp"
+#include "attention_common.hpp"
 
 struct mi355_spmv_attention_bwd {   // the opaque handle of include/mi355_spmv.h
     int off_type = 0, val_type = 0;
@@ -131,11 +132,6 @@ struct AttnBwdArgs {
     AttnBwdScratch<val_t> sc;
 };
 
-__device__ __forceinline__ float attn_bwd_fma(float x, float y, float z) { return __builtin_fmaf(x, y, z); }
-__device__ __forceinline__ double attn_bwd_fma(double x, double y, double z) { return __builtin_fma(x, y, z); }
-__device__ __forceinline__ float attn_bwd_exp(float d) { return expf(d); }
-__device__ __forceinline__ double attn_bwd_exp(double d) { return exp(d); }
-
 // the sum over all slots of a per-slot partial, in every lane of the column group (xor butterfly: the same bits everywhere)
 template <typename val_t, int W, int C>
 __device__ __forceinline__ void attn_bwd_reduce_slots(val_t (&v)[W]) {
@@ -160,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_delta_kernel(int32_t n_r
     if (valid) {
         const val_t* a = dO + r * lddo;
         const val_t* b = O + r * ldo;
-        for (int32_t j = g; j < dv; j += kDeltaLanes) sum = attn_bwd_fma(a[j], b[j], sum);
+        for (int32_t j = g; j < dv; j += kDeltaLanes) sum = attn_fma(a[j], b[j], sum);
     }
 #pragma unroll
     for (int dd = 1; dd < kDeltaLanes; dd <<= 1) sum += __shfl_xor(sum, dd);
@@ -181,17 +177,12 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_slice_kernel(const AttnB
 }
 
 // the fix-up's thread of (slice t, column j): if t is the first slice that carries a line, that line and the sum of its
-// pieces in slice order — the tails, then the head of the slice the line ends in; otherwise false
+// pieces in the order of attn_piece_chain; otherwise false
 template <typename acc_t>
 __device__ __forceinline__ bool attn_bwd_fixup_sum(int64_t n_slices, const AttnBwdScratch<acc_t>& sc, int64_t t, int j, int32_t& r, acc_t& sum) {
-    if (t >= n_slices) return false;
-    r = sc.row[t * 2 + 1];
-    if (r < 0 || (t > 0 && sc.row[(t - 1) * 2 + 1] == r)) return false;
-    sum = sc.acc[(t * 2 + 1) * sc.carry_ld + j];
-    int64_t u = t + 1;
-    for (; u < n_slices && sc.row[u * 2 + 1] == r; ++u) sum = sum + sc.acc[(u * 2 + 1) * sc.carry_ld + j];
-    if (u < n_slices && sc.row[u * 2 + 0] == r) sum = sum + sc.acc[(u * 2 + 0) * sc.carry_ld + j];
-    return true;
+    return attn_piece_chain(
+        n_slices, sc.row, t, r, [&](int64_t piece) { sum = sc.acc[piece * sc.carry_ld + j]; },
+        [&](int64_t piece) { sum = sum + sc.acc[piece * sc.carry_ld + j]; });
 }
 
 // one thread per (slice, column): the first slice that carries a line adds the line's pieces and stores the line of out
@@ -234,15 +225,7 @@ namespace {
 // mi355_spmv_attention_create, then the transpose's limit
 int attention_bwd_check_create(const char* who, int off_type, int val_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
                                const int32_t* Aj, int32_t d_max, int32_t dv_max) {
-    if (off_type != MI355_OFF_I32 && off_type != MI355_OFF_I64) { set_error("%s: unknown off_type %d", who, off_type); return MI355_SPMV_EINVAL; }
-    if (val_type == MI355_VAL_I32) {
-        set_error("%s: val_type MI355_VAL_I32 is not built (fp32 / fp64 values)", who);
-        return MI355_SPMV_ENOTSUP;
-    }
-    if (val_type != MI355_VAL_F32 && val_type != MI355_VAL_F64) {
-        set_error("%s: val_type %d is not a type of Q, K, V, O and dO (F32 or F64; 16-bit operands: mi355_spmv_attention_bwd_create_half)", who, val_type);
-        return MI355_SPMV_EINVAL;
-    }
+    if (const int st = attn_check_types(who, off_type, val_type, "Q, K, V, O and dO", "mi355_spmv_attention_bwd_create_half")) return st;
     if (d_max < 1) { set_error("%s: d_max = %d below 1", who, d_max); return MI355_SPMV_EINVAL; }
     if (dv_max < 1) { set_error("%s: dv_max = %d below 1", who, dv_max); return MI355_SPMV_EINVAL; }
     if (const int st = check_csr_structure(who, off_type, n_rows, n_cols, nnz, Ap, Aj)) return st;
@@ -253,43 +236,24 @@ int attention_bwd_check_create(const char* who, int off_type, int val_type, int3
 // the checks of create_half (and of the 16-bit one-shots): vec_type first, then what a create of fp32 values checks
 int attention_bwd_check_create_half(const char* who, int off_type, int vec_type, int32_t n_rows, int32_t n_cols, int64_t nnz, const void* Ap,
                                     const int32_t* Aj, int32_t d_max, int32_t dv_max) {
-    if (vec_type != MI355_VAL_F16 && vec_type != MI355_VAL_BF16) {
-        set_error("%s: vec_type %d is not a 16-bit type of Q, K, V, O, dO, dQ, dK and dV (MI355_VAL_F16 or MI355_VAL_BF16)", who, vec_type);
-        return MI355_SPMV_EINVAL;
-    }
+    if (const int st = attn_check_half_type(who, vec_type, "Q, K, V, O, dO, dQ, dK and dV")) return st;
     return attention_bwd_check_create(who, off_type, MI355_VAL_F32, n_rows, n_cols, nnz, Ap, Aj, d_max, dv_max);
 }
 
 // argument-only checks of an execute (bias may be null; so may any of dQ, dK, dV, but not all three)
-int attention_bwd_check_execute(const char* who, int32_t n_rows, int32_t n_cols, int64_t nnz, int32_t d_max, int32_t dv_max,
-                                const AttnBwdOperands& o) {
-    if (o.d < 1) { set_error("%s: d = %d below 1", who, o.d); return MI355_SPMV_EINVAL; }
-    if (o.dv < 1) { set_error("%s: dv = %d below 1", who, o.dv); return MI355_SPMV_EINVAL; }
-    if (o.d > d_max) { set_error("%s: d = %d above d_max = %d", who, o.d, d_max); return MI355_SPMV_EINVAL; }
-    if (o.dv > dv_max) { set_error("%s: dv = %d above dv_max = %d", who, o.dv, dv_max); return MI355_SPMV_EINVAL; }
-    if (o.ldq < o.d) { set_error("%s: ldq = %lld below d = %d", who, (long long)o.ldq, o.d); return MI355_SPMV_EINVAL; }
-    if (o.ldk < o.d) { set_error("%s: ldk = %lld below d = %d", who, (long long)o.ldk, o.d); return MI355_SPMV_EINVAL; }
-    if (o.ldv < o.dv) { set_error("%s: ldv = %lld below dv = %d", who, (long long)o.ldv, o.dv); return MI355_SPMV_EINVAL; }
-    if (o.ldo < o.dv) { set_error("%s: ldo = %lld below dv = %d", who, (long long)o.ldo, o.dv); return MI355_SPMV_EINVAL; }
+int attention_bwd_check_execute(const char* who, int32_t n_rows, int64_t nnz, int32_t d_max, int32_t dv_max, const AttnBwdOperands& o) {
+    if (const int st = attn_check_widths(who, o.d, o.dv, d_max, dv_max, o.ldq, o.ldk, o.ldv, o.ldo)) return st;
     if (o.lddo < o.dv) { set_error("%s: lddo = %lld below dv = %d", who, (long long)o.lddo, o.dv); return MI355_SPMV_EINVAL; }
     if (!o.dQ && !o.dK && !o.dV) { set_error("%s: dQ, dK and dV are all null (nothing to compute)", who); return MI355_SPMV_EINVAL; }
     if (o.dbias && !o.dQ) { set_error("%s: dbias without dQ (dbias comes from the walk that makes dQ)", who); return MI355_SPMV_EINVAL; }
     if (o.dQ && o.lddq < o.d) { set_error("%s: lddq = %lld below d = %d", who, (long long)o.lddq, o.d); return MI355_SPMV_EINVAL; }
     if (o.dK && o.lddk < o.d) { set_error("%s: lddk = %lld below d = %d", who, (long long)o.lddk, o.d); return MI355_SPMV_EINVAL; }
     if (o.dV && o.lddv < o.dv) { set_error("%s: lddv = %lld below dv = %d", who, (long long)o.lddv, o.dv); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && !o.Q) { set_error("%s: null Q", who); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && !o.K) { set_error("%s: null K", who); return MI355_SPMV_EINVAL; }
-    if (nnz > 0 && !o.V) { set_error("%s: null V", who); return MI355_SPMV_EINVAL; }
-    if (n_rows > 0 && !o.O) { set_error("%s: null O", who); return MI355_SPMV_EINVAL; }
+    if (const int st = attn_check_inputs(who, n_rows, nnz, o.Q, o.K, o.V, o.O)) return st;
     if (n_rows > 0 && !o.dO) { set_error("%s: null dO", who); return MI355_SPMV_EINVAL; }
     if (n_rows > 0 && !o.lse) { set_error("%s: null lse", who); return MI355_SPMV_EINVAL; }
-    (void)n_cols;
     return MI355_SPMV_OK;
 }
-
-// columns of a lane's 16 bytes of a row of the eight matrices, and the widest tile of an output
-int attention_bwd_lane_cols(int vec_type) { return vec_type == MI355_VAL_F64 ? 2 : vec_type == MI355_VAL_F32 ? 4 : mh::kHalfV; }
-int attention_bwd_widest(int vec_type) { return attention_bwd_lane_cols(vec_type) * kSliceGroupsMax; }
 
 int attention_bwd_free(mi355_spmv_attention_bwd* m) {
     int st = MI355_SPMV_OK;
@@ -314,7 +278,7 @@ int attention_bwd_make(const char* who, mi355_spmv_attention_bwd** out, int off_
     m->d_max = d_max; m->dv_max = dv_max;
     m->n_slices = slice_count(n_rows, nnz);
     m->n_slices_t = slice_count(n_cols, nnz);
-    const int widest = attention_bwd_widest(vec_type);
+    const int widest = attn_widest(vec_type);
     const int64_t wide = d_max > dv_max ? d_max : dv_max;
     m->carry_ld = (wide + widest - 1) / widest * widest;
     const size_t ob = off_type == MI355_OFF_I64 ? 8 : 4;
@@ -371,22 +335,9 @@ struct AttnBwdKernels {
 // the passes of one role over the tiles of its output, then its fix-up
 template <typename off_t, typename K, int ROLE>
 int attention_bwd_role(typename K::Args& a, const off_t* Ap, int32_t width, hipStream_t s) {
-    constexpr int W = K::W;
-    constexpr int kWidest = W * kSliceGroupsMax;
-    if (a.n_slices == 0) return MI355_SPMV_OK;      // no lines: nothing to write
-    const dim3 grid(unsigned(slice_grid(a.n_slices)));
-    for (int32_t cb = 0; cb < width; cb += kWidest) {
-        a.col_begin = cb;
-        a.cols = width - cb < kWidest ? width - cb : kWidest;
-        with_slot_lanes((a.cols + W - 1) / W, [&](auto lanes) { K::template slice<off_t, decltype(lanes)::value, ROLE>(grid, s, a, Ap); });
-        MI355_HIP_TRY(hipGetLastError());
-    }
-    if (a.n_slices > 1) {
-        const int64_t threads = a.n_slices * width;
-        K::fixup(dim3(unsigned((threads + kBlock - 1) / kBlock)), s, a, width);
-        MI355_HIP_TRY(hipGetLastError());
-    }
-    return MI355_SPMV_OK;
+    return attn_tile_passes<K::W>(
+        a, width, [&](dim3 grid, auto lanes) { K::template slice<off_t, decltype(lanes)::value, ROLE>(grid, s, a, Ap); },
+        [&](dim3 grid) { K::fixup(grid, s, a, width); });
 }
 
 // delta, then the roles that are asked for, one behind the other on the stream (they share the pieces' scratch)
@@ -462,7 +413,7 @@ int attention_bwd_one_shot(int off_type, int val_type, int vec_type, int32_t n_r
     if (const int st = vec_type != val_type ? attention_bwd_check_create_half(who, off_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, d1, dv1)
                                             : attention_bwd_check_create(who, off_type, val_type, n_rows, n_cols, nnz, Ap, Aj, d1, dv1))
         return st;
-    if (const int st = attention_bwd_check_execute(who, n_rows, n_cols, nnz, o.d, o.dv, o)) return st;
+    if (const int st = attention_bwd_check_execute(who, n_rows, nnz, o.d, o.dv, o)) return st;
     mi355_spmv_attention_bwd* m = nullptr;
     int st = attention_bwd_make(who, &m, off_type, val_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv, static_cast<hipStream_t>(stream));
     if (st != MI355_SPMV_OK) return st;
@@ -519,7 +470,7 @@ int mi355_spmv_attention_bwd_execute(mi355_spmv_attention_bwd* m, int32_t d, int
     set_error("%s", "");
     if (!m) { set_error("attention_bwd_execute: null object"); return MI355_SPMV_EINVAL; }
     const AttnBwdOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, dbias};
-    if (const int st = attention_bwd_check_execute("attention_bwd_execute", m->n_rows, m->n_cols, m->nnz, m->d_max, m->dv_max, o)) return st;
+    if (const int st = attention_bwd_check_execute("attention_bwd_execute", m->n_rows, m->nnz, m->d_max, m->dv_max, o)) return st;
     return attention_bwd_run(*m, o, stream);
 }
 
@@ -530,8 +481,8 @@ int mi355_spmv_attention_bwd_get_info(const mi355_spmv_attention_bwd* m, mi355_s
     info->slice_len = kSliceLen;
     info->block_threads = kBlock;
     info->d_max = m->d_max; info->dv_max = m->dv_max;
-    info->widest_tile = attention_bwd_widest(m->vec_type);
-    const int per_lane = attention_bwd_lane_cols(m->vec_type);
+    info->widest_tile = attn_widest(m->vec_type);
+    const int per_lane = attn_lane_cols(m->vec_type);
     const int32_t widths[3] = {m->d_max, m->d_max, m->dv_max};      // the outputs of DQ, DK, DV
     for (int i = 0; i < 3; ++i) {
         info->passes[i] = (widths[i] + info->widest_tile - 1) / info->widest_tile;

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_half_delta_kernel(int32_
             mh::load_cols(x, a + cb, nd, do_vec != 0);
             mh::load_cols(y, b + cb, nd, o_vec != 0);
 #pragma unroll
-            for (int j = 0; j < W; ++j) sum = attn_bwd_fma(x[j], y[j], sum);
+            for (int j = 0; j < W; ++j) sum = attn_fma(x[j], y[j], sum);
         }
     }
 #pragma unroll

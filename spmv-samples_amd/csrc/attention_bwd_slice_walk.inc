@@ -78,7 +78,7 @@
                         load_cols(q, qp + cb, nd, a.q_vec != 0);
                         load_cols(k, kp + cb, nd, a.k_vec != 0);
 #pragma unroll
-                        for (int j = 0; j < W; ++j) part = attn_bwd_fma(q[j], k[j], part);
+                        for (int j = 0; j < W; ++j) part = attn_fma(q[j], k[j], part);
                     }
                 }
                 const auto* gp = a.dO + qi * a.lddo + c * W;
@@ -90,7 +90,7 @@
                         load_cols(g, gp + cb, nd, a.do_vec != 0);
                         load_cols(x, vp + cb, nd, a.v_vec != 0);
 #pragma unroll
-                        for (int j = 0; j < W; ++j) dpart = attn_bwd_fma(g[j], x[j], dpart);
+                        for (int j = 0; j < W; ++j) dpart = attn_fma(g[j], x[j], dpart);
                     }
                 }
             }
@@ -108,7 +108,7 @@
                 acc_t v = a.scale * part;
                 if (biased) v = v + bias_s;
                 if (v != kNegInf) {     // (the test comes before the subtraction)
-                    const acc_t p = attn_bwd_exp(v - a.lse[qi]);
+                    const acc_t p = attn_exp(v - a.lse[qi]);
                     ds = p * (dpart - a.delta[qi]);
                     if constexpr (ROLE == kBwdDQ) {
                         coef = a.scale * ds;

@@ -4,8 +4,8 @@
 // Every stored 16-bit value is widened exactly (half_convert.hpp's widen); an element of O is rounded to the 16-bit type
 // exactly ONCE, from the fp32 acc / l (narrow_to: nearest even) — by the slot that holds the row's last nonzero, or, for a
 // row that crosses slices, by the fix-up: the slices leave fp32 states, as the fp32 kernel's do.  Included by
-// attention.hip, which owns the object and the entry points, behind its handle, AttnScratch, AttnOperands and
-// attn_fill_args: this header holds the kernels and their one launch.
+// attention.hip, which owns the object, the entry points and the one launch path of both storage types, behind its
+// AttnScratch and fold: this header holds the kernels and names them for that path.
 //
 //   attention_half_slice_kernel   attention_slice_kernel's walk (the same text, attention_slice_walk.inc) over the same cut
 //                                 (slice_cut.hpp, slice_cut.inc, slice_cut_row.inc) with a lane's 16 bytes being EIGHT
@@ -80,31 +80,22 @@ __global__ __launch_bounds__(kBlock) void attention_half_fixup_kernel(int64_t n_
     if (j == 0 && lse) lse[r] = attn_lse(m, l);
 }
 
-// the passes over the tiles of dv (64 columns each), then the fix-up.  A caller has checked the arguments and that there
-// are rows.
-template <typename off_t, typename vec_t>
-int attention_half_launch(const mi355_spmv_attention& m, const AttnOperands& o, hipStream_t s) {
+// the kernels as attention.hip's launch path names them (AttnKernels<val_t>'s members): the passes run over tiles of
+// W * 8 = 64 columns
+template <typename vec_t>
+struct AttnHalfKernels {
     static_assert(sizeof(vec_t) == 2, "16-bit Q, K, V and O");
-    constexpr int kWidest = mh::kHalfV * kSliceGroupsMax;
-    AttnHalfArgs<vec_t> a;
-    attn_fill_args<vec_t, float>(a, m, o);
-    const off_t* Ap = static_cast<const off_t*>(m.Ap);
-    const dim3 grid(unsigned(slice_grid(m.n_slices))), block(kBlock);
-    for (int32_t cb = 0; cb < o.dv; cb += kWidest) {
-        a.col_begin = cb;
-        a.cols = o.dv - cb < kWidest ? o.dv - cb : kWidest;
-        with_slot_lanes((a.cols + mh::kHalfV - 1) / mh::kHalfV, [&](auto lanes) {
-            hipLaunchKernelGGL((attention_half_slice_kernel<off_t, vec_t, decltype(lanes)::value>), grid, block, 0, s, a, Ap);
-        });
-        MI355_HIP_TRY(hipGetLastError());
+    using elem_t = vec_t;
+    using acc_t = float;
+    using Args = AttnHalfArgs<vec_t>;
+    static constexpr int W = mh::kHalfV;
+    template <typename off_t, int C>
+    static void slice(dim3 grid, hipStream_t s, const Args& a, const off_t* Ap) {
+        hipLaunchKernelGGL((attention_half_slice_kernel<off_t, vec_t, C>), grid, dim3(kBlock), 0, s, a, Ap);
     }
-    if (m.n_slices > 1) {
-        const int64_t threads = m.n_slices * o.dv;
-        hipLaunchKernelGGL((attention_half_fixup_kernel<vec_t>), dim3(unsigned((threads + kBlock - 1) / kBlock)), block, 0, s, m.n_slices, o.dv,
-                           a.sc, a.O, o.ldo, a.lse);
-        MI355_HIP_TRY(hipGetLastError());
+    static void fixup(dim3 grid, hipStream_t s, const Args& a, int32_t dv) {
+        hipLaunchKernelGGL((attention_half_fixup_kernel<vec_t>), grid, dim3(kBlock), 0, s, a.n_slices, dv, a.sc, a.O, a.ldo, a.lse);
     }
-    return MI355_SPMV_OK;
-}
+};
 
 }  // namespace mi355

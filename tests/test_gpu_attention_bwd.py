@@ -264,6 +264,7 @@ def test_side_stream_and_graph_replay(sp):
     torch.cuda.synchronize()
     args = lambda: (P["Q"], P["K"], P["V"], P["O"], P["dO"], P["lse"])
     base = [t.clone() for t in bwd.execute(*args(), bias=P["bias"], dbias=True)]
+    torch.cuda.synchronize()        # one stream at a time per object: the executes share the plan's scratch
     # a side stream
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
