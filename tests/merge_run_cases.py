@@ -26,7 +26,9 @@ tail).  The columns of a float x that no row references hold NaN.
 Not here: the 512- and 1 024-thread run kernels, the sweeping runs (TS > 0) and the segmented runs (NSEG > 1).  Their
 plans need MI355_MERGE_TPS unset and at least 2 kCus runs, so no small matrix reaches them; they stay with the at-size
 tests of tests/test_gpu_parity.py (test_merge_runs_*), tests/test_gpu_merge_fallbacks.py, tests/test_gpu_block_shapes.py
-and tests/test_gpu_kept_plans.py."""
+and tests/test_gpu_kept_plans.py.  (The body the sweeping runs share with the vector and light kinds, chunk_rows_sweep,
+has its edge table in tests/sweep_cases.py, on hand-written plan shapes; merge blocks are shaped on their own, so such a
+shape does not reach merge_rows_kernel, and the run's clipping of the piece stays with the at-size tests.)"""
 import collections
 import os
 import re

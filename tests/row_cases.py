@@ -16,9 +16,10 @@ leaking into or missing from a row changes it, so a row's neighbours always tell
 r + 1 instead (a permuted row mapping is seen); real values in (-1, 1) for the parity bound.  The columns of x that no
 row references hold NaN.
 
-Not here: the swept window (chunk_rows_sweep) needs hundreds of chunks before the planner takes it, the 1 024-thread
-workgroup a band of 16 K columns, and light's dequeue modes more chunks than the chip holds — they are covered at that
-size by tests/test_gpu_parity.py, tests/test_gpu_kept_plans.py and tests/test_gpu_block_shapes.py."""
+Not here: the swept window (chunk_rows_sweep) has its own table, tests/sweep_cases.py, on hand-written plan shapes; the
+1 024-thread workgroup of the window kernels needs a band of 16 K columns, and light's dequeue modes of the window
+kernels more chunks than the chip holds — they are covered at that size by tests/test_gpu_parity.py,
+tests/test_gpu_kept_plans.py and tests/test_gpu_block_shapes.py."""
 import collections
 import functools
 import os
@@ -132,11 +133,16 @@ def structure(m):
 @functools.lru_cache(maxsize=None)
 def operands(m, vb, integer):
     """(Ax, x, y0) in the value type of vb bytes; x holds NaN where no row references it."""
-    t = np.float32 if vb == 4 else np.float64
     Ap, Aj = structure(m)
-    nnz = int(Ap[-1])
-    rng = np.random.default_rng([13, len(m.lens), nnz, int(integer)])
-    if m.data == "rowid":            # x = 1, values 1 except a row's last: row r sums to r + 1, and no value is 0
+    return operands_of(Ap, Aj, m.n_cols, m.data, vb, integer)
+
+
+def operands_of(Ap, Aj, n_cols, data, vb, integer):
+    """operands() for any structure (tests/sweep_cases.py builds its own)."""
+    t = np.float32 if vb == 4 else np.float64
+    n_rows, nnz = len(Ap) - 1, int(Ap[-1])
+    rng = np.random.default_rng([13, n_rows, nnz, int(integer)])
+    if data == "rowid":              # x = 1, values 1 except a row's last: row r sums to r + 1, and no value is 0
         assert integer
         Ax = np.ones(nnz, dtype=t)
         r = np.nonzero(np.diff(Ap))[0]
@@ -144,19 +150,19 @@ def operands(m, vb, integer):
         Ax[Ap[r + 1] - 1] = last
         z = r[last == 0]             # (r + 1 == len - 1, so len >= 2: first 2, last -1, the same sum)
         Ax[Ap[z]], Ax[Ap[z + 1] - 1] = 2, -1
-        x = np.ones(m.n_cols, dtype=t)
+        x = np.ones(n_cols, dtype=t)
     elif integer:
         Ax = rng.choice(np.array([-3, -2, -1, 1, 2, 3]), size=nnz).astype(t)
-        x = rng.choice(np.array([-2, -1, 1, 2]), size=m.n_cols).astype(t)
+        x = rng.choice(np.array([-2, -1, 1, 2]), size=n_cols).astype(t)
     else:
         lim = np.nextafter(t(1), t(0))
         Ax = np.clip((rng.random(nnz) * 2 - 1).astype(t), -lim, lim)
-        x = np.clip((rng.random(m.n_cols) * 2 - 1).astype(t), -lim, lim)
+        x = np.clip((rng.random(n_cols) * 2 - 1).astype(t), -lim, lim)
         x[x == 0] = lim
-    used = np.zeros(m.n_cols, dtype=bool)
+    used = np.zeros(n_cols, dtype=bool)
     used[Aj] = True
     x[~used] = np.nan
-    y0 = rng.integers(-4, 5, size=len(m.lens)).astype(t)
+    y0 = rng.integers(-4, 5, size=n_rows).astype(t)
     return Ax, x, y0
 
 
