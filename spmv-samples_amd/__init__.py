@@ -11,7 +11,8 @@ Contents (only what the hot path needs):
     csrc/      HIP kernels (gfx950) + the C ABI of include/mi355_spmv.h
     lib/       built libmi355spmv.so (git-ignored)
     host/      C++ mirror of the reference's include/spmv.h boundary (SpMV<>, SPMV_KINDS, Timer)
-    capi.py    ctypes binding used by tests and bench.py (also coo_to_csr: COO -> CSR on the device, symmetric expansion included;
+    capi.py    ctypes binding used by tests and bench.py: lib() declares the argument types, the shared helpers (_check, _require_*,
+               _ptr, _stream_ptr) and the handle base _Handle (destroy, __del__, _info) come next, then the entry points (also coo_to_csr: COO -> CSR on the device, symmetric expansion included;
                MultiPlan / spmm / spmm_pattern: Y = A X for k vectors in one pass over A, over a semiring; narrow_values: fp32 -> fp16 / bf16 matrix values;
                SddmmPlan / sddmm / sddmm_half: dot(U[r], V[c]) at every stored entry (r, c) of A in one pass over A, U and V in fp32 / fp64 or in 16 bits;
                RowSoftmaxPlan / row_softmax: softmax over the stored entries of every row, and its gradient;

@@ -6,6 +6,11 @@ is missing or a call fails, a RuntimeError is raised.
 
 The reference interface this mirrors (same argument order and meaning):
     SpMV(kind_str, n_rows, n_cols, nnz, Ap, Aj, Ax, x, y)   include/spmv.h:29-34
+
+Layout: the constants and the *Info structures; lib(), which declares the argument types (plan-level entries one by one,
+as the header lists them; the <off>_<val> one-shot families from one table); the helpers every entry point shares (_check,
+the _require_* checks, _ptr, _stream_ptr) and _Handle, the base of every class that owns a library object; then the entry
+points in the header's order.
 """
 import contextlib
 import ctypes as C
@@ -75,6 +80,12 @@ EXPORTS = (
 )
 
 
+def _struct_dict(s):
+    """The fields of an *Info structure as a dict: character arrays as str, fields named reserved* left out."""
+    d = {n: getattr(s, n) for n, _ in s._fields_ if not n.startswith("reserved")}
+    return {n: v.decode() if isinstance(v, bytes) else v for n, v in d.items()}
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("kind", C.c_int32), ("off_type", C.c_int32), ("val_type", C.c_int32),
                 ("lanes_per_row", C.c_int32), ("elems_per_lane", C.c_int32), ("block_threads", C.c_int32),
@@ -85,10 +96,7 @@ class PlanInfo(C.Structure):
                 ("knobs", C.c_char * 160), ("packed_index_bytes", C.c_int64), ("packed_index_escapes", C.c_int64)]
 
     def as_dict(self):
-        d = {n: getattr(self, n) for n, _ in self._fields_}
-        d["main_kernel"] = d["main_kernel"].decode()
-        d["knobs"] = d["knobs"].decode()
-        return d
+        return _struct_dict(self)
 
 
 class PlanShape(C.Structure):
@@ -152,6 +160,38 @@ EXEC_DEFAULT, EXEC_SKIP_EXCHANGE, EXEC_EXCHANGE_ONLY = 0, 1, 2
 _lib = None
 
 
+# the operands of an attention backward, execute and one-shots alike:
+# (Q, ldq), (K, ldk), (V, ldv), bias, (O, ldo), (dO, lddo), lse, (dQ, lddq), (dK, lddk), (dV, lddv), dbias, stream
+_BWD_OPERANDS = ([C.c_void_p, C.c_int64] * 3 + [C.c_void_p] + [C.c_void_p, C.c_int64] * 2 + [C.c_void_p] + [C.c_void_p, C.c_int64] * 3
+                 + [C.c_void_p, C.c_void_p])
+
+
+def _one_shot_signatures():
+    """(stem, value suffixes, argument types) of the one-shot families mi355_spmv_<stem>_<off>_<val> that declare their
+    types; "off" stands for nnz, int32_t or int64_t by <off>.  Families on one list share a signature in the header too.
+    (The mi355_spmv_<kind>_*, merge_genl_*, merge_pattern_* and merge_f32mat_f64vec_* one-shots declare none: spmv and its
+    kin wrap every argument themselves.)"""
+    i32, i64, dbl, ptr = C.c_int32, C.c_int64, C.c_double, C.c_void_p
+    # n_rows, n_cols, nnz, Ap, Aj, Ax, (X, ldx), (Y, ldy), k, stream
+    multi = [i32, i32, "off", ptr, ptr, ptr, ptr, i64, ptr, i64, i32, ptr]
+    # n_rows, n_cols, nnz, Ap, Aj, Ax, (U, ldu), (V, ldv), out, k, stream
+    sddmm = [i32, i32, "off", ptr, ptr, ptr, ptr, i64, ptr, i64, ptr, i32, ptr]
+    # n_rows, n_cols, nnz, Ap, Aj, d, dv, (Q, ldq), (K, ldk), (V, ldv), bias, scale, (O, ldo), lse, stream
+    attention = [i32, i32, "off", ptr, ptr, i32, i32, ptr, i64, ptr, i64, ptr, i64, ptr, dbl, ptr, i64, ptr, ptr]
+    # ... bias, scale, (O, ldo), ...: the one-shots take the scale behind bias
+    attention_bwd = [i32, i32, "off", ptr, ptr, i32, i32] + _BWD_OPERANDS[:7] + [dbl] + _BWD_OPERANDS[7:]
+    floats, halves = ("f32", "f64"), ("f16", "bf16")
+    return (
+        ("multi", floats, multi), ("multi_half", halves, multi), ("multi_transposed", floats, multi),
+        ("multi_genl", floats + ("i32",), [C.c_int] + multi),                      # the semiring first
+        ("multi_pattern", floats + ("i32",), [C.c_int] + multi[:5] + multi[6:]),   # ... and no Ax
+        ("sddmm", floats, sddmm), ("sddmm_half", halves, sddmm),
+        ("row_softmax", floats, [i32, i32, "off", ptr, ptr, ptr, ptr, dbl, ptr]),
+        ("attention", floats, attention), ("attention_half", halves, attention),
+        ("attention_bwd", floats, attention_bwd), ("attention_bwd_half", halves, attention_bwd),
+    )
+
+
 def lib():
     """Load the shared library (once).  Raises if it has not been built."""
     global _lib
@@ -207,6 +247,11 @@ def lib():
         L.mi355_spmv_dist_device_x.argtypes = [C.c_void_p, C.c_int]
         L.mi355_spmv_dist_device_x.restype = C.c_void_p
         L.mi355_spmv_dist_destroy.argtypes = [C.c_void_p]
+        L.mi355_spmv_functor_compile.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                 C.c_char_p, C.c_char_p]
+        L.mi355_spmv_functor_compile_log.restype = C.c_char_p
+        L.mi355_spmv_functor_spmv.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 6
+        L.mi355_spmv_functor_destroy.argtypes = [C.c_void_p]
         L.mi355_spmv_coo_to_csr.argtypes = [C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_size_t), C.c_void_p]
@@ -222,27 +267,11 @@ def lib():
                                                C.c_int32, C.c_void_p]
         L.mi355_spmv_multi_get_info.argtypes = [C.c_void_p, C.POINTER(MultiInfo)]
         L.mi355_spmv_multi_destroy.argtypes = [C.c_void_p]
-        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
-            for v in ("f32", "f64"):
-                getattr(L, "mi355_spmv_multi_%s_%s" % (o, v)).argtypes = [
-                    C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                    C.c_int64, C.c_int32, C.c_void_p]
         L.mi355_spmv_multi_create_typed.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32,
                                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
         L.mi355_spmv_multi_set_semiring.argtypes = [C.c_void_p, C.c_int]
         L.mi355_spmv_multi_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
-            for v in ("f32", "f64", "i32"):
-                getattr(L, "mi355_spmv_multi_genl_%s_%s" % (o, v)).argtypes = [
-                    C.c_int, C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                    C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-                getattr(L, "mi355_spmv_multi_pattern_%s_%s" % (o, v)).argtypes = [
-                    C.c_int, C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                    C.c_int64, C.c_int32, C.c_void_p]
         L.mi355_spmv_multi_create_half.argtypes = L.mi355_spmv_multi_create_typed.argtypes
-        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
-            for v in ("f16", "bf16"):
-                getattr(L, "mi355_spmv_multi_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_multi_%s_f32" % o).argtypes
         L.mi355_spmv_sddmm_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64,
                                               C.c_void_p, C.c_void_p]
         L.mi355_spmv_sddmm_set_alpha_beta.argtypes = [C.c_void_p, C.c_double, C.c_double]
@@ -250,26 +279,16 @@ def lib():
                                                C.c_void_p, C.c_int32, C.c_void_p]
         L.mi355_spmv_sddmm_get_info.argtypes = [C.c_void_p, C.POINTER(SddmmInfo)]
         L.mi355_spmv_sddmm_destroy.argtypes = [C.c_void_p]
-        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
-            for v in ("f32", "f64"):
-                getattr(L, "mi355_spmv_sddmm_%s_%s" % (o, v)).argtypes = [
-                    C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                    C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
         L.mi355_spmv_sddmm_create_half.argtypes = L.mi355_spmv_sddmm_create.argtypes
         L.mi355_spmv_sddmm_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        for o in ("i32", "i64"):
-            for v in ("f16", "bf16"):
-                getattr(L, "mi355_spmv_sddmm_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_sddmm_%s_f32" % o).argtypes
         L.mi355_spmv_row_softmax_create.argtypes = L.mi355_spmv_sddmm_create.argtypes
         L.mi355_spmv_row_softmax_set_scale.argtypes = [C.c_void_p, C.c_double]
         L.mi355_spmv_row_softmax_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355_spmv_row_softmax_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mi355_spmv_row_softmax_get_info.argtypes = [C.c_void_p, C.POINTER(RowSoftmaxInfo)]
         L.mi355_spmv_row_softmax_destroy.argtypes = [C.c_void_p]
-        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
-            for v in ("f32", "f64"):
-                getattr(L, "mi355_spmv_row_softmax_%s_%s" % (o, v)).argtypes = [
-                    C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        # Deliberate: this create alone takes the handle LAST (include/mi355_spmv.h, mi355_spmv_attention_create); create_half
+        # and every other create take it first.
         L.mi355_spmv_attention_create.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32,
                                                   C.c_int32, C.POINTER(C.c_void_p)]
         L.mi355_spmv_attention_set_scale.argtypes = [C.c_void_p, C.c_double]
@@ -277,17 +296,9 @@ def lib():
                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.mi355_spmv_attention_get_info.argtypes = [C.c_void_p, C.POINTER(AttentionInfo)]
         L.mi355_spmv_attention_destroy.argtypes = [C.c_void_p]
-        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
-            for v in ("f32", "f64"):
-                getattr(L, "mi355_spmv_attention_%s_%s" % (o, v)).argtypes = [
-                    C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                    C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.mi355_spmv_attention_create_half.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
                                                        C.c_void_p, C.c_int32, C.c_int32]
         L.mi355_spmv_attention_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        for o in ("i32", "i64"):
-            for v in ("f16", "bf16"):
-                getattr(L, "mi355_spmv_attention_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_attention_%s_f32" % o).argtypes
         L.mi355_spmv_csr_transpose.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]
         L.mi355_spmv_multi_create_permuted.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64,
@@ -297,31 +308,23 @@ def lib():
                                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.mi355_spmv_multi_get_perm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
         L.mi355_spmv_multi_copy_structure.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        for o in ("i32", "i64"):
-            for v in ("f32", "f64"):
-                getattr(L, "mi355_spmv_multi_transposed_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_multi_%s_%s" % (o, v)).argtypes
         L.mi355_spmv_attention_bwd_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
                                                       C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         L.mi355_spmv_attention_bwd_set_scale.argtypes = [C.c_void_p, C.c_double]
-        # d, dv, (Q, ldq), (K, ldk), (V, ldv), bias, (O, ldo), (dO, lddo), lse, (dQ, lddq), (dK, lddk), (dV, lddv), dbias, stream
-        bwd_operands = ([C.c_void_p, C.c_int64] * 3 + [C.c_void_p] + [C.c_void_p, C.c_int64] * 2 + [C.c_void_p] + [C.c_void_p, C.c_int64] * 3
-                        + [C.c_void_p, C.c_void_p])
-        L.mi355_spmv_attention_bwd_execute.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + bwd_operands
+        L.mi355_spmv_attention_bwd_execute.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + _BWD_OPERANDS   # the handle, d, dv
         L.mi355_spmv_attention_bwd_get_info.argtypes = [C.c_void_p, C.POINTER(AttentionBackwardInfo)]
         L.mi355_spmv_attention_bwd_destroy.argtypes = [C.c_void_p]
-        for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
-            for v in ("f32", "f64"):
-                # ... bias, scale, (O, ldo), ...: the one-shots take the scale behind bias
-                getattr(L, "mi355_spmv_attention_bwd_%s_%s" % (o, v)).argtypes = (
-                    [C.c_int32, C.c_int32, off_c, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + bwd_operands[:7] + [C.c_double]
-                    + bwd_operands[7:])
         L.mi355_spmv_attention_bwd_create_half.argtypes = L.mi355_spmv_attention_bwd_create.argtypes
         L.mi355_spmv_attention_bwd_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        for o in ("i32", "i64"):
-            for v in ("f16", "bf16"):
-                getattr(L, "mi355_spmv_attention_bwd_half_%s_%s" % (o, v)).argtypes = getattr(L, "mi355_spmv_attention_bwd_%s_f32" % o).argtypes
+        for stem, vals, args in _one_shot_signatures():
+            for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
+                for v in vals:
+                    getattr(L, "mi355_spmv_%s_%s_%s" % (stem, o, v)).argtypes = [off_c if a == "off" else a for a in args]
         _lib = L
     return _lib
+
+
+# ---- what every entry point shares
 
 
 def _check(status, what):
@@ -331,17 +334,130 @@ def _check(status, what):
             what, L.mi355_spmv_status_string(status).decode(), L.mi355_spmv_last_error().decode()))
 
 
+_NO_CPU_PATH = "mi355 spmv takes device tensors only (no CPU path exists)"
+
+
 def _require_device(*tensors):
     for t in tensors:
         if not t.is_cuda:
-            raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+            raise RuntimeError(_NO_CPU_PATH)
         if not t.is_contiguous():
             raise RuntimeError("mi355 spmv takes contiguous tensors")
+
+
+def _require_structure(Ap, Aj, *more):
+    """Ap and Aj (and `more`, a one-shot's Ax) are contiguous device tensors and Aj is int32."""
+    _require_device(Ap, Aj, *more)
+    if Aj.dtype != torch.int32:
+        raise TypeError("Aj must be int32")
+
+
+def _require_on_device(t):
+    """A one-shot's first operand, asked before its type is: whatever it is, it must say that it is on the device."""
+    if not getattr(t, "is_cuda", False):
+        raise RuntimeError(_NO_CPU_PATH)
+
+
+def _require_matrix(t, name, rows, dtype):
+    """A 2-D device tensor of `rows` rows whose rows are contiguous (stride(1) == 1); returns its leading dimension."""
+    if not t.is_cuda:
+        raise RuntimeError(_NO_CPU_PATH)
+    if t.dim() != 2:
+        raise ValueError("%s must be 2-D (one row per matrix column / row, one column per vector)" % name)
+    if t.dtype != dtype:
+        raise TypeError("value type differs from the plan's")
+    if t.size(0) < rows:
+        raise ValueError("operand shorter than the plan's sizes")
+    if t.size(1) > 1 and t.stride(1) != 1:
+        raise ValueError("%s must be row-major: stride(1) == 1 (column-major operands are not built)" % name)
+    ld = t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
+    if ld < t.size(1):
+        raise ValueError("%s: rows overlap (stride(0) below the number of columns)" % name)
+    return ld
+
+
+def _edge_values(t, name, nnz, val_dtype):
+    """An operand of nnz values in CSR order: a contiguous 1-D device tensor of the plan's value type."""
+    _require_device(t)
+    if t.dtype != val_dtype:
+        raise TypeError("value type differs from the plan's (%s)" % name)
+    if t.dim() != 1 or t.numel() < nnz:
+        raise ValueError("operand shorter than the plan's sizes (%s)" % name)
+    return t
+
+
+def _require_vectors(X, x_rows, Y, y_rows, dtype):
+    """The k vectors of a multi-vector call, X of x_rows rows and Y of y_rows: (ldx, ldy)."""
+    ldx = _require_matrix(X, "X", x_rows, dtype)
+    ldy = _require_matrix(Y, "Y", y_rows, dtype)
+    if X.size(1) != Y.size(1):
+        raise ValueError("X and Y hold different numbers of vectors")
+    return ldx, ldy
+
+
+def _refuse_alias(X, Y):
+    """Y must not lie over X: a slice writes rows of Y while other slices still gather rows of X."""
+    span = lambda t: (t.data_ptr(), t.data_ptr() + ((t.size(0) - 1) * t.stride(0) + t.size(1)) * t.element_size()) if t.numel() else (0, 0)
+    (x0, x1), (y0, y1) = span(X), span(Y)
+    if x0 < y1 and y0 < x1:
+        raise ValueError("Y aliases X")
+
+
+def _semiring_id(semiring):
+    return SEMIRINGS[semiring] if isinstance(semiring, str) else int(semiring)
+
+
+def _ptr(t):
+    """The address of a tensor's first element as a void*; NULL for None (an optional operand left out)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ptr_or_null(t):
+    """_ptr that also gives NULL for a tensor without elements, whose address means nothing."""
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
 
 
 def _stream_ptr(stream):
     s = stream if stream is not None else torch.cuda.current_stream()
     return C.c_void_p(s.cuda_stream)
+
+
+# Deliberate: which calls run under torch.cuda.device(...) — include/mi355_spmv.h has every entry point work on the CURRENT device.
+# No guard (the caller's current device is the operands', as with the reference's operator; bench.py times the issue rate of
+# the first of these): the mi355_spmv_<kind>_* / merge_* one-shots, narrow_values, coo_to_csr, every mi355_spmv_plan_* call but
+# acquire / release, MultiPlan.execute, SddmmPlan's create (no device call), the functor, DistPlan.scatter_values /
+# replicate_x, every setter and query.  Entered under the device of Ap (rows, y): plan acquire / release, coo_symmetric_nnz,
+# csr_transpose, the multi / row_softmax / attention creates, the sddmm / row_softmax / attention / dist executes, every
+# one-shot from spmm_t on, DistPlan's creates and structure_changed.  Add none and remove none.
+
+
+class _Handle:
+    """Owner of one library object: `_h` is its handle, `_destroy` names the entry that frees it."""
+    _destroy = None
+
+    def _call(self, entry, *args):
+        """entry(handle, *args), checked."""
+        _check(getattr(lib(), entry)(self._h, *args), entry)
+
+    def _info(self, struct_type, entry, *args):
+        """entry(handle, *args, &struct) as a dict (_struct_dict)."""
+        si = struct_type()
+        self._call(entry, *args, C.byref(si))
+        return _struct_dict(si)
+
+    def destroy(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+# ---- SpMV: one-shots, COO -> CSR, Plan
 
 
 def spmv(kind, n_rows, n_cols, nnz, Ap, Aj, Ax, x, y, stream=None):
@@ -377,8 +493,7 @@ def spmv_mixed(n_rows, n_cols, nnz, Ap, Aj, Ax, x, y, stream=None):
     o = OFF_TYPES[Ap.dtype][1]
     fn = getattr(lib(), "mi355_spmv_merge_f32mat_f64vec_%s" % o)
     nnz_c = C.c_int32(nnz) if o == "i32" else C.c_int64(nnz)
-    st = fn(C.c_int32(n_rows), C.c_int32(n_cols), nnz_c, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
-            C.c_void_p(Ax.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), _stream_ptr(stream))
+    st = fn(C.c_int32(n_rows), C.c_int32(n_cols), nnz_c, _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(x), _ptr(y), _stream_ptr(stream))
     _check(st, "mi355_spmv_merge_f32mat_f64vec_%s" % o)
     return y
 
@@ -397,8 +512,7 @@ def narrow_values(Ax, dtype, out=None, stream=None):
         _require_device(out)
         if out.dtype != dtype or out.numel() < Ax.numel():
             raise TypeError("narrow_values: out must hold Ax.numel() values of the asked dtype")
-    st = lib().mi355_spmv_narrow_values(MAT_TYPES[dtype][0], Ax.numel(), C.c_void_p(Ax.data_ptr()),
-                                        C.c_void_p(out.data_ptr()), _stream_ptr(stream))
+    st = lib().mi355_spmv_narrow_values(MAT_TYPES[dtype][0], Ax.numel(), _ptr(Ax), _ptr(out), _stream_ptr(stream))
     _check(st, "mi355_spmv_narrow_values")
     return out
 
@@ -429,7 +543,7 @@ def spmv_genl(semiring, n_rows, n_cols, nnz, Ap, Aj, Ax, x, y, stream=None):
 def spmv_pattern(semiring, n_rows, n_cols, nnz, Ap, Aj, x, y, stream=None):
     """One-shot generalized merge-path SpMV with a PATTERN matrix — a structure and no values, every entry one
     (mi355_spmv_merge_pattern_*): the arguments of spmv_genl without Ax.  Synchronises the stream."""
-    sr = SEMIRINGS[semiring] if isinstance(semiring, str) else int(semiring)
+    sr = _semiring_id(semiring)
     _require_device(Ap, Aj, x, y)
     if Aj.dtype != torch.int32 or x.dtype != y.dtype:
         raise TypeError("Aj must be int32 and x, y one value type")
@@ -437,8 +551,7 @@ def spmv_pattern(semiring, n_rows, n_cols, nnz, Ap, Aj, x, y, stream=None):
     v = VAL_TYPES[x.dtype][1]
     fn = getattr(lib(), "mi355_spmv_merge_pattern_%s_%s" % (o, v))
     nnz_c = C.c_int32(nnz) if o == "i32" else C.c_int64(nnz)
-    st = fn(C.c_int(sr), C.c_int32(n_rows), C.c_int32(n_cols), nnz_c, C.c_void_p(Ap.data_ptr()),
-            C.c_void_p(Aj.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), _stream_ptr(stream))
+    st = fn(C.c_int(sr), C.c_int32(n_rows), C.c_int32(n_cols), nnz_c, _ptr(Ap), _ptr(Aj), _ptr(x), _ptr(y), _stream_ptr(stream))
     _check(st, "mi355_spmv_merge_pattern_%s_%s" % (o, v))
     return y
 
@@ -473,10 +586,9 @@ def coo_symmetric_nnz(rows, cols, stream=None):
     if cols.numel() != rows.numel():
         raise ValueError("rows and cols must have the same length")
     out = C.c_int64(0)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
     with torch.cuda.device(rows.device):
-        st = lib().mi355_spmv_coo_symmetric_nnz(C.c_int64(rows.numel()), ptr(rows), ptr(cols), _stream_ptr(stream),
-                                                C.byref(out))
+        st = lib().mi355_spmv_coo_symmetric_nnz(C.c_int64(rows.numel()), _ptr_or_null(rows), _ptr_or_null(cols),
+                                                _stream_ptr(stream), C.byref(out))
     _check(st, "mi355_spmv_coo_symmetric_nnz")
     return out.value
 
@@ -506,33 +618,27 @@ def coo_to_csr(n_rows, n_cols, rows, cols, vals=None, off_dtype=torch.int32, ret
     Ax = torch.empty(nnz, dtype=vals.dtype, device=dev) if vals is not None else None
     perm = torch.empty(nnz, dtype=torch.int64, device=dev) if return_perm else None
     val_dtype = vals.dtype if vals is not None else torch.float32
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-    if symmetric:
+    ptr = _ptr_or_null
+    if symmetric:       # the symmetric entry takes both counts: stored, expanded
+        what, counts = "coo_to_csr_symmetric", (C.c_int64(n_in), C.c_int64(nnz))
         nbytes = coo_to_csr_symmetric_workspace_bytes(n_rows, n_in, nnz, off_dtype, val_dtype)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        size = C.c_size_t(nbytes)
-        st = lib().mi355_spmv_coo_to_csr_symmetric(OFF_TYPES[off_dtype][0], VAL_TYPES[val_dtype][0], C.c_int32(n_rows),
-                                                   C.c_int32(n_cols), C.c_int64(n_in), C.c_int64(nnz), ptr(rows),
-                                                   ptr(cols), ptr(vals), ptr(Ap), ptr(Aj), ptr(Ax), ptr(perm),
-                                                   C.c_void_p(ws.data_ptr()), C.byref(size), _stream_ptr(stream))
-        _check(st, "mi355_spmv_coo_to_csr_symmetric")
-        csr = Csr(n_rows, n_cols, nnz, Ap, Aj, Ax, "coo_to_csr_symmetric", {"synthetic": False})
-        return (csr, perm) if return_perm else csr
-    nbytes = coo_to_csr_workspace_bytes(n_rows, nnz, off_dtype, val_dtype)
+    else:
+        what, counts = "coo_to_csr", (C.c_int64(nnz),)
+        nbytes = coo_to_csr_workspace_bytes(n_rows, nnz, off_dtype, val_dtype)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     size = C.c_size_t(nbytes)
-    st = lib().mi355_spmv_coo_to_csr(OFF_TYPES[off_dtype][0], VAL_TYPES[val_dtype][0], C.c_int32(n_rows),
-                                     C.c_int32(n_cols), C.c_int64(nnz), ptr(rows), ptr(cols), ptr(vals), ptr(Ap),
-                                     ptr(Aj), ptr(Ax), ptr(perm), C.c_void_p(ws.data_ptr()), C.byref(size),
-                                     _stream_ptr(stream))
-    _check(st, "mi355_spmv_coo_to_csr")
-    csr = Csr(n_rows, n_cols, nnz, Ap, Aj, Ax, "coo_to_csr", {"synthetic": False})
+    st = getattr(lib(), "mi355_spmv_" + what)(OFF_TYPES[off_dtype][0], VAL_TYPES[val_dtype][0], C.c_int32(n_rows), C.c_int32(n_cols),
+                                              *counts, ptr(rows), ptr(cols), ptr(vals), ptr(Ap), ptr(Aj), ptr(Ax), ptr(perm),
+                                              _ptr(ws), C.byref(size), _stream_ptr(stream))
+    _check(st, "mi355_spmv_" + what)
+    csr = Csr(n_rows, n_cols, nnz, Ap, Aj, Ax, what, {"synthetic": False})
     return (csr, perm) if return_perm else csr
 
 
-class Plan:
+class Plan(_Handle):
     """Scratch + launch shapes kept across calls (mi355_spmv_plan_*).  Holds
     references to Ap and Aj so they outlive the plan."""
+    _destroy = "mi355_spmv_plan_destroy"
 
     def __init__(self, kind, n_rows, n_cols, nnz, Ap, Aj, val_dtype, flags=0, mat_dtype=None):
         """val_dtype: the type of x and y (and of all arithmetic).  mat_dtype: the type the matrix values are stored
@@ -545,9 +651,7 @@ class Plan:
         kind = LABELS.get(kind, kind)
         if kind not in KINDS:
             raise ValueError('SpMV kind "%s" is NOT SUPPORTED' % kind)
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         self.kind, self.n_rows, self.n_cols, self.nnz = kind, n_rows, n_cols, nnz
         self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
         self.mat_dtype = mat_dtype if mat_dtype is not None else val_dtype
@@ -557,28 +661,22 @@ class Plan:
                 raise ValueError('mat_dtype is a torch dtype or "pattern"')
             if val_dtype not in VAL_TYPES:
                 raise TypeError("val_dtype must be float32, float64 or int32")
-            st = lib().mi355_spmv_plan_create_typed(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0], VAL_PATTERN,
-                                                    VAL_TYPES[val_dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols,
-                                                    nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
-            _check(st, "mi355_spmv_plan_create_typed")
+            types = (VAL_PATTERN, VAL_TYPES[val_dtype][0], VAL_TYPES[val_dtype][0])
         elif self.mat_dtype in MAT_TYPES:
             if val_dtype != torch.float32:
                 raise TypeError("a float16 / bfloat16 matrix is built under float32 x and y only")
-            st = lib().mi355_spmv_plan_create_typed(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0],
-                                                    MAT_TYPES[self.mat_dtype][0], 0, 0, n_rows, n_cols, nnz,
-                                                    C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
-            _check(st, "mi355_spmv_plan_create_typed")
+            types = (MAT_TYPES[self.mat_dtype][0], 0, 0)
         elif self.mat_dtype == val_dtype:
             st = lib().mi355_spmv_plan_create(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0],
-                                              VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz,
-                                              C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
+                                              VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), flags)
             _check(st, "mi355_spmv_plan_create")
+            return
         else:
-            st = lib().mi355_spmv_plan_create_typed(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0],
-                                                    VAL_TYPES[self.mat_dtype][0], VAL_TYPES[val_dtype][0],
-                                                    VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz,
-                                                    C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
-            _check(st, "mi355_spmv_plan_create_typed")
+            types = (VAL_TYPES[self.mat_dtype][0], VAL_TYPES[val_dtype][0], VAL_TYPES[val_dtype][0])
+        # (mat_type, x_type, y_type)
+        st = lib().mi355_spmv_plan_create_typed(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0], *types, n_rows, n_cols,
+                                                nnz, _ptr(Ap), _ptr(Aj), flags)
+        _check(st, "mi355_spmv_plan_create_typed")
 
     def execute(self, Ax, x, y, stream=None):
         """Asynchronous on `stream` (default: torch's current stream).  A pattern plan ignores Ax: None or any tensor."""
@@ -603,37 +701,32 @@ class Plan:
         return y
 
     def set_semiring(self, semiring):
-        sr = SEMIRINGS[semiring] if isinstance(semiring, str) else int(semiring)
-        _check(lib().mi355_spmv_plan_set_semiring(self._h, C.c_int(sr)), "mi355_spmv_plan_set_semiring")
+        self._call("mi355_spmv_plan_set_semiring", C.c_int(_semiring_id(semiring)))
 
     def set_alpha_beta(self, alpha, beta):
         """y = alpha * A x + beta * y for the following executes (default 1, 0)."""
-        _check(lib().mi355_spmv_plan_set_alpha_beta(self._h, C.c_double(alpha), C.c_double(beta)),
-               "mi355_spmv_plan_set_alpha_beta")
+        self._call("mi355_spmv_plan_set_alpha_beta", C.c_double(alpha), C.c_double(beta))
 
     def mat_type(self):
         """The MI355_VAL_* the plan's matrix values are stored in (3 = VAL_PATTERN: none)."""
         out = C.c_int(-1)
-        _check(lib().mi355_spmv_plan_get_mat_type(self._h, C.byref(out)), "mi355_spmv_plan_get_mat_type")
+        self._call("mi355_spmv_plan_get_mat_type", C.byref(out))
         return out.value
 
     def info(self):
-        pi = PlanInfo()
-        _check(lib().mi355_spmv_plan_get_info(self._h, C.byref(pi)), "mi355_spmv_plan_get_info")
-        return pi.as_dict()
+        return self._info(PlanInfo, "mi355_spmv_plan_get_info")
 
     def shape(self):
         """The plan's launch-shape decisions (mi355_spmv_plan_get_shape)."""
         sh = PlanShape()
-        _check(lib().mi355_spmv_plan_get_shape(self._h, C.byref(sh)), "mi355_spmv_plan_get_shape")
+        self._call("mi355_spmv_plan_get_shape", C.byref(sh))
         return sh
 
     def partition(self, parts):
         """nnz-balanced cuts on the plan's chunk boundaries: (row_cuts, chunk_cuts, nnz_cuts), parts + 1 each."""
         import numpy as np
         arrs = [np.zeros(parts + 1, dtype=np.int64) for _ in range(3)]
-        _check(lib().mi355_spmv_plan_partition(self._h, parts, *[a.ctypes.data_as(C.c_void_p) for a in arrs]),
-               "mi355_spmv_plan_partition")
+        self._call("mi355_spmv_plan_partition", parts, *[a.ctypes.data_as(C.c_void_p) for a in arrs])
         return tuple(a.tolist() for a in arrs)
 
     @classmethod
@@ -650,8 +743,7 @@ class Plan:
         st = lib().mi355_spmv_plan_create_block(
             C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0],
             C.cast(C.byref(whole_shape), C.c_void_p) if whole_shape is not None else None,
-            row_begin, chunk_begin, n_chunks, nnz_begin_whole, n_rows, n_cols, nnz_end,
-            C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), flags)
+            row_begin, chunk_begin, n_chunks, nnz_begin_whole, n_rows, n_cols, nnz_end, _ptr(Ap), _ptr(Aj), flags)
         _check(st, "mi355_spmv_plan_create_block")
         return self
 
@@ -663,17 +755,14 @@ class Plan:
         kind = LABELS.get(kind, kind)
         if kind not in KINDS:
             raise ValueError('SpMV kind "%s" is NOT SUPPORTED' % kind)
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         self = cls.__new__(cls)
         self.kind, self.n_rows, self.n_cols, self.nnz = kind, n_rows, n_cols, nnz
         self.Ap, self.Aj, self.val_dtype, self.mat_dtype = Ap, Aj, val_dtype, val_dtype
         self._h = C.c_void_p()
         with torch.cuda.device(Ap.device):
             st = lib().mi355_spmv_plan_acquire(C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0],
-                                               VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz,
-                                               C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()))
+                                               VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj))
         _check(st, "mi355_spmv_plan_acquire")
         return self
 
@@ -690,45 +779,14 @@ class Plan:
         n = self.info()["n_tiles"] + 1
         rows = np.empty(n, dtype=np.int64)
         nz = np.empty(n, dtype=np.int64)
-        _check(lib().mi355_spmv_plan_merge_coords(self._h, rows.ctypes.data_as(C.c_void_p),
-                                                  nz.ctypes.data_as(C.c_void_p)), "mi355_spmv_plan_merge_coords")
+        self._call("mi355_spmv_plan_merge_coords", rows.ctypes.data_as(C.c_void_p), nz.ctypes.data_as(C.c_void_p))
         return rows, nz
 
-    def destroy(self):
-        if self._h:
-            lib().mi355_spmv_plan_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+# ---- multi-vector SpMV
 
 
-def _require_matrix(t, name, rows, dtype):
-    """A 2-D device tensor of `rows` rows whose rows are contiguous (stride(1) == 1); returns its leading dimension."""
-    if not t.is_cuda:
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
-    if t.dim() != 2:
-        raise ValueError("%s must be 2-D (one row per matrix column / row, one column per vector)" % name)
-    if t.dtype != dtype:
-        raise TypeError("value type differs from the plan's")
-    if t.size(0) < rows:
-        raise ValueError("operand shorter than the plan's sizes")
-    if t.size(1) > 1 and t.stride(1) != 1:
-        raise ValueError("%s must be row-major: stride(1) == 1 (column-major operands are not built)" % name)
-    ld = t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
-    if ld < t.size(1):
-        raise ValueError("%s: rows overlap (stride(0) below the number of columns)" % name)
-    return ld
-
-
-def _semiring_id(semiring):
-    return SEMIRINGS[semiring] if isinstance(semiring, str) else int(semiring)
-
-
-class MultiPlan:
+class MultiPlan(_Handle):
     """mi355_spmv_multi_*: Y = A X for up to k_max vectors in one pass over A — Y = alpha * A X + beta * Y under (+, *),
     Y[r, j] = reduce over the row of combine(Ax, X[Aj, j]) under another semiring (set_semiring, or semiring=).  X
     (n_cols x k) and Y (n_rows x k) are 2-D row-major device tensors; views with a larger stride(0) are taken as they
@@ -738,6 +796,7 @@ class MultiPlan:
     refused, as it was before int32 existed here.  val_dtype float16 / bfloat16 (mi355_spmv_multi_create_half): X and Y
     in 16 bits, fp32 arithmetic, Y rounded once; mat_dtype is then None or val_dtype (Ax in the same 16 bits) or
     torch.float32, and the semiring "plus_times".  Holds references to Ap and Aj so they outlive the object."""
+    _destroy = "mi355_spmv_multi_destroy"
 
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, mat_dtype=None, semiring="plus_times", perm=None,
                  n_values=None, stream=None):
@@ -745,9 +804,7 @@ class MultiPlan:
         nonzero n's value as Ax[perm[n]], Ax holding n_values values (default nnz).  float32 / float64 under "plus_times"
         only.  Every index is checked on the device at create (on `stream`, which is synchronised); the plan keeps its own
         copy of perm."""
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         self.n_values = nnz
         if perm is not None:
             self._init_permuted(n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, mat_dtype, semiring, perm, n_values, stream)
@@ -771,22 +828,17 @@ class MultiPlan:
         self.Ap, self.Aj, self.val_dtype, self.pattern = Ap, Aj, val_dtype, pattern
         self.mat_dtype = val_dtype if mat_dtype is None or pattern else mat_dtype      # the type of Ax
         self._h = C.c_void_p()
+        if half:            # (mat_type, vec_type)
+            what = "mi355_spmv_multi_create_half"
+            types = (VAL_TYPES[torch.float32][0] if self.mat_dtype == torch.float32 else MAT_TYPES[val_dtype][0], MAT_TYPES[val_dtype][0])
+        elif typed:         # (mat_type, vec_type)
+            what = "mi355_spmv_multi_create_typed"
+            types = (VAL_PATTERN if pattern else VAL_TYPES[val_dtype][0], VAL_TYPES[val_dtype][0])
+        else:               # plain fp32 / fp64 (+, *) objects: one type
+            what = "mi355_spmv_multi_create"
+            types = (VAL_TYPES[val_dtype][0],)
         with torch.cuda.device(Ap.device):
-            if half:
-                what = "mi355_spmv_multi_create_half"
-                mat = VAL_TYPES[torch.float32][0] if self.mat_dtype == torch.float32 else MAT_TYPES[val_dtype][0]
-                st = lib().mi355_spmv_multi_create_half(
-                    C.byref(self._h), OFF_TYPES[Ap.dtype][0], mat, MAT_TYPES[val_dtype][0], n_rows, n_cols, nnz,
-                    C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), k_max)
-            elif typed:
-                what = "mi355_spmv_multi_create_typed"
-                st = lib().mi355_spmv_multi_create_typed(
-                    C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_PATTERN if pattern else VAL_TYPES[val_dtype][0],
-                    VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), k_max)
-            else:       # plain fp32 / fp64 (+, *) objects
-                what = "mi355_spmv_multi_create"
-                st = lib().mi355_spmv_multi_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows,
-                                                   n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), k_max)
+            st = getattr(lib(), what)(C.byref(self._h), OFF_TYPES[Ap.dtype][0], *types, n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), k_max)
         _check(st, what)
         if sr != 0:
             self.set_semiring(sr)
@@ -810,15 +862,14 @@ class MultiPlan:
         self._h = C.c_void_p()
         with torch.cuda.device(Ap.device):
             st = lib().mi355_spmv_multi_create_permuted(
-                C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()),
-                C.c_void_p(Aj.data_ptr()), OFF_TYPES[perm.dtype][0], C.c_void_p(perm.data_ptr()), n_values, k_max,
-                _stream_ptr(stream))
+                C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj),
+                OFF_TYPES[perm.dtype][0], _ptr(perm), n_values, k_max, _stream_ptr(stream))
         _check(st, "mi355_spmv_multi_create_permuted")
 
     def perm_info(self):
         """{"n_values", "held_bytes", "owns_structure"} (mi355_spmv_multi_get_perm_info)."""
         n, b, o = C.c_int64(), C.c_int64(), C.c_int()
-        _check(lib().mi355_spmv_multi_get_perm_info(self._h, C.byref(n), C.byref(b), C.byref(o)), "mi355_spmv_multi_get_perm_info")
+        self._call("mi355_spmv_multi_get_perm_info", C.byref(n), C.byref(b), C.byref(o))
         return {"n_values": n.value, "held_bytes": b.value, "owns_structure": o.value}
 
     def execute(self, Ax, X, Y, stream=None):
@@ -834,58 +885,29 @@ class MultiPlan:
                 raise TypeError("value type differs from the plan's")
             if Ax.numel() < (self.n_values if getattr(self, "permuted", False) else self.nnz):
                 raise ValueError("operand shorter than the plan's sizes")
-        ldx = _require_matrix(X, "X", self.n_cols, self.val_dtype)
-        ldy = _require_matrix(Y, "Y", self.n_rows, self.val_dtype)
-        if X.size(1) != Y.size(1):
-            raise ValueError("X and Y hold different numbers of vectors")
+        ldx, ldy = _require_vectors(X, self.n_cols, Y, self.n_rows, self.val_dtype)
         if getattr(self, "permuted", False):
             _refuse_alias(X, Y)
-        st = lib().mi355_spmv_multi_execute(self._h, C.c_void_p(Ax.data_ptr()) if Ax is not None else None,
-                                            C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, X.size(1),
-                                            _stream_ptr(stream))
+        st = lib().mi355_spmv_multi_execute(self._h, _ptr(Ax), _ptr(X), ldx, _ptr(Y), ldy, X.size(1), _stream_ptr(stream))
         _check(st, "mi355_spmv_multi_execute")
         return Y
 
     def set_alpha_beta(self, alpha, beta):
         """Y = alpha * A X + beta * Y for the following executes (default 1, 0); (+, *) on float types only."""
-        _check(lib().mi355_spmv_multi_set_alpha_beta(self._h, C.c_double(alpha), C.c_double(beta)),
-               "mi355_spmv_multi_set_alpha_beta")
+        self._call("mi355_spmv_multi_set_alpha_beta", C.c_double(alpha), C.c_double(beta))
 
     def set_semiring(self, semiring):
         """The semiring of the following executes: a name of SEMIRINGS or its number."""
-        _check(lib().mi355_spmv_multi_set_semiring(self._h, C.c_int(_semiring_id(semiring))), "mi355_spmv_multi_set_semiring")
+        self._call("mi355_spmv_multi_set_semiring", C.c_int(_semiring_id(semiring)))
 
     def types(self):
         """{"mat_type", "vec_type", "semiring"} as the library holds them (MI355_VAL_*, MI355_SEMIRING_*)."""
         m, v, s = C.c_int(), C.c_int(), C.c_int()
-        _check(lib().mi355_spmv_multi_get_types(self._h, C.byref(m), C.byref(v), C.byref(s)), "mi355_spmv_multi_get_types")
+        self._call("mi355_spmv_multi_get_types", C.byref(m), C.byref(v), C.byref(s))
         return {"mat_type": m.value, "vec_type": v.value, "semiring": s.value}
 
     def info(self):
-        mi = MultiInfo()
-        _check(lib().mi355_spmv_multi_get_info(self._h, C.byref(mi)), "mi355_spmv_multi_get_info")
-        d = {n: getattr(mi, n) for n, _ in mi._fields_}
-        d["main_kernel"] = d["main_kernel"].decode()
-        return d
-
-    def destroy(self):
-        if self._h:
-            lib().mi355_spmv_multi_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-def _refuse_alias(X, Y):
-    """Y must not lie over X: a slice writes rows of Y while other slices still gather rows of X."""
-    span = lambda t: (t.data_ptr(), t.data_ptr() + ((t.size(0) - 1) * t.stride(0) + t.size(1)) * t.element_size()) if t.numel() else (0, 0)
-    (x0, x1), (y0, y1) = span(X), span(Y)
-    if x0 < y1 and y0 < x1:
-        raise ValueError("Y aliases X")
+        return self._info(MultiInfo, "mi355_spmv_multi_get_info")
 
 
 def csr_transpose(n_rows, n_cols, Ap, Aj, stream=None):
@@ -893,9 +915,7 @@ def csr_transpose(n_rows, n_cols, Ap, Aj, stream=None):
     Ap's dtype, Ajt[t] = the row of A behind transposed slot t and perm[t] = its CSR slot in A (int32 tensors holding the
     library's unsigned 32-bit indices), so that Axt = Ax[perm.long()].  Inside a column the slots ascend (a stable sort by
     column): deterministic.  Synchronises the stream."""
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
+    _require_structure(Ap, Aj)
     if Ap.dtype not in OFF_TYPES:
         raise TypeError("Ap must be int32 or int64")
     if Ap.dim() != 1 or Ap.numel() < n_rows + 1:
@@ -908,11 +928,9 @@ def csr_transpose(n_rows, n_cols, Ap, Aj, stream=None):
     nbytes = csr_transpose_workspace_bytes(n_cols, nnz, Ap.dtype)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     size = C.c_size_t(nbytes)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
     with torch.cuda.device(dev):
-        st = lib().mi355_spmv_csr_transpose(OFF_TYPES[Ap.dtype][0], n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), ptr(Aj),
-                                            C.c_void_p(Apt.data_ptr()), ptr(Ajt), ptr(perm), C.c_void_p(ws.data_ptr()),
-                                            C.byref(size), _stream_ptr(stream))
+        st = lib().mi355_spmv_csr_transpose(OFF_TYPES[Ap.dtype][0], n_rows, n_cols, nnz, _ptr(Ap), _ptr_or_null(Aj), _ptr(Apt),
+                                            _ptr_or_null(Ajt), _ptr_or_null(perm), _ptr(ws), C.byref(size), _stream_ptr(stream))
     _check(st, "mi355_spmv_csr_transpose")
     return Apt, Ajt, perm
 
@@ -933,9 +951,7 @@ class TransposedMultiPlan(MultiPlan):
     n_rows x k, Y is n_cols x k.  float32 / float64.  The plan owns its structure: Ap and Aj are not retained."""
 
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, k_max, stream=None):
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         if val_dtype not in (torch.float32, torch.float64):
             raise TypeError("val_dtype must be float32 or float64")
         if Ap.dtype not in OFF_TYPES:
@@ -950,8 +966,8 @@ class TransposedMultiPlan(MultiPlan):
         self._h = C.c_void_p()
         with torch.cuda.device(Ap.device):
             st = lib().mi355_spmv_multi_create_transposed(
-                C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()),
-                C.c_void_p(Aj.data_ptr()) if Aj.numel() else None, k_max, _stream_ptr(stream))
+                C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz, _ptr(Ap), _ptr_or_null(Aj),
+                k_max, _stream_ptr(stream))
         _check(st, "mi355_spmv_multi_create_transposed")
 
     def structure(self, stream=None):
@@ -959,9 +975,9 @@ class TransposedMultiPlan(MultiPlan):
         Apt = torch.empty(self.n_rows + 1, dtype=self.off_dtype, device=self.device)
         Ajt = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
         perm = torch.empty(self.nnz, dtype=torch.int32, device=self.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
         with torch.cuda.device(self.device):
-            st = lib().mi355_spmv_multi_copy_structure(self._h, ptr(Apt), ptr(Ajt), ptr(perm), _stream_ptr(stream))
+            st = lib().mi355_spmv_multi_copy_structure(self._h, _ptr_or_null(Apt), _ptr_or_null(Ajt), _ptr_or_null(perm),
+                                                       _stream_ptr(stream))
         _check(st, "mi355_spmv_multi_copy_structure")
         return Apt, Ajt, perm
 
@@ -969,23 +985,17 @@ class TransposedMultiPlan(MultiPlan):
 def spmm_t(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None):
     """One-shot Y = A^T X for the k = X.size(1) vectors of a row-major X (n_rows x k; Y is n_cols x k), Ax in A's CSR order:
     mi355_spmv_multi_transposed_<off>_<val> — create, execute, synchronise the stream, destroy."""
-    _require_device(Ap, Aj, Ax)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
+    _require_structure(Ap, Aj, Ax)
     if Ax.dtype not in (torch.float32, torch.float64):
         raise TypeError("Ax must be float32 or float64")
     if Ax.numel() < nnz or Aj.numel() < nnz or Ap.numel() < n_rows + 1:
         raise ValueError("operand shorter than the matrix")
-    ldx = _require_matrix(X, "X", n_rows, Ax.dtype)
-    ldy = _require_matrix(Y, "Y", n_cols, Ax.dtype)
-    if X.size(1) != Y.size(1):
-        raise ValueError("X and Y hold different numbers of vectors")
+    ldx, ldy = _require_vectors(X, n_rows, Y, n_cols, Ax.dtype)
     _refuse_alias(X, Y)
     name = "mi355_spmv_multi_transposed_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[Ax.dtype][1])
     with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
-                                  C.c_void_p(Ax.data_ptr()), C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy,
-                                  X.size(1), _stream_ptr(stream))
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(X), ldx, _ptr(Y), ldy, X.size(1),
+                                  _stream_ptr(stream))
     _check(st, name)
     return Y
 
@@ -995,37 +1005,18 @@ def spmm(n_rows, n_cols, nnz, Ap, Aj, Ax, X, Y, stream=None, semiring="plus_time
     destroy.  (+, *) on float values: mi355_spmv_multi_<off>_<val>; another semiring, or int32 values:
     mi355_spmv_multi_genl_<off>_<val>; float16 / bfloat16 Ax, X and Y under (+, *): mi355_spmv_multi_half_<off>_<val>
     (fp32 arithmetic, Y rounded once)."""
-    _require_device(Ap, Aj, Ax)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
+    _require_structure(Ap, Aj, Ax)
     sr = _semiring_id(semiring)
     genl = sr != 0 or Ax.dtype == torch.int32
-    if sr == 0 and Ax.dtype in MAT_TYPES:
-        if Ax.numel() < nnz:
-            raise ValueError("operand shorter than the matrix")
-        ldx = _require_matrix(X, "X", n_cols, Ax.dtype)
-        ldy = _require_matrix(Y, "Y", n_rows, Ax.dtype)
-        if X.size(1) != Y.size(1):
-            raise ValueError("X and Y hold different numbers of vectors")
-        name = "mi355_spmv_multi_half_%s_%s" % (OFF_TYPES[Ap.dtype][1], MAT_TYPES[Ax.dtype][1])
-        with torch.cuda.device(Ap.device):
-            st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
-                                      C.c_void_p(Ax.data_ptr()), C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy,
-                                      X.size(1), _stream_ptr(stream))
-        _check(st, name)
-        return Y
-    if Ax.dtype not in ((torch.float32, torch.float64, torch.int32) if genl else (torch.float32, torch.float64)):
+    half = sr == 0 and Ax.dtype in MAT_TYPES
+    if not half and Ax.dtype not in ((torch.float32, torch.float64, torch.int32) if genl else (torch.float32, torch.float64)):
         raise TypeError("Ax must be float32 or float64" + (" or int32" if genl else ""))
     if Ax.numel() < nnz:
         raise ValueError("operand shorter than the matrix")
-    ldx = _require_matrix(X, "X", n_cols, Ax.dtype)
-    ldy = _require_matrix(Y, "Y", n_rows, Ax.dtype)
-    if X.size(1) != Y.size(1):
-        raise ValueError("X and Y hold different numbers of vectors")
-    o, v = OFF_TYPES[Ap.dtype][1], VAL_TYPES[Ax.dtype][1]
-    name = "mi355_spmv_multi_%s%s_%s" % ("genl_" if genl else "", o, v)
-    args = (n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), C.c_void_p(Ax.data_ptr()),
-            C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy, X.size(1), _stream_ptr(stream))
+    ldx, ldy = _require_vectors(X, n_cols, Y, n_rows, Ax.dtype)
+    o, v = OFF_TYPES[Ap.dtype][1], (MAT_TYPES if half else VAL_TYPES)[Ax.dtype][1]
+    name = "mi355_spmv_multi_%s%s_%s" % ("half_" if half else "genl_" if genl else "", o, v)
+    args = (n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(X), ldx, _ptr(Y), ldy, X.size(1), _stream_ptr(stream))
     with torch.cuda.device(Ap.device):
         st = getattr(lib(), name)(*(((sr,) if genl else ()) + args))
     _check(st, name)
@@ -1036,25 +1027,41 @@ def spmm_pattern(semiring, n_rows, n_cols, nnz, Ap, Aj, X, Y, stream=None):
     """One-shot multi-vector SpMV with a PATTERN matrix — a structure and no values, every entry one
     (mi355_spmv_multi_pattern_<off>_<val>): the arguments of spmm without Ax, the semiring first as in spmv_pattern."""
     sr = _semiring_id(semiring)
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
-    if not getattr(X, "is_cuda", False):
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
+    _require_structure(Ap, Aj)
+    _require_on_device(X)
     if X.dtype not in VAL_TYPES:
         raise TypeError("X must be float32, float64 or int32")
-    ldx = _require_matrix(X, "X", n_cols, X.dtype)
-    ldy = _require_matrix(Y, "Y", n_rows, X.dtype)
-    if X.size(1) != Y.size(1):
-        raise ValueError("X and Y hold different numbers of vectors")
-    o, v = OFF_TYPES[Ap.dtype][1], VAL_TYPES[X.dtype][1]
-    name = "mi355_spmv_multi_pattern_%s_%s" % (o, v)
+    ldx, ldy = _require_vectors(X, n_cols, Y, n_rows, X.dtype)
+    name = "mi355_spmv_multi_pattern_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[X.dtype][1])
     with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(sr, n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()),
-                                  C.c_void_p(Aj.data_ptr()), C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy,
-                                  X.size(1), _stream_ptr(stream))
+        st = getattr(lib(), name)(sr, n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), _ptr(X), ldx, _ptr(Y), ldy, X.size(1),
+                                  _stream_ptr(stream))
     _check(st, name)
     return Y
+
+
+# ---- SDDMM, row softmax, fused sparse attention and its backward
+
+# What separates a one-shot on 16-bit matrices from its full-precision sibling: (the types its first operand may have,
+# each with its entry suffix; how the refusal names them; the value type — None: the operand's own; the entry stem).
+_FULL = ({torch.float32: "f32", torch.float64: "f64"}, "float32 or float64", None, "")
+_HALF = ({dt: s for dt, (_, s) in MAT_TYPES.items()}, "float16 or bfloat16", torch.float32, "half_")
+
+
+def _one_shot_value_type(variant, Ap, Aj, first, first_name):
+    """The opening of such a one-shot: the structure, then its first operand's device and type -> the value type."""
+    types, words, val_dtype, _ = variant
+    _require_structure(Ap, Aj)
+    _require_on_device(first)
+    if first.dtype not in types:
+        raise TypeError("%s must be %s" % (first_name, words))
+    return val_dtype or first.dtype
+
+
+def _one_shot_entry(variant, family, Ap, first):
+    """mi355_spmv_<family>_[half_]<off>_<val>, named once every operand has passed."""
+    types, _, _, stem = variant
+    return "mi355_spmv_%s_%s%s_%s" % (family, stem, OFF_TYPES[Ap.dtype][1], types[first.dtype])
 
 
 def _sddmm_operands(n_rows, n_cols, nnz, val_dtype, Ax, U, V, out, k, vec_dtype=None):
@@ -1084,7 +1091,7 @@ def _sddmm_operands(n_rows, n_cols, nnz, val_dtype, Ax, U, V, out, k, vec_dtype=
     return Ax, ldu, ldv, out, k
 
 
-class SddmmPlan:
+class SddmmPlan(_Handle):
     """mi355_spmv_sddmm_*: out[n] = alpha * s[n] * dot(U[r(n), :k], V[Aj[n], :k]) + beta * out[n] for every stored entry n
     of A, in one pass over A and one kernel for any k; s = Ax, or 1 with Ax=None (a pattern matrix).  U (n_rows x k) and
     V (n_cols x k) are 2-D row-major device tensors; views with a larger stride(0) are taken as they are.  out holds nnz
@@ -1095,11 +1102,10 @@ class SddmmPlan:
     vec_dtype=torch.float16 / torch.bfloat16 (mi355_spmv_sddmm_create_half; val_dtype must be float32): U and V are held
     in that type, Ax and out stay float32, every stored value is widened exactly and products and sums are float32.
     plan.vec_dtype is the type of U and V (val_dtype without the argument)."""
+    _destroy = "mi355_spmv_sddmm_destroy"
 
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, vec_dtype=None):
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         if val_dtype not in (torch.float32, torch.float64):
             raise TypeError("val_dtype must be float32 or float64")
         if vec_dtype is not None:
@@ -1111,7 +1117,7 @@ class SddmmPlan:
         self.Ap, self.Aj, self.val_dtype = Ap, Aj, val_dtype
         self.vec_dtype = val_dtype if vec_dtype is None else vec_dtype
         self._h = C.c_void_p()
-        args = (n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()))
+        args = (n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj))
         if vec_dtype is None:
             _check(lib().mi355_spmv_sddmm_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], *args),
                    "mi355_spmv_sddmm_create")
@@ -1124,98 +1130,52 @@ class SddmmPlan:
         k defaults to U.size(1); ldu / ldv are the operands' stride(0)."""
         Ax, ldu, ldv, out, k = _sddmm_operands(self.n_rows, self.n_cols, self.nnz, self.val_dtype, Ax, U, V, out, k, self.vec_dtype)
         with torch.cuda.device(self.Ap.device):
-            st = lib().mi355_spmv_sddmm_execute(self._h, C.c_void_p(Ax.data_ptr()) if Ax is not None else None,
-                                                C.c_void_p(U.data_ptr()), ldu, C.c_void_p(V.data_ptr()), ldv,
-                                                C.c_void_p(out.data_ptr()), k, _stream_ptr(stream))
+            st = lib().mi355_spmv_sddmm_execute(self._h, _ptr(Ax), _ptr(U), ldu, _ptr(V), ldv, _ptr(out), k, _stream_ptr(stream))
         _check(st, "mi355_spmv_sddmm_execute")
         return out
 
     def set_alpha_beta(self, alpha, beta):
         """out = alpha * s * dot + beta * out for the following executes (default 1, 0)."""
-        _check(lib().mi355_spmv_sddmm_set_alpha_beta(self._h, C.c_double(alpha), C.c_double(beta)),
-               "mi355_spmv_sddmm_set_alpha_beta")
+        self._call("mi355_spmv_sddmm_set_alpha_beta", C.c_double(alpha), C.c_double(beta))
 
     def info(self):
-        si = SddmmInfo()
-        _check(lib().mi355_spmv_sddmm_get_info(self._h, C.byref(si)), "mi355_spmv_sddmm_get_info")
-        d = {n: getattr(si, n) for n, _ in si._fields_}
-        d["main_kernel"] = d["main_kernel"].decode()
-        return d
+        return self._info(SddmmInfo, "mi355_spmv_sddmm_get_info")
 
-    def destroy(self):
-        if self._h:
-            lib().mi355_spmv_sddmm_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+def _sddmm(variant, n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out, stream):
+    val_dtype = _one_shot_value_type(variant, Ap, Aj, U, "U")
+    Ax, ldu, ldv, out, k = _sddmm_operands(n_rows, n_cols, nnz, val_dtype, Ax, U, V, out, None, U.dtype)
+    name = _one_shot_entry(variant, "sddmm", Ap, U)
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(U), ldu, _ptr(V), ldv, _ptr(out), k,
+                                  _stream_ptr(stream))
+    _check(st, name)
+    return out
 
 
 def sddmm(n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out=None, stream=None):
     """One-shot SDDMM (mi355_spmv_sddmm_<off>_<val>): out[n] = s[n] * dot(U[r(n)], V[Aj[n]]) for the k = U.size(1) columns
     of row-major U and V; Ax=None is a pattern matrix.  Asynchronous on `stream`: it does not synchronise."""
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
-    if not getattr(U, "is_cuda", False):
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
-    if U.dtype not in (torch.float32, torch.float64):
-        raise TypeError("U must be float32 or float64")
-    Ax, ldu, ldv, out, k = _sddmm_operands(n_rows, n_cols, nnz, U.dtype, Ax, U, V, out, None)
-    name = "mi355_spmv_sddmm_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[U.dtype][1])
-    with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
-                                  C.c_void_p(Ax.data_ptr()) if Ax is not None else None, C.c_void_p(U.data_ptr()), ldu,
-                                  C.c_void_p(V.data_ptr()), ldv, C.c_void_p(out.data_ptr()), k, _stream_ptr(stream))
-    _check(st, name)
-    return out
+    return _sddmm(_FULL, n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out, stream)
 
 
 def sddmm_half(n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out=None, stream=None):
     """One-shot SDDMM on 16-bit U and V (mi355_spmv_sddmm_half_<off>_<f16|bf16>): sddmm's arguments with U and V in one of
     float16 / bfloat16, Ax (or None) and out in float32.  Asynchronous on `stream`: it does not synchronise."""
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
-    if not getattr(U, "is_cuda", False):
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
-    if U.dtype not in MAT_TYPES:
-        raise TypeError("U must be float16 or bfloat16")
-    Ax, ldu, ldv, out, k = _sddmm_operands(n_rows, n_cols, nnz, torch.float32, Ax, U, V, out, None, U.dtype)
-    name = "mi355_spmv_sddmm_half_%s_%s" % (OFF_TYPES[Ap.dtype][1], MAT_TYPES[U.dtype][1])
-    with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
-                                  C.c_void_p(Ax.data_ptr()) if Ax is not None else None, C.c_void_p(U.data_ptr()), ldu,
-                                  C.c_void_p(V.data_ptr()), ldv, C.c_void_p(out.data_ptr()), k, _stream_ptr(stream))
-    _check(st, name)
-    return out
+    return _sddmm(_HALF, n_rows, n_cols, nnz, Ap, Aj, Ax, U, V, out, stream)
 
 
-def _edge_values(t, name, nnz, val_dtype):
-    """An operand of nnz values in CSR order: a contiguous 1-D device tensor of the plan's value type."""
-    _require_device(t)
-    if t.dtype != val_dtype:
-        raise TypeError("value type differs from the plan's (%s)" % name)
-    if t.dim() != 1 or t.numel() < nnz:
-        raise ValueError("operand shorter than the plan's sizes (%s)" % name)
-    return t
-
-
-class RowSoftmaxPlan:
+class RowSoftmaxPlan(_Handle):
     """mi355_spmv_row_softmax_*: the softmax of scale * x over the stored entries of every row of A ("edge softmax"), and
     its gradient.  x, out, p, dp and the gradient are contiguous 1-D device tensors of nnz values in CSR order, float32 or
     float64 (val_dtype).  An entry of -inf is a masked edge and gives exactly 0; a row that is masked whole gives zeros;
     empty rows write nothing.  In place is allowed: execute(x, out=x), backward(p, dp, out=dp) or out=p.  Holds
     references to Ap and Aj (Aj is not read) so they outlive the object; creating one allocates O(n_slices) bytes of
     scratch on Ap's device (info()["scratch_bytes"]).  Executes are asynchronous and never synchronise."""
+    _destroy = "mi355_spmv_row_softmax_destroy"
 
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype):
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         if val_dtype not in (torch.float32, torch.float64):
             raise TypeError("val_dtype must be float32 or float64")
         self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
@@ -1224,7 +1184,7 @@ class RowSoftmaxPlan:
         # (nothing stored: create makes no device call, and no device need exist)
         with torch.cuda.device(Ap.device) if nnz > 0 and n_rows > 0 else contextlib.nullcontext():
             st = lib().mi355_spmv_row_softmax_create(C.byref(self._h), OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols,
-                                                     nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()))
+                                                     nnz, _ptr(Ap), _ptr(Aj))
         _check(st, "mi355_spmv_row_softmax_create")
 
     def _out(self, out, like):
@@ -1238,7 +1198,7 @@ class RowSoftmaxPlan:
         x = _edge_values(x, "x", self.nnz, self.val_dtype)
         out = self._out(out, x)
         with torch.cuda.device(self.Ap.device):
-            st = lib().mi355_spmv_row_softmax_execute(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), _stream_ptr(stream))
+            st = lib().mi355_spmv_row_softmax_execute(self._h, _ptr(x), _ptr(out), _stream_ptr(stream))
         _check(st, "mi355_spmv_row_softmax_execute")
         return out
 
@@ -1249,50 +1209,27 @@ class RowSoftmaxPlan:
         dp = _edge_values(dp, "dp", self.nnz, self.val_dtype)
         out = self._out(out, p)
         with torch.cuda.device(self.Ap.device):
-            st = lib().mi355_spmv_row_softmax_backward(self._h, C.c_void_p(p.data_ptr()), C.c_void_p(dp.data_ptr()),
-                                                       C.c_void_p(out.data_ptr()), _stream_ptr(stream))
+            st = lib().mi355_spmv_row_softmax_backward(self._h, _ptr(p), _ptr(dp), _ptr(out), _stream_ptr(stream))
         _check(st, "mi355_spmv_row_softmax_backward")
         return out
 
     def set_scale(self, s):
         """scale for the following executes and backwards (default 1): the 1 / sqrt(d) of attention."""
-        _check(lib().mi355_spmv_row_softmax_set_scale(self._h, C.c_double(s)), "mi355_spmv_row_softmax_set_scale")
+        self._call("mi355_spmv_row_softmax_set_scale", C.c_double(s))
 
     def info(self):
-        si = RowSoftmaxInfo()
-        _check(lib().mi355_spmv_row_softmax_get_info(self._h, C.byref(si)), "mi355_spmv_row_softmax_get_info")
-        d = {n: getattr(si, n) for n, _ in si._fields_}
-        d["main_kernel"] = d["main_kernel"].decode()
-        return d
-
-    def destroy(self):
-        if self._h:
-            lib().mi355_spmv_row_softmax_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        return self._info(RowSoftmaxInfo, "mi355_spmv_row_softmax_get_info")
 
 
 def row_softmax(n_rows, n_cols, nnz, Ap, Aj, x, out=None, scale=1.0, stream=None):
     """One-shot row softmax (mi355_spmv_row_softmax_<off>_<val>): out = softmax over each row of scale * x, x and out nnz
     values in CSR order (out may be x).  Synchronises `stream` before returning: its scratch lives for the call."""
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
-    if not getattr(x, "is_cuda", False):
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
-    if x.dtype not in (torch.float32, torch.float64):
-        raise TypeError("x must be float32 or float64")
+    _one_shot_value_type(_FULL, Ap, Aj, x, "x")
     x = _edge_values(x, "x", nnz, x.dtype)
     out = torch.empty(nnz, dtype=x.dtype, device=x.device) if out is None else _edge_values(out, "out", nnz, x.dtype)
-    name = "mi355_spmv_row_softmax_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[x.dtype][1])
+    name = _one_shot_entry(_FULL, "row_softmax", Ap, x)
     with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), C.c_void_p(x.data_ptr()),
-                                  C.c_void_p(out.data_ptr()), C.c_double(scale), _stream_ptr(stream))
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), _ptr(x), _ptr(out), C.c_double(scale), _stream_ptr(stream))
     _check(st, name)
     return out
 
@@ -1323,11 +1260,7 @@ def _attention_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, out, lse, bias,
     return d, dv, ldq, ldk, ldv, out, ldo
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-class SparseAttentionPlan:
+class SparseAttentionPlan(_Handle):
     """mi355_spmv_attention_*: fused sparse attention on the structure of A, O = softmax(scale * Q K^T + bias, over the
     stored entries of every row) V in ONE pass over A — the chain SddmmPlan -> RowSoftmaxPlan -> MultiPlan without the
     nnz-sized scores and probabilities.  Q is n_rows x d, K n_cols x d, V n_cols x dv (row-major device tensors of
@@ -1340,11 +1273,10 @@ class SparseAttentionPlan:
     are held in that type; bias, lse, the scale and every operation stay float32, every stored value is widened exactly and
     an element of out is rounded to vec_dtype once.  plan.vec_dtype is the type of Q, K, V and out (val_dtype without the
     argument)."""
+    _destroy = "mi355_spmv_attention_destroy"
 
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, d_max, dv_max, vec_dtype=None):
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         if val_dtype not in (torch.float32, torch.float64):
             raise TypeError("val_dtype must be float32 or float64")
         if vec_dtype is not None:
@@ -1360,13 +1292,12 @@ class SparseAttentionPlan:
         # (no rows: create makes no device call, and no device need exist)
         with torch.cuda.device(Ap.device) if n_rows > 0 else contextlib.nullcontext():
             if vec_dtype is None:
-                st, name = lib().mi355_spmv_attention_create(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
-                                                             OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], d_max, dv_max,
-                                                             C.byref(self._h)), "mi355_spmv_attention_create"
+                # Deliberate: the handle goes LAST here, and here alone (include/mi355_spmv.h, mi355_spmv_attention_create)
+                st, name = lib().mi355_spmv_attention_create(n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), OFF_TYPES[Ap.dtype][0],
+                                                             VAL_TYPES[val_dtype][0], d_max, dv_max, C.byref(self._h)), "mi355_spmv_attention_create"
             else:
                 st, name = lib().mi355_spmv_attention_create_half(C.byref(self._h), OFF_TYPES[Ap.dtype][0], MAT_TYPES[vec_dtype][0], n_rows,
-                                                                  n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d_max,
-                                                                  dv_max), "mi355_spmv_attention_create_half"
+                                                                  n_cols, nnz, _ptr(Ap), _ptr(Aj), d_max, dv_max), "mi355_spmv_attention_create_half"
         _check(st, name)
 
     def execute(self, Q, K, V, out=None, lse=None, bias=None, stream=None):
@@ -1382,66 +1313,34 @@ class SparseAttentionPlan:
 
     def set_scale(self, s):
         """scale for the following executes (default 1): the 1 / sqrt(d) of attention."""
-        _check(lib().mi355_spmv_attention_set_scale(self._h, C.c_double(s)), "mi355_spmv_attention_set_scale")
+        self._call("mi355_spmv_attention_set_scale", C.c_double(s))
 
     def info(self):
-        si = AttentionInfo()
-        _check(lib().mi355_spmv_attention_get_info(self._h, C.byref(si)), "mi355_spmv_attention_get_info")
-        d = {n: getattr(si, n) for n, _ in si._fields_ if n != "reserved"}
-        d["main_kernel"] = d["main_kernel"].decode()
-        return d
+        return self._info(AttentionInfo, "mi355_spmv_attention_get_info")
 
-    def destroy(self):
-        if self._h:
-            lib().mi355_spmv_attention_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+def _sparse_attention(variant, n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias, scale, out, lse, stream):
+    val_dtype = _one_shot_value_type(variant, Ap, Aj, Q, "Q")
+    d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, out, lse, bias, vec_dtype=Q.dtype)
+    name = _one_shot_entry(variant, "attention", Ap, Q)
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), d, dv, _ptr(Q), ldq, _ptr(K), ldk, _ptr(V), ldv, _ptr(bias),
+                                  C.c_double(scale), _ptr(out), ldo, _ptr(lse), _stream_ptr(stream))
+    _check(st, name)
+    return out
 
 
 def sparse_attention(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias=None, scale=1.0, out=None, lse=None, stream=None):
     """One-shot fused sparse attention (mi355_spmv_attention_<off>_<val>): SparseAttentionPlan's execute on a plan made for
     the call.  Synchronises `stream` before returning: its scratch lives for the call."""
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
-    if not getattr(Q, "is_cuda", False):
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
-    if Q.dtype not in (torch.float32, torch.float64):
-        raise TypeError("Q must be float32 or float64")
-    d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(n_rows, n_cols, nnz, Q.dtype, Q, K, V, out, lse, bias)
-    name = "mi355_spmv_attention_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[Q.dtype][1])
-    with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq,
-                                  _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(out), ldo, _ptr(lse),
-                                  _stream_ptr(stream))
-    _check(st, name)
-    return out
+    return _sparse_attention(_FULL, n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias, scale, out, lse, stream)
 
 
 def sparse_attention_half(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias=None, scale=1.0, out=None, lse=None, stream=None):
     """One-shot fused sparse attention on 16-bit Q, K, V and out (mi355_spmv_attention_half_<off>_<f16|bf16>):
     sparse_attention's arguments with Q, K, V (and out) in one of float16 / bfloat16, bias and lse in float32.  Synchronises
     `stream` before returning: its scratch lives for the call."""
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
-    if not getattr(Q, "is_cuda", False):
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
-    if Q.dtype not in MAT_TYPES:
-        raise TypeError("Q must be float16 or bfloat16")
-    d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(n_rows, n_cols, nnz, torch.float32, Q, K, V, out, lse, bias, vec_dtype=Q.dtype)
-    name = "mi355_spmv_attention_half_%s_%s" % (OFF_TYPES[Ap.dtype][1], MAT_TYPES[Q.dtype][1])
-    with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq,
-                                  _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(out), ldo, _ptr(lse),
-                                  _stream_ptr(stream))
-    _check(st, name)
-    return out
+    return _sparse_attention(_HALF, n_rows, n_cols, nnz, Ap, Aj, Q, K, V, bias, scale, out, lse, stream)
 
 
 def _attention_backward_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, d_max=None, dv_max=None,
@@ -1493,7 +1392,7 @@ def _attention_backward_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, O, dO,
     return d, dv, ldq, ldk, ldv, ldo, lddo, outs[0], outs[1], outs[2], dbias, lds
 
 
-class SparseAttentionBackwardPlan:
+class SparseAttentionBackwardPlan(_Handle):
     """mi355_spmv_attention_bwd_*: the fused backward of SparseAttentionPlan — dQ, dK, dV (and dbias) from Q, K, V, bias, the
     forward's O and lse, and dO, with nothing of nnz size kept between forward and backward.  One plan per STRUCTURE: it
     holds the transpose of A (info()["held_bytes"]), built at create on `stream` (which is synchronised), and serves every
@@ -1501,11 +1400,10 @@ class SparseAttentionBackwardPlan:
     and dO n_rows x dv (row-major device tensors, d <= d_max, dv <= dv_max, a row stride above the width is the leading
     dimension); lse n_rows values, bias nnz values in CSR order or None.  Holds references to Ap and Aj.  Executes are
     asynchronous and never synchronise."""
+    _destroy = "mi355_spmv_attention_bwd_destroy"
 
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, dtype, d_max, dv_max, stream=None):
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         if dtype not in (torch.float32, torch.float64):
             raise TypeError("dtype must be float32 or float64 (16-bit operands: SparseAttentionBackwardHalfPlan)")
         self._create("mi355_spmv_attention_bwd_create", VAL_TYPES[dtype][0], n_rows, n_cols, nnz, Ap, Aj, dtype, dtype, d_max, dv_max, stream)
@@ -1518,8 +1416,8 @@ class SparseAttentionBackwardPlan:
         self.d_max, self.dv_max = d_max, dv_max
         self._h = C.c_void_p()
         with torch.cuda.device(Ap.device):
-            st = getattr(lib(), entry)(C.byref(self._h), OFF_TYPES[Ap.dtype][0], type_code, n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()),
-                                       C.c_void_p(Aj.data_ptr()), d_max, dv_max, _stream_ptr(stream))
+            st = getattr(lib(), entry)(C.byref(self._h), OFF_TYPES[Ap.dtype][0], type_code, n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), d_max,
+                                       dv_max, _stream_ptr(stream))
         _check(st, entry)
 
     def execute(self, Q, K, V, O, dO, lse, bias=None, dQ=None, dK=None, dV=None, dbias=None, need=(True, True, True), stream=None):
@@ -1538,49 +1436,13 @@ class SparseAttentionBackwardPlan:
 
     def set_scale(self, s):
         """scale for the following executes (default 1): the forward plan's."""
-        _check(lib().mi355_spmv_attention_bwd_set_scale(self._h, C.c_double(s)), "mi355_spmv_attention_bwd_set_scale")
+        self._call("mi355_spmv_attention_bwd_set_scale", C.c_double(s))
 
     def info(self):
-        si = AttentionBackwardInfo()
-        _check(lib().mi355_spmv_attention_bwd_get_info(self._h, C.byref(si)), "mi355_spmv_attention_bwd_get_info")
-        d = {n: getattr(si, n) for n, _ in si._fields_ if n != "reserved"}
-        d["main_kernel"] = d["main_kernel"].decode()
-        d["lanes_per_slot"] = dict(zip(("dq", "dk", "dv"), d["lanes_per_slot"]))
+        d = self._info(AttentionBackwardInfo, "mi355_spmv_attention_bwd_get_info")
+        d["lanes_per_slot"] = dict(zip(("dq", "dk", "dv"), d["lanes_per_slot"]))      # one per walk
         d["passes"] = dict(zip(("dq", "dk", "dv"), d["passes"]))
         return d
-
-    def destroy(self):
-        if self._h:
-            lib().mi355_spmv_attention_bwd_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-def sparse_attention_backward(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, bias=None, scale=1.0, dQ=None, dK=None, dV=None, dbias=None,
-                              need=(True, True, True), stream=None):
-    """One-shot fused attention backward (mi355_spmv_attention_bwd_<off>_<val>): SparseAttentionBackwardPlan's execute on a
-    plan made for the call -> (dQ, dK, dV, dbias).  Synchronises `stream` before returning."""
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
-    if not getattr(Q, "is_cuda", False):
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
-    if Q.dtype not in (torch.float32, torch.float64):
-        raise TypeError("Q must be float32 or float64")
-    d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
-        n_rows, n_cols, nnz, Q.dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need)
-    name = "mi355_spmv_attention_bwd_%s_%s" % (OFF_TYPES[Ap.dtype][1], VAL_TYPES[Q.dtype][1])
-    with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq, _ptr(K), ldk,
-                                  _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(O), ldo, _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0],
-                                  _ptr(dK), lds[1], _ptr(dV), lds[2], _ptr(dbias), _stream_ptr(stream))
-    _check(st, name)
-    return dQ, dK, dV, dbias
 
 
 class SparseAttentionBackwardHalfPlan(SparseAttentionBackwardPlan):
@@ -1592,11 +1454,29 @@ class SparseAttentionBackwardHalfPlan(SparseAttentionBackwardPlan):
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, vec_dtype, d_max, dv_max, stream=None):
         if vec_dtype not in MAT_TYPES:
             raise TypeError("vec_dtype must be float16 or bfloat16 (float32 / float64 operands: SparseAttentionBackwardPlan)")
-        _require_device(Ap, Aj)
-        if Aj.dtype != torch.int32:
-            raise TypeError("Aj must be int32")
+        _require_structure(Ap, Aj)
         self._create("mi355_spmv_attention_bwd_create_half", MAT_TYPES[vec_dtype][0], n_rows, n_cols, nnz, Ap, Aj, torch.float32, vec_dtype, d_max,
                      dv_max, stream)
+
+
+def _sparse_attention_backward(variant, n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, bias, scale, dQ, dK, dV, dbias, need, stream):
+    val_dtype = _one_shot_value_type(variant, Ap, Aj, Q, "Q")
+    d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
+        n_rows, n_cols, nnz, val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, vec_dtype=Q.dtype)
+    name = _one_shot_entry(variant, "attention_bwd", Ap, Q)
+    with torch.cuda.device(Ap.device):
+        st = getattr(lib(), name)(n_rows, n_cols, nnz, _ptr(Ap), _ptr(Aj), d, dv, _ptr(Q), ldq, _ptr(K), ldk, _ptr(V), ldv, _ptr(bias),
+                                  C.c_double(scale), _ptr(O), ldo, _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0], _ptr(dK), lds[1], _ptr(dV),
+                                  lds[2], _ptr(dbias), _stream_ptr(stream))
+    _check(st, name)
+    return dQ, dK, dV, dbias
+
+
+def sparse_attention_backward(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, bias=None, scale=1.0, dQ=None, dK=None, dV=None, dbias=None,
+                              need=(True, True, True), stream=None):
+    """One-shot fused attention backward (mi355_spmv_attention_bwd_<off>_<val>): SparseAttentionBackwardPlan's execute on a
+    plan made for the call -> (dQ, dK, dV, dbias).  Synchronises `stream` before returning."""
+    return _sparse_attention_backward(_FULL, n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, bias, scale, dQ, dK, dV, dbias, need, stream)
 
 
 def sparse_attention_backward_half(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, bias=None, scale=1.0, dQ=None, dK=None, dV=None, dbias=None,
@@ -1604,28 +1484,15 @@ def sparse_attention_backward_half(n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, 
     """One-shot fused attention backward on 16-bit matrices (mi355_spmv_attention_bwd_half_<off>_<f16|bf16>):
     sparse_attention_backward's arguments with Q, K, V, O, dO (and dQ, dK, dV) in one of float16 / bfloat16, lse, bias and
     dbias in float32 -> (dQ, dK, dV, dbias).  Synchronises `stream` before returning."""
-    _require_device(Ap, Aj)
-    if Aj.dtype != torch.int32:
-        raise TypeError("Aj must be int32")
-    if not getattr(Q, "is_cuda", False):
-        raise RuntimeError("mi355 spmv takes device tensors only (no CPU path exists)")
-    if Q.dtype not in MAT_TYPES:
-        raise TypeError("Q must be float16 or bfloat16")
-    d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
-        n_rows, n_cols, nnz, torch.float32, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, vec_dtype=Q.dtype)
-    name = "mi355_spmv_attention_bwd_half_%s_%s" % (OFF_TYPES[Ap.dtype][1], MAT_TYPES[Q.dtype][1])
-    with torch.cuda.device(Ap.device):
-        st = getattr(lib(), name)(n_rows, n_cols, nnz, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), d, dv, _ptr(Q), ldq, _ptr(K), ldk,
-                                  _ptr(V), ldv, _ptr(bias), C.c_double(scale), _ptr(O), ldo, _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0],
-                                  _ptr(dK), lds[1], _ptr(dV), lds[2], _ptr(dbias), _stream_ptr(stream))
-    _check(st, name)
-    return dQ, dK, dV, dbias
+    return _sparse_attention_backward(_HALF, n_rows, n_cols, nnz, Ap, Aj, Q, K, V, O, dO, lse, bias, scale, dQ, dK, dV, dbias, need, stream)
 
+
+# ---- run-time functors, row blocks over the GPUs of a node
 
 C_TYPE_NAMES = {torch.float32: "float", torch.float64: "double", torch.int32: "int", torch.int64: "long long"}
 
 
-class Functor:
+class Functor(_Handle):
     """mi355_spmv_functor_*: a generalized SpMV whose functor is C++ source text, compiled for gfx950 at run time.
 
     source        text defining the functor the way the reference writes one (merge_genl.cuh:19-38): a struct with
@@ -1633,17 +1500,13 @@ class Functor:
     functor_type  the type to use ("MyFunctor", "MergeFunctor<float, float, double>")
     off_dtype     torch.int32 / torch.int64;  mat / x / y: torch dtypes or C++ type names (a struct of the source)
     Compiling needs no device; .spmv() runs on the tensors' device, asynchronously on `stream`."""
+    _destroy = "mi355_spmv_functor_destroy"
 
     def __init__(self, source, functor_type, off_dtype=torch.int32, mat=torch.float32, x=torch.float32, y=torch.float32):
         self._h = C.c_void_p()
         self.off_dtype = off_dtype
         names = [t if isinstance(t, str) else C_TYPE_NAMES[t] for t in (mat, x, y)]
         L = lib()
-        L.mi355_spmv_functor_compile.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
-                                                 C.c_char_p, C.c_char_p]
-        L.mi355_spmv_functor_compile_log.restype = C.c_char_p
-        L.mi355_spmv_functor_spmv.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 6
-        L.mi355_spmv_functor_destroy.argtypes = [C.c_void_p]
         st = L.mi355_spmv_functor_compile(C.byref(self._h), source.encode(), functor_type.encode(), OFF_TYPES[off_dtype][0],
                                           names[0].encode(), names[1].encode(), names[2].encode())
         self.log = (L.mi355_spmv_functor_compile_log() or b"").decode(errors="replace")
@@ -1653,27 +1516,18 @@ class Functor:
         _require_device(Ap, Aj, Ax, x, y)
         if Ap.dtype != self.off_dtype or Aj.dtype != torch.int32:
             raise TypeError("Functor.spmv: Ap must be %s and Aj int32" % self.off_dtype)
-        _check(lib().mi355_spmv_functor_spmv(self._h, n_rows, n_cols, nnz, Ap.data_ptr(), Aj.data_ptr(), Ax.data_ptr(),
-                                             x.data_ptr(), y.data_ptr(), _stream_ptr(stream)), "mi355_spmv_functor_spmv")
-
-    def destroy(self):
-        if self._h:
-            lib().mi355_spmv_functor_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        # (bare addresses: the declared void* slots of lib() take them)
+        self._call("mi355_spmv_functor_spmv", n_rows, n_cols, nnz, Ap.data_ptr(), Aj.data_ptr(), Ax.data_ptr(), x.data_ptr(), y.data_ptr(),
+                   _stream_ptr(stream))
 
 
-class DistPlan:
+class DistPlan(_Handle):
     """mi355_spmv_dist_*: row blocks over the GPUs of a node, x replicated, allgatherv(y) over RCCL.
 
     DistPlan.local(...)  one process drives `devices` (the whole structure lives on the current device)
     DistPlan.rank(...)   one process per GPU: this rank's slice + the global cut lists + a 128-byte id
     """
+    _destroy = "mi355_spmv_dist_destroy"
 
     def __init__(self):
         self._h = C.c_void_p()
@@ -1695,8 +1549,7 @@ class DistPlan:
         with torch.cuda.device(Ap.device):
             st = lib().mi355_spmv_dist_create_local(
                 C.byref(self._h), KINDS[kind], OFF_TYPES[Ap.dtype][0], VAL_TYPES[val_dtype][0], n_rows, n_cols, nnz,
-                C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()), len(devices), C.cast(devs, C.c_void_p),
-                sub_blocks, flags)
+                _ptr(Ap), _ptr(Aj), len(devices), C.cast(devs, C.c_void_p), sub_blocks, flags)
         _check(st, "mi355_spmv_dist_create_local")
         return self
 
@@ -1727,8 +1580,7 @@ class DistPlan:
                 C.cast(idbuf, C.c_void_p) if idbuf is not None else None, parts_per_rank,
                 rc.ctypes.data_as(C.c_void_p), cc.ctypes.data_as(C.c_void_p), nc.ctypes.data_as(C.c_void_p),
                 C.cast(C.byref(whole_shape), C.c_void_p) if whole_shape is not None else None,
-                n_cols, n_rows_local, nnz_end_local, C.c_void_p(Ap_local.data_ptr()), C.c_void_p(Aj_local.data_ptr()),
-                flags)
+                n_cols, n_rows_local, nnz_end_local, _ptr(Ap_local), _ptr(Aj_local), flags)
         _check(st, "mi355_spmv_dist_create_rank")
         return self
 
@@ -1736,24 +1588,20 @@ class DistPlan:
         import numpy as np
         n = lib().mi355_spmv_dist_parts(self._h)
         a = np.zeros(n + 1, dtype=np.int64)
-        _check(lib().mi355_spmv_dist_cuts(self._h, a.ctypes.data_as(C.c_void_p)), "mi355_spmv_dist_cuts")
+        self._call("mi355_spmv_dist_cuts", a.ctypes.data_as(C.c_void_p))
         return a.tolist()
 
     def info(self, part=0):
         """Launch shape of this process's block `part`."""
-        pi = PlanInfo()
-        _check(lib().mi355_spmv_dist_part_info(self._h, part, C.byref(pi)), "mi355_spmv_dist_part_info")
-        return pi.as_dict()
+        return self._info(PlanInfo, "mi355_spmv_dist_part_info", part)
 
     def scatter_values(self, Ax, stream=None):
         _require_device(Ax)
-        _check(lib().mi355_spmv_dist_scatter_values(self._h, C.c_void_p(Ax.data_ptr()), _stream_ptr(stream)),
-               "mi355_spmv_dist_scatter_values")
+        self._call("mi355_spmv_dist_scatter_values", _ptr(Ax), _stream_ptr(stream))
 
     def replicate_x(self, x, stream=None):
         _require_device(x)
-        _check(lib().mi355_spmv_dist_replicate_x(self._h, C.c_void_p(x.data_ptr()), _stream_ptr(stream)),
-               "mi355_spmv_dist_replicate_x")
+        self._call("mi355_spmv_dist_replicate_x", _ptr(x), _stream_ptr(stream))
 
     def execute(self, Ax, x, y, stream=None, flags=EXEC_DEFAULT):
         """Asynchronous on `stream`.  LOCAL: home-device Ax / x (None = unchanged since scatter_values /
@@ -1774,14 +1622,12 @@ class DistPlan:
 
     def set_exchange(self, name):
         """'bcast' | 'sendrecv' | 'allgather' (collective: every rank the same)."""
-        _check(lib().mi355_spmv_dist_set_exchange(self._h, EXCHANGES[name]), "mi355_spmv_dist_set_exchange")
+        self._call("mi355_spmv_dist_set_exchange", EXCHANGES[name])
 
     def dist_info(self):
-        di = DistInfo()
-        _check(lib().mi355_spmv_dist_get_info(self._h, C.byref(di)), "mi355_spmv_dist_get_info")
-        d = {n: getattr(di, n) for n, _ in di._fields_ if n not in ("trial_us", "exchange_name", "reserved0")}
-        d["exchange_name"] = di.exchange_name.decode()
-        d["trial_us"] = {k: float(di.trial_us[v]) for k, v in EXCHANGES.items() if v}
+        d = self._info(DistInfo, "mi355_spmv_dist_get_info")
+        trial_us = d.pop("trial_us")       # one time per exchange that the auto pick tried
+        d["trial_us"] = {k: float(trial_us[v]) for k, v in EXCHANGES.items() if v}
         return d
 
     def structure_changed(self, Ap, Aj, stream=None):
@@ -1789,22 +1635,9 @@ class DistPlan:
         _require_device(Ap, Aj)
         out = C.c_int(0)
         with torch.cuda.device(Ap.device):
-            st = lib().mi355_spmv_dist_structure_changed(self._h, C.c_void_p(Ap.data_ptr()), C.c_void_p(Aj.data_ptr()),
-                                                         _stream_ptr(stream), C.byref(out))
+            st = lib().mi355_spmv_dist_structure_changed(self._h, _ptr(Ap), _ptr(Aj), _stream_ptr(stream), C.byref(out))
         _check(st, "mi355_spmv_dist_structure_changed")
         return bool(out.value)
 
     def set_alpha_beta(self, alpha, beta):
-        _check(lib().mi355_spmv_dist_set_alpha_beta(self._h, C.c_double(alpha), C.c_double(beta)),
-               "mi355_spmv_dist_set_alpha_beta")
-
-    def destroy(self):
-        if self._h:
-            lib().mi355_spmv_dist_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        self._call("mi355_spmv_dist_set_alpha_beta", C.c_double(alpha), C.c_double(beta))
