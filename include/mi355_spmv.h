@@ -52,6 +52,7 @@ extern "C" {
 #define MI355_SPMV_HAS_ATTENTION 1 /* mi355_spmv_attention_*: O = softmax(scale Q K^T + bias, on the stored entries of A) V in one pass over A */
 #define MI355_SPMV_HAS_ATTENTION_HALF 1 /* mi355_spmv_attention_create_half / _get_types / _half_*: Q, K, V and O in binary16 / bfloat16, fp32 bias, lse and arithmetic */
 #define MI355_SPMV_HAS_ATTENTION_BACKWARD 1 /* mi355_spmv_attention_bwd_*: dQ, dK, dV (and dbias) of fused sparse attention from O, dO and lse, nothing of nnz size kept */
+#define MI355_SPMV_HAS_ATTENTION_HEADS 1 /* mi355_spmv_attention[_bwd]_reserve_heads / _get_heads_max / _execute_heads: the heads of sparse attention, forward and backward, in one call */
 #define MI355_SPMV_HAS_ATTENTION_BACKWARD_HALF 1 /* mi355_spmv_attention_bwd_create_half / _get_types / _half_*: the eight matrices in binary16 / bfloat16, fp32 bias, lse, dbias and arithmetic */
 #define MI355_SPMV_HAS_HALF_MATRIX 1 /* MI355_VAL_F16 / MI355_VAL_BF16 as a mat_type (VECTOR), mi355_spmv_narrow_values */
 
@@ -893,8 +894,8 @@ int mi355_spmv_row_softmax_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, 
  * edges fall in a row (states are combined by step, then by slice, in ascending order), as row softmax's do.
  * Types: {I32, I64} offsets x {F32, F64} values.  MI355_VAL_I32: MI355_SPMV_ENOTSUP; PATTERN / F16 / BF16 / unknown:
  * MI355_SPMV_EINVAL.  16-bit Q, K, V and O under fp32 everything else are an object of their own
- * (mi355_spmv_attention_create_half, below).  The fused backward is mi355_spmv_attention_bwd_* (below); heads in one call and
- * dist_* are not built.
+ * (mi355_spmv_attention_create_half, below).  The fused backward is mi355_spmv_attention_bwd_* (below), heads in one call
+ * mi355_spmv_attention_execute_heads (below); dist_* is not built.
  * The work is cut as the multi-vector kind's (slice_len merge items per wave, lanes_per_slot lanes per nonzero from the
  * tile of dv).  An execute launches ceil(dv / widest_tile) slice kernels (each recomputes the scores; widest_tile is 32
  * fp32 / 16 fp64 columns) and, with more than one slice, one fix-up of the rows that cross slices.
@@ -960,8 +961,8 @@ int mi355_spmv_attention_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz, co
  * create_half: vec_type outside {F16, BF16} is MI355_SPMV_EINVAL ("vec_type" in the text); every other check is
  * create's, before any device call, and *out stays NULL.
  * The fused backward on the same 16-bit type is mi355_spmv_attention_bwd_create_half (below).
- * Out of scope: an fp32 O under 16-bit inputs, mixed Q / K / V types, a 16-bit bias or lse, fp8, heads in one call,
- * dist_*, harness labels.                                                                                           */
+ * Out of scope: an fp32 O under 16-bit inputs, mixed Q / K / V types, a 16-bit bias or lse, fp8, dist_*,
+ * harness labels.                                                                                                   */
 int mi355_spmv_attention_create_half(mi355_spmv_attention** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols,
                                      int64_t nnz, const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max);
 int mi355_spmv_attention_get_types(const mi355_spmv_attention* m, int* val_type, int* vec_type);
@@ -1014,8 +1015,8 @@ int mi355_spmv_attention_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64_t n
  * only, never synchronises and decides nothing from device data (graph-capturable); one stream at a time per object.
  * Any of dQ / dK / dV may be NULL; all three NULL is MI355_SPMV_EINVAL, and so is dbias without dQ (it comes from the DQ
  * walk).  Every argument error is refused before any device call, and the text of the last error names the argument.
- * Out of scope: heads in one call, dist_*, harness labels, semirings, sharing the held transpose with a transposed
- * multi-vector object.                                                                            */
+ * Out of scope: dist_*, harness labels, semirings, sharing the held transpose with a transposed multi-vector object
+ * (DESIGN.md 3.15.2).  Heads in one call: mi355_spmv_attention_bwd_execute_heads (below).                            */
 typedef struct mi355_spmv_attention_bwd mi355_spmv_attention_bwd;
 typedef struct mi355_spmv_attention_bwd_info {
     int32_t off_type, val_type;
@@ -1083,8 +1084,8 @@ int mi355_spmv_attention_bwd_i64_f64(int32_t n_rows, int32_t n_cols, int64_t nnz
  * get_info and destroy serve both.
  * create_half: vec_type outside {F16, BF16} is MI355_SPMV_EINVAL ("vec_type" in the text); every other check is
  * mi355_spmv_attention_bwd_create's, before any device call, and *out stays NULL.
- * Out of scope: fp32 gradients under 16-bit inputs, mixed 16-bit types, a 16-bit bias / lse / dbias, fp8, heads in one
- * call, dist_*, harness labels, a 16-bit transposed multi-vector object.                                             */
+ * Out of scope: fp32 gradients under 16-bit inputs, mixed 16-bit types, a 16-bit bias / lse / dbias, fp8, dist_*,
+ * harness labels, a 16-bit transposed multi-vector object.                                                           */
 int mi355_spmv_attention_bwd_create_half(mi355_spmv_attention_bwd** out, int off_type, int vec_type, int32_t n_rows, int32_t n_cols,
                                          int64_t nnz, const void* Ap, const int32_t* Aj, int32_t d_max, int32_t dv_max, void* stream);
 int mi355_spmv_attention_bwd_get_types(const mi355_spmv_attention_bwd* m, int* val_type, int* vec_type);
@@ -1106,6 +1107,60 @@ int mi355_spmv_attention_bwd_half_i64_bf16(int32_t n_rows, int32_t n_cols, int64
     const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const float* bias, double scale,
     const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk,
     void* dV, int64_t lddv, float* dbias, void* stream);
+
+/* ---- The heads of sparse attention in one call (MI355_SPMV_HAS_ATTENTION_HEADS) ---------------------------------------
+ * A layer of H heads on one structure is ONE execute, forward or backward, instead of H: the same launches as one head's
+ * (2 forward, up to 7 backward), each over H times the workgroups.  The structure, the cut and the backward's held
+ * transpose are shared; a head is a pointer offset and a private copy of the O(slices) scratch.  The objects are the
+ * existing ones, of either storage type (create and create_half): set_scale (ONE scale for all heads), get_info,
+ * get_types and destroy serve them unchanged, and execute is execute_heads with n_heads = 1.
+ * Strides: a stride is the number of ELEMENTS, in the operand's own type, between head h and head h + 1 of that operand;
+ * the arguments behind hs are exactly execute's and describe head 0.
+ *   (n, H, d) interleaved:  ld = H * d, stride = d.          (H, n, d) head-major:  ld = d, stride = n * d.
+ *   bias, lse and dbias are head-major vectors: stride >= nnz (bias, dbias), >= n_rows (lse).
+ *   An INPUT stride of 0 shares that operand between all heads (q, k, v, bias; in the backward also o, d_o, lse): one K and
+ *   V for every head is multi-query attention, one bias a shared mask.  A negative stride is MI355_SPMV_EINVAL.
+ *   With n_heads = 1 no stride is read and hs may be NULL; with n_heads > 1 a NULL hs is MI355_SPMV_EINVAL.
+ * The heads of an OUTPUT may not overlap, and this is checked (a wrong stride would silently corrupt another head): for
+ * a matrix of rows x width at leading dimension ld the stride must be >= width and satisfy either
+ *   stride >= (rows - 1) * ld + width   (head-major)     or     ld >= (n_heads - 1) * stride + width   (interleaved);
+ * lse, when asked for, needs stride >= n_rows and dbias stride >= nnz.  Anything else is MI355_SPMV_EINVAL and the text
+ * names the stride (o, lse, dq, dk, dv, dbias).  An overlap between an output and an input stays unchecked, as in execute.
+ * reserve_heads: after create n_heads_max is 1.  reserve_heads(n) allocates n copies of the per-head scratch (the
+ * backward's: delta and every role's pieces), THEN frees the old scratch; on failure the object keeps the old scratch
+ * and the old maximum.  get_info().scratch_bytes reports the new size; the backward's held_bytes (the transpose, which
+ * every head shares) is not touched.  It is a device call like create (none on an object without rows): NOT for use
+ * during stream capture or while an execute of the object is in flight.  n below 1: MI355_SPMV_EINVAL.
+ * execute_heads: every check of execute first, in the same order and with the same messages; then n_heads must lie in
+ * 1 .. n_heads_max ("n_heads" in the text); then the strides.  A grid of 2^31 workgroups or more is MI355_SPMV_ENOTSUP.
+ * All checks come before any device call.  It is asynchronous on `stream`, allocates nothing, decides nothing from
+ * device data and is graph-capturable; heads beyond n_heads leave their scratch unused.  In the backward a NULL role is
+ * not launched for any head, and dbias without dQ is refused as in execute.
+ * THE PROMISE: head h of an execute_heads equals execute on the operands offset by h strides, BIT FOR BIT, in every
+ * element of every output, for any alignment and any stride.  It holds because a row takes the 16-byte path only where
+ * head 0's rows are 16-byte aligned (pointer and ld * sizeof) AND the head stride in bytes is a multiple of 16 (or
+ * n_heads is 1), and both paths fill the same registers; and because workgroup b of a slice kernel serves head
+ * b % n_heads and slice block b / n_heads, so every head is cut exactly as one head is.
+ * Out of scope: a head -> KV-head map (grouped-query attention beyond stride 0), per-head scales, one-shots with heads,
+ * a sum of dK / dV over heads inside the kernel, dist_*, harness labels.                                            */
+typedef struct mi355_spmv_attention_head_strides {
+    int64_t q, k, v, bias, o, lse;
+} mi355_spmv_attention_head_strides;
+typedef struct mi355_spmv_attention_bwd_head_strides {
+    int64_t q, k, v, bias, o, d_o, lse, dq, dk, dv, dbias;
+} mi355_spmv_attention_bwd_head_strides;
+int mi355_spmv_attention_reserve_heads(mi355_spmv_attention* m, int32_t n_heads_max);
+int mi355_spmv_attention_get_heads_max(const mi355_spmv_attention* m, int32_t* n_heads_max);
+int mi355_spmv_attention_execute_heads(mi355_spmv_attention* m, int32_t n_heads, const mi355_spmv_attention_head_strides* hs, int32_t d,
+                                       int32_t dv, const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                                       const void* bias, void* O, int64_t ldo, void* lse, void* stream);
+int mi355_spmv_attention_bwd_reserve_heads(mi355_spmv_attention_bwd* m, int32_t n_heads_max);
+int mi355_spmv_attention_bwd_get_heads_max(const mi355_spmv_attention_bwd* m, int32_t* n_heads_max);
+int mi355_spmv_attention_bwd_execute_heads(mi355_spmv_attention_bwd* m, int32_t n_heads, const mi355_spmv_attention_bwd_head_strides* hs,
+                                           int32_t d, int32_t dv, const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
+                                           int64_t ldv, const void* bias, const void* O, int64_t ldo, const void* dO, int64_t lddo,
+                                           const void* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv,
+                                           void* dbias, void* stream);
 
 /* ---- misc ------------------------------------------------------------------ */
 int mi355_spmv_version(void);

@@ -19,6 +19,7 @@ Contents (only what the hot path needs):
                SparseAttentionPlan / sparse_attention / sparse_attention_half: O = softmax(Q K^T on A) V fused into one pass over A, Q, K, V and O in fp32 / fp64 or in 16 bits;
                SparseAttentionBackwardPlan / sparse_attention_backward: dQ, dK, dV (and dbias) of that attention from O, dO and lse, nothing of nnz size kept;
                SparseAttentionBackwardHalfPlan / sparse_attention_backward_half: the same with the eight matrices in 16 bits;
+               reserve_heads / n_heads_max / with_heads on the three attention plans, 3-D (rows, H, width) operands of their execute: the heads of a layer in one call;
                csr_transpose / MultiPlan(perm=) / TransposedMultiPlan / spmm_t: Y = A^T X with Ax read in place through a slot map)
     autograd.py  sparse_attention_function: the two attention plans as one torch.autograd.Function-backed callable
     synth.py   seeded synthetic CSR matrices (stand-ins for the BASELINE configs)

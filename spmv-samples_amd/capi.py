@@ -77,6 +77,7 @@ EXPORTS = (
     + ["mi355_spmv_attention_bwd_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f32", "f64")]
     + ["mi355_spmv_attention_bwd_create_half", "mi355_spmv_attention_bwd_get_types"]
     + ["mi355_spmv_attention_bwd_half_%s_%s" % (o, v) for o in ("i32", "i64") for v in ("f16", "bf16")]
+    + ["mi355_spmv_attention%s_%s" % (b, n) for b in ("", "_bwd") for n in ("reserve_heads", "get_heads_max", "execute_heads")]
 )
 
 
@@ -144,6 +145,16 @@ class AttentionInfo(C.Structure):
                 ("lanes_per_slot", C.c_int32), ("reserved", C.c_int32),
                 ("n_slices", C.c_int64), ("grid_blocks", C.c_int64), ("scratch_bytes", C.c_int64),
                 ("main_kernel", C.c_char * 64)]
+
+
+class AttentionHeadStrides(C.Structure):
+    """mi355_spmv_attention_head_strides: elements between head h and head h + 1 of each operand (0: shared by all heads)."""
+    _fields_ = [(n, C.c_int64) for n in ("q", "k", "v", "bias", "o", "lse")]
+
+
+class AttentionBackwardHeadStrides(C.Structure):
+    """mi355_spmv_attention_bwd_head_strides."""
+    _fields_ = [(n, C.c_int64) for n in ("q", "k", "v", "bias", "o", "d_o", "lse", "dq", "dk", "dv", "dbias")]
 
 
 class AttentionBackwardInfo(C.Structure):
@@ -316,6 +327,11 @@ def lib():
         L.mi355_spmv_attention_bwd_destroy.argtypes = [C.c_void_p]
         L.mi355_spmv_attention_bwd_create_half.argtypes = L.mi355_spmv_attention_bwd_create.argtypes
         L.mi355_spmv_attention_bwd_get_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        for stem, strides in (("mi355_spmv_attention", AttentionHeadStrides), ("mi355_spmv_attention_bwd", AttentionBackwardHeadStrides)):
+            getattr(L, stem + "_reserve_heads").argtypes = [C.c_void_p, C.c_int32]
+            getattr(L, stem + "_get_heads_max").argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+            # the handle, n_heads, hs, then exactly execute's arguments behind its handle
+            getattr(L, stem + "_execute_heads").argtypes = [C.c_void_p, C.c_int32, C.POINTER(strides)] + getattr(L, stem + "_execute").argtypes[1:]
         for stem, vals, args in _one_shot_signatures():
             for o, off_c in (("i32", C.c_int32), ("i64", C.c_int64)):
                 for v in vals:
@@ -1234,6 +1250,73 @@ def row_softmax(n_rows, n_cols, nnz, Ap, Aj, x, out=None, scale=1.0, stream=None
     return out
 
 
+def _heads_of(matrices):
+    """The ranks of an attention execute's matrices [(tensor or None, name)]: 0 when every one is 2-D (the single-head call),
+    else H of 3-D operands shaped (rows, H, width), which must all agree (the library refuses H above the plan's reserve)."""
+    given = [(t, name) for t, name in matrices if t is not None]
+    for t, _ in given:
+        if not t.is_cuda:
+            raise RuntimeError(_NO_CPU_PATH)
+    ranks = {t.dim() for t, _ in given}
+    if ranks == {2}:
+        return 0
+    if ranks != {3}:
+        raise ValueError("%s: %s (every matrix 2-D, or every matrix 3-D shaped (rows, H, width))"
+                         % ("mixed ranks" if len(ranks) > 1 else "matrices must be 2-D or 3-D",
+                            ", ".join("%s is %d-D" % (name, t.dim()) for t, name in given)))
+    heads = {t.size(1) for t, _ in given}
+    if len(heads) != 1:
+        raise ValueError("the matrices differ in their heads: %s" % ", ".join("%s has %d" % (name, t.size(1)) for t, name in given))
+    H = heads.pop()
+    if H < 1:
+        raise ValueError("3-D operands need at least one head")
+    return H
+
+
+def _head0(t):
+    """Head 0 of a 3-D matrix as the 2-D operand that every matrix check takes (None stays None)."""
+    return None if t is None else t.select(1, 0)
+
+
+def _head_vector(t, name, H, n):
+    """A per-head vector operand, (H, n) with unit stride along n — or, for an input, (n,) shared by all heads: (head 0 as a
+    1-D tensor, the head stride).  None: (None, 0)."""
+    if t is None:
+        return None, 0
+    if t.dim() == 1:
+        return t, 0
+    if t.dim() != 2 or t.size(0) != H:
+        raise ValueError("%s must be (H, %s) = (%d, %d)" % (name, name, H, n))
+    if t.size(1) > 1 and t.stride(1) != 1:
+        raise ValueError("%s must have unit stride along its last dimension" % name)
+    return t[0], (t.stride(0) if H > 1 else 0)
+
+
+class _AttentionHeads:
+    """reserve_heads and n_heads_max of the three attention plans (`_stem` names the C object's entry points)."""
+    _stem = None
+
+    @classmethod
+    def with_heads(cls, n_heads_max, *args, **kwargs):
+        """cls(*args, **kwargs) with scratch reserved for n_heads_max heads."""
+        plan = cls(*args, **kwargs)
+        if n_heads_max > 1:
+            plan.reserve_heads(n_heads_max)
+        return plan
+
+    def reserve_heads(self, n_heads_max):
+        """Scratch for up to n_heads_max heads in one execute (mi355_spmv_attention[_bwd]_reserve_heads): a device call
+        like the create — not during stream capture, not with an execute in flight."""
+        with torch.cuda.device(self.Ap.device) if self.n_rows > 0 else contextlib.nullcontext():
+            self._call(self._stem + "_reserve_heads", int(n_heads_max))
+
+    @property
+    def n_heads_max(self):
+        n = C.c_int32()
+        self._call(self._stem + "_get_heads_max", C.byref(n))
+        return n.value
+
+
 def _attention_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, out, lse, bias, d_max=None, dv_max=None, vec_dtype=None):
     """The operand checks of a fused sparse attention: (d, dv, ldq, ldk, ldv, out, ldo).  Q, K, V and out are 2-D device
     tensors of vec_dtype (the value type when None) with unit stride along their columns (any row stride >= the width: a
@@ -1260,7 +1343,7 @@ def _attention_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, out, lse, bias,
     return d, dv, ldq, ldk, ldv, out, ldo
 
 
-class SparseAttentionPlan(_Handle):
+class SparseAttentionPlan(_AttentionHeads, _Handle):
     """mi355_spmv_attention_*: fused sparse attention on the structure of A, O = softmax(scale * Q K^T + bias, over the
     stored entries of every row) V in ONE pass over A — the chain SddmmPlan -> RowSoftmaxPlan -> MultiPlan without the
     nnz-sized scores and probabilities.  Q is n_rows x d, K n_cols x d, V n_cols x dv (row-major device tensors of
@@ -1272,10 +1355,13 @@ class SparseAttentionPlan(_Handle):
     vec_dtype=torch.float16 / torch.bfloat16 (mi355_spmv_attention_create_half; val_dtype must be float32): Q, K, V and out
     are held in that type; bias, lse, the scale and every operation stay float32, every stored value is widened exactly and
     an element of out is rounded to vec_dtype once.  plan.vec_dtype is the type of Q, K, V and out (val_dtype without the
-    argument)."""
+    argument).
+    Heads in one call: n_heads_max=H (or reserve_heads(H)) reserves H copies of the scratch; execute then takes 3-D
+    operands shaped (rows, H, width) — see execute."""
     _destroy = "mi355_spmv_attention_destroy"
+    _stem = "mi355_spmv_attention"
 
-    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, d_max, dv_max, vec_dtype=None):
+    def __init__(self, n_rows, n_cols, nnz, Ap, Aj, val_dtype, d_max, dv_max, vec_dtype=None, n_heads_max=1):
         _require_structure(Ap, Aj)
         if val_dtype not in (torch.float32, torch.float64):
             raise TypeError("val_dtype must be float32 or float64")
@@ -1299,10 +1385,20 @@ class SparseAttentionPlan(_Handle):
                 st, name = lib().mi355_spmv_attention_create_half(C.byref(self._h), OFF_TYPES[Ap.dtype][0], MAT_TYPES[vec_dtype][0], n_rows,
                                                                   n_cols, nnz, _ptr(Ap), _ptr(Aj), d_max, dv_max), "mi355_spmv_attention_create_half"
         _check(st, name)
+        if n_heads_max > 1:
+            self.reserve_heads(n_heads_max)
 
     def execute(self, Q, K, V, out=None, lse=None, bias=None, stream=None):
         """out[r] = sum over the row of softmax(scale * Q[r] . K[c] + bias)[n] * V[c]; lse (n_rows values, optional) takes
-        the row's log-sum-exp.  Asynchronous on `stream` (default: torch's current stream); returns out (made when None)."""
+        the row's log-sum-exp.  Asynchronous on `stream` (default: torch's current stream); returns out (made when None).
+        Heads in one call (mi355_spmv_attention_execute_heads): Q, K, V (and out) 3-D, shaped (rows, H, width) with unit
+        stride in the last dimension and ANY other strides — (n, H, d) contiguous is the interleaved layout, a head-major
+        (H, n, d) tensor is passed as t.permute(1, 0, 2), and a stride of 0 from expand shares K, V or Q between the heads.
+        bias is (H, nnz), or (nnz,) shared by all heads; lse is (H, n_rows); out is made as a contiguous (n_rows, H, dv)
+        when None.  Head h equals the 2-D call on head h's operands bit for bit.  Mixed ranks are a ValueError."""
+        H = _heads_of(((Q, "Q"), (K, "K"), (V, "V"), (out, "out")))
+        if H:
+            return self._execute_heads(H, Q, K, V, out, lse, bias, stream)
         d, dv, ldq, ldk, ldv, out, ldo = _attention_operands(self.n_rows, self.n_cols, self.nnz, self.val_dtype, Q, K, V, out, lse, bias,
                                                              self.d_max, self.dv_max, self.vec_dtype)
         with torch.cuda.device(self.Ap.device):
@@ -1311,8 +1407,24 @@ class SparseAttentionPlan(_Handle):
         _check(st, "mi355_spmv_attention_execute")
         return out
 
+    def _execute_heads(self, H, Q, K, V, out, lse, bias, stream):
+        if out is None:
+            out = torch.empty((self.n_rows, H, V.size(2)), dtype=self.vec_dtype, device=Q.device)
+        lse0, s_lse = _head_vector(lse, "lse", H, self.n_rows)
+        if lse is not None and lse.dim() != 2:
+            raise ValueError("lse must be (H, n_rows) with 3-D operands")
+        bias0, s_bias = _head_vector(bias, "bias", H, self.nnz)
+        d, dv, ldq, ldk, ldv, out0, ldo = _attention_operands(self.n_rows, self.n_cols, self.nnz, self.val_dtype, _head0(Q), _head0(K), _head0(V),
+                                                              _head0(out), lse0, bias0, self.d_max, self.dv_max, self.vec_dtype)
+        hs = AttentionHeadStrides(Q.stride(1), K.stride(1), V.stride(1), s_bias, out.stride(1), s_lse)
+        with torch.cuda.device(self.Ap.device):
+            st = lib().mi355_spmv_attention_execute_heads(self._h, H, C.byref(hs), d, dv, _ptr(Q), ldq, _ptr(K), ldk, _ptr(V), ldv, _ptr(bias), _ptr(out),
+                                                          ldo, _ptr(lse), _stream_ptr(stream))
+        _check(st, "mi355_spmv_attention_execute_heads")
+        return out
+
     def set_scale(self, s):
-        """scale for the following executes (default 1): the 1 / sqrt(d) of attention."""
+        """scale for the following executes (default 1): the 1 / sqrt(d) of attention; one scale for all heads."""
         self._call("mi355_spmv_attention_set_scale", C.c_double(s))
 
     def info(self):
@@ -1392,15 +1504,18 @@ def _attention_backward_operands(n_rows, n_cols, nnz, val_dtype, Q, K, V, O, dO,
     return d, dv, ldq, ldk, ldv, ldo, lddo, outs[0], outs[1], outs[2], dbias, lds
 
 
-class SparseAttentionBackwardPlan(_Handle):
+class SparseAttentionBackwardPlan(_AttentionHeads, _Handle):
     """mi355_spmv_attention_bwd_*: the fused backward of SparseAttentionPlan — dQ, dK, dV (and dbias) from Q, K, V, bias, the
     forward's O and lse, and dO, with nothing of nnz size kept between forward and backward.  One plan per STRUCTURE: it
     holds the transpose of A (info()["held_bytes"]), built at create on `stream` (which is synchronised), and serves every
     head, layer and step on that structure.  dtype is float32 or float64; Q is n_rows x d, K n_cols x d, V n_cols x dv, O
     and dO n_rows x dv (row-major device tensors, d <= d_max, dv <= dv_max, a row stride above the width is the leading
     dimension); lse n_rows values, bias nnz values in CSR order or None.  Holds references to Ap and Aj.  Executes are
-    asynchronous and never synchronise."""
+    asynchronous and never synchronise.
+    Heads in one call: reserve_heads(H), or making the plan with with_heads(H, ...), reserves H copies of the scratch (not of
+    the transpose, which the heads share); execute then takes 3-D operands shaped (rows, H, width) — see execute."""
     _destroy = "mi355_spmv_attention_bwd_destroy"
+    _stem = "mi355_spmv_attention_bwd"
 
     def __init__(self, n_rows, n_cols, nnz, Ap, Aj, dtype, d_max, dv_max, stream=None):
         _require_structure(Ap, Aj)
@@ -1423,7 +1538,13 @@ class SparseAttentionBackwardPlan(_Handle):
     def execute(self, Q, K, V, O, dO, lse, bias=None, dQ=None, dK=None, dV=None, dbias=None, need=(True, True, True), stream=None):
         """-> (dQ, dK, dV, dbias).  need = which of dQ, dK, dV to compute (a given tensor is computed whatever need says; an
         output neither given nor needed is None and its walk is not launched).  dbias: a tensor of nnz values, True to have
-        one made, or None.  Asynchronous on `stream` (default: torch's current stream)."""
+        one made, or None.  Asynchronous on `stream` (default: torch's current stream).
+        Heads in one call (mi355_spmv_attention_bwd_execute_heads): every matrix 3-D, shaped (rows, H, width) as
+        SparseAttentionPlan.execute takes them (any strides but the last, 0 from expand on an input); lse is (H, n_rows),
+        bias (H, nnz) or (nnz,) shared, dbias (H, nnz); outputs are made as contiguous (rows, H, width) where needed."""
+        H = _heads_of(((Q, "Q"), (K, "K"), (V, "V"), (O, "O"), (dO, "dO"), (dQ, "dQ"), (dK, "dK"), (dV, "dV")))
+        if H:
+            return self._execute_heads(H, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, stream)
         d, dv, ldq, ldk, ldv, ldo, lddo, dQ, dK, dV, dbias, lds = _attention_backward_operands(
             self.n_rows, self.n_cols, self.nnz, self.val_dtype, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, self.d_max, self.dv_max,
             self.vec_dtype)
@@ -1432,6 +1553,33 @@ class SparseAttentionBackwardPlan(_Handle):
                                                         _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0], _ptr(dK), lds[1], _ptr(dV), lds[2],
                                                         _ptr(dbias), _stream_ptr(stream))
         _check(st, "mi355_spmv_attention_bwd_execute")
+        return dQ, dK, dV, dbias
+
+    def _execute_heads(self, H, Q, K, V, O, dO, lse, bias, dQ, dK, dV, dbias, need, stream):
+        need = tuple(bool(x) for x in need)
+        if len(need) != 3:
+            raise ValueError("need is (dQ, dK, dV)")
+        make = lambda t, want, rows, width: torch.empty((rows, H, width), dtype=self.vec_dtype, device=Q.device) if t is None and want else t
+        dQ, dK, dV = (make(dQ, need[0], self.n_rows, Q.size(2)), make(dK, need[1], self.n_cols, K.size(2)),
+                      make(dV, need[2], self.n_cols, V.size(2)))
+        if dbias is True:
+            dbias = torch.empty((H, self.nnz), dtype=self.val_dtype, device=Q.device)
+        if lse.dim() != 2 or (dbias is not None and dbias.dim() != 2):
+            raise ValueError("lse must be (H, n_rows) and dbias (H, nnz) with 3-D operands")
+        lse0, s_lse = _head_vector(lse, "lse", H, self.n_rows)
+        bias0, s_bias = _head_vector(bias, "bias", H, self.nnz)
+        dbias0, s_dbias = _head_vector(dbias, "dbias", H, self.nnz)
+        d, dv, ldq, ldk, ldv, ldo, lddo, _, _, _, _, lds = _attention_backward_operands(
+            self.n_rows, self.n_cols, self.nnz, self.val_dtype, _head0(Q), _head0(K), _head0(V), _head0(O), _head0(dO), lse0, bias0, _head0(dQ),
+            _head0(dK), _head0(dV), dbias0, (False, False, False), self.d_max, self.dv_max, self.vec_dtype)
+        stride = lambda t: 0 if t is None else t.stride(1)
+        hs = AttentionBackwardHeadStrides(Q.stride(1), K.stride(1), V.stride(1), s_bias, O.stride(1), dO.stride(1), s_lse, stride(dQ), stride(dK),
+                                          stride(dV), s_dbias)
+        with torch.cuda.device(self.Ap.device):
+            st = lib().mi355_spmv_attention_bwd_execute_heads(self._h, H, C.byref(hs), d, dv, _ptr(Q), ldq, _ptr(K), ldk, _ptr(V), ldv, _ptr(bias),
+                                                              _ptr(O), ldo, _ptr(dO), lddo, _ptr(lse), _ptr(dQ), lds[0], _ptr(dK), lds[1], _ptr(dV),
+                                                              lds[2], _ptr(dbias), _stream_ptr(stream))
+        _check(st, "mi355_spmv_attention_bwd_execute_heads")
         return dQ, dK, dV, dbias
 
     def set_scale(self, s):

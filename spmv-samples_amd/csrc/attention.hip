@@ -58,8 +58,10 @@ struct mi355_spmv_attention {       // the opaque handle of include/mi355_spmv.h
     double scale = 1.0;
     int64_t n_slices = 0;
     int64_t carry_ld = 0;           // dv_max rounded up to whole widest tiles
-    void* scratch = nullptr;        // the slices' two pieces: rows, (m, l) and acc
+    void* scratch = nullptr;        // the slices' two pieces: rows, (m, l) and acc; n_heads_max copies, head h at h * head stride
     size_t scratch_bytes = 0;
+    size_t head_bytes = 0;          // of one head's copy (what a create allocates)
+    int32_t n_heads_max = 1;        // reserve_heads
 };
 
 namespace mi355 {
@@ -119,7 +121,33 @@ struct AttnArgs {
     int32_t q_vec, k_vec, v_vec, o_vec;     // 1 = rows are 16-byte aligned: one 16-byte access per lane
     val_t scale;
     AttnScratch<val_t> sc;
+    int32_t n_heads;        // heads in this launch: workgroup b serves head b % n_heads
+    int64_t hq, hk, hv, hbias, ho, hlse;    // elements between two heads of an operand (0: shared; not read with one head)
+    int64_t hsc;            // bytes between two heads' scratch
 };
+
+// The scratch of head h: the single-head layout at h * bytes.
+template <typename acc_t>
+__device__ __forceinline__ AttnScratch<acc_t> attn_scratch_of_head(AttnScratch<acc_t> sc, int64_t h, int64_t bytes) {
+    sc.acc = attn_head_scratch(sc.acc, h, bytes);
+    sc.ml = attn_head_scratch(sc.ml, h, bytes);
+    sc.row = attn_head_scratch(sc.row, h, bytes);
+    return sc;
+}
+
+// A slice kernel's local copy of its arguments, rebased to head h (AttnArgs<val_t> or AttnHalfArgs<vec_t>): the walk then
+// reads a.Q, a.K, ... as it does with one head.
+template <typename Args>
+__device__ __forceinline__ Args attn_args_of_head(Args a, int64_t h) {
+    a.Q = attn_head_ptr(a.Q, h, a.hq);
+    a.K = attn_head_ptr(a.K, h, a.hk);
+    a.V = attn_head_ptr(a.V, h, a.hv);
+    a.bias = attn_head_ptr(a.bias, h, a.hbias);
+    a.O = attn_head_ptr(a.O, h, a.ho);
+    a.lse = attn_head_ptr(a.lse, h, a.hlse);
+    a.sc = attn_scratch_of_head(a.sc, h, a.hsc);
+    return a;
+}
 
 // exp of a difference d = m - M <= 0: exactly 1 at 0 and exactly +0 at -inf, whatever the math library gives at its ends
 template <typename val_t>
@@ -165,13 +193,16 @@ __device__ __forceinline__ void attn_reduce_slots(val_t& m, val_t& l, val_t (&ac
 
 // C = lanes per nonzero slot (16-byte column groups of this pass's tile of dv); the wave holds S = 64 / C slots
 template <typename off_t, typename val_t, int C>
-__global__ __launch_bounds__(kBlock) void attention_slice_kernel(const AttnArgs<val_t> a, const off_t* __restrict__ Ap) {
+__global__ __launch_bounds__(kBlock) void attention_slice_kernel(const AttnArgs<val_t> args, const off_t* __restrict__ Ap) {
     using acc_t = val_t;                            // what attention_slice_walk.inc asks its includer
     constexpr int W = 16 / int(sizeof(val_t));      // columns of a lane per tile
     constexpr int S = kWave / C;
     constexpr val_t kNegInf = -std::numeric_limits<val_t>::infinity();
     constexpr bool kCutCarriedIn = true, kCutKeepsR1 = true;        // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = -1;
+    // the head varies fastest over the grid: the workgroups that read one range of Ap / Aj are dispatched together
+    const unsigned cut_block = blockIdx.x / unsigned(args.n_heads);
+    const AttnArgs<val_t> a = attn_args_of_head(args, blockIdx.x % unsigned(args.n_heads));
 #include "slice_cut.inc"            // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
 #include "attention_slice_walk.inc"     // the slice's nonzeros, 64 at a time, and its empty rows
 }
@@ -193,13 +224,23 @@ __device__ __forceinline__ bool attn_fixup_fold(int64_t n_slices, const AttnScra
         });
 }
 
-// one thread per (slice, column): the first slice that carries a row folds the row's pieces and writes the row of O;
+// what the fix-up needs of the heads: how many, and what lies between two heads of the scratch, of O and of lse
+struct AttnFixupHeads {
+    uint32_t per_head;      // workgroups per head (attn_blocks_per_head of n_slices * dv)
+    int64_t hsc, ho, hlse;
+};
+
+// one thread per (head, slice, column), every head whole workgroups: the first slice that carries a row folds the row's pieces and writes the row of O;
 // column 0 writes lse
 template <typename val_t>
-__global__ __launch_bounds__(kBlock) void attention_fixup_kernel(int64_t n_slices, int32_t dv, const AttnScratch<val_t> sc, val_t* __restrict__ O,
-                                                                 int64_t ldo, val_t* __restrict__ lse) {
-    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kBlock) void attention_fixup_kernel(int64_t n_slices, int32_t dv, const AttnScratch<val_t> sc0, val_t* __restrict__ O0,
+                                                                 int64_t ldo, val_t* __restrict__ lse0, const AttnFixupHeads hd) {
+    unsigned h;
+    const int64_t gid = attn_head_thread(hd.per_head, h);
     const int j = int(gid % dv);
+    const AttnScratch<val_t> sc = attn_scratch_of_head(sc0, h, hd.hsc);
+    val_t* O = attn_head_ptr(O0, h, hd.ho);
+    val_t* lse = attn_head_ptr(lse0, h, hd.hlse);
     int32_t r;
     val_t m, l, acc;
     if (!attn_fixup_fold(n_slices, sc, gid / dv, j, r, m, l, acc)) return;
@@ -261,7 +302,7 @@ int attention_make(const char* who, mi355_spmv_attention** out, int off_type, in
     const int widest = attn_widest(vec_type);
     m->carry_ld = (int64_t(dv_max) + widest - 1) / widest * widest;
     if (m->n_slices > 0) {      // (no rows: nothing is ever launched, nothing allocated)
-        m->scratch_bytes = attn_scratch_bytes(m->n_slices, m->carry_ld, val_type == MI355_VAL_F64 ? 8 : 4);
+        m->scratch_bytes = m->head_bytes = attn_scratch_bytes(m->n_slices, m->carry_ld, val_type == MI355_VAL_F64 ? 8 : 4);
         const hipError_t e = hipMalloc(&m->scratch, m->scratch_bytes);
         if (e != hipSuccess) {
             set_error("%s: hipMalloc(%zu) -> %s", who, m->scratch_bytes, hipGetErrorString(e));
@@ -286,13 +327,14 @@ struct AttnKernels {
         hipLaunchKernelGGL((attention_slice_kernel<off_t, val_t, C>), grid, dim3(kBlock), 0, s, a, Ap);
     }
     static void fixup(dim3 grid, hipStream_t s, const Args& a, int32_t dv) {
-        hipLaunchKernelGGL((attention_fixup_kernel<val_t>), grid, dim3(kBlock), 0, s, a.n_slices, dv, a.sc, a.O, a.ldo, a.lse);
+        hipLaunchKernelGGL((attention_fixup_kernel<val_t>), grid, dim3(kBlock), 0, s, a.n_slices, dv, a.sc, a.O, a.ldo, a.lse,
+                           AttnFixupHeads{uint32_t(attn_blocks_per_head(a.n_slices * dv)), a.hsc, a.ho, a.hlse});
     }
 };
 
-// the passes over the tiles of dv, then the fix-up
+// the passes over the tiles of dv, then the fix-up: n_heads heads in every launch (hs is not read with one head)
 template <typename off_t, typename K>
-int attention_launch(const mi355_spmv_attention& m, const AttnOperands& o, hipStream_t s) {
+int attention_launch(const mi355_spmv_attention& m, const AttnOperands& o, int32_t n_heads, const mi355_spmv_attention_head_strides* hs, hipStream_t s) {
     using elem_t = typename K::elem_t;
     using acc_t = typename K::acc_t;
     typename K::Args a;
@@ -303,10 +345,14 @@ int attention_launch(const mi355_spmv_attention& m, const AttnOperands& o, hipSt
     a.O = static_cast<elem_t*>(o.O); a.lse = static_cast<acc_t*>(o.lse);
     a.ldq = o.ldq; a.ldk = o.ldk; a.ldv = o.ldv; a.ldo = o.ldo;
     a.d = o.d;
-    a.q_vec = rows_aligned16<elem_t>(o.Q, o.ldq) ? 1 : 0;
-    a.k_vec = rows_aligned16<elem_t>(o.K, o.ldk) ? 1 : 0;
-    a.v_vec = rows_aligned16<elem_t>(o.V, o.ldv) ? 1 : 0;
-    a.o_vec = rows_aligned16<elem_t>(o.O, o.ldo) ? 1 : 0;
+    const mi355_spmv_attention_head_strides h = n_heads > 1 ? *hs : mi355_spmv_attention_head_strides{0, 0, 0, 0, 0, 0};
+    a.n_heads = n_heads;
+    a.hq = h.q; a.hk = h.k; a.hv = h.v; a.hbias = h.bias; a.ho = h.o; a.hlse = h.lse;
+    a.hsc = int64_t(attn_head_scratch_stride(m.head_bytes));
+    a.q_vec = attn_rows_vec<elem_t>(o.Q, o.ldq, n_heads, h.q) ? 1 : 0;
+    a.k_vec = attn_rows_vec<elem_t>(o.K, o.ldk, n_heads, h.k) ? 1 : 0;
+    a.v_vec = attn_rows_vec<elem_t>(o.V, o.ldv, n_heads, h.v) ? 1 : 0;
+    a.o_vec = attn_rows_vec<elem_t>(o.O, o.ldo, n_heads, h.o) ? 1 : 0;
     a.scale = acc_t(m.scale);
     a.sc = attn_scratch<acc_t>(m.scratch, m.n_slices, m.carry_ld);
     const off_t* Ap = static_cast<const off_t*>(m.Ap);
@@ -315,11 +361,11 @@ int attention_launch(const mi355_spmv_attention& m, const AttnOperands& o, hipSt
         [&](dim3 grid) { K::fixup(grid, s, a, o.dv); });
 }
 
-int attention_run(const mi355_spmv_attention& m, const AttnOperands& o, void* stream) {
+int attention_run(const mi355_spmv_attention& m, const AttnOperands& o, int32_t n_heads, const mi355_spmv_attention_head_strides* hs, void* stream) {
     if (m.n_rows == 0) return MI355_SPMV_OK;        // no rows: nothing to write, nothing launched
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool i32 = m.off_type == MI355_OFF_I32;
-    auto run = [&](auto off, auto kernels) { return attention_launch<decltype(off), decltype(kernels)>(m, o, s); };
+    auto run = [&](auto off, auto kernels) { return attention_launch<decltype(off), decltype(kernels)>(m, o, n_heads, hs, s); };
     auto either = [&](auto kernels) { return i32 ? run(int32_t(), kernels) : run(int64_t(), kernels); };
     if (m.vec_type == MI355_VAL_F16) return either(AttnHalfKernels<F16>());     // 16-bit Q, K, V and O under fp32 everything else
     if (m.vec_type == MI355_VAL_BF16) return either(AttnHalfKernels<Bf16>());
@@ -340,7 +386,7 @@ int attention_one_shot(int off_type, int val_type, int vec_type, int32_t n_rows,
     int st = attention_make("attention", &m, off_type, val_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv);
     if (st != MI355_SPMV_OK) return st;
     m->scale = scale;
-    st = attention_run(*m, o, stream);
+    st = attention_run(*m, o, 1, nullptr, stream);
     if (st == MI355_SPMV_OK) st = mi355_spmv_stream_synchronize(stream);
     const int st2 = mi355_spmv_attention_destroy(m);
     return st != MI355_SPMV_OK ? st : st2;
@@ -388,7 +434,45 @@ int mi355_spmv_attention_execute(mi355_spmv_attention* m, int32_t d, int32_t dv,
     if (!m) { set_error("attention_execute: null object"); return MI355_SPMV_EINVAL; }
     const AttnOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, lse};
     if (const int st = attention_check_execute("attention_execute", m->n_rows, m->nnz, m->d_max, m->dv_max, o)) return st;
-    return attention_run(*m, o, stream);
+    return attention_run(*m, o, 1, nullptr, stream);
+}
+
+int mi355_spmv_attention_reserve_heads(mi355_spmv_attention* m, int32_t n_heads_max) {
+    set_error("%s", "");
+    if (!m) { set_error("attention_reserve_heads: null object"); return MI355_SPMV_EINVAL; }
+    if (n_heads_max < 1) { set_error("attention_reserve_heads: n_heads_max = %d below 1", n_heads_max); return MI355_SPMV_EINVAL; }
+    void* fresh = nullptr;
+    const size_t bytes = attn_heads_scratch_bytes(m->head_bytes, n_heads_max);
+    const int st = attn_reserve_scratch("attention_reserve_heads", &m->scratch, bytes, &fresh);
+    if (bytes == 0 || fresh) { m->scratch_bytes = bytes; m->n_heads_max = n_heads_max; }
+    return st;
+}
+
+int mi355_spmv_attention_get_heads_max(const mi355_spmv_attention* m, int32_t* n_heads_max) {
+    if (!m || !n_heads_max) { set_error("attention_get_heads_max: null argument"); return MI355_SPMV_EINVAL; }
+    *n_heads_max = m->n_heads_max;
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_attention_execute_heads(mi355_spmv_attention* m, int32_t n_heads, const mi355_spmv_attention_head_strides* hs, int32_t d, int32_t dv,
+                                       const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const void* bias, void* O,
+                                       int64_t ldo, void* lse, void* stream) {
+    const char* const who = "attention_execute_heads";
+    set_error("%s", "");
+    if (!m) { set_error("%s: null object", who); return MI355_SPMV_EINVAL; }
+    const AttnOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, lse};
+    if (const int st = attention_check_execute(who, m->n_rows, m->nnz, m->d_max, m->dv_max, o)) return st;
+    if (const int st = attn_check_n_heads(who, n_heads, m->n_heads_max, hs)) return st;
+    if (n_heads > 1) {
+        const std::pair<const char*, int64_t> all[] = {{"q", hs->q}, {"k", hs->k}, {"v", hs->v}, {"bias", hs->bias}, {"o", hs->o}, {"lse", hs->lse}};
+        for (const auto& [name, stride] : all)
+            if (const int st = attn_check_stride_sign(who, name, stride)) return st;
+        if (const int st = attn_check_out_stride(who, "o", n_heads, hs->o, m->n_rows, dv, ldo)) return st;
+        if (lse && m->n_rows > 0)
+            if (const int st = attn_check_out_vector_stride(who, "lse", hs->lse, m->n_rows, "n_rows")) return st;
+    }
+    if (const int st = attn_check_heads_grid(who, n_heads, m->n_slices, dv)) return st;
+    return attention_run(*m, o, n_heads, hs, stream);
 }
 
 int mi355_spmv_attention_get_info(const mi355_spmv_attention* m, mi355_spmv_attention_info* info) {

@@ -63,8 +63,11 @@ struct mi355_spmv_attention_bwd {   // the opaque handle of include/mi355_spmv.h
     int64_t carry_ld = 0;           // max(d_max, dv_max) rounded up to whole widest tiles
     char* held = nullptr;           // perm, Ajt, Apt in one allocation (multi_transposed.hip's layout)
     size_t held_bytes = 0;
-    void* scratch = nullptr;        // delta, then the slices' two pieces (rows and sums), shared by the roles in stream order
+    void* scratch = nullptr;        // delta, then the slices' two pieces (rows and sums), shared by the roles in stream order;
+                                    // n_heads_max copies, head h at h * head stride
     size_t scratch_bytes = 0;
+    size_t head_bytes = 0;          // of one head's copy (what a create allocates)
+    int32_t n_heads_max = 1;        // reserve_heads
 };
 
 namespace mi355 {
@@ -130,6 +133,42 @@ struct AttnBwdArgs {
     int32_t q_vec, k_vec, v_vec, do_vec, out_vec;   // 1 = rows are 16-byte aligned: one 16-byte access per lane
     val_t scale;
     AttnBwdScratch<val_t> sc;
+    int32_t n_heads;        // heads in this launch: workgroup b serves head b % n_heads
+    int64_t hq, hk, hv, hdo, hbias, hlse, hout, hdbias;     // elements between two heads of an operand (0: shared)
+    int64_t hsc;            // bytes between two heads' scratch
+};
+
+// The scratch of head h: the single-head layout at h * bytes.
+template <typename acc_t>
+__device__ __forceinline__ AttnBwdScratch<acc_t> attn_bwd_scratch_of_head(AttnBwdScratch<acc_t> sc, int64_t h, int64_t bytes) {
+    sc.delta = attn_head_scratch(sc.delta, h, bytes);
+    sc.acc = attn_head_scratch(sc.acc, h, bytes);
+    sc.row = attn_head_scratch(sc.row, h, bytes);
+    return sc;
+}
+
+// A slice kernel's local copy of its arguments, rebased to head h (AttnBwdArgs<val_t> or AttnBwdHalfArgs<vec_t>)
+template <typename Args>
+__device__ __forceinline__ Args attn_bwd_args_of_head(Args a, int64_t h) {
+    a.Q = attn_head_ptr(a.Q, h, a.hq);
+    a.K = attn_head_ptr(a.K, h, a.hk);
+    a.V = attn_head_ptr(a.V, h, a.hv);
+    a.dO = attn_head_ptr(a.dO, h, a.hdo);
+    a.bias = attn_head_ptr(a.bias, h, a.hbias);
+    a.lse = attn_head_ptr(a.lse, h, a.hlse);
+    a.out = attn_head_ptr(a.out, h, a.hout);
+    a.dbias = attn_head_ptr(a.dbias, h, a.hdbias);
+    a.sc = attn_bwd_scratch_of_head(a.sc, h, a.hsc);
+    a.delta = a.sc.delta;
+    return a;
+}
+
+// what the delta kernel and the fix-up need of the heads: how many, and what lies between two heads of the scratch and of
+// their operands (delta: dO and O; fix-up: out)
+struct AttnBwdHeads {
+    int32_t n_heads;
+    uint32_t per_head;      // workgroups per head (attn_blocks_per_head of the head's threads)
+    int64_t hsc, ha, hb;
 };
 
 // the sum over all slots of a per-slot partial, in every lane of the column group (xor butterfly: the same bits everywhere)
@@ -147,15 +186,18 @@ __device__ __forceinline__ void attn_bwd_reduce_slots(val_t (&v)[W]) {
 constexpr int kDeltaLanes = 8;
 template <typename val_t>
 __global__ __launch_bounds__(kBlock) void attention_bwd_delta_kernel(int32_t n_rows, int32_t dv, const val_t* __restrict__ dO, int64_t lddo,
-                                                                     const val_t* __restrict__ O, int64_t ldo, val_t* __restrict__ delta) {
-    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+                                                                     const val_t* __restrict__ O, int64_t ldo, val_t* __restrict__ delta0,
+                                                                     const AttnBwdHeads hd) {
+    unsigned h;
+    const int64_t gid = attn_head_thread(hd.per_head, h);
     const int64_t r = gid / kDeltaLanes;
     const int g = int(gid % kDeltaLanes);
     const bool valid = r < n_rows;      // (every lane stays for the shuffles)
+    val_t* delta = attn_head_scratch(delta0, h, hd.hsc);
     val_t sum = val_t(0);
     if (valid) {
-        const val_t* a = dO + r * lddo;
-        const val_t* b = O + r * ldo;
+        const val_t* a = dO + h * hd.ha + r * lddo;
+        const val_t* b = O + h * hd.hb + r * ldo;
         for (int32_t j = g; j < dv; j += kDeltaLanes) sum = attn_fma(a[j], b[j], sum);
     }
 #pragma unroll
@@ -165,13 +207,16 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_delta_kernel(int32_t n_r
 
 // C = lanes per nonzero slot (16-byte column groups of this pass's tile of out); the wave holds S = 64 / C slots
 template <typename off_t, typename val_t, int C, int ROLE>
-__global__ __launch_bounds__(kBlock) void attention_bwd_slice_kernel(const AttnBwdArgs<val_t> a, const off_t* __restrict__ Ap) {
+__global__ __launch_bounds__(kBlock) void attention_bwd_slice_kernel(const AttnBwdArgs<val_t> args, const off_t* __restrict__ Ap) {
     using acc_t = val_t;                            // what attention_bwd_slice_walk.inc asks its includer
     constexpr int W = 16 / int(sizeof(val_t));      // columns of a lane per tile
     constexpr int S = kWave / C;
     constexpr val_t kNegInf = -std::numeric_limits<val_t>::infinity();
     constexpr bool kCutCarriedIn = true, kCutKeepsR1 = true;        // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = -1;
+    // the head varies fastest over the grid: the workgroups that read one range of Ap / Aj are dispatched together
+    const unsigned cut_block = blockIdx.x / unsigned(args.n_heads);
+    const AttnBwdArgs<val_t> a = attn_bwd_args_of_head(args, blockIdx.x % unsigned(args.n_heads));
 #include "slice_cut.inc"            // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
 #include "attention_bwd_slice_walk.inc"     // the slice's entries, 64 at a time, and its lines without entries
 }
@@ -185,12 +230,15 @@ __device__ __forceinline__ bool attn_bwd_fixup_sum(int64_t n_slices, const AttnB
         [&](int64_t piece) { sum = sum + sc.acc[piece * sc.carry_ld + j]; });
 }
 
-// one thread per (slice, column): the first slice that carries a line adds the line's pieces and stores the line of out
+// one thread per (head, slice, column): the first slice that carries a line adds the line's pieces and stores the line of out
 template <typename val_t>
-__global__ __launch_bounds__(kBlock) void attention_bwd_fixup_kernel(int64_t n_slices, int32_t width, const AttnBwdScratch<val_t> sc,
-                                                                     val_t* __restrict__ out, int64_t ldout) {
-    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kBlock) void attention_bwd_fixup_kernel(int64_t n_slices, int32_t width, const AttnBwdScratch<val_t> sc0,
+                                                                     val_t* __restrict__ out0, int64_t ldout, const AttnBwdHeads hd) {
+    unsigned h;
+    const int64_t gid = attn_head_thread(hd.per_head, h);
     const int j = int(gid % width);
+    const AttnBwdScratch<val_t> sc = attn_bwd_scratch_of_head(sc0, h, hd.hsc);
+    val_t* out = out0 + h * hd.ha;
     int32_t r;
     val_t sum;
     if (!attn_bwd_fixup_sum(n_slices, sc, gid / width, j, r, sum)) return;
@@ -294,7 +342,7 @@ int attention_bwd_make(const char* who, mi355_spmv_attention_bwd** out, int off_
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->held), m->held_bytes);
     if (e != hipSuccess) { m->held = nullptr; return failed("hipMalloc", m->held_bytes, e); }
     const int64_t slices = m->n_slices > m->n_slices_t ? m->n_slices : m->n_slices_t;
-    m->scratch_bytes = attn_bwd_scratch_bytes(n_rows, slices, m->carry_ld, val_type == MI355_VAL_F64 ? 8 : 4);
+    m->scratch_bytes = m->head_bytes = attn_bwd_scratch_bytes(n_rows, slices, m->carry_ld, val_type == MI355_VAL_F64 ? 8 : 4);
     e = hipMalloc(&m->scratch, m->scratch_bytes);
     if (e != hipSuccess) { m->scratch = nullptr; return failed("hipMalloc", m->scratch_bytes, e); }
     void* ws = nullptr;
@@ -320,15 +368,17 @@ struct AttnBwdKernels {
     using acc_t = val_t;
     using Args = AttnBwdArgs<val_t>;
     static constexpr int W = 16 / int(sizeof(val_t));
-    static void delta(dim3 grid, hipStream_t s, int32_t n_rows, int32_t dv, const val_t* dO, int64_t lddo, const val_t* O, int64_t ldo, val_t* delta) {
-        hipLaunchKernelGGL((attention_bwd_delta_kernel<val_t>), grid, dim3(kBlock), 0, s, n_rows, dv, dO, lddo, O, ldo, delta);
+    static void delta(dim3 grid, hipStream_t s, int32_t n_rows, int32_t dv, const val_t* dO, int64_t lddo, const val_t* O, int64_t ldo, val_t* delta,
+                      const AttnBwdHeads& hd) {
+        hipLaunchKernelGGL((attention_bwd_delta_kernel<val_t>), grid, dim3(kBlock), 0, s, n_rows, dv, dO, lddo, O, ldo, delta, hd);
     }
     template <typename off_t, int C, int ROLE>
     static void slice(dim3 grid, hipStream_t s, const Args& a, const off_t* Ap) {
         hipLaunchKernelGGL((attention_bwd_slice_kernel<off_t, val_t, C, ROLE>), grid, dim3(kBlock), 0, s, a, Ap);
     }
     static void fixup(dim3 grid, hipStream_t s, const Args& a, int32_t width) {
-        hipLaunchKernelGGL((attention_bwd_fixup_kernel<val_t>), grid, dim3(kBlock), 0, s, a.n_slices, width, a.sc, a.out, a.ldout);
+        hipLaunchKernelGGL((attention_bwd_fixup_kernel<val_t>), grid, dim3(kBlock), 0, s, a.n_slices, width, a.sc, a.out, a.ldout,
+                           AttnBwdHeads{a.n_heads, uint32_t(attn_blocks_per_head(a.n_slices * width)), a.hsc, a.hout, 0});
     }
 };
 
@@ -342,7 +392,8 @@ int attention_bwd_role(typename K::Args& a, const off_t* Ap, int32_t width, hipS
 
 // delta, then the roles that are asked for, one behind the other on the stream (they share the pieces' scratch)
 template <typename off_t, typename K>
-int attention_bwd_launch(const mi355_spmv_attention_bwd& m, const AttnBwdOperands& o, hipStream_t s) {
+int attention_bwd_launch(const mi355_spmv_attention_bwd& m, const AttnBwdOperands& o, int32_t n_heads, const mi355_spmv_attention_bwd_head_strides* hs,
+                         hipStream_t s) {
     using elem_t = typename K::elem_t;
     using acc_t = typename K::acc_t;
     const int64_t slices = m.n_slices > m.n_slices_t ? m.n_slices : m.n_slices_t;
@@ -354,23 +405,29 @@ int attention_bwd_launch(const mi355_spmv_attention_bwd& m, const AttnBwdOperand
     a.lse = static_cast<const acc_t*>(o.lse);
     a.ldq = o.ldq; a.ldk = o.ldk; a.ldv = o.ldv; a.lddo = o.lddo;
     a.d = o.d; a.dv = o.dv;
-    a.q_vec = rows_aligned16<elem_t>(o.Q, o.ldq) ? 1 : 0;
-    a.k_vec = rows_aligned16<elem_t>(o.K, o.ldk) ? 1 : 0;
-    a.v_vec = rows_aligned16<elem_t>(o.V, o.ldv) ? 1 : 0;
-    a.do_vec = rows_aligned16<elem_t>(o.dO, o.lddo) ? 1 : 0;
+    const mi355_spmv_attention_bwd_head_strides h = n_heads > 1 ? *hs : mi355_spmv_attention_bwd_head_strides{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    a.n_heads = n_heads;
+    a.hq = h.q; a.hk = h.k; a.hv = h.v; a.hdo = h.d_o; a.hbias = h.bias; a.hlse = h.lse; a.hdbias = h.dbias;
+    a.hsc = int64_t(attn_head_scratch_stride(m.head_bytes));
+    a.q_vec = attn_rows_vec<elem_t>(o.Q, o.ldq, n_heads, h.q) ? 1 : 0;
+    a.k_vec = attn_rows_vec<elem_t>(o.K, o.ldk, n_heads, h.k) ? 1 : 0;
+    a.v_vec = attn_rows_vec<elem_t>(o.V, o.ldv, n_heads, h.v) ? 1 : 0;
+    a.do_vec = attn_rows_vec<elem_t>(o.dO, o.lddo, n_heads, h.d_o) ? 1 : 0;
     a.scale = acc_t(m.scale);
     a.sc = attn_bwd_scratch<acc_t>(m.scratch, m.n_rows, slices, m.carry_ld);
     a.delta = a.sc.delta;
     a.col_begin = 0; a.cols = 0;
     if (m.n_rows > 0 && m.nnz > 0) {
-        K::delta(dim3(unsigned((int64_t(m.n_rows) * kDeltaLanes + kBlock - 1) / kBlock)), s, m.n_rows, o.dv, a.dO, o.lddo, static_cast<const elem_t*>(o.O),
-                 o.ldo, a.sc.delta);
+        const int64_t per_head = attn_blocks_per_head(int64_t(m.n_rows) * kDeltaLanes);
+        K::delta(dim3(unsigned(per_head * n_heads)), s, m.n_rows, o.dv, a.dO, o.lddo, static_cast<const elem_t*>(o.O), o.ldo, a.sc.delta,
+                 AttnBwdHeads{n_heads, uint32_t(per_head), a.hsc, h.d_o, h.o});
         MI355_HIP_TRY(hipGetLastError());
     }
-    const auto role = [&](auto which, void* out, int64_t ldout, int32_t width) {
+    const auto role = [&](auto which, void* out, int64_t ldout, int64_t hout, int32_t width) {
         a.out = static_cast<elem_t*>(out);
         a.ldout = ldout;
-        a.out_vec = rows_aligned16<elem_t>(out, ldout) ? 1 : 0;
+        a.hout = hout;
+        a.out_vec = attn_rows_vec<elem_t>(out, ldout, n_heads, hout) ? 1 : 0;
         constexpr int ROLE = decltype(which)::value;
         if constexpr (ROLE == kBwdDQ) {
             a.n_rows = m.n_rows; a.n_slices = m.n_slices;
@@ -386,18 +443,19 @@ int attention_bwd_launch(const mi355_spmv_attention_bwd& m, const AttnBwdOperand
         }
     };
     if (o.dQ)
-        if (const int st = role(std::integral_constant<int, kBwdDQ>(), o.dQ, o.lddq, o.d)) return st;
+        if (const int st = role(std::integral_constant<int, kBwdDQ>(), o.dQ, o.lddq, h.dq, o.d)) return st;
     if (o.dK)
-        if (const int st = role(std::integral_constant<int, kBwdDK>(), o.dK, o.lddk, o.d)) return st;
+        if (const int st = role(std::integral_constant<int, kBwdDK>(), o.dK, o.lddk, h.dk, o.d)) return st;
     if (o.dV)
-        if (const int st = role(std::integral_constant<int, kBwdDV>(), o.dV, o.lddv, o.dv)) return st;
+        if (const int st = role(std::integral_constant<int, kBwdDV>(), o.dV, o.lddv, h.dv, o.dv)) return st;
     return MI355_SPMV_OK;
 }
 
-int attention_bwd_run(const mi355_spmv_attention_bwd& m, const AttnBwdOperands& o, void* stream) {
+int attention_bwd_run(const mi355_spmv_attention_bwd& m, const AttnBwdOperands& o, int32_t n_heads, const mi355_spmv_attention_bwd_head_strides* hs,
+                      void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool i32 = m.off_type == MI355_OFF_I32;
-    auto run = [&](auto off, auto kernels) { return attention_bwd_launch<decltype(off), decltype(kernels)>(m, o, s); };
+    auto run = [&](auto off, auto kernels) { return attention_bwd_launch<decltype(off), decltype(kernels)>(m, o, n_heads, hs, s); };
     auto either = [&](auto kernels) { return i32 ? run(int32_t(), kernels) : run(int64_t(), kernels); };
     if (m.vec_type == MI355_VAL_F16) return either(AttnBwdHalfKernels<F16>());      // 16-bit matrices under fp32 everything else
     if (m.vec_type == MI355_VAL_BF16) return either(AttnBwdHalfKernels<Bf16>());
@@ -418,7 +476,7 @@ int attention_bwd_one_shot(int off_type, int val_type, int vec_type, int32_t n_r
     int st = attention_bwd_make(who, &m, off_type, val_type, vec_type, n_rows, n_cols, nnz, Ap, Aj, o.d, o.dv, static_cast<hipStream_t>(stream));
     if (st != MI355_SPMV_OK) return st;
     m->scale = scale;
-    st = attention_bwd_run(*m, o, stream);
+    st = attention_bwd_run(*m, o, 1, nullptr, stream);
     if (st == MI355_SPMV_OK) st = mi355_spmv_stream_synchronize(stream);
     const int st2 = attention_bwd_free(m);
     return st != MI355_SPMV_OK ? st : st2;
@@ -471,7 +529,57 @@ int mi355_spmv_attention_bwd_execute(mi355_spmv_attention_bwd* m, int32_t d, int
     if (!m) { set_error("attention_bwd_execute: null object"); return MI355_SPMV_EINVAL; }
     const AttnBwdOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, dbias};
     if (const int st = attention_bwd_check_execute("attention_bwd_execute", m->n_rows, m->nnz, m->d_max, m->dv_max, o)) return st;
-    return attention_bwd_run(*m, o, stream);
+    return attention_bwd_run(*m, o, 1, nullptr, stream);
+}
+
+int mi355_spmv_attention_bwd_reserve_heads(mi355_spmv_attention_bwd* m, int32_t n_heads_max) {
+    set_error("%s", "");
+    if (!m) { set_error("attention_bwd_reserve_heads: null object"); return MI355_SPMV_EINVAL; }
+    if (n_heads_max < 1) { set_error("attention_bwd_reserve_heads: n_heads_max = %d below 1", n_heads_max); return MI355_SPMV_EINVAL; }
+    void* fresh = nullptr;      // (the held transpose is what every head shares: not touched)
+    const size_t bytes = attn_heads_scratch_bytes(m->head_bytes, n_heads_max);
+    const int st = attn_reserve_scratch("attention_bwd_reserve_heads", &m->scratch, bytes, &fresh);
+    if (bytes == 0 || fresh) { m->scratch_bytes = bytes; m->n_heads_max = n_heads_max; }
+    return st;
+}
+
+int mi355_spmv_attention_bwd_get_heads_max(const mi355_spmv_attention_bwd* m, int32_t* n_heads_max) {
+    if (!m || !n_heads_max) { set_error("attention_bwd_get_heads_max: null argument"); return MI355_SPMV_EINVAL; }
+    *n_heads_max = m->n_heads_max;
+    return MI355_SPMV_OK;
+}
+
+int mi355_spmv_attention_bwd_execute_heads(mi355_spmv_attention_bwd* m, int32_t n_heads, const mi355_spmv_attention_bwd_head_strides* hs, int32_t d,
+                                           int32_t dv, const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                                           const void* bias, const void* O, int64_t ldo, const void* dO, int64_t lddo, const void* lse, void* dQ,
+                                           int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, void* dbias, void* stream) {
+    const char* const who = "attention_bwd_execute_heads";
+    set_error("%s", "");
+    if (!m) { set_error("%s: null object", who); return MI355_SPMV_EINVAL; }
+    const AttnBwdOperands o{d, dv, Q, ldq, K, ldk, V, ldv, bias, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, dbias};
+    if (const int st = attention_bwd_check_execute(who, m->n_rows, m->nnz, m->d_max, m->dv_max, o)) return st;
+    if (const int st = attn_check_n_heads(who, n_heads, m->n_heads_max, hs)) return st;
+    if (n_heads > 1) {
+        const std::pair<const char*, int64_t> all[] = {{"q", hs->q},   {"k", hs->k},     {"v", hs->v},   {"bias", hs->bias}, {"o", hs->o},        {"d_o", hs->d_o},
+                                                       {"lse", hs->lse}, {"dq", hs->dq}, {"dk", hs->dk}, {"dv", hs->dv},     {"dbias", hs->dbias}};
+        for (const auto& [name, stride] : all)
+            if (const int st = attn_check_stride_sign(who, name, stride)) return st;
+        if (dQ)
+            if (const int st = attn_check_out_stride(who, "dq", n_heads, hs->dq, m->n_rows, d, lddq)) return st;
+        if (dK)
+            if (const int st = attn_check_out_stride(who, "dk", n_heads, hs->dk, m->n_cols, d, lddk)) return st;
+        if (dV)
+            if (const int st = attn_check_out_stride(who, "dv", n_heads, hs->dv, m->n_cols, dv, lddv)) return st;
+        if (dbias && m->nnz > 0)
+            if (const int st = attn_check_out_vector_stride(who, "dbias", hs->dbias, m->nnz, "nnz")) return st;
+    }
+    const int64_t wide = d > dv ? d : dv;
+    if (const int st = attn_check_heads_grid(who, n_heads, m->n_slices > m->n_slices_t ? m->n_slices : m->n_slices_t, wide)) return st;
+    if (attn_blocks_per_head(int64_t(m->n_rows) * kDeltaLanes) * n_heads >= (int64_t(1) << 31)) {
+        set_error("%s: n_heads = %d makes a grid of 2^31 workgroups or more (%d rows)", who, n_heads, m->n_rows);
+        return MI355_SPMV_ENOTSUP;
+    }
+    return attention_bwd_run(*m, o, n_heads, hs, stream);
 }
 
 int mi355_spmv_attention_bwd_get_info(const mi355_spmv_attention_bwd* m, mi355_spmv_attention_bwd_info* info) {

@@ -58,22 +58,27 @@ struct AttnBwdHalfArgs {
     int32_t q_vec, k_vec, v_vec, do_vec, out_vec;   // 1 = rows are 16-byte aligned: one 16-byte access per lane
     float scale;
     AttnBwdScratch<float> sc;
+    int32_t n_heads;        // AttnBwdArgs' heads: the same members, in elements of vec_t for the matrices
+    int64_t hq, hk, hv, hdo, hbias, hlse, hout, hdbias;
+    int64_t hsc;
 };
 
 // delta[r] = dot(float(dO[r, :dv]), float(O[r, :dv])) in fp32: kDeltaLanes lanes per row, lane g the columns 64 k + 8 g .. + 7
 template <typename vec_t>
 __global__ __launch_bounds__(kBlock) void attention_bwd_half_delta_kernel(int32_t n_rows, int32_t dv, const vec_t* __restrict__ dO, int64_t lddo,
                                                                           int32_t do_vec, const vec_t* __restrict__ O, int64_t ldo, int32_t o_vec,
-                                                                          float* __restrict__ delta) {
+                                                                          float* __restrict__ delta0, const AttnBwdHeads hd) {
     constexpr int W = mh::kHalfV;
-    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+    unsigned h;
+    const int64_t gid = attn_head_thread(hd.per_head, h);
     const int64_t r = gid / kDeltaLanes;
     const int g = int(gid % kDeltaLanes);
     const bool valid = r < n_rows;      // (every lane stays for the shuffles)
+    float* delta = attn_head_scratch(delta0, h, hd.hsc);
     float sum = 0.0f;
     if (valid) {
-        const vec_t* a = dO + r * lddo;
-        const vec_t* b = O + r * ldo;
+        const vec_t* a = dO + h * hd.ha + r * lddo;
+        const vec_t* b = O + h * hd.hb + r * ldo;
         for (int32_t cb = g * W; cb < dv; cb += kDeltaLanes * W) {
             const int nd = min(dv - cb, W);
             float x[W], y[W];
@@ -90,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_half_delta_kernel(int32_
 
 // C = lanes per nonzero slot (16-byte column groups of this pass's tile of out); the wave holds S = 64 / C slots
 template <typename off_t, typename vec_t, int C, int ROLE>
-__global__ __launch_bounds__(kBlock) void attention_bwd_half_slice_kernel(const AttnBwdHalfArgs<vec_t> a, const off_t* __restrict__ Ap) {
+__global__ __launch_bounds__(kBlock) void attention_bwd_half_slice_kernel(const AttnBwdHalfArgs<vec_t> args, const off_t* __restrict__ Ap) {
     using acc_t = float;                // what attention_bwd_slice_walk.inc asks its includer
     using mh::load_cols;                // the lane's eight 16-bit columns, widened
     using mh::store_cols;               // and narrowed, once each
@@ -99,16 +104,21 @@ __global__ __launch_bounds__(kBlock) void attention_bwd_half_slice_kernel(const 
     constexpr float kNegInf = -std::numeric_limits<float>::infinity();
     constexpr bool kCutCarriedIn = true, kCutKeepsR1 = true;        // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = -1;
+    const unsigned cut_block = blockIdx.x / unsigned(args.n_heads);     // the head varies fastest, as in attention_bwd_slice_kernel
+    const AttnBwdHalfArgs<vec_t> a = attn_bwd_args_of_head(args, blockIdx.x % unsigned(args.n_heads));
 #include "slice_cut.inc"            // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
 #include "attention_bwd_slice_walk.inc"     // the slice's entries, 64 at a time: attention_bwd_slice_kernel's walk
 }
 
-// one thread per (slice, column), as attention_bwd_fixup_kernel: the line's only rounding to 16 bits, after the fp32 sum
+// one thread per (head, slice, column), as attention_bwd_fixup_kernel: the line's only rounding to 16 bits, after the fp32 sum
 template <typename vec_t>
-__global__ __launch_bounds__(kBlock) void attention_bwd_half_fixup_kernel(int64_t n_slices, int32_t width, const AttnBwdScratch<float> sc,
-                                                                          vec_t* __restrict__ out, int64_t ldout) {
-    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kBlock) void attention_bwd_half_fixup_kernel(int64_t n_slices, int32_t width, const AttnBwdScratch<float> sc0,
+                                                                          vec_t* __restrict__ out0, int64_t ldout, const AttnBwdHeads hd) {
+    unsigned h;
+    const int64_t gid = attn_head_thread(hd.per_head, h);
     const int j = int(gid % width);
+    const AttnBwdScratch<float> sc = attn_bwd_scratch_of_head(sc0, h, hd.hsc);
+    vec_t* out = out0 + h * hd.ha;
     int32_t r;
     float sum;
     if (!attn_bwd_fixup_sum(n_slices, sc, gid / width, j, r, sum)) return;
@@ -124,16 +134,19 @@ struct AttnBwdHalfKernels {
     using acc_t = float;
     using Args = AttnBwdHalfArgs<vec_t>;
     static constexpr int W = mh::kHalfV;
-    static void delta(dim3 grid, hipStream_t s, int32_t n_rows, int32_t dv, const vec_t* dO, int64_t lddo, const vec_t* O, int64_t ldo, float* delta) {
-        hipLaunchKernelGGL((attention_bwd_half_delta_kernel<vec_t>), grid, dim3(kBlock), 0, s, n_rows, dv, dO, lddo, rows_aligned16<vec_t>(dO, lddo) ? 1 : 0,
-                           O, ldo, rows_aligned16<vec_t>(O, ldo) ? 1 : 0, delta);
+    static void delta(dim3 grid, hipStream_t s, int32_t n_rows, int32_t dv, const vec_t* dO, int64_t lddo, const vec_t* O, int64_t ldo, float* delta,
+                      const AttnBwdHeads& hd) {
+        hipLaunchKernelGGL((attention_bwd_half_delta_kernel<vec_t>), grid, dim3(kBlock), 0, s, n_rows, dv, dO, lddo,
+                           attn_rows_vec<vec_t>(dO, lddo, hd.n_heads, hd.ha) ? 1 : 0, O, ldo, attn_rows_vec<vec_t>(O, ldo, hd.n_heads, hd.hb) ? 1 : 0, delta,
+                           hd);
     }
     template <typename off_t, int C, int ROLE>
     static void slice(dim3 grid, hipStream_t s, const Args& a, const off_t* Ap) {
         hipLaunchKernelGGL((attention_bwd_half_slice_kernel<off_t, vec_t, C, ROLE>), grid, dim3(kBlock), 0, s, a, Ap);
     }
     static void fixup(dim3 grid, hipStream_t s, const Args& a, int32_t width) {
-        hipLaunchKernelGGL((attention_bwd_half_fixup_kernel<vec_t>), grid, dim3(kBlock), 0, s, a.n_slices, width, a.sc, a.out, a.ldout);
+        hipLaunchKernelGGL((attention_bwd_half_fixup_kernel<vec_t>), grid, dim3(kBlock), 0, s, a.n_slices, width, a.sc, a.out, a.ldout,
+                           AttnBwdHeads{a.n_heads, uint32_t(attn_blocks_per_head(a.n_slices * width)), a.hsc, a.hout, 0});
     }
 };
 

@@ -50,11 +50,14 @@ struct AttnHalfArgs {
     int32_t q_vec, k_vec, v_vec, o_vec;     // 1 = rows are 16-byte aligned: one 16-byte access per lane
     float scale;
     AttnScratch<float> sc;
+    int32_t n_heads;        // AttnArgs' heads: the same members, in elements of vec_t for Q, K, V and O
+    int64_t hq, hk, hv, hbias, ho, hlse;
+    int64_t hsc;
 };
 
 // C = lanes per nonzero slot (16-byte column groups of this pass's tile of dv); the wave holds S = 64 / C slots
 template <typename off_t, typename vec_t, int C>
-__global__ __launch_bounds__(kBlock) void attention_half_slice_kernel(const AttnHalfArgs<vec_t> a, const off_t* __restrict__ Ap) {
+__global__ __launch_bounds__(kBlock) void attention_half_slice_kernel(const AttnHalfArgs<vec_t> args, const off_t* __restrict__ Ap) {
     using acc_t = float;                // what attention_slice_walk.inc asks its includer
     using mh::load_cols;                // the lane's eight 16-bit columns, widened
     using mh::store_cols;               // and narrowed, once each
@@ -63,16 +66,23 @@ __global__ __launch_bounds__(kBlock) void attention_half_slice_kernel(const Attn
     constexpr float kNegInf = -std::numeric_limits<float>::infinity();
     constexpr bool kCutCarriedIn = true, kCutKeepsR1 = true;        // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = -1;
+    const unsigned cut_block = blockIdx.x / unsigned(args.n_heads);     // the head varies fastest, as in attention_slice_kernel
+    const AttnHalfArgs<vec_t> a = attn_args_of_head(args, blockIdx.x % unsigned(args.n_heads));
 #include "slice_cut.inc"            // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
 #include "attention_slice_walk.inc"     // the slice's nonzeros, 64 at a time: attention_slice_kernel's walk
 }
 
-// one thread per (slice, column), as attention_fixup_kernel: the row's only rounding to 16 bits
+// one thread per (head, slice, column), as attention_fixup_kernel: the row's only rounding to 16 bits
 template <typename vec_t>
-__global__ __launch_bounds__(kBlock) void attention_half_fixup_kernel(int64_t n_slices, int32_t dv, const AttnScratch<float> sc,
-                                                                      vec_t* __restrict__ O, int64_t ldo, float* __restrict__ lse) {
-    const int64_t gid = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+__global__ __launch_bounds__(kBlock) void attention_half_fixup_kernel(int64_t n_slices, int32_t dv, const AttnScratch<float> sc0,
+                                                                      vec_t* __restrict__ O0, int64_t ldo, float* __restrict__ lse0,
+                                                                      const AttnFixupHeads hd) {
+    unsigned h;
+    const int64_t gid = attn_head_thread(hd.per_head, h);
     const int j = int(gid % dv);
+    const AttnScratch<float> sc = attn_scratch_of_head(sc0, h, hd.hsc);
+    vec_t* O = attn_head_ptr(O0, h, hd.ho);
+    float* lse = attn_head_ptr(lse0, h, hd.hlse);
     int32_t r;
     float m, l, acc;
     if (!attn_fixup_fold(n_slices, sc, gid / dv, j, r, m, l, acc)) return;
@@ -94,7 +104,8 @@ struct AttnHalfKernels {
         hipLaunchKernelGGL((attention_half_slice_kernel<off_t, vec_t, C>), grid, dim3(kBlock), 0, s, a, Ap);
     }
     static void fixup(dim3 grid, hipStream_t s, const Args& a, int32_t dv) {
-        hipLaunchKernelGGL((attention_half_fixup_kernel<vec_t>), grid, dim3(kBlock), 0, s, a.n_slices, dv, a.sc, a.O, a.ldo, a.lse);
+        hipLaunchKernelGGL((attention_half_fixup_kernel<vec_t>), grid, dim3(kBlock), 0, s, a.n_slices, dv, a.sc, a.O, a.ldo, a.lse,
+                           AttnFixupHeads{uint32_t(attn_blocks_per_head(a.n_slices * dv)), a.hsc, a.ho, a.hlse});
     }
 };
 

@@ -34,6 +34,7 @@
     constexpr int S = kWave / C;
     constexpr bool kCutCarriedIn = P::kTails, kCutKeepsR1 = true;   // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = -1;
+    const unsigned cut_block = blockIdx.x;
 #include "slice_cut.inc"        // leaves lane, c, s, w, r0, r1, n0, nn, nr, rel, carried_in
 
     acc_t acc[V];           // per-slot partial of the open row (the row whose nonzeros are not all seen yet)

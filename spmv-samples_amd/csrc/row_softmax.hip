@@ -205,6 +205,7 @@ __global__ __launch_bounds__(kBlock) void row_softmax_slice_kernel(const RowSoft
     constexpr int C = 1;                                            // one lane per nonzero
     constexpr bool kCutCarriedIn = true, kCutKeepsR1 = false;       // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = 0;
+    const unsigned cut_block = blockIdx.x;
 #include "slice_cut.inc"            // leaves lane, c, s, w, r0, n0, nn, nr, rel, carried_in
     (void)c; (void)s;
 

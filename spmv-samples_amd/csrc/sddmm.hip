@@ -96,6 +96,7 @@ __global__ __launch_bounds__(kBlock) void sddmm_slice_kernel(const SddmmArgs<val
     constexpr bool kCutCarriedIn = false, kCutKeepsR1 = false;      // what slice_cut.inc asks its includer
     constexpr int kCutNrInit = 0;
     constexpr bool kWalkFmaInPlace = false;                         // what sddmm_slice_walk.inc asks its includer
+    const unsigned cut_block = blockIdx.x;
 #include "slice_cut.inc"            // leaves lane, c, s, w, r0, n0, nn, nr, rel
 #include "sddmm_slice_walk.inc"     // the slice's nonzeros, 64 at a time: load_cols is slice_cut.hpp's
 }

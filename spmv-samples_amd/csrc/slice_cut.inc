@@ -9,6 +9,8 @@
 //   C                the kernel's template argument: lanes per nonzero slot
 //   kCutCarriedIn    constexpr bool: carried_in is computed (one more read of Ap[r0]); false leaves it false
 //   kCutKeepsR1      constexpr bool: r1 outlives the cut (the multi-vector walk's empty rows end at it); false leaves it 0
+//   cut_block        the workgroup's index among those that cut this structure: blockIdx.x everywhere but in the attention
+//                    kernels, whose grid holds every head's workgroups (blockIdx.x / n_heads, DESIGN.md §3.15.4)
 //   kCutNrInit       constexpr int: what nr holds in a wave without a slice, which returns below and never reads it.
 //                    Each family keeps the value it was written with (multi -1, SDDMM 0): the value is an
 //                    instruction's immediate, and the kernels compile as on record only with their own
@@ -21,7 +23,7 @@
     const int lane = threadIdx.x & (kWave - 1);
     const int c = lane % C, s = lane / C;
     int32_t* rel = rel_all[threadIdx.x / kWave];
-    const int64_t w = int64_t(blockIdx.x) * kSliceWaves + threadIdx.x / kWave;
+    const int64_t w = int64_t(cut_block) * kSliceWaves + threadIdx.x / kWave;
     const bool active = w < a.n_slices;
     [[maybe_unused]] int64_t r0 = 0, r1 = 0, n0 = 0;     // (r1 may go unused; one declaration in this order, as on record)
     int nr = kCutNrInit, nn = 0;
