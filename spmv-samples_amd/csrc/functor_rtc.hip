@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "functor_shape.hpp"
 
 namespace mi355 {
 
@@ -94,7 +95,8 @@ static RtcApi* rtc_api() {
 using namespace mi355;
 
 namespace {
-constexpr int kLaneChoices = 6;                      // T = 2, 4, 8, 16, 32, 64
+constexpr int kLaneChoices = kFunctorLaneChoices;    // T = 2, 4, 8, 16, 32, 64
+static_assert(kFunctorBlock == kBlock && kFunctorWave == kWave && kFunctorCus == kCus, "functor_shape.hpp restates common.hpp");
 struct Loaded {                                      // the code object on one device
     int device = -1;
     hipModule_t module = nullptr;
@@ -220,27 +222,12 @@ int mi355_spmv_functor_spmv(mi355_spmv_functor* f, int32_t n_rows, int32_t n_col
     if (nnz > 0 && n_cols == 0) { set_error("functor_spmv: nonzeros but no columns"); return MI355_SPMV_EINVAL; }
     const Loaded* l = nullptr;
     if (const int st = load_on_current_device(f, &l)) return st;
-    // lanes per row from the mean row length (the CSR-vector rule of the reference, cusp.cuh:203-221, on a 64-wide wave)
-    // (a lane takes four nonzeros per step: T lanes cover a row of 4 T in one)
-    const int64_t mean = nnz / n_rows;
-    int choice = 0;                                  // T = 2 << choice
-    while (choice < kLaneChoices - 1 && (int64_t(8) << choice) < mean) ++choice;
-    const int T = 2 << choice;
-    long long long_len = 128ll * T;                  // (32 steps of the row's T lanes)
-    if (long_len < 2048) long_len = 2048;
-    const int rows_per_wg = kBlock / T;
-    const int64_t want = (int64_t(n_rows) + rows_per_wg - 1) / rows_per_wg;
-    const unsigned grid = unsigned(want < int64_t(kCus) * 32 ? want : int64_t(kCus) * 32);
+    const FunctorShape shape = functor_shape(n_rows, nnz);
+    long long long_len = shape.long_len;
     void* args[] = {&n_rows, &Ap, &Aj, &Ax, &x, &y, &long_len};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    MI355_HIP_TRY(hipModuleLaunchKernel(l->rows[choice], grid, 1, 1, kBlock, 1, 1, 0, s, args, nullptr));
-    // the long rows: a row of that length only exists when nnz allows it
-    if (nnz > long_len) {
-        const int64_t waves = (int64_t(n_rows) + kWave - 1) / kWave;
-        const int64_t wgs = (waves + kBlock / kWave - 1) / (kBlock / kWave);
-        const unsigned g2 = unsigned(wgs < int64_t(kCus) * 8 ? wgs : int64_t(kCus) * 8);
-        MI355_HIP_TRY(hipModuleLaunchKernel(l->long_rows, g2, 1, 1, kBlock, 1, 1, 0, s, args, nullptr));
-    }
+    MI355_HIP_TRY(hipModuleLaunchKernel(l->rows[shape.choice], shape.rows_grid, 1, 1, kBlock, 1, 1, 0, s, args, nullptr));
+    if (shape.long_launch) MI355_HIP_TRY(hipModuleLaunchKernel(l->long_rows, shape.long_grid, 1, 1, kBlock, 1, 1, 0, s, args, nullptr));
     return MI355_SPMV_OK;
 }
 

@@ -3,9 +3,12 @@
 //
 //   lanes      every lane of a workgroup is a fiber with a stack of its own, all in one host thread.  A lane runs until
 //              its next collective (__shfl, __shfl_xor, __shfl_up, __shfl_down, __ballot, __syncthreads), posts its operand and
-//              yields; when every lane of its wave has arrived the wave goes on.  Width 64.
+//              yields; when every lane of its wave has arrived the wave goes on.  Width 64.  __shfl_down alone honours a
+//              narrower `width` (what csrc/functor_kernel.inc needs): its collective is then the aligned group of `width`
+//              lanes, which may run apart from the other groups of the wave — some skip a round, some return earlier.
 //   out of step  every collective records its kind and operand size, and the lanes of a wave are compared after each
-//              exchange: a mismatch, or a lane that has returned while others wait in a collective, ends the program
+//              exchange (the lanes of a group, under a narrower width): a mismatch, or a lane that has returned while
+//              others wait in a collective, ends the program
 //              with a message naming the wave and its collective count (exit status 3) — no deadlock.
 //   blocks     run one after another, so `__shared__` (= static) is shared by exactly one workgroup at a time.
 //              Waves of a workgroup meet only in __syncthreads.
@@ -13,7 +16,7 @@
 //              (a row far outside any Y of a test), a float as 1.5e16, a double as 1.7e127.
 //   alignment  float4 / double2 are alignas(16): the host's alignment check fires on a 16-byte access to an address
 //              that is not 16-byte aligned.
-// Covered: what csrc/multi.hip, csrc/coo_csr.hip and csrc/common.hpp use.  No LDS-staging builtins, no sched_barrier; the
+// Covered: what csrc/multi.hip, csrc/coo_csr.hip, csrc/functor_kernel.inc and csrc/common.hpp use.  No LDS-staging builtins, no sched_barrier; the
 // atomics and copies of the units that have them are in tests/cpp/sim_runtime.hpp.
 #pragma once
 
@@ -80,6 +83,7 @@ inline int min(int a, int b) { return b < a ? b : a; }
 inline int max(int a, int b) { return a < b ? b : a; }
 inline int __clzll(unsigned long long v) { return v ? __builtin_clzll(v) : 64; }
 inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
+inline int __ffsll(long long v) { return __builtin_ffsll(v); }      // 1 + the index of the lowest set bit; 0 for 0
 
 namespace simt {
 
@@ -104,6 +108,7 @@ struct Lane {
     unsigned char* stack = nullptr;     // kStackBytes above one guard page
     void* fake_stack = nullptr;
     uint8_t kind = kRunning, size = 0;  // the collective the lane waits in
+    uint8_t width = kWidth;             // ... and the lanes that take part in it: the aligned group of `width` around the lane
     bool done = false;
     uint64_t ops = 0;                   // collectives finished
 };
@@ -222,7 +227,7 @@ inline void prepare_lane(Lane& l) {
         mprotect(m, 4096, PROT_NONE);
         l.stack = static_cast<unsigned char*>(m) + 4096;
     }
-    l.kind = kRunning; l.size = 0; l.done = false; l.ops = 0; l.fake_stack = nullptr;
+    l.kind = kRunning; l.size = 0; l.width = kWidth; l.done = false; l.ops = 0; l.fake_stack = nullptr;
 #ifdef SIMT_UCONTEXT
     getcontext(&l.ctx);
     l.ctx.uc_stack.ss_sp = l.stack;
@@ -240,10 +245,12 @@ inline void prepare_lane(Lane& l) {
 }
 
 // the calling lane posts `bits`, waits for its wave and gets the wave's posted operands
-inline const uint64_t* collective(uint8_t kind, uint8_t size, uint64_t bits) {
+inline const uint64_t* collective(uint8_t kind, uint8_t size, uint64_t bits, int width = kWidth) {
     Lane& l = g.lanes[g.cur];
+    if (width < 1 || width > kWidth || (width & (width - 1))) { fprintf(stderr, "simt: collective of width %d\n", width); _Exit(4); }
     l.kind = kind;
     l.size = size;
+    l.width = uint8_t(width);
     g.xchg[l.ops & 1][g.cur & (kWidth - 1)] = bits;
     to_scheduler(l, false);
     const uint64_t* got = g.xchg[l.ops & 1];
@@ -265,10 +272,17 @@ inline bool run_wave(int w) {
         int done = 0, sync = 0;
         for (int i = 0; i < kWidth; ++i) { done += L[i].done; sync += !L[i].done && L[i].kind == kSync; }
         if (done == kWidth) return true;
-        if (done) fail(w, "lanes have returned while others of the wave wait in a collective");
-        for (int i = 1; i < kWidth; ++i)
-            if (L[i].kind != L[0].kind || L[i].size != L[0].size || L[i].ops != L[0].ops)
-                fail(w, "the lanes of the wave are out of step (kind or operand size of the collective differs)");
+        // every waiting lane's group (the whole wave, but for a narrower __shfl_down) waits with it, in the same collective
+        for (int i = 0; i < kWidth;) {
+            if (L[i].done) { ++i; continue; }
+            const int width = L[i].width, first = i & ~(width - 1);
+            for (int j = first; j < first + width; ++j) {
+                if (L[j].done) fail(w, "lanes have returned while others of the wave wait in a collective");
+                if (L[j].kind != L[i].kind || L[j].size != L[i].size || L[j].ops != L[i].ops || L[j].width != L[i].width)
+                    fail(w, "the lanes of the wave are out of step (kind or operand size of the collective differs)");
+            }
+            i = first + width;
+        }
         if (sync) return false;
     }
 }
@@ -341,10 +355,9 @@ inline T __shfl_up(T v, unsigned delta, int width = simt::kWidth) {
 }
 template <typename T>
 inline T __shfl_down(T v, unsigned delta, int width = simt::kWidth) {
-    (void)width;
     const int lane = simt::g.cur & (simt::kWidth - 1);
-    const uint64_t* w = simt::collective(simt::kShflDown, sizeof(T), simt::to_bits(v));
-    return simt::from_bits<T>(w[unsigned(lane) + delta >= unsigned(simt::kWidth) ? lane : lane + int(delta)]);
+    const uint64_t* w = simt::collective(simt::kShflDown, sizeof(T), simt::to_bits(v), width);
+    return simt::from_bits<T>(w[unsigned(lane & (width - 1)) + delta >= unsigned(width) ? lane : lane + int(delta)]);
 }
 inline unsigned long long __ballot(int pred) {
     const uint64_t* w = simt::collective(simt::kBallot, sizeof(int), pred ? 1 : 0);

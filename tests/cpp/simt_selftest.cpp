@@ -1,6 +1,6 @@
 // simt_selftest — TEST CODE.  What tests/cpp/simt/hip/hip_runtime.h promises, on kernels of a few lines: the host
 // execution of csrc/multi.hip (multi_sim.cpp) means what it says only while these hold.
-//   simt_selftest semantics   shuffles, ballot, barrier, __shared__ and its reuse behind a second barrier, block order, the
+//   simt_selftest semantics   shuffles (__shfl_down under a width, its groups running apart), __ffsll, ballot, barrier, __shared__ and its reuse behind a second barrier, block order, the
 //                             hipMalloc fill:                                                   exit status 0
 //   simt_selftest returned    a lane returns while the others of its wave wait in a collective: exit status 3
 //   simt_selftest kind        one lane calls another collective than the others:                exit status 3
@@ -24,6 +24,9 @@ __global__ void semantics(int* ok, int* order) {
     good = good && __shfl(int64_t(lane) << 40, 5) == int64_t(5) << 40 && __shfl(float(lane) / 4, 9) == 2.25f;
     good = good && __ballot(lane & 1) == 0xAAAAAAAAAAAAAAAAull && __ballot(lane == 63) == 1ull << 63 && __ballot(0) == 0;
     good = good && __clzll(0) == 64 && __clzll(1) == 63;
+    good = good && __ffsll(0) == 0 && __ffsll(1) == 1 && __ffsll(0x60) == 6 && __ffsll((long long)(1ull << 63)) == 64;
+    for (unsigned d = 1; d < 8; d *= 2)                     // __shfl_down under a width: the last d lanes of each group keep theirs
+        good = good && __shfl_down(lane + 100, d, 8) == ((lane & 7) + d >= 8 ? lane + 100 : lane + 100 + int(d));
     if (lane == 0) total[wave] = int(blockIdx.x) * 10 + wave;
     __syncthreads();                                        // the waves of a block meet here, and only here
     for (int w = 0; w < 4; ++w) good = good && total[w] == int(blockIdx.x) * 10 + w;
@@ -53,6 +56,18 @@ __global__ void lds_reuse(int* ok) {
     const int t = threadIdx.x, b = blockIdx.x;
     const int ones = sum_before(1), ramp = sum_before(t + b), again = sum_before(2);
     ok[b * blockDim.x + t] = ones == t && ramp == t * (t - 1) / 2 + b * t && again == 2 * t;
+}
+
+// groups of a narrower __shfl_down run apart (csrc/functor_kernel.inc, rows_body): the odd groups of 8 lanes return at
+// once, group 0 goes a second round, and every group sums its own lanes only
+__global__ void groups_apart(int* sum) {
+    const int lane = threadIdx.x & 63, group = lane / 8;
+    if (group & 1) return;
+    for (int round = 0; round < (group == 0 ? 2 : 1); ++round) {
+        int t = lane + round;
+        for (int o = 4; o >= 1; o >>= 1) t += __shfl_down(t, o, 8);
+        if ((lane & 7) == 0) sum[(threadIdx.x / 8) * 2 + round] = t;
+    }
 }
 
 __global__ void out_of_step(int mode) {
@@ -86,6 +101,14 @@ int main(int argc, char** argv) {
         hipLaunchKernelGGL(lds_reuse, dim3(3), dim3(256), 0, nullptr, ok);
         for (int i = 0; i < 3 * 256; ++i)
             if (!ok[i]) { fprintf(stderr, "a sum over __shared__ reused behind a second barrier is wrong in thread %d\n", i); return 1; }
+        static int sum[2 * 32];
+        hipLaunchKernelGGL(groups_apart, dim3(1), dim3(256), 0, nullptr, sum);
+        for (int g8 = 0; g8 < 32; ++g8)
+            for (int round = 0; round < 2; ++round) {
+                const bool ran = !(g8 & 1) && round < ((g8 & 7) == 0 ? 2 : 1);
+                const int first = (g8 & 7) * 8, want = ran ? 8 * first + 28 + 8 * round : 0;
+                if (sum[g8 * 2 + round] != want) { fprintf(stderr, "groups of 8 lanes running apart: group %d round %d sums to %d\n", g8, round, sum[g8 * 2 + round]); return 1; }
+            }
         return alignof(float4) == 16 && alignof(double2) == 16 ? 0 : 1;
     }
     const int mode = !strcmp(what, "returned") ? 0 : !strcmp(what, "kind") ? 1 : !strcmp(what, "size") ? 2 : !strcmp(what, "down") ? 3 : -1;

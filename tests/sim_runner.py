@@ -16,14 +16,15 @@ CPP = os.path.join(ROOT, "tests", "cpp")
 TIME_LIMIT = 900        # seconds per child: ~30 x what the slowest batch of any table takes
 
 
-def build(target):
-    """The program, built on demand by the one rule of tests/cpp/Makefile for every host simulation (its SIM_SAN flags).
+def build(target, *variables):
+    """The program, built on demand by the one rule of tests/cpp/Makefile for every host simulation (its SIM_SAN flags);
+    variables: NAME=value words for make's command line (the functor simulation's type names).
     Skips only where the host compiler cannot link with those flags at all (a trivial program, the same flags); any other
     failure to build is a failure."""
     probe = subprocess.run(["make", "-s", "-C", CPP, "sanitizer_probe"], capture_output=True, text=True)
     if probe.returncode != 0:
         pytest.skip("the host compiler cannot link with the sanitizer runtimes: " + probe.stderr.strip()[-300:])
-    subprocess.run(["make", "-s", "-C", CPP, target], check=True)
+    subprocess.run(["make", "-s", "-C", CPP, target] + list(variables), check=True)
     return os.path.join(CPP, target)
 
 
@@ -75,8 +76,9 @@ def batches(groups, weight, n):
     return [b[1] for b in out if b[1]]
 
 
-def run_table(exe, tmp, groups, weight, write_batch, read_results):
-    """Every case of the groups through the sanitized program, in at most min(8, CPUs) concurrent children:
+def run_table(exe, tmp, groups, weight, write_batch, read_results, time_limit=TIME_LIMIT):
+    """Every case of the groups through the sanitized program, in at most min(8, CPUs) concurrent children, each under
+    time_limit seconds (a table whose batches take seconds passes a shorter one: a wrong loop bound is an endless loop here):
     ({case name: what read_results gives for it}, [(exit status, stdout + stderr) per child])."""
     try:
         cpus = len(os.sched_getaffinity(0))
@@ -92,11 +94,11 @@ def run_table(exe, tmp, groups, weight, write_batch, read_results):
     results, reports = {}, []
     for child, order, dst in children:
         try:
-            out, err = child.communicate(timeout=TIME_LIMIT)
+            out, err = child.communicate(timeout=time_limit)
         except subprocess.TimeoutExpired:
             child.kill()
             out, err = child.communicate()
-            err += "\n(killed after %d s)" % TIME_LIMIT
+            err += "\n(killed after %d s)" % time_limit
         reports.append((child.returncode, out + err))
         if child.returncode == 0:
             for c, res in zip(order, read_results(dst, order)):
